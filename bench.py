@@ -7,10 +7,14 @@ inputs (scene, camera) are resident in HBM before the timed region; outputs stay
 finished strips are gathered to rank 0 over RCCL inside the timed region).
 
     python bench.py --gpus 1 --steps 3 --warmup 1
+    python bench.py --gpus 1 --steps 3 --warmup 1 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
-A ray = one closest-hit query (one path segment), counted on the device.  Rank 0 prints ONE JSON line.
+A ray = one closest-hit query (one path segment), counted on the device.  Rank 0 prints ONE JSON line.  A plain run does only what
+that line's headline needs (set-up, warm-up, the K timed frames); --full adds the roofline object (its counters come from an
+instrumented first warm-up frame), the untimed default-camera frame and the CPU baseline.  --dump-outputs DIR writes the last timed
+frame as DIR/rgb8.npy and DIR/radiance.npy (float32) for output-for-output comparisons of two builds.
 """
 import argparse
 import ctypes
@@ -28,6 +32,8 @@ NODE_BYTES, TRI_BYTES, RAY_BYTES = 112, 48, 24  # algorithmic bytes per 4-wide B
 # 2 cycles per SIMD, 2.4 GHz -> 1228.8 G wave-instructions/s
 SIMDS, CLOCK_HZ, VALU_CYCLES_PER_INST = 1024, 2.4e9, 2.0
 VALU_PEAK_GINST = SIMDS * CLOCK_HZ / VALU_CYCLES_PER_INST / 1e9
+DUMP_BUDGET_BYTES = 64 * 10**6  # --dump-outputs: all arrays together (a 1080p frame's two float32 arrays take 49.8 MB)
+DUMP_SAMPLE_SEED = 0
 
 
 def parse_args():
@@ -53,7 +59,16 @@ def parse_args():
     ap.add_argument("--keep-primary-hits", action="store_true",
                     help="let the library keep the pixels' stored primary hits from frame to frame (the viewer with its camera at rest); "
                          "by default every timed frame pays for its own pre-pass")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the roofline object (node/triangle counters from the first warm-up "
+                         "frame, committed PMC file), the untimed default-camera frame and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed frames, write the last one as DIR/rgb8.npy and DIR/radiance.npy (float32; a frame over "
+                         f"{DUMP_BUDGET_BYTES // 10**6} MB is written as a fixed sample of pixels, DIR/pixel_index.npy)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def algorithmic_bytes(st, width, rows, spp):
@@ -105,6 +120,24 @@ def _measured_pmc(args, world, kernel):
     if best is not None:
         return best, None
     return None, stale or "no committed PMC measurement (profiles/*_pmc.json) matches this workload and kernel instantiation"
+
+
+def dump_outputs(out_dir, rgb8, radiance):
+    """What a caller of the timed path receives from its last frame: rgb8 (H, W, 3; values exact in float32) and radiance (H, W, 3),
+    as float32 .npy files.  A frame over DUMP_BUDGET_BYTES is written as the same fixed, seeded sample of pixels on every run:
+    (k, 3) arrays plus their flat pixel indices (pixel_index.npy, float64, ascending)."""
+    import numpy as np
+    arrays = {"rgb8": rgb8.cpu().numpy().astype(np.float32), "radiance": radiance.cpu().numpy().astype(np.float32)}
+    h, w, c = arrays["radiance"].shape
+    per_pixel = 4 * c * len(arrays)
+    if h * w * per_pixel > DUMP_BUDGET_BYTES:
+        k = (DUMP_BUDGET_BYTES - 4096) // (per_pixel + 8)  # (4096: room for the three .npy headers)
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(h * w, size=k, replace=False))
+        arrays = {name: a.reshape(h * w, c)[idx] for name, a in arrays.items()}
+        arrays["pixel_index"] = idx.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def host_cores():
@@ -285,8 +318,8 @@ def main():
                 tracer.deinterleave_strips(gr.data_ptr(), full_rad.data_ptr(), args.width, args.height, strip_rows, world, 12)
         return tracer.stats()
 
-    # ---- warmup (untimed); the first warmup frame also collects the node/triangle visit counters ----
-    tracer.set_collect_stats(True)
+    # ---- warmup (untimed, at least one frame); with --full the first warmup frame also collects the node/triangle visit counters ----
+    tracer.set_collect_stats(args.full)
     counted = step()
     tracer.set_collect_stats(False)
     for _ in range(max(0, args.warmup - 1)):
@@ -313,6 +346,8 @@ def main():
     barrier_sync()
     elapsed = time.perf_counter() - t0
     kernel = tracer.kernel_name()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, full_rgb8, full_rad)
 
     if world > 1:
         red_dev = device if backend == "nccl" else torch.device("cpu")
@@ -327,7 +362,7 @@ def main():
 
     # ---- companion figure (untimed region, N = 1 only): the same frame from the reference's default camera ----
     companion = None
-    if world == 1 and args.camera == "inside" and args.scene == "c2" and not args.no_companion:
+    if args.full and world == 1 and args.camera == "inside" and args.scene == "c2" and not args.no_companion:
         dcam = scenes.default_camera(args.width, args.height)
         step(dcam)
         torch.cuda.synchronize()
@@ -342,43 +377,45 @@ def main():
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
         value = total_rays / elapsed / 1e6
-        # The dominant kernel on this rank: mean launch duration from the HIP events the library records on its launch stream.
-        mean_launch_s = kernel_ms / max(1, launches) / 1e3
-        rays_per_launch = rays / max(1, launches)
-        algo_bytes_launch = algorithmic_bytes(counted, args.width, local_rows, args.spp) / max(1, counted.kernel_launches)
-        pmc, pmc_why_not, pmc_scope = measured_pmc(args, world, kernel)
-        roof = {
-            # What binds this kernel is VALU issue at partial lane occupancy, not HBM: the scene is
-            # LDS/L2 resident.  achieved = wave-level VALU instructions per second, from the committed PMC count per ray of
-            # this kernel instantiation on this workload x the rays and the launch duration measured live in this run.
-            "bound": "valu_issue", "unit": "G wave-inst/s", "peak": round(VALU_PEAK_GINST, 1),
-            "kernel": kernel, "kernel_ms_per_launch": round(mean_launch_s * 1e3, 3), "rays_per_launch": int(rays_per_launch),
-            "algorithmic_bytes_per_launch": int(algo_bytes_launch),
-            "algorithmic_GBps": round(algo_bytes_launch / mean_launch_s / 1e9, 1),
-            "per_ray": {"nodes": round(counted.nodes_visited / max(1, counted.rays_traced), 3),
-                        "tris": round(counted.tris_tested / max(1, counted.rays_traced), 3)},
-            # the same per path segment that went through the closest-hit machinery (all segments minus those answered from a
-            # block's parked primary hit or dropped with a culled pixel); `valu` joins it below when a PMC file matches
-            "per_traversed_ray": {"nodes": round(counted.nodes_visited / max(1, counted.rays_traced - counted.rays_answered), 3),
-                                  "tris": round(counted.tris_tested / max(1, counted.rays_traced - counted.rays_answered), 3)},
-        }
-        if pmc is not None:
-            achieved = pmc["valu_insts_per_ray"] * rays_per_launch / mean_launch_s / 1e9
-            traffic = pmc["hbm_bytes_per_ray"] * rays_per_launch
-            roof.update({
-                "achieved": round(achieved, 1), "frac": round(achieved / VALU_PEAK_GINST, 4),
-                "lane_occupancy": pmc["lane_occupancy"], "fp32_lane_throughput_frac": round(achieved / VALU_PEAK_GINST * pmc["lane_occupancy"], 4),
-                "traffic": int(traffic), "hbm_GBps": round(traffic / mean_launch_s / 1e9, 2),
-                "hbm_frac": round(traffic / mean_launch_s / 1e9 / HBM_PEAK_GBS, 5),
-                "algorithmic_vs_hbm": round(algo_bytes_launch / max(traffic, 1.0), 1),
-                "pmc_source": pmc["file"], "pmc_kernel_source_hash": pmc["kernel_source_hash"], "pmc_scope": pmc_scope,
-                "note": "algorithmic bytes (SURVEY.md section 8d: 24/ray + 112/node visit + 48/triangle test + framebuffer) are served by LDS and L2; "
-                        "`traffic` is what reaches HBM (FETCH_SIZE x2 + WRITE_SIZE from the PMC passes, scaled by rays)",
-            })
-            roof["per_ray"]["valu"] = round(pmc["valu_insts_per_ray"], 2)
-            roof["per_traversed_ray"]["valu"] = round(pmc["valu_insts_per_ray"] * total_rays / max(1.0, total_rays - total_answered), 2)
-        else:
-            roof.update({"achieved": None, "frac": None, "traffic": None, "note": "PMC-derived fields withheld: " + pmc_why_not})
+        roof = None
+        if args.full:
+            # The dominant kernel on this rank: mean launch duration from the HIP events the library records on its launch stream.
+            mean_launch_s = kernel_ms / max(1, launches) / 1e3
+            rays_per_launch = rays / max(1, launches)
+            algo_bytes_launch = algorithmic_bytes(counted, args.width, local_rows, args.spp) / max(1, counted.kernel_launches)
+            pmc, pmc_why_not, pmc_scope = measured_pmc(args, world, kernel)
+            roof = {
+                # What binds this kernel is VALU issue at partial lane occupancy, not HBM: the scene is
+                # LDS/L2 resident.  achieved = wave-level VALU instructions per second, from the committed PMC count per ray of
+                # this kernel instantiation on this workload x the rays and the launch duration measured live in this run.
+                "bound": "valu_issue", "unit": "G wave-inst/s", "peak": round(VALU_PEAK_GINST, 1),
+                "kernel": kernel, "kernel_ms_per_launch": round(mean_launch_s * 1e3, 3), "rays_per_launch": int(rays_per_launch),
+                "algorithmic_bytes_per_launch": int(algo_bytes_launch),
+                "algorithmic_GBps": round(algo_bytes_launch / mean_launch_s / 1e9, 1),
+                "per_ray": {"nodes": round(counted.nodes_visited / max(1, counted.rays_traced), 3),
+                            "tris": round(counted.tris_tested / max(1, counted.rays_traced), 3)},
+                # the same per path segment that went through the closest-hit machinery (all segments minus those answered from a
+                # block's parked primary hit or dropped with a culled pixel); `valu` joins it below when a PMC file matches
+                "per_traversed_ray": {"nodes": round(counted.nodes_visited / max(1, counted.rays_traced - counted.rays_answered), 3),
+                                      "tris": round(counted.tris_tested / max(1, counted.rays_traced - counted.rays_answered), 3)},
+            }
+            if pmc is not None:
+                achieved = pmc["valu_insts_per_ray"] * rays_per_launch / mean_launch_s / 1e9
+                traffic = pmc["hbm_bytes_per_ray"] * rays_per_launch
+                roof.update({
+                    "achieved": round(achieved, 1), "frac": round(achieved / VALU_PEAK_GINST, 4),
+                    "lane_occupancy": pmc["lane_occupancy"], "fp32_lane_throughput_frac": round(achieved / VALU_PEAK_GINST * pmc["lane_occupancy"], 4),
+                    "traffic": int(traffic), "hbm_GBps": round(traffic / mean_launch_s / 1e9, 2),
+                    "hbm_frac": round(traffic / mean_launch_s / 1e9 / HBM_PEAK_GBS, 5),
+                    "algorithmic_vs_hbm": round(algo_bytes_launch / max(traffic, 1.0), 1),
+                    "pmc_source": pmc["file"], "pmc_kernel_source_hash": pmc["kernel_source_hash"], "pmc_scope": pmc_scope,
+                    "note": "algorithmic bytes (SURVEY.md section 8d: 24/ray + 112/node visit + 48/triangle test + framebuffer) are served by LDS and L2; "
+                            "`traffic` is what reaches HBM (FETCH_SIZE x2 + WRITE_SIZE from the PMC passes, scaled by rays)",
+                })
+                roof["per_ray"]["valu"] = round(pmc["valu_insts_per_ray"], 2)
+                roof["per_traversed_ray"]["valu"] = round(pmc["valu_insts_per_ray"] * total_rays / max(1.0, total_rays - total_answered), 2)
+            else:
+                roof.update({"achieved": None, "frac": None, "traffic": None, "note": "PMC-derived fields withheld: " + pmc_why_not})
         frame_ms.sort()
         out = {
             "metric": f"Mrays/s (path segments = closest-hit queries, device-counted) at {'1080p' if (args.width, args.height) == (1920, 1080) else f'{args.width}x{args.height}'}, "
@@ -407,11 +444,12 @@ def main():
                 "partition": f"{strip_rows}-row strips round-robin over {world} rank(s)",
                 "gather": gather if gather_note is None else f"{gather} ({gather_note})",
             },
-            "roofline": roof,
         }
+        if roof is not None:
+            out["roofline"] = roof
         if companion is not None:
             out["default_camera"] = companion
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(scene, camera, args)
         print(json.dumps(out), flush=True)
 

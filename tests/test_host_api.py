@@ -12,7 +12,6 @@ from gpupathtracer_amd import scenes
 from gpupathtracer_amd import types as T
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF_RES = "/root/reference/sceneResources"
 
 
 def test_library_exports_every_declared_symbol(ff):
@@ -184,14 +183,48 @@ def test_obj_loader_errors(ff, tmp_path):
     assert e.value.status == T.FF_ERR_IO
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_RES), reason="reference assets are only mounted in the build container")
+def _write_obj(path, tris, style):
+    """An OBJ file for a flattened mesh (FfTriangle rows): shared `v` / `vt` / `vn` records, `f v/vt/vn` faces, with the other
+    statements the mesh fixtures' files carry (comments, blank lines, mtllib, o, g, s, usemtl).  Numbers: "%.6f" (as the exporter of
+    most fixtures wrote them; every fixture value rounds back from it) or "exact" (the float32 value's double repr, many digits)."""
+    def number(x):
+        return "%.6f" % x if style == "%.6f" else repr(float(x))
+
+    def records(cols, k):
+        rows = np.ascontiguousarray(tris[:, cols].reshape(-1, k))
+        uniq, inv = np.unique(rows.view(np.uint32), axis=0, return_inverse=True)
+        return uniq.view(np.float32), inv.reshape(-1, 3) + 1
+    pos, pi = records(slice(0, 9), 3)
+    uv, ti = records(slice(9, 15), 2)
+    nrm, ni = records(slice(15, 24), 3)
+    lines = ["# mesh fixture written back as OBJ text", "mtllib fixture.mtl", "o fixture", ""]
+    lines += ["v " + " ".join(number(c) for c in r) for r in pos]
+    lines += ["vt " + " ".join(number(c) for c in r) for r in uv]
+    lines += ["vn " + " ".join(number(c) for c in r) for r in nrm]
+    lines += ["", "g default", "s 1", "usemtl initialShadingGroup"]
+    lines += ["f " + " ".join(f"{p}/{t}/{n}" for p, t, n in zip(pi[i], ti[i], ni[i])) for i in range(len(tris))]
+    with open(path, "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
 @pytest.mark.parametrize("name", ["cube", "wahoo", "rocketman", "sphereBlender", "sphere"])
-def test_obj_loader_matches_reference_tinyobj(ff, name):
-    """ff_load_obj vs the fixture the reference's own tiny_obj_loader.h produced (oracle/ref_tinyobj_dump.cpp), bit for bit."""
-    mine = ff.load_obj(os.path.join(REF_RES, name + ".obj"))
+def test_obj_loader_matches_reference_tinyobj(ff, name, tmp_path):
+    """ff_load_obj vs the reference's own tiny_obj_loader.h (oracle/ref_tinyobj_dump.cpp), bit for bit.  The mesh fixture
+    assets/meshes/NAME.fftri is what tinyobj made of the reference's NAME.obj; the test writes that mesh back as OBJ text (numbers
+    as "%.6f" or as long exact decimals) and reads it with ff_load_obj.  Where the build made the tinyobj generator (oracle/_ref/),
+    tinyobj reads the same text and must give the fixture too."""
     ref = scenes.load_mesh(name)
+    path = str(tmp_path / (name + ".obj"))
+    _write_obj(path, ref, "exact" if name.startswith("sphere") else "%.6f")
+    mine = ff.load_obj(path)
     assert mine.shape == ref.shape
     assert np.array_equal(mine.view(np.uint32), ref.view(np.uint32))
+    tool = os.path.join(ROOT, "oracle", "_ref", "tinyobj_dump")
+    if os.access(tool, os.X_OK):
+        import subprocess
+        subprocess.check_call([tool, path, str(tmp_path / "tinyobj.fftri")], stdout=subprocess.DEVNULL)
+        theirs = scenes.load_fftri(str(tmp_path / "tinyobj.fftri"))
+        assert np.array_equal(theirs.view(np.uint32), ref.view(np.uint32))
 
 
 def test_strip_rows_helper(ff):

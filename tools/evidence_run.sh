@@ -8,7 +8,7 @@ mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 stats() {  # name, bench args...
   name=$1; shift
-  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_$name" -- python3 bench.py --no-cpu-baseline --no-companion "$@" > "$OUT/prof_$name.log" 2>&1
+  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_$name" -- python3 bench.py --full --no-cpu-baseline --no-companion "$@" > "$OUT/prof_$name.log" 2>&1
   echo "stats $name rc=$?"
   find "$OUT/prof_$name" -name "*kernel_stats.csv" -exec cp {} "$OUT/${TAG}_${name}_kernel_stats.csv" \;
   rm -rf "$OUT/prof_$name"
@@ -24,9 +24,9 @@ python3 tools/pmc_summary.py "$OUT/pmc_c4" > "$OUT/${TAG}_c4_pmc_summary.txt"
 python3 tools/pmc_to_json.py "$OUT/pmc_c4" "$OUT/${TAG}_c4_pmc.json" "round 4 kernel, C4: the config whose tree does not fit LDS"
 rm -rf "$OUT"/pmc_c4/*/
 cp "$OUT/${TAG}_c2_pmc.json" "$OUT/${TAG}_c4_pmc.json" profiles/  # (on the GPU box: so that the bench lines below find them)
-timeout -k 10 400 python3 bench.py --steps 5 --warmup 1 > "$OUT/${TAG}_bench.json" 2> "$OUT/bench.err"
+timeout -k 10 400 python3 bench.py --full --steps 5 --warmup 1 > "$OUT/${TAG}_bench.json" 2> "$OUT/bench.err"
 echo "bench rc=$?"
 tail -c 3000 "$OUT/${TAG}_bench.json"
-timeout -k 10 300 python3 bench.py --scene c4 --steps 3 --warmup 1 --no-cpu-baseline > "$OUT/${TAG}_c4_bench.json" 2>> "$OUT/bench.err"
-timeout -k 10 300 python3 bench.py --scene c3 --spp 4096 --steps 3 --warmup 1 --no-cpu-baseline > "$OUT/${TAG}_c3_bench.json" 2>> "$OUT/bench.err"
+timeout -k 10 300 python3 bench.py --full --scene c4 --steps 3 --warmup 1 --no-cpu-baseline > "$OUT/${TAG}_c4_bench.json" 2>> "$OUT/bench.err"
+timeout -k 10 300 python3 bench.py --full --scene c3 --spp 4096 --steps 3 --warmup 1 --no-cpu-baseline > "$OUT/${TAG}_c3_bench.json" 2>> "$OUT/bench.err"
 tail -c 700 "$OUT/${TAG}_c4_bench.json"; tail -c 700 "$OUT/${TAG}_c3_bench.json"

@@ -19,6 +19,6 @@ GROUP[tcc1]="FETCH_SIZE"
 GROUP[tcc2]="WRITE_SIZE TCC_HIT_sum TCC_MISS_sum"
 GROUP[grbm]="GRBM_GUI_ACTIVE"
 for name in $PASSES; do
-  timeout -k 10 400 rocprofv3 --kernel-trace --pmc ${GROUP[$name]} --output-format csv -d "$OUT/$name" -- python3 bench.py --no-cpu-baseline "$@" > "$OUT/$name.log" 2>&1
+  timeout -k 10 400 rocprofv3 --kernel-trace --pmc ${GROUP[$name]} --output-format csv -d "$OUT/$name" -- python3 bench.py --full --no-cpu-baseline "$@" > "$OUT/$name.log" 2>&1
   echo "pass $name rc=$?"
 done

@@ -7,7 +7,7 @@
 N=${1:-2}; OUT=${2:-gpurun_out/bench_n$N.json}; shift 2
 PORT=$((20000 + RANDOM % 20000))
 FF_DIST_BACKEND=gloo timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port $PORT \
-  bench.py --gpus $N --steps 2 --warmup 1 --spp 64 "$@" > $OUT 2> ${OUT%.json}.err
+  bench.py --full --gpus $N --steps 2 --warmup 1 --spp 64 "$@" > $OUT 2> ${OUT%.json}.err
 rc=$?
 echo "rank_rehearsal N=$N rc=$rc"; tail -c 1500 $OUT
 exit $rc
