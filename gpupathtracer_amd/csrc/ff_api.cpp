@@ -14,6 +14,7 @@
 // (the interop header relies on hip_runtime.h having been included first)
 #include <hip/hip_gl_interop.h>
 
+#include "ff_denoise.h"
 #include "ff_state.h"
 
 using namespace ff;
@@ -829,6 +830,9 @@ int ff_destroy(FfState* s)
     if (s->d_accum) (void)hipFree(s->d_accum);
     if (s->d_frame) (void)hipFree(s->d_frame);
     if (s->d_mean) (void)hipFree(s->d_mean);
+    if (s->d_gb_hits) (void)hipFree(s->d_gb_hits);
+    if (s->d_img_stage) (void)hipFree(s->d_img_stage);
+    if (s->d_dn_work) (void)hipFree(s->d_dn_work);
     free_build_scratch(s->scratch);
     if (s->d_blocksums) (void)hipFree(s->d_blocksums);
     if (s->d_rgb8) (void)hipFree(s->d_rgb8);
@@ -1652,6 +1656,299 @@ int ff_render_to_pbo_progressive(FfState* s, const FfCamera* camera, const FfRen
     if (st == FF_OK && ue != hipSuccess) st = fail(FF_ERR_HIP, "hipGraphicsUnmapResources failed: %s", hipGetErrorString(ue));
     s->stats.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return st;
+}
+
+// ---- G-buffer and denoiser (kernels in ff_denoise.hip) ---------------------
+
+namespace {
+
+// Host buffers of ff_gbuffer / ff_denoise go through one state-owned staging area: carve() hands out 16-byte aligned pieces.
+struct Carver {
+    char* base;
+    size_t used;
+    void* carve(size_t bytes)
+    {
+        void* p = base + used;
+        used += (bytes + 15) & ~(size_t)15;
+        return p;
+    }
+};
+
+size_t padded(size_t bytes) { return (bytes + 15) & ~(size_t)15; }
+
+// The primary-hit pre-pass of a whole W x H frame (render_enqueue's, with the pixel mapping of ff_render) into `hits`, on the
+// state's stream.  It writes nothing else of the state: not the stored hits of the frames or their key, not the cull mask; the
+// work-queue counters are zeroed behind it as after the frame's own pre-pass.
+int enqueue_gbuffer_prepass(FfState* s, KParams& k, float4* hits)
+{
+    const int block_threads = s->scene_block_threads;
+    int grid = s->num_cus;
+    const uint64_t max_useful = ((uint64_t)k.pix_items + (uint64_t)block_threads - 1) / (uint64_t)block_threads;
+    if ((uint64_t)grid > max_useful) grid = (int)max_useful;
+    if (grid < 1) grid = 1;
+    k.shade_mode = kShadePrimaryPass;
+    k.bounces = k.spp_total = k.block_spp = k.num_blocks = 1;
+    k.block_begin = 0;
+    k.block_end = 1;
+    k.whole_blocks = 1u;
+    k.total_items = k.pix_items;
+    k.frame_blocks = 1;
+    k.tail_block = -1;
+    k.setup_threshold = s->setup_threshold;
+    k.leaf_threshold = s->leaf_threshold;
+    k.num_geoms = s->num_geoms;
+    k.num_planes = s->num_planes;
+    k.num_quads = s->num_quads;
+    k.has_specular = s->has_specular ? 1 : 0;
+    k.geoms = s->d_geoms;
+    k.tris = s->d_tris;
+    k.trinormals = nullptr; // (geometric normals; the resolve recomputes a triangle's from its record anyway)
+    k.nodes4 = s->d_nodes4;
+    if (s->sw.lds_fill) {
+        const size_t bytes = bvh_lds_bytes(s->lds_cap, s->stack_lds_levels, block_threads, lds_records(s));
+        k.debug_lds_words = (unsigned)std::min<size_t>(s->sw.lds_fill_words, bytes / 4);
+        k.debug_lds_pattern = (unsigned)s->sw.lds_fill_pattern;
+    }
+    k.stack_depth = s->stack_lds_levels;
+    k.stack_spill = nullptr;
+    if (s->stack_lds_levels < s->stack_entries) {
+        const int st = ensure_bytes((void**)&s->d_stack_spill, &s->stack_spill_bytes,
+                                    (size_t)(s->stack_entries - s->stack_lds_levels) * (size_t)grid * (size_t)block_threads * sizeof(int));
+        if (st != FF_OK) return st;
+        k.stack_spill = s->d_stack_spill;
+    }
+    k.lds_nodes = s->lds_cap;
+    k.top_first = (int)s->node_capacity;
+    k.top_lds_first = 0;
+    k.top_lds_count = s->top_lds_count;
+    k.num_scan = s->num_scan;
+    k.walls = s->walls;
+    k.primary_hits = hits;
+    k.reuse_quorum = s->sw.reuse_quorum;
+    k.queue = s->d_queue;
+    k.counters = s->d_counters;
+    k.timeline_ticks = 1;
+    k.queue_chunk = s->sw.queue_chunk > 0 ? (unsigned)s->sw.queue_chunk : 32u;
+    k.queue_counters = std::min(kQueueCountersDefault, grid);
+    if (s->sw.queue_counters > 0) k.queue_counters = std::min(std::min(kQueueCounters, grid), s->sw.queue_counters);
+    const int waves_per_counter = (grid * (block_threads / 64) + k.queue_counters - 1) / k.queue_counters;
+    k.queue_tail_items = (unsigned)(waves_per_counter * (s->sw.queue_tail >= 0 ? s->sw.queue_tail : 8));
+    hipStream_t st = s->stream;
+    FF_HIP(hipMemsetAsync(s->d_counters, 0, (size_t)(1 + k.queue_counters) * kQueueStride * sizeof(unsigned), st));
+    FF_HIP(launch_trace(k, FF_TRACE_BVH, false, grid, block_threads, st, nullptr, false, /*prepass=*/true));
+    FF_HIP(hipMemsetAsync(s->d_queue, 0, (size_t)k.queue_counters * kQueueStride * sizeof(unsigned), st));
+    return FF_OK;
+}
+
+} // namespace
+
+int ff_gbuffer(FfState* s, const FfCamera* camera, const FfRenderParams* params, float* depth, float* position, float* normal, float* albedo,
+               int32_t* ids, int on_device)
+{
+    clear_error();
+    int st = check_render_call(s, camera, params, "ff_gbuffer");
+    if (st != FF_OK) return st;
+    if (s->scene_block_threads == 0)
+        return fail(FF_ERR_UNSUPPORTED, "ff_gbuffer: 4-wide BVH of depth %d does not fit the LDS traversal stack; upload with FF_BUILD_HOST_SAH", s->max_depth4);
+    FF_HIP(hipSetDevice(s->device));
+    const int W = params->width, H = params->height;
+    // the pixel mapping of a whole frame (ff_render: one part, strips of H rows, the window is the image)
+    KParams k;
+    std::memset(&k, 0, sizeof k);
+    FfMat4 cm;
+    ff_camera_ray_matrix(camera, &cm);
+    std::memcpy(k.cam_c0, &cm.m[0], 16);
+    std::memcpy(k.cam_c1, &cm.m[4], 16);
+    std::memcpy(k.cam_c2, &cm.m[8], 16);
+    std::memcpy(k.cam_c3, &cm.m[12], 16);
+    k.cam_pos[0] = camera->m_position.x;
+    k.cam_pos[1] = camera->m_position.y;
+    k.cam_pos[2] = camera->m_position.z;
+    k.far_clip = camera->m_farClip;
+    k.screen_w = camera->m_screenWidth;
+    k.screen_h = camera->m_screenHeight;
+    k.width = k.xlim = W;
+    k.height = k.ylim = H;
+    if (params->grid_mode == FF_GRID_REFERENCE_FLOOR) { // kernel.cu:306-309
+        k.xlim = (W / 16) * 16;
+        k.ylim = (H / 16) * 16;
+    }
+    k.strip_rows = H;
+    k.part = 0;
+    k.num_parts = 1;
+    k.local_rows = H;
+    k.local_width = W;
+    k.tiles_per_row = (W + 7) / 8;
+    const uint64_t tiles = (uint64_t)k.tiles_per_row * (uint64_t)((H + 7) / 8);
+    if (tiles * 64 * 65 >= (1ull << 31)) return fail(FF_ERR_INVALID_ARG, "ff_gbuffer: image too large for the work queue");
+    k.pix_items = (unsigned)(tiles * 64);
+    // The frame's stored hits serve if they were computed for this camera and pixel mapping (render_enqueue's key; the last dims
+    // entry says whether that frame shaded with vertex normals, which changes the stored normal but not what the resolve reads).
+    FfState::PrimaryKey key;
+    std::memset(&key, 0, sizeof key);
+    std::memcpy(key.cam, k.cam_c0, 16 * sizeof(float));
+    std::memcpy(key.cam + 16, k.cam_pos, 3 * sizeof(float));
+    key.cam[19] = k.far_clip; key.cam[20] = k.screen_w; key.cam[21] = k.screen_h;
+    const int dims[12] = { W, H, k.xlim, k.ylim, H, 0, 1, H, 0, 0, W, 0 };
+    std::memcpy(key.dims, dims, sizeof dims);
+    key.pix_items = k.pix_items;
+    const size_t hits_bytes = (size_t)3 * (size_t)k.pix_items * sizeof(float4);
+    bool kept = false;
+    for (int smooth = 0; smooth < 2 && !kept; ++smooth) {
+        key.dims[11] = smooth;
+        kept = s->primary_valid && s->primary_cache_bytes >= hits_bytes && std::memcmp(&key, &s->primary_key, sizeof key) == 0;
+    }
+    // outputs: the caller's device buffers, or the staging area and a copy back
+    const size_t px = (size_t)W * (size_t)H;
+    float* d_depth = depth;
+    float* d_pos = position;
+    float* d_nrm = normal;
+    float* d_alb = albedo;
+    int* d_ids = ids;
+    if (!on_device) {
+        const size_t need = (depth ? padded(px * 4) : 0) + (position ? padded(px * 12) : 0) + (normal ? padded(px * 12) : 0) +
+                            (albedo ? padded(px * 12) : 0) + (ids ? padded(px * 12) : 0);
+        if (need > 0) {
+            st = ensure_bytes(&s->d_img_stage, &s->img_stage_bytes, need);
+            if (st != FF_OK) return st;
+        }
+        Carver c = { (char*)s->d_img_stage, 0 };
+        d_depth = depth ? (float*)c.carve(px * 4) : nullptr;
+        d_pos = position ? (float*)c.carve(px * 12) : nullptr;
+        d_nrm = normal ? (float*)c.carve(px * 12) : nullptr;
+        d_alb = albedo ? (float*)c.carve(px * 12) : nullptr;
+        d_ids = ids ? (int*)c.carve(px * 12) : nullptr;
+    }
+    const float4* hits = s->d_primary_cache;
+    if (!kept) {
+        st = ensure_bytes((void**)&s->d_gb_hits, &s->gb_hits_bytes, hits_bytes);
+        if (st == FF_OK) st = enqueue_gbuffer_prepass(s, k, s->d_gb_hits);
+        if (st != FF_OK) return st;
+        hits = s->d_gb_hits;
+    }
+    GbufferResolveParams r;
+    r.hits = hits;
+    r.pix_items = k.pix_items;
+    r.tiles_per_row = k.tiles_per_row;
+    r.width = W;
+    r.height = H;
+    r.xlim = k.xlim;
+    r.ylim = k.ylim;
+    r.geoms = s->d_geoms;
+    r.tris = s->d_tris;
+    r.num_geoms = s->num_geoms;
+    r.num_tris = (long long)s->num_tris;
+    r.depth = d_depth;
+    r.position = d_pos;
+    r.normal = d_nrm;
+    r.albedo = d_alb;
+    r.ids = d_ids;
+    FF_HIP(launch_gbuffer_resolve(r, s->stream));
+    FF_HIP(hipStreamSynchronize(s->stream));
+    if (!kept) {
+        unsigned long long cut = 0;
+        FF_HIP(hipMemcpy(&cut, s->d_counters, sizeof cut, hipMemcpyDeviceToHost));
+        if (cut != 0) return fail(FF_ERR_HIP, "ff_gbuffer: the traversal loop guard cut %llu queries short (a malformed or absurdly deep tree)", cut);
+    }
+    if (!on_device) {
+        if (depth) FF_HIP(hipMemcpy(depth, d_depth, px * 4, hipMemcpyDeviceToHost));
+        if (position) FF_HIP(hipMemcpy(position, d_pos, px * 12, hipMemcpyDeviceToHost));
+        if (normal) FF_HIP(hipMemcpy(normal, d_nrm, px * 12, hipMemcpyDeviceToHost));
+        if (albedo) FF_HIP(hipMemcpy(albedo, d_alb, px * 12, hipMemcpyDeviceToHost));
+        if (ids) FF_HIP(hipMemcpy(ids, d_ids, px * 12, hipMemcpyDeviceToHost));
+    }
+    return FF_OK;
+}
+
+void ff_denoise_params_init(FfDenoiseParams* p)
+{
+    if (!p) return;
+    // (cornell_wahoo at the C2 pose, 320x180, 16 spp against 4 096 spp: the MSE falls to 0.32 of the raw frame's;
+    // sigma_color 1 / 2 / 4 / 8 leave 0.38 / 0.34 / 0.32 / 0.33; the other two sigmas move it by less than 0.002)
+    p->iterations = 5;
+    p->sigma_color = 4.0f;
+    p->sigma_normal = 0.1f;
+    p->sigma_plane = 0.1f;
+    p->flags = FF_DENOISE_SAME_GEOMETRY | FF_DENOISE_DEMODULATE_ALBEDO;
+}
+
+int ff_denoise(FfState* s, int width, int height, const FfDenoiseParams* dn, const float* radiance_in, const float* position, const float* normal,
+               const float* albedo, const int32_t* ids, int inputs_on_device, void* rgb8, int rgb8_on_device, float* radiance_out,
+               int radiance_out_on_device)
+{
+    clear_error();
+    if (!s) return fail(FF_ERR_INVALID_ARG, "ff_denoise: state is null");
+    if (!dn) return fail(FF_ERR_INVALID_ARG, "ff_denoise: params are null");
+    if (width <= 0 || height <= 0 || width > 65535 || height > 65535) return fail(FF_ERR_INVALID_ARG, "ff_denoise: image size %dx%d is invalid", width, height);
+    if (dn->iterations < 0 || dn->iterations > 10) return fail(FF_ERR_INVALID_ARG, "ff_denoise: iterations must be in 0..10 (got %d)", dn->iterations);
+    if (!(dn->sigma_color > 0.f && dn->sigma_normal > 0.f && dn->sigma_plane > 0.f) || !std::isfinite(dn->sigma_color) ||
+        !std::isfinite(dn->sigma_normal) || !std::isfinite(dn->sigma_plane))
+        return fail(FF_ERR_INVALID_ARG, "ff_denoise: the sigmas must be positive and finite");
+    if (dn->flags & ~(FF_DENOISE_SAME_GEOMETRY | FF_DENOISE_DEMODULATE_ALBEDO)) return fail(FF_ERR_INVALID_ARG, "ff_denoise: unknown flags 0x%x", dn->flags);
+    const int demod = (dn->flags & FF_DENOISE_DEMODULATE_ALBEDO) ? 1 : 0;
+    if (!radiance_in || !position || !normal || !ids || (demod && !albedo))
+        return fail(FF_ERR_INVALID_ARG, "ff_denoise: radiance, position, normal and ids are required (and albedo with FF_DENOISE_DEMODULATE_ALBEDO)");
+    FF_HIP(hipSetDevice(s->device));
+    const size_t px = (size_t)width * (size_t)height;
+    const bool filter = dn->iterations > 0;
+    // host buffers are staged: the inputs the call reads, the outputs it writes
+    const bool in_host = !inputs_on_device, rgb_host = rgb8 && !rgb8_on_device, out_host = radiance_out && !radiance_out_on_device;
+    const size_t need = (in_host ? padded(px * 12) * (filter ? 4 + demod : 1) : 0) + (rgb_host ? padded(px * 3) : 0) +
+                        (out_host ? padded(px * 12) : 0);
+    if (need > 0) {
+        const int st = ensure_bytes(&s->d_img_stage, &s->img_stage_bytes, need);
+        if (st != FF_OK) return st;
+    }
+    Carver c = { (char*)s->d_img_stage, 0 };
+    hipStream_t stream = s->stream;
+    auto stage_in = [&](const void* host, size_t bytes) -> const void* {
+        void* d = c.carve(bytes);
+        return hipMemcpyAsync(d, host, bytes, hipMemcpyHostToDevice, stream) == hipSuccess ? d : nullptr;
+    };
+    const float* d_rad = radiance_in;
+    const float* d_pos = position;
+    const float* d_nrm = normal;
+    const float* d_alb = demod ? albedo : nullptr;
+    const int* d_ids = ids;
+    if (in_host) {
+        d_rad = (const float*)stage_in(radiance_in, px * 12);
+        if (filter) {
+            d_pos = (const float*)stage_in(position, px * 12);
+            d_nrm = (const float*)stage_in(normal, px * 12);
+            if (demod) d_alb = (const float*)stage_in(albedo, px * 12);
+            d_ids = (const int*)stage_in(ids, px * 12);
+        }
+        if (!d_rad || (filter && (!d_pos || !d_nrm || !d_ids || (demod && !d_alb)))) return fail(FF_ERR_HIP, "ff_denoise: staging the inputs failed");
+    }
+    unsigned char* d_rgb8 = rgb_host ? (unsigned char*)c.carve(px * 3) : (unsigned char*)rgb8;
+    float* d_out = out_host ? (float*)c.carve(px * 12) : radiance_out;
+    DenoiseBuffers b;
+    b.width = width;
+    b.height = height;
+    b.guide_pos = b.guide_nrm = b.color[0] = b.color[1] = nullptr;
+    int src = -1;
+    if (filter) {
+        const int st = ensure_bytes((void**)&s->d_dn_work, &s->dn_work_bytes, 4 * px * sizeof(float4));
+        if (st != FF_OK) return st;
+        b.guide_pos = s->d_dn_work;
+        b.guide_nrm = s->d_dn_work + px;
+        b.color[0] = s->d_dn_work + 2 * px;
+        b.color[1] = s->d_dn_work + 3 * px;
+        FF_HIP(launch_denoise_pack(b, d_rad, d_pos, d_nrm, d_alb, d_ids, demod, stream));
+        src = 0;
+        const int same = (dn->flags & FF_DENOISE_SAME_GEOMETRY) ? 1 : 0;
+        for (int i = 0; i < dn->iterations; ++i) {
+            const double sigma_i = (double)dn->sigma_color * std::ldexp(1.0, -i); // halved every pass
+            FF_HIP(launch_denoise_pass(b, src, i, (float)(1.0 / (sigma_i * sigma_i)), (float)(1.0 / (double)dn->sigma_normal),
+                                       dn->sigma_plane * dn->sigma_plane, same, stream));
+            src = 1 - src;
+        }
+    }
+    FF_HIP(launch_denoise_finish(b, src, d_rad, d_alb, demod, d_rgb8, d_out, stream));
+    FF_HIP(hipStreamSynchronize(stream));
+    if (rgb_host) FF_HIP(hipMemcpy(rgb8, d_rgb8, px * 3, hipMemcpyDeviceToHost));
+    if (out_host) FF_HIP(hipMemcpy(radiance_out, d_out, px * 12, hipMemcpyDeviceToHost));
+    return FF_OK;
 }
 
 // ---- measurement ---------------------------------------------------------------------------------------------------

@@ -99,6 +99,14 @@ struct FfState {
     float* d_mean = nullptr;
     size_t mean_bytes = 0;
     int accum_width = 0, accum_height = 0, accum_frames = 0;
+    // G-buffer and denoiser (ff_gbuffer / ff_denoise, ff_denoise.hip): ff_gbuffer's own primary hits ([3][pix_items] float4, never
+    // the frame's d_primary_cache), staging for host buffers, the filter's packed guides and its two colour buffers
+    float4* d_gb_hits = nullptr;
+    size_t gb_hits_bytes = 0;
+    void* d_img_stage = nullptr;
+    size_t img_stage_bytes = 0;
+    float4* d_dn_work = nullptr; // 4 float4 per pixel: guide_pos, guide_nrm, colour 0, colour 1
+    size_t dn_work_bytes = 0;
     unsigned* d_queue = nullptr;               // work-queue counter: lives right behind the counters (one memset clears both)
     unsigned long long* d_counters = nullptr;  // 28 counters + 4 queue words
     unsigned long long* h_counters = nullptr;  // pinned mirror for the per-frame read-back

@@ -26,6 +26,7 @@ EXPORTS = [
     "ff_dist_unique_id", "ff_dist_init", "ff_dist_available", "ff_dist_shutdown", "ff_dist_strip_rows", "ff_dist_strip_rows_for", "ff_dist_part_bytes", "ff_render_distributed", "ff_debug_dist_fail_rank",
     "ff_multi_create", "ff_multi_destroy", "ff_multi_count", "ff_multi_state", "ff_multi_uses_rccl", "ff_multi_upload_scene",
     "ff_multi_render", "ff_multi_render_to_pbo", "ff_multi_stats",
+    "ff_gbuffer", "ff_denoise_params_init", "ff_denoise",
 ]
 DIST_ID_BYTES = 128
 
@@ -143,6 +144,10 @@ def load():
     lib.ff_multi_render.argtypes = [vp, P(T.FfCamera), P(T.FfRenderParams), i32, vp, i32, vp, i32]
     lib.ff_multi_render_to_pbo.argtypes = [vp, P(T.FfCamera), P(T.FfRenderParams), i32]
     lib.ff_multi_stats.argtypes = [vp, P(T.FfStats)]
+    lib.ff_gbuffer.argtypes = [vp, P(T.FfCamera), P(T.FfRenderParams), vp, vp, vp, vp, vp, i32]
+    lib.ff_denoise_params_init.argtypes = [P(T.FfDenoiseParams)]
+    lib.ff_denoise_params_init.restype = None
+    lib.ff_denoise.argtypes = [vp, i32, i32, P(T.FfDenoiseParams), vp, vp, vp, vp, vp, i32, vp, i32, vp, i32]
     _lib = real
     return real
 
@@ -217,6 +222,21 @@ def scene_info(scene):
 def render_params(width, height, bounces=1, spp=1, seed=1234, trace_mode=T.TRACE_BVH, shade_mode=T.SHADE_DIFFUSE_PATH,
                   grid_mode=T.GRID_FULL, spp_per_launch=0):
     return T.FfRenderParams(width, height, bounces, spp, seed, trace_mode, shade_mode, grid_mode, spp_per_launch)
+
+
+def denoise_params(**overrides):
+    """ff_denoise_params_init's defaults with the given fields replaced (iterations, sigma_color, sigma_normal, sigma_plane, flags)."""
+    dn = T.FfDenoiseParams()
+    load().ff_denoise_params_init(C.byref(dn))
+    for name, value in overrides.items():
+        if name not in dict(T.FfDenoiseParams._fields_):
+            raise TypeError(f"FfDenoiseParams has no field {name!r}")
+        setattr(dn, name, value)
+    return dn
+
+
+GBUFFER_CHANNELS = (("depth", np.float32, ()), ("position", np.float32, (3,)), ("normal", np.float32, (3,)), ("albedo", np.float32, (3,)),
+                    ("ids", np.int32, (3,)))
 
 
 class Tracer:
@@ -358,6 +378,38 @@ class Tracer:
         check(self._lib.ff_render(self._state, C.byref(camera), C.byref(params),
                                   C.c_void_p(rgb8_ptr) if rgb8_ptr else None, 1,
                                   C.c_void_p(radiance_ptr) if radiance_ptr else None, 1))
+
+    def gbuffer(self, camera, params):
+        """What every pixel's primary ray hits (ff_gbuffer) -> dict of numpy arrays: depth [H,W] float32, position / normal / albedo
+        [H,W,3] float32, ids [H,W,3] int32 (geometry, triangle, bxdf type; -1 on a miss)."""
+        h, w = params.height, params.width
+        out = {name: np.zeros((h, w) + shape, dtype=dt) for name, dt, shape in GBUFFER_CHANNELS}
+        check(self._lib.ff_gbuffer(self._state, C.byref(camera), C.byref(params), *(out[name].ctypes.data for name, _, _ in GBUFFER_CHANNELS), 0))
+        return out
+
+    def gbuffer_device(self, camera, params, depth_ptr=None, position_ptr=None, normal_ptr=None, albedo_ptr=None, ids_ptr=None):
+        """ff_gbuffer into caller-owned DEVICE buffers (raw pointers; any may be None)."""
+        ptrs = [C.c_void_p(p) if p else None for p in (depth_ptr, position_ptr, normal_ptr, albedo_ptr, ids_ptr)]
+        check(self._lib.ff_gbuffer(self._state, C.byref(camera), C.byref(params), *ptrs, 1))
+
+    def denoise(self, radiance, gbuffer, dn=None):
+        """ff_denoise of host radiance [H,W,3] guided by a gbuffer() dict -> (rgb8 [H,W,3] uint8, radiance [H,W,3] float32)."""
+        rad = np.ascontiguousarray(radiance, dtype=np.float32)
+        h, w = rad.shape[:2]
+        dn = dn if dn is not None else denoise_params()
+        g = {k: np.ascontiguousarray(gbuffer[k], dtype=np.int32 if k == "ids" else np.float32) for k in ("position", "normal", "albedo", "ids")}
+        rgb8 = np.zeros((h, w, 3), dtype=np.uint8)
+        out = np.zeros((h, w, 3), dtype=np.float32)
+        check(self._lib.ff_denoise(self._state, w, h, C.byref(dn), rad.ctypes.data, g["position"].ctypes.data, g["normal"].ctypes.data,
+                                   g["albedo"].ctypes.data, g["ids"].ctypes.data, 0, rgb8.ctypes.data, 0, out.ctypes.data, 0))
+        return rgb8, out
+
+    def denoise_device(self, width, height, radiance_ptr, position_ptr, normal_ptr, albedo_ptr, ids_ptr, dn=None, rgb8_ptr=None, radiance_out_ptr=None):
+        """ff_denoise on DEVICE buffers (raw pointers); radiance_out_ptr may equal radiance_ptr."""
+        dn = dn if dn is not None else denoise_params()
+        vp = lambda p: C.c_void_p(p) if p else None  # noqa: E731
+        check(self._lib.ff_denoise(self._state, width, height, C.byref(dn), vp(radiance_ptr), vp(position_ptr), vp(normal_ptr), vp(albedo_ptr),
+                                   vp(ids_ptr), 1, vp(rgb8_ptr), 1, vp(radiance_out_ptr), 1))
 
     def strips_local_rows(self, height, strip_rows, part, num_parts):
         return self._lib.ff_strips_local_rows(height, strip_rows, part, num_parts)

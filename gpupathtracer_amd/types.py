@@ -119,6 +119,14 @@ class FfBuildStats(C.Structure):
     ]
 
 
+class FfDenoiseParams(C.Structure):
+    _fields_ = [
+        ("iterations", C.c_int32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_plane", C.c_float), ("flags", C.c_int32),
+    ]
+
+
+DENOISE_SAME_GEOMETRY, DENOISE_DEMODULATE_ALBEDO = 1, 2
+
 BUILD_HOST_SAH, BUILD_GPU_LBVH, BUILD_GPU_PLOC = 0, 1, 2
 UPDATE_REFIT, UPDATE_REBUILD = 0, 1
 

@@ -267,6 +267,51 @@ FF_API int ff_render_progressive(FfState* state, const FfCamera* camera, const F
 /* The same into the registered pixel buffer (the per-frame block of kernel.cu:335-344). */
 FF_API int ff_render_to_pbo_progressive(FfState* state, const FfCamera* camera, const FfRenderParams* params, int frame_index);
 
+/* ---- G-buffer and denoiser (no counterpart in the reference) ----------------------------- */
+
+/* What every pixel's primary ray (kernel.cu:197-205) hits: I = intersectRays (kernel.cu:127-176) for that ray, the FfIntersect
+ * of ff_intersect_rays bit for bit.  Buffers are row-major, top row first; any may be NULL; on_device as ff_render's flags.
+ *   depth     W*H   floats  I.m_t (world distance)                                   miss: 0
+ *   position  W*H*3 floats  I.m_intersectionPoint                                    miss: 0
+ *   normal    W*H*3 floats  I.m_normal: the signed world normal NORMAL_DEBUG shades, in every shade mode (not the interpolated
+ *                           normal of SMOOTH mode); not renormalised after the inverse-transpose      miss: 0
+ *   albedo    W*H*3 floats  emitter m_emissiveColor * m_intensity, mirror m_specularColor, glass m_transmittanceColor,
+ *                           anything else m_albedo                                   miss: 0
+ *   ids       W*H*3 int32   {I.geometryIndex (caller's order), I.triangleIndex (-1 for planes and spheres), bxdf type}
+ *                                                                                    miss: {-1, -1, -1}
+ * Only the camera, the scene, width, height and grid_mode matter (FF_GRID_REFERENCE_FLOOR: untraced pixels read as misses);
+ * spp, bounces, seed, trace_mode, shade_mode and spp_per_launch do not change a bit.  When the state still holds the last
+ * frame's primary hits for this camera and pixel mapping (a camera at rest), they are resolved without a traversal; otherwise
+ * the call traces the primary rays into a buffer of its own.  It leaves the state's stored hits, "camera at rest" test and
+ * FfStats as they were: it is not a frame.  FF_ERR_UNSUPPORTED for a tree too deep for BVH rendering. */
+FF_API int ff_gbuffer(FfState* state, const FfCamera* camera, const FfRenderParams* params,
+                      float* depth, float* position, float* normal, float* albedo, int32_t* ids, int on_device);
+
+/* Defaults (DESIGN.md section 10 measured them): 5 passes, sigma_color 4, sigma_normal 0.1, sigma_plane 0.1, both flags. */
+FF_API void ff_denoise_params_init(FfDenoiseParams* p);
+
+/* Edge-avoiding à-trous filter (Dammertz et al. 2010) of W x H float3 radiance (e.g. ff_render's or ff_render_progressive's mean),
+ * guided by a G-buffer of ff_gbuffer (position, normal, ids; albedo with FF_DENOISE_DEMODULATE_ALBEDO, else it may be NULL).
+ * A pure image operation: the scene is not read.
+ *   filterable pixel: a hit whose bxdf is not emitter, mirror or glass.  Every other pixel is copied through bit for bit and
+ *                     weighs 0 as a tap.
+ *   c               = radiance / albedo per channel (DEMODULATE_ALBEDO; channels with albedo <= 0 undivided), else radiance
+ *   pass i          : c'_p = sum_q w c_q / sum_q w over the 5x5 taps q = p + 2^i (dx, dy), dx, dy in -2..2,
+ *                     w = h(dx) h(dy) w_c w_n w_x,  h = (1/16, 1/4, 3/8, 1/4, 1/16);  the centre tap weighs h(0)^2
+ *                     w_c = exp(-|c_p - c_q|^2 / (sigma_i^2 (|c_p|^2 + 1e-30))),  sigma_i = sigma_color 2^-i
+ *                     w_n = exp(-(1 - n_p . n_q) / sigma_normal)          (n: the G-buffer normal made unit length)
+ *                     w_x = exp(-(n_p . (x_q - x_p))^2 / (sigma_plane^2 |x_q - x_p|^2 + 1e-30))
+ *                     taps outside the image, not filterable, (FF_DENOISE_SAME_GEOMETRY) on another geometry or with
+ *                     w_c w_n w_x < e^-30 weigh 0
+ *   output          = c * albedo after the last pass (where it was divided); rgb8 = trunc(clamp(v * 255)) as ff_render's.
+ * iterations = 0 copies every pixel through.  Scaling all radiance by k scales the output by k.  rgb8 (W*H*3 bytes) and
+ * radiance_out (W*H*3 floats) may each be NULL; radiance_out may alias radiance_in.  Synchronous; FfStats keeps describing
+ * the last frame. */
+FF_API int ff_denoise(FfState* state, int width, int height, const FfDenoiseParams* dn,
+                      const float* radiance_in, const float* position, const float* normal,
+                      const float* albedo, const int32_t* ids, int inputs_on_device,
+                      void* rgb8, int rgb8_on_device, float* radiance_out, int radiance_out_on_device);
+
 /* saveToPPM (utilities.h:842-856) for the 8-bit framebuffer: P3 text, one "r g b" line per pixel, top row first. */
 FF_API int ff_save_ppm(const char* path, const unsigned char* rgb8, int width, int height);
 

@@ -222,6 +222,18 @@ typedef struct FfSceneInfo {
                                   SAH build and the insertion-based optimisation pass reduce */
 } FfSceneInfo;
 
+/* ff_denoise: edge-avoiding à-trous filter guided by the G-buffer of ff_gbuffer (Dammertz et al. 2010, with albedo
+ * demodulation).  ff_denoise_params_init gives the defaults; the formulas are in ff_api.h. */
+#define FF_DENOISE_SAME_GEOMETRY      1 /* taps on another geometry weigh 0 */
+#define FF_DENOISE_DEMODULATE_ALBEDO  2 /* filter radiance / albedo and multiply back after the last pass */
+typedef struct FfDenoiseParams {
+    int32_t iterations;    /* à-trous passes, step 2^i for pass i; 0 = copy through; at most 10 */
+    float   sigma_color;   /* colour edge-stop, relative to the pixel's own magnitude; halved every pass (> 0) */
+    float   sigma_normal;  /* normal edge-stop (> 0) */
+    float   sigma_plane;   /* distance of a tap from the pixel's tangent plane, relative to the tap's distance (> 0) */
+    int32_t flags;         /* FF_DENOISE_* bits */
+} FfDenoiseParams;
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif
