@@ -16,6 +16,7 @@
 
 #include "ff_denoise.h"
 #include "ff_state.h"
+#include "ff_temporal.h"
 
 using namespace ff;
 
@@ -833,6 +834,8 @@ int ff_destroy(FfState* s)
     if (s->d_gb_hits) (void)hipFree(s->d_gb_hits);
     if (s->d_img_stage) (void)hipFree(s->d_img_stage);
     if (s->d_dn_work) (void)hipFree(s->d_dn_work);
+    if (s->d_tp_work) (void)hipFree(s->d_tp_work);
+    if (s->d_tp_geoms) (void)hipFree(s->d_tp_geoms);
     free_build_scratch(s->scratch);
     if (s->d_blocksums) (void)hipFree(s->d_blocksums);
     if (s->d_rgb8) (void)hipFree(s->d_rgb8);
@@ -1020,6 +1023,7 @@ int ff_upload_scene(FfState* s, const FfGeometry* host_geometries, int n)
     clear_error();
     if (!s) return fail(FF_ERR_INVALID_ARG, "ff_upload_scene: state is null");
     s->primary_valid = s->last_key_valid = false; // (the stored primary hits belong to the scene that goes)
+    s->tp_valid = s->tp_last = false;             // (and so does the temporal history)
     const auto t_call = std::chrono::steady_clock::now();
     s->build_stats = FfBuildStats();
     const BvhBuildParams bp = default_bvh_params();
@@ -1135,6 +1139,7 @@ int upload_compiled_scene(FfState* s, const CompiledScene& cs, double build_ms)
 {
     const auto t_call = std::chrono::steady_clock::now();
     s->primary_valid = s->last_key_valid = false;
+    s->tp_valid = s->tp_last = false;
     s->build_stats = FfBuildStats();
     s->build_stats.build_ms = build_ms;
     const int st = upload_compiled(s, cs);
@@ -1208,6 +1213,7 @@ int ff_update_mesh(FfState* s, int geometry_index, const FfTriangle* triangles, 
     if (count != rec.tri_count || count <= 0) return fail(FF_ERR_INVALID_ARG, "ff_update_mesh: %d triangles, the uploaded mesh has %d", count, rec.tri_count);
     if (mode == FF_UPDATE_REBUILD && s->scene_builder == FF_BUILD_HOST_SAH)
         return fail(FF_ERR_UNSUPPORTED, "ff_update_mesh: rebuilding in place needs a scene uploaded with a device builder (host-built trees are packed)");
+    if ((size_t)geometry_index < s->tp_replaced.size()) s->tp_replaced[geometry_index] = 1; // (its temporal history restarts)
     const auto t_call = std::chrono::steady_clock::now();
     FfBuildStats& bs = s->build_stats;
     bs.copy_ms = bs.build_ms = 0.0;
@@ -1948,6 +1954,307 @@ int ff_denoise(FfState* s, int width, int height, const FfDenoiseParams* dn, con
     FF_HIP(hipStreamSynchronize(stream));
     if (rgb_host) FF_HIP(hipMemcpy(rgb8, d_rgb8, px * 3, hipMemcpyDeviceToHost));
     if (out_host) FF_HIP(hipMemcpy(radiance_out, d_out, px * 12, hipMemcpyDeviceToHost));
+    return FF_OK;
+}
+
+// ---- temporal denoiser (SVGF; kernels in ff_temporal.hip) ---------------------------------------------------------
+
+void ff_temporal_params_init(FfTemporalParams* p)
+{
+    if (!p) return;
+    // (the paper's values, with max_history chosen on the C2 scene's moving camera)
+    p->iterations = 5;
+    p->sigma_luminance = 4.0f;
+    p->sigma_normal = 0.1f;
+    p->sigma_plane = 0.1f;
+    p->flags = FF_DENOISE_SAME_GEOMETRY | FF_DENOISE_DEMODULATE_ALBEDO;
+    p->max_history = 16;
+    p->variance_history = 4;
+    p->feedback_pass = 0;
+    p->reuse_normal = 0.9f;
+    p->reuse_plane = 0.01f;
+}
+
+} // extern "C"
+
+namespace {
+
+// inverse of a 4x4 matrix in double (Gauss-Jordan with partial pivoting); column-major in and out.  False if singular.
+bool invert4(const double* m, double* out)
+{
+    double a[4][8];
+    for (int r = 0; r < 4; ++r)
+        for (int c = 0; c < 4; ++c) {
+            a[r][c] = m[c * 4 + r];
+            a[r][4 + c] = r == c ? 1.0 : 0.0;
+        }
+    for (int c = 0; c < 4; ++c) {
+        int piv = c;
+        for (int r = c + 1; r < 4; ++r)
+            if (std::fabs(a[r][c]) > std::fabs(a[piv][c])) piv = r;
+        if (a[piv][c] == 0.0) return false;
+        if (piv != c)
+            for (int k = 0; k < 8; ++k) std::swap(a[c][k], a[piv][k]);
+        const double d = a[c][c];
+        for (int k = 0; k < 8; ++k) a[c][k] /= d;
+        for (int r = 0; r < 4; ++r) {
+            if (r == c || a[r][c] == 0.0) continue;
+            const double f = a[r][c];
+            for (int k = 0; k < 8; ++k) a[r][k] -= f * a[c][k];
+        }
+    }
+    for (int r = 0; r < 4; ++r)
+        for (int c = 0; c < 4; ++c) out[c * 4 + r] = a[r][4 + c];
+    return true;
+}
+
+// the model matrix of a record as 12 floats (columns, xyz)
+void record_model(const GeomRecord& g, float* out12)
+{
+    const float* cols[4] = { g.mod_c0, g.mod_c1, g.mod_c2, g.mod_c3 };
+    for (int c = 0; c < 4; ++c)
+        for (int r = 0; r < 3; ++r) out12[c * 3 + r] = cols[c][r];
+}
+
+// The table row of one geometry: A = M_prev * inverse(M_cur) from the previous call's model matrix and this record's inverse model
+// matrix, composed in double; N = inverse(A)^T (3x3: the cofactors over the determinant).
+TemporalGeom temporal_row(const float* prev12, const GeomRecord& g, int flags)
+{
+    TemporalGeom row;
+    double A[3][4] = { { 1, 0, 0, 0 }, { 0, 1, 0, 0 }, { 0, 0, 1, 0 } };
+    if (flags & kTpMoved) {
+        const float* inv[4] = { g.inv_c0, g.inv_c1, g.inv_c2, g.inv_c3 };
+        for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 4; ++c) {
+                double v = c == 3 ? (double)prev12[9 + r] : 0.0;
+                for (int k = 0; k < 3; ++k) v += (double)prev12[k * 3 + r] * (double)inv[c][k];
+                A[r][c] = v;
+            }
+    }
+    double cof[3][3];
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) {
+            const int r1 = (r + 1) % 3, r2 = (r + 2) % 3, c1 = (c + 1) % 3, c2 = (c + 2) % 3;
+            cof[r][c] = A[r1][c1] * A[r2][c2] - A[r1][c2] * A[r2][c1];
+        }
+    const double det = A[0][0] * cof[0][0] + A[0][1] * cof[0][1] + A[0][2] * cof[0][2];
+    const double id = det != 0.0 ? 1.0 / det : 0.0;
+    for (int r = 0; r < 3; ++r) {
+        row.a[r] = make_float4((float)A[r][0], (float)A[r][1], (float)A[r][2], (float)A[r][3]);
+        row.n[r] = make_float4((float)(cof[r][0] * id), (float)(cof[r][1] * id), (float)(cof[r][2] * id), 0.f);
+    }
+    std::memcpy(&row.n[0].w, &flags, sizeof flags);
+    return row;
+}
+
+// ff_denoise_temporal's history and working buffers: 10 float4 and one float2 per pixel (ff_state.h)
+TemporalBuffers temporal_buffers(FfState* s, int width, int height)
+{
+    const size_t px = (size_t)width * (size_t)height;
+    TemporalBuffers b;
+    b.width = width;
+    b.height = height;
+    float4* base = s->d_tp_work;
+    for (int k = 0; k < 2; ++k) {
+        b.pos[k] = base + (4 * k + 0) * px;
+        b.nrm[k] = base + (4 * k + 1) * px;
+        b.col[k] = base + (4 * k + 2) * px;
+        b.mom[k] = base + (4 * k + 3) * px;
+        b.work[k] = base + (8 + k) * px;
+    }
+    b.motion = (float2*)(base + 10 * px);
+    return b;
+}
+
+} // namespace
+
+extern "C" {
+
+int ff_denoise_temporal(FfState* s, const FfCamera* camera, int width, int height, const FfTemporalParams* tp, const float* radiance_in,
+                        const float* position, const float* normal, const float* albedo, const int32_t* ids, int inputs_on_device, void* rgb8,
+                        int rgb8_on_device, float* radiance_out, int radiance_out_on_device)
+{
+    clear_error();
+    if (!s) return fail(FF_ERR_INVALID_ARG, "ff_denoise_temporal: state is null");
+    if (!camera) return fail(FF_ERR_INVALID_ARG, "ff_denoise_temporal: camera is null");
+    if (!tp) return fail(FF_ERR_INVALID_ARG, "ff_denoise_temporal: params are null");
+    if (width <= 0 || height <= 0 || width > 65535 || height > 65535)
+        return fail(FF_ERR_INVALID_ARG, "ff_denoise_temporal: image size %dx%d is invalid", width, height);
+    if (tp->iterations < 0 || tp->iterations > 10) return fail(FF_ERR_INVALID_ARG, "ff_denoise_temporal: iterations must be in 0..10 (got %d)", tp->iterations);
+    if (tp->feedback_pass < -1 || tp->feedback_pass >= tp->iterations)
+        return fail(FF_ERR_INVALID_ARG, "ff_denoise_temporal: feedback_pass must be in -1..iterations-1 (got %d)", tp->feedback_pass);
+    if (tp->max_history < 1) return fail(FF_ERR_INVALID_ARG, "ff_denoise_temporal: max_history must be at least 1 (got %d)", tp->max_history);
+    if (tp->variance_history < 1) return fail(FF_ERR_INVALID_ARG, "ff_denoise_temporal: variance_history must be at least 1 (got %d)", tp->variance_history);
+    if (!(tp->sigma_luminance > 0.f && tp->sigma_normal > 0.f && tp->sigma_plane > 0.f) || !std::isfinite(tp->sigma_luminance) ||
+        !std::isfinite(tp->sigma_normal) || !std::isfinite(tp->sigma_plane))
+        return fail(FF_ERR_INVALID_ARG, "ff_denoise_temporal: the sigmas must be positive and finite");
+    if (!std::isfinite(tp->reuse_normal) || !(tp->reuse_plane >= 0.f) || !std::isfinite(tp->reuse_plane))
+        return fail(FF_ERR_INVALID_ARG, "ff_denoise_temporal: reuse_normal must be finite and reuse_plane finite and >= 0");
+    if (tp->flags & ~(FF_DENOISE_SAME_GEOMETRY | FF_DENOISE_DEMODULATE_ALBEDO))
+        return fail(FF_ERR_INVALID_ARG, "ff_denoise_temporal: unknown flags 0x%x", tp->flags);
+    const int demod = (tp->flags & FF_DENOISE_DEMODULATE_ALBEDO) ? 1 : 0;
+    if (!radiance_in || !position || !normal || !ids || (demod && !albedo))
+        return fail(FF_ERR_INVALID_ARG, "ff_denoise_temporal: radiance, position, normal and ids are required (and albedo with FF_DENOISE_DEMODULATE_ALBEDO)");
+    if (!s->has_scene) return fail(FF_ERR_NO_SCENE, "ff_denoise_temporal: no scene uploaded (the history follows its geometries)");
+    FF_HIP(hipSetDevice(s->device));
+    const size_t px = (size_t)width * (size_t)height;
+    // host buffers are staged, as in ff_denoise
+    const bool in_host = !inputs_on_device, rgb_host = rgb8 && !rgb8_on_device, out_host = radiance_out && !radiance_out_on_device;
+    const size_t need = (in_host ? padded(px * 12) * (4 + demod) : 0) + (rgb_host ? padded(px * 3) : 0) + (out_host ? padded(px * 12) : 0);
+    if (need > 0) {
+        const int st = ensure_bytes(&s->d_img_stage, &s->img_stage_bytes, need);
+        if (st != FF_OK) return st;
+    }
+    Carver c = { (char*)s->d_img_stage, 0 };
+    hipStream_t stream = s->stream;
+    auto stage_in = [&](const void* host, size_t bytes) -> const void* {
+        void* d = c.carve(bytes);
+        return hipMemcpyAsync(d, host, bytes, hipMemcpyHostToDevice, stream) == hipSuccess ? d : nullptr;
+    };
+    const float* d_rad = radiance_in;
+    const float* d_pos = position;
+    const float* d_nrm = normal;
+    const float* d_alb = demod ? albedo : nullptr;
+    const int* d_ids = ids;
+    if (in_host) {
+        d_rad = (const float*)stage_in(radiance_in, px * 12);
+        d_pos = (const float*)stage_in(position, px * 12);
+        d_nrm = (const float*)stage_in(normal, px * 12);
+        if (demod) d_alb = (const float*)stage_in(albedo, px * 12);
+        d_ids = (const int*)stage_in(ids, px * 12);
+        if (!d_rad || !d_pos || !d_nrm || !d_ids || (demod && !d_alb)) return fail(FF_ERR_HIP, "ff_denoise_temporal: staging the inputs failed");
+    }
+    unsigned char* d_rgb8 = rgb_host ? (unsigned char*)c.carve(px * 3) : (unsigned char*)rgb8;
+    float* d_out = out_host ? (float*)c.carve(px * 12) : radiance_out;
+    // history: kept only for the same image size (a new size, a reset or a new scene start afresh)
+    const bool has_history = s->tp_valid && width == s->tp_width && height == s->tp_height;
+    s->tp_valid = s->tp_last = false; // (from here on the history sets are being rewritten)
+    int st = ensure_bytes((void**)&s->d_tp_work, &s->tp_work_bytes, 10 * px * sizeof(float4) + px * sizeof(float2));
+    if (st != FF_OK) return st;
+    const TemporalBuffers b = temporal_buffers(s, width, height);
+    TemporalReproject r;
+    std::memset(&r, 0, sizeof r);
+    r.cur = has_history ? 1 - s->tp_cur : 0;
+    r.has_history = has_history ? 1 : 0;
+    // the per-geometry table, indexed by the caller's geometry index
+    int num = 0;
+    for (const GeomRecord& g : s->h_geoms) num = std::max(num, g.orig_index + 1);
+    s->h_tp_geoms.assign((size_t)num * sizeof(TemporalGeom), 0);
+    TemporalGeom* rows = (TemporalGeom*)s->h_tp_geoms.data();
+    for (const GeomRecord& g : s->h_geoms) {
+        const int o = g.orig_index;
+        if (o < 0) continue;
+        float cur12[12];
+        record_model(g, cur12);
+        int flags = 0;
+        const float* prev12 = cur12;
+        if (has_history && (size_t)o < s->tp_has_model.size() && s->tp_has_model[o]) {
+            prev12 = &s->tp_model[(size_t)o * 12];
+            if (std::memcmp(prev12, cur12, sizeof cur12) != 0) flags |= kTpMoved;
+        }
+        if ((size_t)o < s->tp_replaced.size() && s->tp_replaced[o]) flags |= kTpReplaced;
+        rows[o] = temporal_row(prev12, g, flags);
+    }
+    r.num_geoms = num;
+    if (num > 0) {
+        st = ensure_bytes(&s->d_tp_geoms, &s->tp_geoms_bytes, s->h_tp_geoms.size());
+        if (st != FF_OK) return st;
+        FF_HIP(hipMemcpyAsync(s->d_tp_geoms, s->h_tp_geoms.data(), s->h_tp_geoms.size(), hipMemcpyHostToDevice, stream));
+    }
+    r.geoms = (const TemporalGeom*)s->d_tp_geoms;
+    if (has_history) {
+        r.at_rest = std::memcmp(camera, &s->tp_camera, sizeof(FfCamera)) == 0 ? 1 : 0;
+        FfMat4 cm;
+        ff_camera_ray_matrix(&s->tp_camera, &cm);
+        double m[16], inv[16];
+        for (int k = 0; k < 16; ++k) m[k] = cm.m[k];
+        if (!invert4(m, inv)) return fail(FF_ERR_INVALID_ARG, "ff_denoise_temporal: the previous camera's ray matrix is singular");
+        for (int k = 0; k < 16; ++k) r.proj[k] = (float)inv[k];
+        r.eye[0] = s->tp_camera.m_position.x;
+        r.eye[1] = s->tp_camera.m_position.y;
+        r.eye[2] = s->tp_camera.m_position.z;
+        r.screen_w = s->tp_camera.m_screenWidth;
+        r.screen_h = s->tp_camera.m_screenHeight;
+    }
+    r.reuse_normal = tp->reuse_normal;
+    r.reuse_plane = tp->reuse_plane;
+    r.max_history = (float)tp->max_history;
+    r.variance_history = (float)tp->variance_history;
+    r.demodulate = demod;
+    r.feedback_unfiltered = tp->feedback_pass < 0 ? 1 : 0;
+    FF_HIP(launch_temporal_reproject(b, r, d_rad, d_pos, d_nrm, d_alb, d_ids, stream));
+    int src = 0;
+    if (tp->iterations > 0) {
+        const float inv_sigma_normal = (float)(1.0 / (double)tp->sigma_normal), sigma_plane2 = tp->sigma_plane * tp->sigma_plane;
+        FF_HIP(launch_temporal_variance(b, r.cur, r.variance_history, inv_sigma_normal, sigma_plane2, stream));
+        const int same = (tp->flags & FF_DENOISE_SAME_GEOMETRY) ? 1 : 0;
+        for (int i = 0; i < tp->iterations; ++i) {
+            FF_HIP(launch_temporal_pass(b, r.cur, src, i, tp->sigma_luminance, inv_sigma_normal, sigma_plane2, same,
+                                        i == tp->feedback_pass ? b.col[r.cur] : nullptr, stream));
+            src = 1 - src;
+        }
+    }
+    // output: ff_denoise's finish on the last colour buffer (the class in the guide's w decides what is copied through)
+    DenoiseBuffers fb;
+    fb.width = width;
+    fb.height = height;
+    fb.guide_pos = b.pos[r.cur];
+    fb.guide_nrm = b.nrm[r.cur];
+    fb.color[0] = b.work[src];
+    fb.color[1] = b.work[1 - src];
+    FF_HIP(launch_denoise_finish(fb, 0, d_rad, d_alb, demod, d_rgb8, d_out, stream));
+    FF_HIP(hipStreamSynchronize(stream));
+    // the history now describes this call
+    s->tp_valid = s->tp_last = true;
+    s->tp_cur = r.cur;
+    s->tp_width = width;
+    s->tp_height = height;
+    s->tp_camera = *camera;
+    s->tp_model.assign((size_t)num * 12, 0.f);
+    s->tp_has_model.assign((size_t)num, 0);
+    for (const GeomRecord& g : s->h_geoms) {
+        if (g.orig_index < 0) continue;
+        record_model(g, &s->tp_model[(size_t)g.orig_index * 12]);
+        s->tp_has_model[g.orig_index] = 1;
+    }
+    s->tp_replaced.assign((size_t)num, 0);
+    if (rgb_host) FF_HIP(hipMemcpy(rgb8, d_rgb8, px * 3, hipMemcpyDeviceToHost));
+    if (out_host) FF_HIP(hipMemcpy(radiance_out, d_out, px * 12, hipMemcpyDeviceToHost));
+    return FF_OK;
+}
+
+int ff_temporal_reset(FfState* s)
+{
+    clear_error();
+    if (!s) return fail(FF_ERR_INVALID_ARG, "ff_temporal_reset: state is null");
+    s->tp_valid = s->tp_last = false;
+    return FF_OK;
+}
+
+int ff_temporal_history(FfState* s, float* motion, float* length, int on_device)
+{
+    clear_error();
+    if (!s) return fail(FF_ERR_INVALID_ARG, "ff_temporal_history: state is null");
+    if (!s->tp_last) return fail(FF_ERR_INVALID_ARG, "ff_temporal_history: no ff_denoise_temporal call since the last reset");
+    if (!motion && !length) return FF_OK;
+    FF_HIP(hipSetDevice(s->device));
+    const size_t px = (size_t)s->tp_width * (size_t)s->tp_height;
+    const TemporalBuffers b = temporal_buffers(s, s->tp_width, s->tp_height);
+    float* d_motion = motion;
+    float* d_length = length;
+    if (!on_device) {
+        const int st = ensure_bytes(&s->d_img_stage, &s->img_stage_bytes, padded(px * 8) + padded(px * 4));
+        if (st != FF_OK) return st;
+        Carver c = { (char*)s->d_img_stage, 0 };
+        d_motion = motion ? (float*)c.carve(px * 8) : nullptr;
+        d_length = length ? (float*)c.carve(px * 4) : nullptr;
+    }
+    FF_HIP(launch_temporal_history(b, s->tp_cur, d_motion, d_length, s->stream));
+    FF_HIP(hipStreamSynchronize(s->stream));
+    if (!on_device) {
+        if (motion) FF_HIP(hipMemcpy(motion, d_motion, px * 8, hipMemcpyDeviceToHost));
+        if (length) FF_HIP(hipMemcpy(length, d_length, px * 4, hipMemcpyDeviceToHost));
+    }
     return FF_OK;
 }
 

@@ -107,6 +107,21 @@ struct FfState {
     size_t img_stage_bytes = 0;
     float4* d_dn_work = nullptr; // 4 float4 per pixel: guide_pos, guide_nrm, colour 0, colour 1
     size_t dn_work_bytes = 0;
+    // temporal denoiser (ff_denoise_temporal, ff_temporal.hip): two history sets of 4 float4 per pixel (guide position and class,
+    // unit normal, colour history, moments {l, l^2, len}) that swap by index, then the two working colour buffers and the motion
+    // (float2 per pixel).  tp_cur: the set the last call wrote.  The history describes the camera, image size and per-geometry
+    // model matrices (caller's order) of that call; tp_replaced marks the meshes ff_update_mesh changed since.
+    float4* d_tp_work = nullptr;
+    size_t tp_work_bytes = 0;
+    void* d_tp_geoms = nullptr; // the per-geometry table (ff::TemporalGeom rows)
+    size_t tp_geoms_bytes = 0;
+    std::vector<unsigned char> h_tp_geoms; // its host copy (kept alive until the upload has completed)
+    bool tp_valid = false;                  // history to reproject from
+    bool tp_last = false;                   // a call's motion and lengths are there to read (ff_temporal_history)
+    int tp_cur = 0, tp_width = 0, tp_height = 0;
+    FfCamera tp_camera = {};
+    std::vector<float> tp_model;            // 12 floats (model matrix columns, xyz) per caller geometry index
+    std::vector<unsigned char> tp_has_model, tp_replaced;
     unsigned* d_queue = nullptr;               // work-queue counter: lives right behind the counters (one memset clears both)
     unsigned long long* d_counters = nullptr;  // 28 counters + 4 queue words
     unsigned long long* h_counters = nullptr;  // pinned mirror for the per-frame read-back

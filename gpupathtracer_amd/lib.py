@@ -27,6 +27,7 @@ EXPORTS = [
     "ff_multi_create", "ff_multi_destroy", "ff_multi_count", "ff_multi_state", "ff_multi_uses_rccl", "ff_multi_upload_scene",
     "ff_multi_render", "ff_multi_render_to_pbo", "ff_multi_stats",
     "ff_gbuffer", "ff_denoise_params_init", "ff_denoise",
+    "ff_temporal_params_init", "ff_denoise_temporal", "ff_temporal_reset", "ff_temporal_history",
 ]
 DIST_ID_BYTES = 128
 
@@ -148,6 +149,11 @@ def load():
     lib.ff_denoise_params_init.argtypes = [P(T.FfDenoiseParams)]
     lib.ff_denoise_params_init.restype = None
     lib.ff_denoise.argtypes = [vp, i32, i32, P(T.FfDenoiseParams), vp, vp, vp, vp, vp, i32, vp, i32, vp, i32]
+    lib.ff_temporal_params_init.argtypes = [P(T.FfTemporalParams)]
+    lib.ff_temporal_params_init.restype = None
+    lib.ff_denoise_temporal.argtypes = [vp, P(T.FfCamera), i32, i32, P(T.FfTemporalParams), vp, vp, vp, vp, vp, i32, vp, i32, vp, i32]
+    lib.ff_temporal_reset.argtypes = [vp]
+    lib.ff_temporal_history.argtypes = [vp, vp, vp, i32]
     _lib = real
     return real
 
@@ -233,6 +239,17 @@ def denoise_params(**overrides):
             raise TypeError(f"FfDenoiseParams has no field {name!r}")
         setattr(dn, name, value)
     return dn
+
+
+def temporal_params(**overrides):
+    """ff_temporal_params_init's defaults with the given fields replaced (any FfTemporalParams field)."""
+    tp = T.FfTemporalParams()
+    load().ff_temporal_params_init(C.byref(tp))
+    for name, value in overrides.items():
+        if name not in dict(T.FfTemporalParams._fields_):
+            raise TypeError(f"FfTemporalParams has no field {name!r}")
+        setattr(tp, name, value)
+    return tp
 
 
 GBUFFER_CHANNELS = (("depth", np.float32, ()), ("position", np.float32, (3,)), ("normal", np.float32, (3,)), ("albedo", np.float32, (3,)),
@@ -410,6 +427,44 @@ class Tracer:
         vp = lambda p: C.c_void_p(p) if p else None  # noqa: E731
         check(self._lib.ff_denoise(self._state, width, height, C.byref(dn), vp(radiance_ptr), vp(position_ptr), vp(normal_ptr), vp(albedo_ptr),
                                    vp(ids_ptr), 1, vp(rgb8_ptr), 1, vp(radiance_out_ptr), 1))
+
+    def denoise_temporal(self, radiance, gbuffer, camera, tp=None):
+        """ff_denoise_temporal of this frame's host radiance [H,W,3] guided by gbuffer() of `camera`; the history stays in the state
+        -> (rgb8 [H,W,3] uint8, radiance [H,W,3] float32)."""
+        rad = np.ascontiguousarray(radiance, dtype=np.float32)
+        h, w = rad.shape[:2]
+        if rad.shape != (h, w, 3) or any(np.shape(gbuffer[k])[:2] != (h, w) for k in ("position", "normal", "albedo", "ids")):
+            raise ValueError("denoise_temporal: radiance must be [H,W,3] and the G-buffer of the same size")
+        tp = tp if tp is not None else temporal_params()
+        g = {k: np.ascontiguousarray(gbuffer[k], dtype=np.int32 if k == "ids" else np.float32) for k in ("position", "normal", "albedo", "ids")}
+        rgb8 = np.zeros((h, w, 3), dtype=np.uint8)
+        out = np.zeros((h, w, 3), dtype=np.float32)
+        check(self._lib.ff_denoise_temporal(self._state, C.byref(camera), w, h, C.byref(tp), rad.ctypes.data, g["position"].ctypes.data,
+                                            g["normal"].ctypes.data, g["albedo"].ctypes.data, g["ids"].ctypes.data, 0, rgb8.ctypes.data, 0,
+                                            out.ctypes.data, 0))
+        self._temporal_size = (h, w)
+        return rgb8, out
+
+    def denoise_temporal_device(self, camera, width, height, radiance_ptr, position_ptr, normal_ptr, albedo_ptr, ids_ptr, tp=None, rgb8_ptr=None,
+                                radiance_out_ptr=None):
+        """ff_denoise_temporal on DEVICE buffers (raw pointers); radiance_out_ptr may equal radiance_ptr."""
+        tp = tp if tp is not None else temporal_params()
+        vp = lambda p: C.c_void_p(p) if p else None  # noqa: E731
+        check(self._lib.ff_denoise_temporal(self._state, C.byref(camera), width, height, C.byref(tp), vp(radiance_ptr), vp(position_ptr),
+                                            vp(normal_ptr), vp(albedo_ptr), vp(ids_ptr), 1, vp(rgb8_ptr), 1, vp(radiance_out_ptr), 1))
+        self._temporal_size = (height, width)
+
+    def temporal_reset(self):
+        """Drop the temporal history (ff_temporal_reset)."""
+        check(self._lib.ff_temporal_reset(self._state))
+
+    def temporal_history(self):
+        """The last denoise_temporal call's (motion [H,W,2] float32, history length [H,W] float32)."""
+        h, w = getattr(self, "_temporal_size", (0, 0))
+        motion = np.zeros((h, w, 2), dtype=np.float32)
+        length = np.zeros((h, w), dtype=np.float32)
+        check(self._lib.ff_temporal_history(self._state, motion.ctypes.data if h * w else None, length.ctypes.data if h * w else None, 0))
+        return motion, length
 
     def strips_local_rows(self, height, strip_rows, part, num_parts):
         return self._lib.ff_strips_local_rows(height, strip_rows, part, num_parts)

@@ -127,6 +127,17 @@ class FfDenoiseParams(C.Structure):
 
 DENOISE_SAME_GEOMETRY, DENOISE_DEMODULATE_ALBEDO = 1, 2
 
+
+class FfTemporalParams(C.Structure):
+    _fields_ = [
+        ("iterations", C.c_int32), ("sigma_luminance", C.c_float), ("sigma_normal", C.c_float), ("sigma_plane", C.c_float), ("flags", C.c_int32),
+        ("max_history", C.c_int32), ("variance_history", C.c_int32), ("feedback_pass", C.c_int32), ("reuse_normal", C.c_float),
+        ("reuse_plane", C.c_float),
+    ]
+
+
+TEMPORAL_PARAMS_BYTES = 40
+
 BUILD_HOST_SAH, BUILD_GPU_LBVH, BUILD_GPU_PLOC = 0, 1, 2
 UPDATE_REFIT, UPDATE_REBUILD = 0, 1
 

@@ -312,6 +312,56 @@ FF_API int ff_denoise(FfState* state, int width, int height, const FfDenoisePara
                       const float* albedo, const int32_t* ids, int inputs_on_device,
                       void* rgb8, int rgb8_on_device, float* radiance_out, int radiance_out_on_device);
 
+/* ---- temporal denoiser (SVGF: Schied et al., HPG 2017) ---------------------------------------- */
+
+/* Defaults: 5 passes, sigma_luminance 4, sigma_normal 0.1, sigma_plane 0.1, both flags, max_history 16, variance_history 4,
+ * feedback after pass 0, reuse_normal 0.9, reuse_plane 0.01 (DESIGN.md section 8 row 6 records what was measured). */
+FF_API void ff_temporal_params_init(FfTemporalParams* p);
+
+/* Spatiotemporal variance-guided filter of a moving camera's 1-spp frames.  radiance_in is THIS frame's own samples (ff_render's
+ * radiance, not a progressive mean); position, normal, albedo and ids are ff_gbuffer's for `camera` (albedo may be NULL without
+ * FF_DENOISE_DEMODULATE_ALBEDO).  The state keeps the history from call to call: the previous camera, guides, colour, moments,
+ * history length and per-geometry model matrices.  Filterable pixels and the demodulated colour c are as in ff_denoise; every
+ * other pixel is copied through bit for bit and has length 0.  Per filterable pixel p at (x, y) of geometry g:
+ *   x^, n^    x^ = Mprev_g inverse(Mcur_g) x_p, n^ = unit(inverse-transpose of that map n_p) (composed in double on the host;
+ *             a geometry whose model matrix is bitwise unchanged keeps x^ = x_p, n^ = n_p exactly)
+ *   project   q = inverse(ff_camera_ray_matrix(previous camera)) (x^, 1); fx = (q.x/q.w + 1)/2 * screen_w,
+ *             fy = (1 - q.y/q.w)/2 * screen_h (the previous camera's m_screenWidth / m_screenHeight; the inverse of the
+ *             primary ray's Px = x/screen_w*2-1, Py = 1-y/screen_h*2).  q.w <= 0: no history.  Camera bitwise the previous
+ *             call's and g not moved: fx = x, fy = y exactly (the one tap is p itself, weight 1)
+ *   taps      (floor(fx) + {0,1}, floor(fy) + {0,1}) with bilinear weights w_q; a tap counts when it lies in the previous image,
+ *             has p's class there (same geometry, filterable), dot(n^, n_q) >= reuse_normal, |n^.(x_q - x^)| <= reuse_plane *
+ *             |x^ - previous eye|, g's mesh was not replaced by ff_update_mesh since the previous call, and w_q > 0
+ *   history   W = sum w_q over the taps that count.  W >= 1e-3: h = sum w_q h_q / W for the colour history, both moments and the
+ *             length; len = len_h + 1, alpha = 1 / min(len, max_history), acc = h + alpha (cur - h) for colour c and moments
+ *             (l, l^2), l = 0.2126 r + 0.7152 g + 0.0722 b of c.  Otherwise len = 1, acc = cur.
+ *   variance  len >= variance_history: var = max(0, mu2 - mu1^2) of the accumulated moments.  Otherwise the 7x7 average of the
+ *             accumulated moments with weight w_n w_x [same class] (ff_denoise's w_n, w_x; exponent > 30 weighs 0), then
+ *             var = max(0, mu2 - mu1^2) * 4 / len
+ *   pass i    c'_p = sum w c_q / sum w, var'_p = sum w^2 var_q / (sum w)^2 over the 5x5 taps 2^i apart, w = h(dx) h(dy) w_l w_n w_x
+ *             (h, w_n, w_x and the tap exclusions of ff_denoise, including the e^-30 cut-off on the product w_l w_n w_x),
+ *             w_l = exp(-|l_p - l_q| / (sigma_luminance sqrt(g_p) + 1e-30)), g_p = sum k var_q / sum k over the 3x3
+ *             neighbours that are taps of the pass (k = (1 2 1) x (1 2 1)), the centre always
+ *   feedback  the next call's colour history is c after pass feedback_pass (-1: the accumulation before any pass); the
+ *             moments history is always the unfiltered accumulation
+ *   output    remodulated c after the last pass (the accumulation for iterations 0); rgb8 = trunc(clamp(v * 255)).
+ * History is dropped by ff_temporal_reset, the first call, a change of width or height and ff_upload_scene; ff_update_mesh(g)
+ * drops geometry g's only; ff_update_transforms moves it with its geometry.  The call leaves FfStats, the stored primary hits
+ * and their key, the cull mask, ff_denoise's buffers and the progressive sum as they were.  Buffers as in ff_denoise
+ * (radiance_out may alias radiance_in).  FF_ERR_NO_SCENE without a scene.  Synchronous. */
+FF_API int ff_denoise_temporal(FfState* state, const FfCamera* camera, int width, int height, const FfTemporalParams* tp,
+                               const float* radiance_in, const float* position, const float* normal, const float* albedo,
+                               const int32_t* ids, int inputs_on_device,
+                               void* rgb8, int rgb8_on_device, float* radiance_out, int radiance_out_on_device);
+
+/* Drops the temporal history: the next ff_denoise_temporal call starts afresh. */
+FF_API int ff_temporal_reset(FfState* state);
+
+/* The last ff_denoise_temporal call's per-pixel motion (W*H*2 floats: fx - x, fy - y for every hit pixel whose point the
+ * previous camera sees; 0 for misses and on the first call after a reset) and history length (W*H floats; 0 for pixels that
+ * are not filterable).  Either may be NULL.  FF_ERR_INVALID_ARG when no call was made since the last reset. */
+FF_API int ff_temporal_history(FfState* state, float* motion, float* length, int on_device);
+
 /* saveToPPM (utilities.h:842-856) for the 8-bit framebuffer: P3 text, one "r g b" line per pixel, top row first. */
 FF_API int ff_save_ppm(const char* path, const unsigned char* rgb8, int width, int height);
 

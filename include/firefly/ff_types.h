@@ -234,6 +234,21 @@ typedef struct FfDenoiseParams {
     int32_t flags;         /* FF_DENOISE_* bits */
 } FfDenoiseParams;
 
+/* ff_denoise_temporal: spatiotemporal variance-guided filtering (SVGF, Schied et al. 2017) of 1-spp frames across camera and
+ * rigid object motion.  ff_temporal_params_init gives the defaults; the formulas are in ff_api.h. */
+typedef struct FfTemporalParams {
+    int32_t iterations;       /* variance-guided à-trous passes after the temporal step, step 2^i for pass i; 0..10 */
+    float   sigma_luminance;  /* luminance edge-stop in units of the local standard deviation (SVGF sigma_l, > 0) */
+    float   sigma_normal;     /* normal edge-stop, as FfDenoiseParams (> 0) */
+    float   sigma_plane;      /* plane-distance edge-stop, as FfDenoiseParams (> 0) */
+    int32_t flags;            /* FF_DENOISE_SAME_GEOMETRY | FF_DENOISE_DEMODULATE_ALBEDO, meaning as in ff_denoise */
+    int32_t max_history;      /* >= 1: the blend factor is 1 / min(len, max_history) */
+    int32_t variance_history; /* >= 1: pixels with len < this use the spatial variance estimate */
+    int32_t feedback_pass;    /* which pass's output becomes the colour history: -1 = the unfiltered accumulation, else 0..iterations-1 */
+    float   reuse_normal;     /* a history tap needs dot(moved normal, tap normal) >= this */
+    float   reuse_plane;      /* ... and |n^ . (x_q - x^)| <= this * |x^ - previous eye| */
+} FfTemporalParams;           /* 40 bytes */
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif
