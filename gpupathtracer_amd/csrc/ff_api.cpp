@@ -16,6 +16,7 @@
 
 #include "ff_denoise.h"
 #include "ff_state.h"
+#include "ff_taa.h"
 #include "ff_temporal.h"
 
 using namespace ff;
@@ -302,7 +303,7 @@ int render_enqueue(FfState* s, const FfCamera* camera, const FfRenderParams* prm
     KParams k;
     std::memset(&k, 0, sizeof k);
     FfMat4 cm;
-    ff_camera_ray_matrix(camera, &cm);
+    ff_camera_ray_matrix_jittered(camera, s->jitter_x, s->jitter_y, &cm); // (the state's pixel jitter; 0 0: ff_camera_ray_matrix)
     std::memcpy(k.cam_c0, &cm.m[0], 16);
     std::memcpy(k.cam_c1, &cm.m[4], 16);
     std::memcpy(k.cam_c2, &cm.m[8], 16);
@@ -836,6 +837,8 @@ int ff_destroy(FfState* s)
     if (s->d_dn_work) (void)hipFree(s->d_dn_work);
     if (s->d_tp_work) (void)hipFree(s->d_tp_work);
     if (s->d_tp_geoms) (void)hipFree(s->d_tp_geoms);
+    if (s->d_taa_work) (void)hipFree(s->d_taa_work);
+    if (s->d_taa_geoms) (void)hipFree(s->d_taa_geoms);
     free_build_scratch(s->scratch);
     if (s->d_blocksums) (void)hipFree(s->d_blocksums);
     if (s->d_rgb8) (void)hipFree(s->d_rgb8);
@@ -1024,6 +1027,7 @@ int ff_upload_scene(FfState* s, const FfGeometry* host_geometries, int n)
     if (!s) return fail(FF_ERR_INVALID_ARG, "ff_upload_scene: state is null");
     s->primary_valid = s->last_key_valid = false; // (the stored primary hits belong to the scene that goes)
     s->tp_valid = s->tp_last = false;             // (and so does the temporal history)
+    s->taa_valid = s->taa_last = false;           // (and the TAA history)
     const auto t_call = std::chrono::steady_clock::now();
     s->build_stats = FfBuildStats();
     const BvhBuildParams bp = default_bvh_params();
@@ -1140,6 +1144,7 @@ int upload_compiled_scene(FfState* s, const CompiledScene& cs, double build_ms)
     const auto t_call = std::chrono::steady_clock::now();
     s->primary_valid = s->last_key_valid = false;
     s->tp_valid = s->tp_last = false;
+    s->taa_valid = s->taa_last = false;
     s->build_stats = FfBuildStats();
     s->build_stats.build_ms = build_ms;
     const int st = upload_compiled(s, cs);
@@ -1214,6 +1219,7 @@ int ff_update_mesh(FfState* s, int geometry_index, const FfTriangle* triangles, 
     if (mode == FF_UPDATE_REBUILD && s->scene_builder == FF_BUILD_HOST_SAH)
         return fail(FF_ERR_UNSUPPORTED, "ff_update_mesh: rebuilding in place needs a scene uploaded with a device builder (host-built trees are packed)");
     if ((size_t)geometry_index < s->tp_replaced.size()) s->tp_replaced[geometry_index] = 1; // (its temporal history restarts)
+    if ((size_t)geometry_index < s->taa_replaced.size()) s->taa_replaced[geometry_index] = 1; // (and its TAA history)
     const auto t_call = std::chrono::steady_clock::now();
     FfBuildStats& bs = s->build_stats;
     bs.copy_ms = bs.build_ms = 0.0;
@@ -1762,7 +1768,7 @@ int ff_gbuffer(FfState* s, const FfCamera* camera, const FfRenderParams* params,
     KParams k;
     std::memset(&k, 0, sizeof k);
     FfMat4 cm;
-    ff_camera_ray_matrix(camera, &cm);
+    ff_camera_ray_matrix_jittered(camera, s->jitter_x, s->jitter_y, &cm); // (the state's pixel jitter; 0 0: ff_camera_ray_matrix)
     std::memcpy(k.cam_c0, &cm.m[0], 16);
     std::memcpy(k.cam_c1, &cm.m[4], 16);
     std::memcpy(k.cam_c2, &cm.m[8], 16);
@@ -2250,6 +2256,218 @@ int ff_temporal_history(FfState* s, float* motion, float* length, int on_device)
         d_length = length ? (float*)c.carve(px * 4) : nullptr;
     }
     FF_HIP(launch_temporal_history(b, s->tp_cur, d_motion, d_length, s->stream));
+    FF_HIP(hipStreamSynchronize(s->stream));
+    if (!on_device) {
+        if (motion) FF_HIP(hipMemcpy(motion, d_motion, px * 8, hipMemcpyDeviceToHost));
+        if (length) FF_HIP(hipMemcpy(length, d_length, px * 4, hipMemcpyDeviceToHost));
+    }
+    return FF_OK;
+}
+
+// ---- sub-pixel jitter and temporal anti-aliasing (kernel in ff_taa.hip) ----------------------------------------------
+
+int ff_set_pixel_jitter(FfState* s, float jx, float jy)
+{
+    clear_error();
+    if (!s) return fail(FF_ERR_INVALID_ARG, "ff_set_pixel_jitter: state is null");
+    if (!(jx >= 0.f && jx < 1.f && jy >= 0.f && jy < 1.f))
+        return fail(FF_ERR_INVALID_ARG, "ff_set_pixel_jitter: the jitter must be finite and in [0, 1) (got %g %g)", (double)jx, (double)jy);
+    s->jitter_x = jx;
+    s->jitter_y = jy;
+    return FF_OK;
+}
+
+void ff_taa_params_init(FfTaaParams* p)
+{
+    if (!p) return;
+    // 
+    p->alpha_min = 0.1f;
+    p->gamma = 1.0f;
+    p->flags = 0;
+    p->reserved = 0;
+}
+
+} // extern "C"
+
+namespace {
+
+// ff_taa's history and motion: two float4 per pixel {rgb, len} and one float2 (ff_state.h)
+TaaArgs taa_buffers(FfState* s, int width, int height, int cur)
+{
+    const size_t px = (size_t)width * (size_t)height;
+    TaaArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.width = width;
+    a.height = height;
+    a.cur = cur;
+    a.hist[0] = s->d_taa_work;
+    a.hist[1] = s->d_taa_work + px;
+    a.motion = (float2*)(s->d_taa_work + 2 * px);
+    return a;
+}
+
+// inverse(ff_camera_ray_matrix(c)) in double, rounded to float; false if singular
+bool inverse_ray_matrix(const FfCamera* c, float* out16, FfMat4* ray)
+{
+    ff_camera_ray_matrix(c, ray);
+    double m[16], inv[16];
+    for (int k = 0; k < 16; ++k) m[k] = ray->m[k];
+    if (!invert4(m, inv)) return false;
+    for (int k = 0; k < 16; ++k) out16[k] = (float)inv[k];
+    return true;
+}
+
+} // namespace
+
+extern "C" {
+
+int ff_taa(FfState* s, const FfCamera* camera, int width, int height, const FfTaaParams* p, const float* radiance_in, const float* position,
+           const int32_t* ids, int inputs_on_device, void* rgb8, int rgb8_on_device, float* radiance_out, int radiance_out_on_device)
+{
+    clear_error();
+    if (!s) return fail(FF_ERR_INVALID_ARG, "ff_taa: state is null");
+    if (!camera) return fail(FF_ERR_INVALID_ARG, "ff_taa: camera is null");
+    if (!p) return fail(FF_ERR_INVALID_ARG, "ff_taa: params are null");
+    if (width <= 0 || height <= 0 || width > 65535 || height > 65535)
+        return fail(FF_ERR_INVALID_ARG, "ff_taa: image size %dx%d is invalid", width, height);
+    if (!(p->alpha_min > 0.f && p->alpha_min <= 1.f)) return fail(FF_ERR_INVALID_ARG, "ff_taa: alpha_min must be in (0, 1] (got %g)", (double)p->alpha_min);
+    if (!(p->gamma > 0.f) || !std::isfinite(p->gamma)) return fail(FF_ERR_INVALID_ARG, "ff_taa: gamma must be positive and finite (got %g)", (double)p->gamma);
+    if (p->flags & ~(FF_TAA_BILINEAR | FF_TAA_NO_CLAMP)) return fail(FF_ERR_INVALID_ARG, "ff_taa: unknown flags 0x%x", p->flags);
+    if (p->reserved != 0) return fail(FF_ERR_INVALID_ARG, "ff_taa: reserved must be 0");
+    if (!radiance_in || !position || !ids) return fail(FF_ERR_INVALID_ARG, "ff_taa: radiance, position and ids are required");
+    if (!s->has_scene) return fail(FF_ERR_NO_SCENE, "ff_taa: no scene uploaded (the history follows its geometries)");
+    FF_HIP(hipSetDevice(s->device));
+    const size_t px = (size_t)width * (size_t)height;
+    // host buffers are staged, as in ff_denoise; a device radiance_out that overlaps radiance_in reads a copy of the input (the
+    // kernel's apron reads neighbours that another workgroup may already have written)
+    const bool in_host = !inputs_on_device, rgb_host = rgb8 && !rgb8_on_device, out_host = radiance_out && !radiance_out_on_device;
+    const char* rin = (const char*)radiance_in;
+    const char* rout = (const char*)radiance_out;
+    const bool alias = !in_host && !out_host && radiance_out && rin < rout + px * 12 && rout < rin + px * 12;
+    const size_t need = (in_host ? padded(px * 12) * 3 : 0) + (alias ? padded(px * 12) : 0) + (rgb_host ? padded(px * 3) : 0) +
+                        (out_host ? padded(px * 12) : 0);
+    if (need > 0) {
+        const int st = ensure_bytes(&s->d_img_stage, &s->img_stage_bytes, need);
+        if (st != FF_OK) return st;
+    }
+    Carver c = { (char*)s->d_img_stage, 0 };
+    hipStream_t stream = s->stream;
+    auto stage_in = [&](const void* src, size_t bytes, hipMemcpyKind kind) -> const void* {
+        void* d = c.carve(bytes);
+        return hipMemcpyAsync(d, src, bytes, kind, stream) == hipSuccess ? d : nullptr;
+    };
+    const float* d_rad = radiance_in;
+    const float* d_pos = position;
+    const int* d_ids = ids;
+    if (in_host) {
+        d_rad = (const float*)stage_in(radiance_in, px * 12, hipMemcpyHostToDevice);
+        d_pos = (const float*)stage_in(position, px * 12, hipMemcpyHostToDevice);
+        d_ids = (const int*)stage_in(ids, px * 12, hipMemcpyHostToDevice);
+        if (!d_rad || !d_pos || !d_ids) return fail(FF_ERR_HIP, "ff_taa: staging the inputs failed");
+    } else if (alias) {
+        d_rad = (const float*)stage_in(radiance_in, px * 12, hipMemcpyDeviceToDevice);
+        if (!d_rad) return fail(FF_ERR_HIP, "ff_taa: copying the input failed");
+    }
+    unsigned char* d_rgb8 = rgb_host ? (unsigned char*)c.carve(px * 3) : (unsigned char*)rgb8;
+    float* d_out = out_host ? (float*)c.carve(px * 12) : radiance_out;
+    // history: kept only for the same image size (a new size, a reset or a new scene start afresh)
+    const bool has_history = s->taa_valid && width == s->taa_width && height == s->taa_height;
+    s->taa_valid = s->taa_last = false; // (from here on the history is being rewritten)
+    int st = ensure_bytes((void**)&s->d_taa_work, &s->taa_work_bytes, 2 * px * sizeof(float4) + px * sizeof(float2));
+    if (st != FF_OK) return st;
+    TaaArgs a = taa_buffers(s, width, height, has_history ? 1 - s->taa_cur : 0);
+    a.has_history = has_history ? 1 : 0;
+    a.bilinear = (p->flags & FF_TAA_BILINEAR) ? 1 : 0;
+    a.clamp = (p->flags & FF_TAA_NO_CLAMP) ? 0 : 1;
+    a.alpha_min = p->alpha_min;
+    a.gamma = p->gamma;
+    FfMat4 cm;
+    if (!inverse_ray_matrix(camera, a.inv_cur, &cm)) return fail(FF_ERR_INVALID_ARG, "ff_taa: the camera's ray matrix is singular");
+    std::memcpy(a.ray, cm.m, sizeof a.ray);
+    a.far_clip = camera->m_farClip;
+    a.screen_w = camera->m_screenWidth;
+    a.screen_h = camera->m_screenHeight;
+    // the per-geometry table: ff_denoise_temporal's rows from the TAA history's model matrices
+    int num = 0;
+    for (const GeomRecord& g : s->h_geoms) num = std::max(num, g.orig_index + 1);
+    s->h_taa_geoms.assign((size_t)num * sizeof(TemporalGeom), 0);
+    TemporalGeom* rows = (TemporalGeom*)s->h_taa_geoms.data();
+    for (const GeomRecord& g : s->h_geoms) {
+        const int o = g.orig_index;
+        if (o < 0) continue;
+        float cur12[12];
+        record_model(g, cur12);
+        int flags = 0;
+        const float* prev12 = cur12;
+        if (has_history && (size_t)o < s->taa_has_model.size() && s->taa_has_model[o]) {
+            prev12 = &s->taa_model[(size_t)o * 12];
+            if (std::memcmp(prev12, cur12, sizeof cur12) != 0) flags |= kTpMoved;
+        }
+        if ((size_t)o < s->taa_replaced.size() && s->taa_replaced[o]) flags |= kTpReplaced;
+        rows[o] = temporal_row(prev12, g, flags);
+    }
+    a.num_geoms = num;
+    if (num > 0) {
+        st = ensure_bytes(&s->d_taa_geoms, &s->taa_geoms_bytes, s->h_taa_geoms.size());
+        if (st != FF_OK) return st;
+        FF_HIP(hipMemcpyAsync(s->d_taa_geoms, s->h_taa_geoms.data(), s->h_taa_geoms.size(), hipMemcpyHostToDevice, stream));
+    }
+    a.geoms = (const TemporalGeom*)s->d_taa_geoms;
+    if (has_history) {
+        a.cam_rest = std::memcmp(camera, &s->taa_camera, sizeof(FfCamera)) == 0 ? 1 : 0;
+        FfMat4 pm;
+        if (!inverse_ray_matrix(&s->taa_camera, a.inv_prev, &pm)) return fail(FF_ERR_INVALID_ARG, "ff_taa: the previous camera's ray matrix is singular");
+        a.prev_screen_w = s->taa_camera.m_screenWidth;
+        a.prev_screen_h = s->taa_camera.m_screenHeight;
+    }
+    FF_HIP(launch_taa(a, d_rad, d_pos, d_ids, d_rgb8, d_out, stream));
+    FF_HIP(hipStreamSynchronize(stream));
+    // the history now describes this call
+    s->taa_valid = s->taa_last = true;
+    s->taa_cur = a.cur;
+    s->taa_width = width;
+    s->taa_height = height;
+    s->taa_camera = *camera;
+    s->taa_model.assign((size_t)num * 12, 0.f);
+    s->taa_has_model.assign((size_t)num, 0);
+    for (const GeomRecord& g : s->h_geoms) {
+        if (g.orig_index < 0) continue;
+        record_model(g, &s->taa_model[(size_t)g.orig_index * 12]);
+        s->taa_has_model[g.orig_index] = 1;
+    }
+    s->taa_replaced.assign((size_t)num, 0);
+    if (rgb_host) FF_HIP(hipMemcpy(rgb8, d_rgb8, px * 3, hipMemcpyDeviceToHost));
+    if (out_host) FF_HIP(hipMemcpy(radiance_out, d_out, px * 12, hipMemcpyDeviceToHost));
+    return FF_OK;
+}
+
+int ff_taa_reset(FfState* s)
+{
+    clear_error();
+    if (!s) return fail(FF_ERR_INVALID_ARG, "ff_taa_reset: state is null");
+    s->taa_valid = s->taa_last = false;
+    return FF_OK;
+}
+
+int ff_taa_history(FfState* s, float* motion, float* length, int on_device)
+{
+    clear_error();
+    if (!s) return fail(FF_ERR_INVALID_ARG, "ff_taa_history: state is null");
+    if (!s->taa_last) return fail(FF_ERR_INVALID_ARG, "ff_taa_history: no ff_taa call since the last reset");
+    if (!motion && !length) return FF_OK;
+    FF_HIP(hipSetDevice(s->device));
+    const size_t px = (size_t)s->taa_width * (size_t)s->taa_height;
+    const TaaArgs a = taa_buffers(s, s->taa_width, s->taa_height, s->taa_cur);
+    float* d_motion = motion;
+    float* d_length = length;
+    if (!on_device) {
+        const int st = ensure_bytes(&s->d_img_stage, &s->img_stage_bytes, padded(px * 8) + padded(px * 4));
+        if (st != FF_OK) return st;
+        Carver c = { (char*)s->d_img_stage, 0 };
+        d_motion = motion ? (float*)c.carve(px * 8) : nullptr;
+        d_length = length ? (float*)c.carve(px * 4) : nullptr;
+    }
+    FF_HIP(launch_taa_history(a, d_motion, d_length, s->stream));
     FF_HIP(hipStreamSynchronize(s->stream));
     if (!on_device) {
         if (motion) FF_HIP(hipMemcpy(motion, d_motion, px * 8, hipMemcpyDeviceToHost));

@@ -724,6 +724,17 @@ int ff_multi_render_to_pbo(FfMulti* m, const FfCamera* camera, const FfRenderPar
     return st;
 }
 
+int ff_multi_set_pixel_jitter(FfMulti* m, float jx, float jy)
+{
+    clear_error();
+    if (!m) return fail(FF_ERR_INVALID_ARG, "ff_multi_set_pixel_jitter: handle is null");
+    for (FfState* s : m->states) {
+        const int st = ff_set_pixel_jitter(s, jx, jy); // (checks the values before the first state changes)
+        if (st != FF_OK) return st;
+    }
+    return FF_OK;
+}
+
 int ff_multi_stats(FfMulti* m, FfStats* out)
 {
     clear_error();

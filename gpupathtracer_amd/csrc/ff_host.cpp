@@ -135,6 +135,39 @@ void ff_camera_ray_matrix(const FfCamera* c, FfMat4* out)
     store(mul(inverse(view), inverse(proj)), out->m);
 }
 
+void ff_camera_ray_matrix_jittered(const FfCamera* c, float jx, float jy, FfMat4* out)
+{
+    // kernel.cu:200-203 with the pixel moved by (jx, jy): v = (Px f, Py f, f, f) gains (dPx f, dPy f, 0, 0), which is column 2 of
+    // the matrix gaining dPx c0 + dPy c1 (the kernel's v2 = f).  No jitter: the reference's matrix, untouched.
+    if (!c || !out) return;
+    ff_camera_ray_matrix(c, out);
+    if (jx == 0.f && jy == 0.f) return;
+    const double dpx = 2.0 * (double)jx / (double)c->m_screenWidth, dpy = -2.0 * (double)jy / (double)c->m_screenHeight;
+    for (int r = 0; r < 4; ++r)
+        out->m[8 + r] = (float)((double)out->m[8 + r] + dpx * (double)out->m[r] + dpy * (double)out->m[4 + r]);
+}
+
+int ff_jitter_sequence(int index, int period, float* jx, float* jy)
+{
+    ff::clear_error();
+    if (period < 1) return ff::fail(FF_ERR_INVALID_ARG, "ff_jitter_sequence: period must be at least 1 (got %d)", period);
+    if (!jx || !jy) return ff::fail(FF_ERR_INVALID_ARG, "ff_jitter_sequence: null output");
+    const int n = ((index % period) + period) % period + 1;
+    // radical inverses of n in bases 2 and 3 (Halton 1964), summed in double and rounded once
+    double h[2] = { 0.0, 0.0 };
+    const int bases[2] = { 2, 3 };
+    for (int k = 0; k < 2; ++k) {
+        double f = 1.0;
+        for (int i = n; i > 0; i /= bases[k]) {
+            f /= bases[k];
+            h[k] += f * (i % bases[k]);
+        }
+    }
+    *jx = (float)h[0];
+    *jy = (float)h[1];
+    return FF_OK;
+}
+
 // -------------------------------------------------------------------------------------------------
 // OBJ reader with LoadMesh's flattening (utilities.h:781-840).  A small from-scratch parser: v / vt / vn / f
 // records, 1-based and negative (relative) indices, `v`, `v/vt`, `v//vn`, `v/vt/vn` corners.  Faces with more

@@ -122,6 +122,21 @@ struct FfState {
     FfCamera tp_camera = {};
     std::vector<float> tp_model;            // 12 floats (model matrix columns, xyz) per caller geometry index
     std::vector<unsigned char> tp_has_model, tp_replaced;
+    // sub-pixel jitter of the primary rays (ff_set_pixel_jitter): composed into the ray matrix of ff_render* and ff_gbuffer
+    float jitter_x = 0.f, jitter_y = 0.f;
+    // temporal anti-aliasing (ff_taa, ff_taa.hip): two history buffers of one float4 per pixel {rgb, len} that swap by index, then
+    // the motion (float2 per pixel).  taa_cur: the buffer the last call wrote.  The history describes the camera, image size and
+    // per-geometry model matrices of that call; taa_replaced marks the meshes ff_update_mesh changed since.
+    float4* d_taa_work = nullptr;
+    size_t taa_work_bytes = 0;
+    void* d_taa_geoms = nullptr; // the per-geometry table (ff::TemporalGeom rows, as the temporal denoiser's)
+    size_t taa_geoms_bytes = 0;
+    std::vector<unsigned char> h_taa_geoms;
+    bool taa_valid = false, taa_last = false;
+    int taa_cur = 0, taa_width = 0, taa_height = 0;
+    FfCamera taa_camera = {};
+    std::vector<float> taa_model;
+    std::vector<unsigned char> taa_has_model, taa_replaced;
     unsigned* d_queue = nullptr;               // work-queue counter: lives right behind the counters (one memset clears both)
     unsigned long long* d_counters = nullptr;  // 28 counters + 4 queue words
     unsigned long long* h_counters = nullptr;  // pinned mirror for the per-frame read-back

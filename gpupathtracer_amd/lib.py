@@ -28,6 +28,8 @@ EXPORTS = [
     "ff_multi_render", "ff_multi_render_to_pbo", "ff_multi_stats",
     "ff_gbuffer", "ff_denoise_params_init", "ff_denoise",
     "ff_temporal_params_init", "ff_denoise_temporal", "ff_temporal_reset", "ff_temporal_history",
+    "ff_camera_ray_matrix_jittered", "ff_set_pixel_jitter", "ff_multi_set_pixel_jitter", "ff_jitter_sequence",
+    "ff_taa_params_init", "ff_taa", "ff_taa_reset", "ff_taa_history",
 ]
 DIST_ID_BYTES = 128
 
@@ -154,6 +156,16 @@ def load():
     lib.ff_denoise_temporal.argtypes = [vp, P(T.FfCamera), i32, i32, P(T.FfTemporalParams), vp, vp, vp, vp, vp, i32, vp, i32, vp, i32]
     lib.ff_temporal_reset.argtypes = [vp]
     lib.ff_temporal_history.argtypes = [vp, vp, vp, i32]
+    lib.ff_camera_ray_matrix_jittered.argtypes = [P(T.FfCamera), C.c_float, C.c_float, P(T.FfMat4)]
+    lib.ff_camera_ray_matrix_jittered.restype = None
+    lib.ff_set_pixel_jitter.argtypes = [vp, C.c_float, C.c_float]
+    lib.ff_multi_set_pixel_jitter.argtypes = [vp, C.c_float, C.c_float]
+    lib.ff_jitter_sequence.argtypes = [i32, i32, P(C.c_float), P(C.c_float)]
+    lib.ff_taa_params_init.argtypes = [P(T.FfTaaParams)]
+    lib.ff_taa_params_init.restype = None
+    lib.ff_taa.argtypes = [vp, P(T.FfCamera), i32, i32, P(T.FfTaaParams), vp, vp, vp, i32, vp, i32, vp, i32]
+    lib.ff_taa_reset.argtypes = [vp]
+    lib.ff_taa_history.argtypes = [vp, vp, vp, i32]
     _lib = real
     return real
 
@@ -250,6 +262,31 @@ def temporal_params(**overrides):
             raise TypeError(f"FfTemporalParams has no field {name!r}")
         setattr(tp, name, value)
     return tp
+
+
+def taa_params(**overrides):
+    """ff_taa_params_init's defaults with the given fields replaced (any FfTaaParams field)."""
+    p = T.FfTaaParams()
+    load().ff_taa_params_init(C.byref(p))
+    for name, value in overrides.items():
+        if name not in dict(T.FfTaaParams._fields_):
+            raise TypeError(f"FfTaaParams has no field {name!r}")
+        setattr(p, name, value)
+    return p
+
+
+def jitter_sequence(index, period=16):
+    """ff_jitter_sequence: the (jx, jy) of frame `index` of a Halton(2, 3) cycle of `period` jitters."""
+    jx, jy = C.c_float(), C.c_float()
+    check(load().ff_jitter_sequence(index, period, C.byref(jx), C.byref(jy)))
+    return jx.value, jy.value
+
+
+def camera_ray_matrix_jittered(camera, jx, jy):
+    """ff_camera_ray_matrix_jittered -> T.FfMat4."""
+    m = T.FfMat4()
+    load().ff_camera_ray_matrix_jittered(C.byref(camera), jx, jy, C.byref(m))
+    return m
 
 
 GBUFFER_CHANNELS = (("depth", np.float32, ()), ("position", np.float32, (3,)), ("normal", np.float32, (3,)), ("albedo", np.float32, (3,)),
@@ -466,6 +503,47 @@ class Tracer:
         check(self._lib.ff_temporal_history(self._state, motion.ctypes.data if h * w else None, length.ctypes.data if h * w else None, 0))
         return motion, length
 
+    def set_pixel_jitter(self, jx, jy):
+        """ff_set_pixel_jitter: the following render* and gbuffer calls trace pixel (x, y) through (x + jx, y + jy)."""
+        check(self._lib.ff_set_pixel_jitter(self._state, jx, jy))
+
+    def taa(self, radiance, gbuffer, camera, p=None):
+        """ff_taa of this frame's host radiance [H,W,3] with gbuffer() of `camera` (same jitter); the history stays in the state
+        -> (rgb8 [H,W,3] uint8, radiance [H,W,3] float32)."""
+        rad = np.ascontiguousarray(radiance, dtype=np.float32)
+        h, w = rad.shape[:2]
+        if rad.shape != (h, w, 3) or any(np.shape(gbuffer[k])[:2] != (h, w) for k in ("position", "ids")):
+            raise ValueError("taa: radiance must be [H,W,3] and the G-buffer of the same size")
+        p = p if p is not None else taa_params()
+        pos = np.ascontiguousarray(gbuffer["position"], dtype=np.float32)
+        ids = np.ascontiguousarray(gbuffer["ids"], dtype=np.int32)
+        rgb8 = np.zeros((h, w, 3), dtype=np.uint8)
+        out = np.zeros((h, w, 3), dtype=np.float32)
+        check(self._lib.ff_taa(self._state, C.byref(camera), w, h, C.byref(p), rad.ctypes.data, pos.ctypes.data, ids.ctypes.data, 0,
+                               rgb8.ctypes.data, 0, out.ctypes.data, 0))
+        self._taa_size = (h, w)
+        return rgb8, out
+
+    def taa_device(self, camera, width, height, radiance_ptr, position_ptr, ids_ptr, p=None, rgb8_ptr=None, radiance_out_ptr=None):
+        """ff_taa on DEVICE buffers (raw pointers); radiance_out_ptr may equal radiance_ptr."""
+        p = p if p is not None else taa_params()
+        vp = lambda q: C.c_void_p(q) if q else None  # noqa: E731
+        check(self._lib.ff_taa(self._state, C.byref(camera), width, height, C.byref(p), vp(radiance_ptr), vp(position_ptr), vp(ids_ptr), 1,
+                               vp(rgb8_ptr), 1, vp(radiance_out_ptr), 1))
+        self._taa_size = (height, width)
+
+    def taa_reset(self):
+        """Drop the TAA history (ff_taa_reset)."""
+        check(self._lib.ff_taa_reset(self._state))
+
+    def taa_history(self):
+        """The last taa call's (motion [H,W,2] float32, history length [H,W] float32)."""
+        h, w = getattr(self, "_taa_size", (0, 0))
+        motion = np.zeros((h, w, 2), dtype=np.float32)
+        length = np.zeros((h, w), dtype=np.float32)
+        check(self._lib.ff_taa_history(self._state, motion.ctypes.data if h * w else None, length.ctypes.data if h * w else None, 0))
+        return motion, length
+
     def strips_local_rows(self, height, strip_rows, part, num_parts):
         return self._lib.ff_strips_local_rows(height, strip_rows, part, num_parts)
 
@@ -594,6 +672,9 @@ class MultiTracer:
     def render_device(self, camera, params, strip_rows=0, rgb8_ptr=None, radiance_ptr=None):
         check(self._lib.ff_multi_render(self._handle, C.byref(camera), C.byref(params), strip_rows,
                                         C.c_void_p(rgb8_ptr) if rgb8_ptr else None, 1, C.c_void_p(radiance_ptr) if radiance_ptr else None, 1))
+
+    def set_pixel_jitter(self, jx, jy):
+        check(self._lib.ff_multi_set_pixel_jitter(self._handle, jx, jy))
 
     def stats(self):
         st = T.FfStats()

@@ -138,6 +138,14 @@ class FfTemporalParams(C.Structure):
 
 TEMPORAL_PARAMS_BYTES = 40
 
+
+class FfTaaParams(C.Structure):
+    _fields_ = [("alpha_min", C.c_float), ("gamma", C.c_float), ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+TAA_PARAMS_BYTES = 16
+TAA_BILINEAR, TAA_NO_CLAMP = 1, 2
+
 BUILD_HOST_SAH, BUILD_GPU_LBVH, BUILD_GPU_PLOC = 0, 1, 2
 UPDATE_REFIT, UPDATE_REBUILD = 0, 1
 

@@ -85,6 +85,24 @@ FF_API void ff_camera_update_basis(FfCamera* c);
  * hoisted out of the per-pixel path.  Exposed for tests. */
 FF_API void ff_camera_ray_matrix(const FfCamera* c, FfMat4* out_inv_view_times_inv_proj);
 
+/* ff_camera_ray_matrix with a sub-pixel jitter (jx, jy) composed in: the primary ray of pixel (x, y) goes through (x + jx, y + jy)
+ * instead of the pixel corner.  The kernel forms v = (Px f, Py f, f, f) (f = m_farClip) and multiplies it by the matrix, so adding
+ * (dPx f, dPy f, 0, 0) to v is the same as replacing column 2: c2' = c2 + dPx c0 + dPy c1, dPx = 2 jx / m_screenWidth,
+ * dPy = -2 jy / m_screenHeight, composed in double and rounded to float.  Columns 0, 1 and 3 are ff_camera_ray_matrix's;
+ * jx = jy = 0 gives ff_camera_ray_matrix's matrix bit for bit. */
+FF_API void ff_camera_ray_matrix_jittered(const FfCamera* c, float jx, float jy, FfMat4* out);
+
+/* Sub-pixel jitter of the state's primary rays: the following ff_render* and ff_gbuffer calls trace pixel (x, y) through
+ * (x + jx, y + jy), i.e. Px = (x + jx) / screen_w * 2 - 1, Py = 1 - (y + jy) / screen_h * 2 (ff_camera_ray_matrix_jittered).
+ * jx, jy finite and in [0, 1); the default 0 0 is the reference's ray bit for bit.  Every sample of one call shares the jitter
+ * (the stored primary hits are keyed by the jittered matrix, so a new jitter re-traces them).  ff_denoise_temporal does not
+ * see the jitter: it reprojects in unjittered pixel coordinates, and ff_taa cancels the jitter through the G-buffer. */
+FF_API int ff_set_pixel_jitter(FfState* state, float jx, float jy);
+
+/* Halton(2), Halton(3) of (index mod period) + 1 (the modulus taken into 0..period-1): (1/2, 1/3), (1/4, 2/3), (3/4, 1/9), ...
+ * period >= 1.  A viewer at rest that cycles through `period` jitters converges to the pixel's box-filtered image. */
+FF_API int ff_jitter_sequence(int index, int period, float* jx, float* jy);
+
 /* ---- scene upload (kernel.cu:268-298) ---------------------------------------------------------- */
 
 /* Deep-copies `n` geometries (and the triangles / BXDFs they point to) to the device, flattened to
@@ -239,6 +257,8 @@ FF_API int ff_multi_render(FfMulti* multi, const FfCamera* camera, const FfRende
 FF_API int ff_multi_render_to_pbo(FfMulti* multi, const FfCamera* camera, const FfRenderParams* params, int strip_rows);
 /* Sums over the devices of the last frame (kernel_ms: the slowest device). */
 FF_API int ff_multi_stats(FfMulti* multi, FfStats* out);
+/* ff_set_pixel_jitter on every device's state. */
+FF_API int ff_multi_set_pixel_jitter(FfMulti* multi, float jx, float jy);
 
 /* Batch closest-hit query = intersectRays (kernel.cu:127-176) for `n` arbitrary world-space rays.
  * rays/out are host arrays. trace_mode is an FfTraceMode. */
@@ -348,7 +368,10 @@ FF_API void ff_temporal_params_init(FfTemporalParams* p);
  * History is dropped by ff_temporal_reset, the first call, a change of width or height and ff_upload_scene; ff_update_mesh(g)
  * drops geometry g's only; ff_update_transforms moves it with its geometry.  The call leaves FfStats, the stored primary hits
  * and their key, the cull mask, ff_denoise's buffers and the progressive sum as they were.  Buffers as in ff_denoise
- * (radiance_out may alias radiance_in).  FF_ERR_NO_SCENE without a scene.  Synchronous. */
+ * (radiance_out may alias radiance_in).  FF_ERR_NO_SCENE without a scene.  Synchronous.
+ * The pixel jitter (ff_set_pixel_jitter) is not seen here: the previous camera's matrix is the unjittered ff_camera_ray_matrix
+ * and "at rest" means FfCamera bitwise equal, so a jittered sequence at rest accumulates each pixel's jittered samples like a
+ * progressive mean. */
 FF_API int ff_denoise_temporal(FfState* state, const FfCamera* camera, int width, int height, const FfTemporalParams* tp,
                                const float* radiance_in, const float* position, const float* normal, const float* albedo,
                                const int32_t* ids, int inputs_on_device,
@@ -361,6 +384,51 @@ FF_API int ff_temporal_reset(FfState* state);
  * previous camera sees; 0 for misses and on the first call after a reset) and history length (W*H floats; 0 for pixels that
  * are not filterable).  Either may be NULL.  FF_ERR_INVALID_ARG when no call was made since the last reset. */
 FF_API int ff_temporal_history(FfState* state, float* motion, float* length, int on_device);
+
+/* ---- temporal anti-aliasing (TAA: Karis, SIGGRAPH 2014; Salvi, GDC 2016) ----------------------- */
+
+/* Defaults: alpha_min 0.1, gamma 1, Catmull-Rom history with the clamp (flags 0). */
+FF_API void ff_taa_params_init(FfTaaParams* p);
+
+/* Temporal anti-aliasing resolve of frames rendered with a sub-pixel jitter (ff_set_pixel_jitter, ff_jitter_sequence).
+ * radiance_in is this frame's image (raw, ff_denoise's or ff_denoise_temporal's output); position and ids are ff_gbuffer's for
+ * `camera` and the same jitter.  The state keeps its own history (colour and length per pixel, the previous camera and the
+ * per-geometry model matrices), separate from ff_denoise_temporal's.  P(M, X) is ff_denoise_temporal's projection:
+ * q = inverse(M) (X, 1), P = ((q.x/q.w + 1)/2 * screen_w, (1 - q.y/q.w)/2 * screen_h) with that camera's m_screenWidth and
+ * m_screenHeight.  M_cur, M_prev: the UNJITTERED ff_camera_ray_matrix of this call's camera and of the previous call's.
+ * Per pixel p = (x, y):
+ *   motion    hit of geometry g: x^ = Mprev_g inverse(Mcur_g) x_p (ff_denoise_temporal's rows, composed in double on the host),
+ *             m = P(M_prev, x^) - P(M_cur, x_p), which cancels the jitter (P(M_cur, x_p) ~ (x + jx, y + jy)).  Miss: X = the
+ *             kernel.cu:203 far point of the pixel's unjittered ray under M_cur, m = P(M_prev, X) - (x, y).  Camera bitwise
+ *             the previous call's and g not moved (a miss: the camera alone): m = 0 exactly, nothing is projected
+ *   history   looked up at h = (x, y) + m.  Valid when there is history, q.w > 0 (of P(M_prev, .)), 0 <= h.x <= W-1,
+ *             0 <= h.y <= H-1 and g's mesh was not replaced by ff_update_mesh since the previous call.  Colour: the 4x4
+ *             Catmull-Rom sum around floor(h), taps clamped into the image, t = h - floor(h) per axis, weights
+ *             ((-t^3 + 2t^2 - t)/2, (3t^3 - 5t^2 + 2)/2, (-3t^3 + 4t^2 + t)/2, (t^3 - t^2)/2) for floor(h) - 1 .. floor(h) + 2,
+ *             not renormalised (FF_TAA_BILINEAR: the 2x2 taps floor(h) + {0, 1} with weights (1 - t, t)).  len_h: the
+ *             history length at the nearest tap floor(h + 0.5).  m = 0 gives t = 0: exactly the pixel's own history
+ *   clamp     (not with FF_TAA_NO_CLAMP) in YCoCg, Y = r/4 + g/2 + b/4, Co = r/2 - b/2, Cg = -r/4 + g/2 - b/4: over the 3x3
+ *             neighbourhood of radiance_in (coordinates clamped at the borders) the mean mu, sigma = sqrt(max(0, E[c^2] - mu^2))
+ *             and min / max per channel; the history is clamped per channel to [max(min, mu - gamma sigma),
+ *             min(max, mu + gamma sigma)] and converted back (r = Y + Co - Cg, g = Y + Cg, b = Y - Co - Cg)
+ *   blend     valid history: len = min(len_h + 1, 4096), alpha = max(alpha_min, 1 / len), o = h + alpha (c - h) in RGB.
+ *             Otherwise len = 1 and o = c
+ *   stored    o and len are the next call's history; rgb8 = trunc(clamp(o * 255)).
+ * History is dropped by ff_taa_reset, the first call, a change of width or height and ff_upload_scene; ff_update_mesh(g)
+ * drops geometry g's only; ff_update_transforms moves it with its geometry.  The call leaves FfStats, the stored primary hits
+ * and their key, the cull mask, ff_denoise's buffers, the temporal denoiser's history and the progressive sum as they were.
+ * Buffers as in ff_denoise (radiance_out may alias radiance_in).  FF_ERR_NO_SCENE without a scene; FF_ERR_INVALID_ARG for
+ * alpha_min outside (0, 1], gamma <= 0 or NaN, unknown flags or a nonzero `reserved`.  Synchronous. */
+FF_API int ff_taa(FfState* state, const FfCamera* camera, int width, int height, const FfTaaParams* p, const float* radiance_in,
+                  const float* position, const int32_t* ids, int inputs_on_device, void* rgb8, int rgb8_on_device, float* radiance_out,
+                  int radiance_out_on_device);
+
+/* Drops the TAA history: the next ff_taa call starts afresh. */
+FF_API int ff_taa_reset(FfState* state);
+
+/* The last ff_taa call's per-pixel motion m (W*H*2 floats; 0 on the first call after a reset and where q.w <= 0) and history
+ * length (W*H floats).  Either may be NULL.  FF_ERR_INVALID_ARG when no call was made since the last reset. */
+FF_API int ff_taa_history(FfState* state, float* motion, float* length, int on_device);
 
 /* saveToPPM (utilities.h:842-856) for the 8-bit framebuffer: P3 text, one "r g b" line per pixel, top row first. */
 FF_API int ff_save_ppm(const char* path, const unsigned char* rgb8, int width, int height);

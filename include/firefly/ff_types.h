@@ -249,6 +249,17 @@ typedef struct FfTemporalParams {
     float   reuse_plane;      /* ... and |n^ . (x_q - x^)| <= this * |x^ - previous eye| */
 } FfTemporalParams;           /* 40 bytes */
 
+/* ff_taa: temporal anti-aliasing resolve of jittered frames (Karis 2014, Salvi 2016).  ff_taa_params_init gives the defaults;
+ * the formulas are in ff_api.h. */
+#define FF_TAA_BILINEAR  1 /* the history is sampled with 2x2 bilinear taps instead of 4x4 Catmull-Rom */
+#define FF_TAA_NO_CLAMP  2 /* the history is not clamped to the current frame's neighbourhood */
+typedef struct FfTaaParams {
+    float   alpha_min;  /* least weight of the current frame, in (0, 1] */
+    float   gamma;      /* half-width of the clamp box in standard deviations (> 0) */
+    int32_t flags;      /* FF_TAA_* bits */
+    int32_t reserved;   /* 0 */
+} FfTaaParams;          /* 16 bytes */
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif
