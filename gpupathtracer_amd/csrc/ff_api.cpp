@@ -90,13 +90,20 @@ int check_params(const FfRenderParams* p)
     if (p->bounces < 1 || p->bounces > 255) return fail(FF_ERR_INVALID_ARG, "bounces must be in 1..255 (got %d)", p->bounces);
     if (p->spp < 1 || p->spp >= (1 << 24)) return fail(FF_ERR_INVALID_ARG, "spp must be in 1..2^24-1 (got %d)", p->spp);
     if (p->trace_mode != FF_TRACE_BRUTE_FORCE && p->trace_mode != FF_TRACE_BVH) return fail(FF_ERR_INVALID_ARG, "unknown trace_mode %d", p->trace_mode);
-    if (p->shade_mode != FF_SHADE_NORMAL_DEBUG && p->shade_mode != FF_SHADE_DIFFUSE_PATH && p->shade_mode != FF_SHADE_DIFFUSE_PATH_SMOOTH) return fail(FF_ERR_INVALID_ARG, "unknown shade_mode %d", p->shade_mode);
+    if (p->shade_mode != FF_SHADE_NORMAL_DEBUG && p->shade_mode != FF_SHADE_DIFFUSE_PATH && p->shade_mode != FF_SHADE_DIFFUSE_PATH_SMOOTH &&
+        p->shade_mode != FF_SHADE_DIFFUSE_PATH_NEE) return fail(FF_ERR_INVALID_ARG, "unknown shade_mode %d", p->shade_mode);
     if (p->grid_mode != FF_GRID_FULL && p->grid_mode != FF_GRID_REFERENCE_FLOOR) return fail(FF_ERR_INVALID_ARG, "unknown grid_mode %d", p->grid_mode);
     if (p->spp_per_launch < 0) return fail(FF_ERR_INVALID_ARG, "spp_per_launch must be >= 0");
     return FF_OK;
 }
 
 } // namespace
+
+extern "C" int ff_check_render_params(const FfRenderParams* params)
+{
+    clear_error();
+    return check_params(params);
+}
 
 namespace ff {
 
@@ -377,6 +384,12 @@ int render_enqueue(FfState* s, const FfCamera* camera, const FfRenderParams* prm
     k.top_lds_count = s->top_lds_count;
     k.num_scan = s->num_scan;
     k.walls = s->walls;
+    if (prm->shade_mode == FF_SHADE_DIFFUSE_PATH_NEE) {
+        // (its own kernels: the rest of this function prepares the mega-kernels' frame)
+        k.rgb8 = rgb8_dev;
+        k.radiance = radiance_dev;
+        return enqueue_nee(s, k, prm, launches, blocks_per_launch, local_pixels);
+    }
     k.emitter_mask = 0u;
     k.cut_last = 0;
     if (prm->trace_mode == FF_TRACE_BVH && !debug && !s->sw.no_last_bounce_cut) {
@@ -839,6 +852,8 @@ int ff_destroy(FfState* s)
     if (s->d_tp_geoms) (void)hipFree(s->d_tp_geoms);
     if (s->d_taa_work) (void)hipFree(s->d_taa_work);
     if (s->d_taa_geoms) (void)hipFree(s->d_taa_geoms);
+    if (s->d_nee_lights) (void)hipFree(s->d_nee_lights);
+    if (s->d_nee_pdf) (void)hipFree(s->d_nee_pdf);
     free_build_scratch(s->scratch);
     if (s->d_blocksums) (void)hipFree(s->d_blocksums);
     if (s->d_rgb8) (void)hipFree(s->d_rgb8);
@@ -1031,13 +1046,22 @@ int ff_upload_scene(FfState* s, const FfGeometry* host_geometries, int n)
     const auto t_call = std::chrono::steady_clock::now();
     s->build_stats = FfBuildStats();
     const BvhBuildParams bp = default_bvh_params();
+    s->nee_valid = false; // (the light table belongs to the scene that goes)
     if (s->builder != FF_BUILD_HOST_SAH) {
-        const int st = upload_with_device_builder(s, host_geometries, n, bp);
+        int st = upload_with_device_builder(s, host_geometries, n, bp);
+        if (st == FF_OK) {
+            nee_capture(s, host_geometries, n, /*upload=*/true);
+            st = nee_rebuild(s);
+        }
         s->build_stats.total_ms = ms_since(t_call);
         if (st != FF_OK) free_scene(s);
         return st;
     }
-    const int st = upload_host_built(s, host_geometries, n, bp);
+    int st = upload_host_built(s, host_geometries, n, bp);
+    if (st == FF_OK) {
+        nee_capture(s, host_geometries, n, /*upload=*/true);
+        st = nee_rebuild(s);
+    }
     if (st != FF_OK) free_scene(s); // never leave a half-allocated scene behind (has_scene is false again)
     s->build_stats.total_ms = ms_since(t_call);
     return st;
@@ -1145,6 +1169,9 @@ int upload_compiled_scene(FfState* s, const CompiledScene& cs, double build_ms)
     s->primary_valid = s->last_key_valid = false;
     s->tp_valid = s->tp_last = false;
     s->taa_valid = s->taa_last = false;
+    s->nee_valid = false; // (no light table: FF_SHADE_DIFFUSE_PATH_NEE is not offered on a compiled upload)
+    s->nee_geoms.clear();
+    s->nee_tris.clear();
     s->build_stats = FfBuildStats();
     s->build_stats.build_ms = build_ms;
     const int st = upload_compiled(s, cs);
@@ -1196,6 +1223,11 @@ int ff_update_transforms(FfState* s, const FfGeometry* host_geometries, int n)
     if (st != FF_OK) return st;
     s->has_specular = false; // materials may have changed
     for (const GeomRecord& g : cs.geoms) s->has_specular = s->has_specular || g.bxdf_type == FF_BXDF_MIRROR || g.bxdf_type == FF_BXDF_GLASS;
+    if (!s->nee_geoms.empty() || s->nee_valid) { // (the light table follows the emitters' new transforms and materials)
+        nee_capture(s, host_geometries, n, /*upload=*/false);
+        st = nee_rebuild(s);
+        if (st != FF_OK) return st;
+    }
     s->build_stats.last_operation = 3;
     s->build_stats.total_ms = ms_since(t_call);
     s->build_stats.copy_ms = s->build_stats.total_ms;
@@ -1277,6 +1309,14 @@ int ff_update_mesh(FfState* s, int geometry_index, const FfTriangle* triangles, 
     }
     set_world_box(rec, omn, omx);
     refresh_scene_extent(s);
+    if (s->nee_valid && (size_t)geometry_index < s->nee_geoms.size()) {
+        const FfBXDF* m = s->nee_geoms[(size_t)geometry_index].m_bxdf;
+        nee_replace_mesh(s, geometry_index, triangles, count);
+        if (m && m->m_type == FF_BXDF_EMITTER) {
+            st = nee_rebuild(s);
+            if (st != FF_OK) return st;
+        }
+    }
     if (s->scene_builder == FF_BUILD_HOST_SAH) s->num_nodes = (int)s->node_capacity;
     st = finalize_layout(s); // (a rebuilt tree may differ in size and depth: LDS shares and workgroup size follow; copies the records)
     if (st != FF_OK) return st;

@@ -396,6 +396,8 @@ int ff_render_distributed(FfState* s, const FfCamera* camera, const FfRenderPara
     RootOutputs out;
     unsigned char* pack = nullptr;
     int local = check_render_call(s, camera, params, "ff_render_distributed");
+    if (local == FF_OK && params->shade_mode == FF_SHADE_DIFFUSE_PATH_NEE)
+        local = fail(FF_ERR_UNSUPPORTED, "ff_render_distributed: FF_SHADE_DIFFUSE_PATH_NEE renders on one device only");
     if (local == FF_OK && d->fail_rank == rank) local = fail(FF_ERR_OOM, "injected failure on rank %d (FF_DEBUG_DIST_FAIL_RANK)", rank);
     if (local == FF_OK) {
         if (strip_rows <= 0) strip_rows = default_strip_rows(world, params->height);
@@ -681,6 +683,7 @@ int ff_multi_render(FfMulti* m, const FfCamera* camera, const FfRenderParams* pa
         const int st = check_render_call(s, camera, params, "ff_multi_render");
         if (st != FF_OK) return st;
     }
+    if (params->shade_mode == FF_SHADE_DIFFUSE_PATH_NEE) return fail(FF_ERR_UNSUPPORTED, "ff_multi_render: FF_SHADE_DIFFUSE_PATH_NEE renders on one device only");
     FfState* root = m->states[0];
     FF_HIP(hipSetDevice(root->device));
     RootOutputs out;
@@ -705,6 +708,7 @@ int ff_multi_render_to_pbo(FfMulti* m, const FfCamera* camera, const FfRenderPar
         const int st = check_render_call(s, camera, params, "ff_multi_render_to_pbo");
         if (st != FF_OK) return st;
     }
+    if (params->shade_mode == FF_SHADE_DIFFUSE_PATH_NEE) return fail(FF_ERR_UNSUPPORTED, "ff_multi_render_to_pbo: FF_SHADE_DIFFUSE_PATH_NEE renders on one device only");
     if (params->width != root->pbo_width || params->height != root->pbo_height)
         return fail(FF_ERR_INVALID_ARG, "ff_multi_render_to_pbo: params are %dx%d but the registered buffer is %dx%d", params->width, params->height, root->pbo_width, root->pbo_height);
     FF_HIP(hipSetDevice(root->device));

@@ -147,6 +147,20 @@ struct RayBatchParams {
     unsigned long long* guard_hits; // += 1 per query the traversal loop guard cut short (must stay 0)
 };
 
+// Next-event estimation (FF_SHADE_DIFFUSE_PATH_NEE, nee_path_kernel): the frame's KParams plus the device light table.
+// The light sample's random numbers come from the BSDF stream's counter (pixel, s << 8 | b) under these keys (ff_api.h).
+constexpr unsigned kNeeKeySelect = 0x6A09E667u; // key ^ this: (primitive by the alias table, alias coin)
+constexpr unsigned kNeeKeyPoint = 0xBB67AE85u;  // key ^ this: (u, v) of the point on the primitive
+struct NeeParams {
+    KParams k;
+    // 5 float4 per entry: {v0 (world corner / vertex), record index}, {edge a, caller's triangle index or -1 for a plane},
+    // {edge b, alias entry}, {unit normal, alias acceptance probability}, {pdf per unit area of the entry's geometry, 0, 0, 0}
+    const float4* lights;
+    int num_lights;
+    const float* light_pdf; // per record (processing order): pdf per unit area of a light sample on it; 0 for geometries not in the table
+    unsigned items;         // items of this launch: pix_items x (block_end - block_begin)
+};
+
 // LDS bytes the BVH kernels need for (lds_nodes, stack_depth).
 size_t bvh_lds_bytes(int lds_nodes, int stack_depth, int block_threads, int num_geoms);
 // Largest node count that fits LDS next to a stack of `stack_depth` entries per lane.
@@ -176,6 +190,8 @@ hipError_t launch_deinterleave(const void* src, void* dst, int width, int height
 // image order; rgb8 / radiance are the full-frame outputs (either may be null).
 hipError_t launch_unpack_strips(const void* src, unsigned char* rgb8, float* radiance, int width, int height, int strip_rows, int num_parts,
                                 hipStream_t stream);
+// One launch of the NEE path kernel (grid_blocks workgroups of kBlockThreads, persistent over np.items).
+hipError_t launch_nee(const NeeParams& np, int trace_mode, int grid_blocks, hipStream_t stream, const char** kernel_name);
 hipError_t prepare_kernels(); // one-time function attributes (dynamic LDS limit)
 
 } // namespace ff

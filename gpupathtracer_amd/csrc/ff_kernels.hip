@@ -3108,6 +3108,207 @@ __global__ void unpack_strips_kernel(const unsigned char* __restrict__ src, unsi
     }
 }
 
+
+// ---- next-event estimation (FF_SHADE_DIFFUSE_PATH_NEE; the estimator is spelled out in ff_api.h) ------------------------------
+//
+// One thread per (pixel, sample block) item, persistent: thread t of the launch takes the items t, t + T, t + 2T, ... (T threads;
+// item i is pixel item i % pix_items of block i / pix_items, so a wave's lanes start on neighbouring pixels of one tile).  Every
+// pass of the loop answers ONE closest-hit query per lane - a path's extension ray or the shadow ray of its last diffuse vertex -
+// with the mega-kernels' own closest_hit_deferred / closest_hit_brute, and the path then goes on with the mega-kernels' own scatter().
+// A block's samples are summed in order into blocksums[pixel][block] and combine_kernel adds the blocks, so with an empty light table
+// every sum is FF_SHADE_DIFFUSE_PATH's bit for bit.  Kept apart from trace_bvh_kernel, which it leaves as it was.
+__device__ __forceinline__ float nee_u24(unsigned r) { return (float)(r >> 8) * 5.9604644775390625e-08f; }
+
+template <int MODE, int BIG = 0>
+__global__ __launch_bounds__(kBlockThreads) void nee_path_kernel(const NeeParams np)
+{
+    const KParams& p = np.k;
+    const int tid = threadIdx.x;
+    const int lane = tid & (kWave - 1);
+    const LdsT<BIG> L = make_lds<BIG>(p.lds_nodes, p.stack_depth, kBlockThreads, tid, p.num_quads, nullptr, p.geoms, p.top_first, p.top_lds_first,
+                                      p.top_lds_count, BIG ? p.num_scan : 0, p.stack_spill);
+    const uint4* nodes4 = reinterpret_cast<const uint4*>(p.nodes4);
+    if (MODE == FF_TRACE_BVH) stage_scene(L, nodes4, p.geoms, p.num_geoms, p.num_planes, tid, kBlockThreads);
+    float4* batch = reinterpret_cast<float4*>(ff_smem);
+    constexpr float kInvPi = 0.31830988618379067f;
+    Counters cnt = {};
+    Path P;
+    init_path(P);
+    unsigned next = blockIdx.x * kBlockThreads + tid;
+    const unsigned stride = gridDim.x * kBlockThreads;
+    bool active = false;
+    float Lx = 0.f, Ly = 0.f, Lz = 0.f; // radiance of the current sample
+    float prev_pdf = 0.f;               // pdf_b (solid angle) of the direction the current ray was drawn with; 0: camera or specular
+    bool shadow = false;                // the next query is the shadow ray below
+    Ray sray = { 0.f, 0.f, 0.f, 0.f, 0.f, 1.f };
+    int sgeom = -1, sprim = -1;         // the sampled primitive: record index, caller's triangle index (-1: a plane)
+    float scx = 0.f, scy = 0.f, scz = 0.f; // what the light sample adds if the shadow ray reaches it
+    for (;;) {
+        while (!active && next < np.items) {
+            const unsigned item = next;
+            next += stride;
+            const unsigned blk = item / p.pix_items, pitem = item - blk * p.pix_items;
+            const int tile = (int)(pitem >> 6), in = (int)(pitem & 63u);
+            const int lx = (tile % p.tiles_per_row) * 8 + (in & 7);
+            const int ly = (tile / p.tiles_per_row) * 8 + (in >> 3);
+            const int strip = ly / p.strip_rows;
+            const int gy = p.y0 + (strip * p.num_parts + p.part) * p.strip_rows + (ly - strip * p.strip_rows);
+            const int gx = p.x0 + lx;
+            if (lx < p.local_width && gx < p.xlim && ly < p.local_rows && gy < p.ylim) {
+                const int block = p.block_begin + (int)blk;
+                active = true;
+                P.gxy = (unsigned)gx | ((unsigned)gy << 16);
+                P.item = (int)(((unsigned)block << kItemBlockShift) | pitem);
+                P.s = block * p.block_spp;
+                P.send = min(p.spp_total, P.s + p.block_spp);
+                P.ax = P.ay = P.az = 0.f;
+                primary_ray(p, P.gxy, P.ray);
+                P.pdx = P.ray.dx;
+                P.pdy = P.ray.dy;
+                P.pdz = P.ray.dz;
+                start_sample(p, P);
+                Lx = Ly = Lz = 0.f;
+                prev_pdf = 0.f;
+                shadow = false;
+            }
+        }
+        Best best;
+        if (MODE == FF_TRACE_BRUTE_FORCE) {
+            if (__syncthreads_or(active ? 1 : 0) == 0) break; // (every thread of the workgroup stages the triangle batches)
+            closest_hit_brute<false>(p.geoms, p.num_geoms, p.tris, batch, active, shadow ? sray : P.ray, best, cnt);
+        } else {
+            if (__ballot(active) == 0ull) break;
+            if (active) closest_hit_deferred<false>(L, p.walls, p.geoms, p.num_geoms, p.num_planes, p.tris, nodes4, shadow ? sray : P.ray, best, cnt);
+        }
+        if (!active) continue;
+        if (shadow) {
+            // visible iff the closest hit is the sampled primitive itself
+            shadow = false;
+            if (best.geom == sgeom && (sprim < 0 || (best.rec >= 0 && p.tris[best.rec].orig_index == sprim))) {
+                Lx = Lx + scx;
+                Ly = Ly + scy;
+                Lz = Lz + scz;
+            }
+            continue;
+        }
+        const bool hit = best.geom >= 0;
+        MaterialRef M;
+        M.global = p.geoms + (hit ? best.geom : 0);
+        M.geom_base = 0;
+        M.g = 0;
+        bool goes_on = false;
+        if (hit) {
+            const int bxdf = mat_bxdf(M);
+            if (bxdf == FF_BXDF_EMITTER) {
+                // BSDF-sampled emitter hit: weight 1 after the camera or a specular bounce and for emitters the table leaves out
+                const float4 emission = mat_f4(M, 13);
+                float cx = P.bx * emission.x, cy = P.by * emission.y, cz = P.bz * emission.z;
+                const float area_pdf = np.light_pdf[best.geom];
+                if (prev_pdf > 0.f && area_pdf > 0.f) {
+                    float nx, ny, nz;
+                    world_normal(M, best, false, nx, ny, nz);
+                    const float ninv = ieee_rcp(ieee_sqrt(dot3(nx, ny, nz, nx, ny, nz)));
+                    const float cos_y = fabsf(dot3(nx * ninv, ny * ninv, nz * ninv, P.ray.dx, P.ray.dy, P.ray.dz));
+                    const float pl = area_pdf * (best.dist * best.dist) / cos_y;
+                    const float pb2 = prev_pdf * prev_pdf;
+                    const float w = pb2 / (pb2 + pl * pl);
+                    cx = cx * w;
+                    cy = cy * w;
+                    cz = cz * w;
+                }
+                Lx = Lx + cx;
+                Ly = Ly + cy;
+                Lz = Lz + cz;
+            } else {
+                const bool glass = bxdf == FF_BXDF_GLASS;
+                const float4 albedo = mat_f4(M, 12);
+                if (!glass) {
+                    P.bx = P.bx * albedo.x;
+                    P.by = P.by * albedo.y;
+                    P.bz = P.bz * albedo.z;
+                }
+                goes_on = P.b != p.bounces - 1;
+            }
+        }
+        if (goes_on) {
+            const int bxdf = mat_bxdf(M);
+            const bool diffuse = bxdf != FF_BXDF_MIRROR && bxdf != FF_BXDF_GLASS;
+            // the flipped unit shading normal scatter() uses
+            float ux, uy, uz;
+            {
+                float nx, ny, nz;
+                world_normal(M, best, false, nx, ny, nz);
+                const float ninv = ieee_rcp(ieee_sqrt(dot3(nx, ny, nz, nx, ny, nz)));
+                ux = nx * ninv; uy = ny * ninv; uz = nz * ninv;
+                if (dot3(ux, uy, uz, P.ray.dx, P.ray.dy, P.ray.dz) > 0.0f) { ux = -ux; uy = -uy; uz = -uz; }
+            }
+            if (diffuse && np.num_lights > 0) {
+                // light sample: primitive by the alias table, point uniform on it (keys in ff_api.h)
+                const unsigned gpix = (P.gxy >> 16) * (unsigned)p.width + (P.gxy & 0xFFFFu);
+                const unsigned ctr = ((unsigned)P.s << 8) | ((unsigned)P.b & 0xFFu);
+                unsigned r0, r1, q0, q1;
+                philox2x32_10(gpix, ctr, p.key ^ kNeeKeySelect, r0, r1);
+                philox2x32_10(gpix, ctr, p.key ^ kNeeKeyPoint, q0, q1);
+                int e = (int)(((unsigned long long)r0 * (unsigned long long)np.num_lights) >> 32);
+                const float4 a0 = np.lights[5 * e + 3];
+                if (!(nee_u24(r1) < a0.w)) e = __float_as_int(np.lights[5 * e + 2].w);
+                const float4 v0 = np.lights[5 * e], ea = np.lights[5 * e + 1], eb = np.lights[5 * e + 2], nrm = np.lights[5 * e + 3], ex = np.lights[5 * e + 4];
+                const int prim = __float_as_int(ea.w);
+                float su = nee_u24(q0), sv = nee_u24(q1);
+                if (prim >= 0) { // triangle: the square-root warp
+                    const float r = ieee_sqrt(su);
+                    su = r * (1.0f - sv);
+                    sv = r * sv;
+                }
+                const float yx = v0.x + (su * ea.x + sv * eb.x), yy = v0.y + (su * ea.y + sv * eb.y), yz = v0.z + (su * ea.z + sv * eb.z);
+                const float dx = yx - best.px, dy = yy - best.py, dz = yz - best.pz;
+                const float d2 = dot3(dx, dy, dz, dx, dy, dz);
+                const float dinv = ieee_rcp(ieee_sqrt(d2));
+                const float wx = dx * dinv, wy = dy * dinv, wz = dz * dinv;
+                const float cos_x = dot3(ux, uy, uz, wx, wy, wz);
+                const float cos_y = fabsf(dot3(nrm.x, nrm.y, nrm.z, wx, wy, wz));
+                if (cos_x > 0.f && cos_y > 0.f && d2 > 0.f) {
+                    const int g = __float_as_int(v0.w);
+                    const float4 le = reinterpret_cast<const float4*>(p.geoms + g)[13];
+                    const float pl = ex.x * d2 / cos_y;
+                    const float pb = cos_x * kInvPi;
+                    const float pl2 = pl * pl;
+                    const float f = (pb * (pl2 / (pl2 + pb * pb))) / pl; // (cos_x / pi) * w_l / pdf_l
+                    scx = (P.bx * le.x) * f;
+                    scy = (P.by * le.y) * f;
+                    scz = (P.bz * le.z) * f;
+                    sgeom = g;
+                    sprim = prim;
+                    sray.ox = best.px + ux * kRayEps;
+                    sray.oy = best.py + uy * kRayEps;
+                    sray.oz = best.pz + uz * kRayEps;
+                    sray.dx = wx;
+                    sray.dy = wy;
+                    sray.dz = wz;
+                    shadow = true;
+                }
+            }
+            scatter<true>(p, best, M, P);
+            prev_pdf = diffuse ? dot3(ux, uy, uz, P.ray.dx, P.ray.dy, P.ray.dz) * kInvPi : 0.f;
+            continue;
+        }
+        // the sample ends here: its radiance joins the block's sum
+        P.ax = P.ax + Lx;
+        P.ay = P.ay + Ly;
+        P.az = P.az + Lz;
+        Lx = Ly = Lz = 0.f;
+        prev_pdf = 0.f;
+        ++P.s;
+        if (P.s < P.send) {
+            start_sample(p, P);
+        } else {
+            p.blocksums[(size_t)((unsigned)P.item & kItemPixelMask) * p.num_blocks + ((unsigned)P.item >> kItemBlockShift)] = make_float4(P.ax, P.ay, P.az, 0.f);
+            active = false;
+        }
+    }
+    flush_counters(p, lane, cnt, false);
+}
+
 } // namespace
 
 #ifdef FF_PROBE
@@ -3178,6 +3379,9 @@ hipError_t prepare_kernels()
     FF_SET_LDS((ray_batch_kernel<FF_TRACE_BVH>))
     FF_SET_LDS((ray_batch_kernel<FF_TRACE_BVH, 1>))
     FF_SET_LDS((ray_batch_kernel<FF_TRACE_BVH, 2>))
+    FF_SET_LDS((nee_path_kernel<FF_TRACE_BVH>))
+    FF_SET_LDS((nee_path_kernel<FF_TRACE_BVH, 1>))
+    FF_SET_LDS((nee_path_kernel<FF_TRACE_BVH, 2>))
 #undef FF_SET_LDS
     return hipSuccess;
 }
@@ -3300,6 +3504,23 @@ hipError_t launch_ray_batch(const RayBatchParams& p, int trace_mode, hipStream_t
     else if (trace_mode == FF_TRACE_BVH && big == 2) hipLaunchKernelGGL((ray_batch_kernel<FF_TRACE_BVH, 2>), grid, block, lds, stream, p);
     else if (trace_mode == FF_TRACE_BVH) hipLaunchKernelGGL((ray_batch_kernel<FF_TRACE_BVH>), grid, block, lds, stream, p);
     else hipLaunchKernelGGL((ray_batch_kernel<FF_TRACE_BRUTE_FORCE>), grid, block, lds, stream, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_nee(const NeeParams& np, int trace_mode, int grid_blocks, hipStream_t stream, const char** kernel_name)
+{
+    if (np.items == 0u) return hipSuccess;
+    const KParams& p = np.k;
+    const int big = p.num_geoms <= kChunkGeometries ? 0 : (p.num_geoms <= kMaxLdsRecords ? 1 : 2);
+    const size_t lds = trace_mode == FF_TRACE_BVH ? bvh_lds_bytes(p.lds_nodes, p.stack_depth, kBlockThreads, big == 2 ? 0 : p.num_geoms)
+                                                  : (size_t)kBruteBatchTris * sizeof(TriRecord);
+    const dim3 grid(grid_blocks), block(kBlockThreads);
+    const char* name;
+    if (trace_mode == FF_TRACE_BVH && big == 1) { hipLaunchKernelGGL((nee_path_kernel<FF_TRACE_BVH, 1>), grid, block, lds, stream, np); name = "nee_path_kernel<1, 1>"; }
+    else if (trace_mode == FF_TRACE_BVH && big == 2) { hipLaunchKernelGGL((nee_path_kernel<FF_TRACE_BVH, 2>), grid, block, lds, stream, np); name = "nee_path_kernel<1, 2>"; }
+    else if (trace_mode == FF_TRACE_BVH) { hipLaunchKernelGGL((nee_path_kernel<FF_TRACE_BVH>), grid, block, lds, stream, np); name = "nee_path_kernel<1, 0>"; }
+    else { hipLaunchKernelGGL((nee_path_kernel<FF_TRACE_BRUTE_FORCE>), grid, block, lds, stream, np); name = "nee_path_kernel<0, 0>"; }
+    if (kernel_name) *kernel_name = name;
     return hipGetLastError();
 }
 

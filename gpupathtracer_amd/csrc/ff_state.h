@@ -124,6 +124,17 @@ struct FfState {
     std::vector<unsigned char> tp_has_model, tp_replaced;
     // sub-pixel jitter of the primary rays (ff_set_pixel_jitter): composed into the ray matrix of ff_render* and ff_gbuffer
     float jitter_x = 0.f, jitter_y = 0.f;
+    // Next-event estimation (ff_nee.cpp): what the light table is built from - the uploaded geometries (caller order) with their
+    // materials and, for meshes, the object-space triangles kept since the upload or the last ff_update_mesh - and the device table
+    std::vector<FfGeometry> nee_geoms;
+    std::vector<FfBXDF> nee_bxdfs;
+    std::vector<std::vector<FfTriangle>> nee_tris;
+    bool nee_valid = false;            // the device table belongs to the uploaded scene (scenes uploaded compiled have none)
+    int nee_num_lights = 0;
+    float4* d_nee_lights = nullptr;    // ff::NeeParams::lights
+    size_t nee_lights_bytes = 0;
+    float* d_nee_pdf = nullptr;        // ff::NeeParams::light_pdf
+    size_t nee_pdf_bytes = 0;
     // temporal anti-aliasing (ff_taa, ff_taa.hip): two history buffers of one float4 per pixel {rgb, len} that swap by index, then
     // the motion (float2 per pixel).  taa_cur: the buffer the last call wrote.  The history describes the camera, image size and
     // per-geometry model matrices of that call; taa_replaced marks the meshes ff_update_mesh changed since.
@@ -216,6 +227,13 @@ int render_enqueue(FfState* s, const FfCamera* camera, const FfRenderParams* prm
 int render_finish(FfState* s);
 
 void dist_release(FfState* s); // ff_dist.cpp: frees s->dist (called by ff_destroy)
+
+// Next-event estimation (ff_nee.cpp): keep the geometries the light table is built from (upload: drop the old ones first), take a
+// mesh's replaced triangles, rebuild the device table, and enqueue a frame of FF_SHADE_DIFFUSE_PATH_NEE (called by render_enqueue).
+void nee_capture(FfState* s, const FfGeometry* g, int n, bool upload);
+void nee_replace_mesh(FfState* s, int geometry_index, const FfTriangle* tris, int count);
+int nee_rebuild(FfState* s);
+int enqueue_nee(FfState* s, KParams& k, const FfRenderParams* prm, int launches, int blocks_per_launch, size_t local_pixels);
 
 // ff_upload_scene for a scene already compiled on the host (ff_api.cpp).
 int upload_compiled_scene(FfState* s, const CompiledScene& cs, double build_ms);

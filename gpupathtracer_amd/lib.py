@@ -30,6 +30,7 @@ EXPORTS = [
     "ff_temporal_params_init", "ff_denoise_temporal", "ff_temporal_reset", "ff_temporal_history",
     "ff_camera_ray_matrix_jittered", "ff_set_pixel_jitter", "ff_multi_set_pixel_jitter", "ff_jitter_sequence",
     "ff_taa_params_init", "ff_taa", "ff_taa_reset", "ff_taa_history",
+    "ff_light_table", "ff_check_render_params",
 ]
 DIST_ID_BYTES = 128
 
@@ -161,6 +162,8 @@ def load():
     lib.ff_set_pixel_jitter.argtypes = [vp, C.c_float, C.c_float]
     lib.ff_multi_set_pixel_jitter.argtypes = [vp, C.c_float, C.c_float]
     lib.ff_jitter_sequence.argtypes = [i32, i32, P(C.c_float), P(C.c_float)]
+    lib.ff_light_table.argtypes = [P(T.FfGeometry), i32, P(T.FfLightEntry), i32, P(C.c_float)]
+    lib.ff_check_render_params.argtypes = [P(T.FfRenderParams)]
     lib.ff_taa_params_init.argtypes = [P(T.FfTaaParams)]
     lib.ff_taa_params_init.restype = None
     lib.ff_taa.argtypes = [vp, P(T.FfCamera), i32, i32, P(T.FfTaaParams), vp, vp, vp, i32, vp, i32, vp, i32]
@@ -235,6 +238,33 @@ def scene_info(scene):
     info = T.FfSceneInfo()
     check(load().ff_scene_info(scene.geometries, len(scene), C.byref(info)))
     return info
+
+
+def light_table(scene):
+    """The light table FF_SHADE_DIFFUSE_PATH_NEE samples (host-only, ff_light_table): (entries, pdf_area) with entries a dict of
+    numpy arrays - geometry, primitive, area, probability, v0, e1, e2, normal [n, 3], alias_probability, alias - and pdf_area the
+    pdf per unit area of a light sample on each caller geometry (0 outside the table)."""
+    lib = load()
+    n = len(scene)
+    count = lib.ff_light_table(scene.geometries, n, None, 0, None)
+    if count < 0:
+        check(-count)
+    buf = (T.FfLightEntry * max(count, 1))()
+    pdf = np.zeros(max(n, 1), dtype=np.float32)
+    got = lib.ff_light_table(scene.geometries, n, buf, count, pdf.ctypes.data_as(C.POINTER(C.c_float)))
+    if got < 0:
+        check(-got)
+    rows = list(buf)[:count]
+    vec = lambda name: np.array([[getattr(r, name).x, getattr(r, name).y, getattr(r, name).z] for r in rows], dtype=np.float32).reshape(count, 3)
+    entries = {name: np.array([getattr(r, name) for r in rows], dtype=np.int32) for name in ("geometry", "primitive", "alias")}
+    entries.update({name: np.array([getattr(r, name) for r in rows], dtype=np.float32) for name in ("area", "probability", "alias_probability")})
+    entries.update({name: vec(name) for name in ("v0", "e1", "e2", "normal")})
+    return entries, pdf[:n]
+
+
+def check_render_params(params):
+    """ff_check_render_params: the status every render entry point's parameter check gives `params` (host-only)."""
+    return load().ff_check_render_params(C.byref(params))
 
 
 def render_params(width, height, bounces=1, spp=1, seed=1234, trace_mode=T.TRACE_BVH, shade_mode=T.SHADE_DIFFUSE_PATH,

@@ -172,6 +172,15 @@ class FfSceneInfo(C.Structure):
     ]
 
 
+class FfLightEntry(C.Structure):
+    _fields_ = [
+        ("geometry", C.c_int32), ("primitive", C.c_int32), ("area", C.c_float), ("probability", C.c_float),
+        ("v0", FfVec3), ("e1", FfVec3), ("e2", FfVec3), ("normal", FfVec3),
+        ("alias_probability", C.c_float), ("alias", C.c_int32),
+    ]
+
+
+assert C.sizeof(FfLightEntry) == 72
 assert C.sizeof(FfBXDF) == 60
 assert C.sizeof(FfTriangle) == 96
 assert C.sizeof(FfGeometry) == 208
@@ -183,7 +192,7 @@ assert C.sizeof(FfCamera) == 108
 BXDF_EMITTER, BXDF_DIFFUSE, BXDF_MIRROR, BXDF_GLASS, BXDF_COUNT = range(5)
 GEOM_SPHERE, GEOM_PLANE, GEOM_TRIANGLEMESH = range(3)
 TRACE_BRUTE_FORCE, TRACE_BVH = 0, 1
-SHADE_NORMAL_DEBUG, SHADE_DIFFUSE_PATH, SHADE_DIFFUSE_PATH_SMOOTH = 0, 1, 2
+SHADE_NORMAL_DEBUG, SHADE_DIFFUSE_PATH, SHADE_DIFFUSE_PATH_SMOOTH, SHADE_DIFFUSE_PATH_NEE = 0, 1, 2, 3
 GRID_FULL, GRID_REFERENCE_FLOOR = 0, 1
 
 # status codes (ff_api.h)

@@ -287,6 +287,46 @@ FF_API int ff_render_progressive(FfState* state, const FfCamera* camera, const F
 /* The same into the registered pixel buffer (the per-frame block of kernel.cu:335-344). */
 FF_API int ff_render_to_pbo_progressive(FfState* state, const FfCamera* camera, const FfRenderParams* params, int frame_index);
 
+/* ---- next-event estimation (FF_SHADE_DIFFUSE_PATH_NEE; no counterpart in the reference) ---- */
+
+/* FF_SHADE_DIFFUSE_PATH_NEE has FF_SHADE_DIFFUSE_PATH's expectation for the same scene, camera, jitter and bounces, with lower
+ * variance.  Per sample, with beta the throughput and L the sample's radiance (L = 0 at the camera):
+ *   BSDF side: camera rays, scatter directions, throughput updates, mirror, glass, the 1e-4 n^ origin offset and the accumulation
+ *     (blocks of 64 samples summed in order, blocks added in order, times 1/spp) are FF_SHADE_DIFFUSE_PATH's, with its random
+ *     numbers: Philox2x32-10, counter (gpix, s << 8 | b), key = seed ^ (seed >> 32) (gpix = y * width + x, s sample, b segment).
+ *   Light table (ff_light_table): one entry per emitting plane (the world image of its unit quad) and per triangle of an emitting
+ *     mesh; spheres and emitters of zero luminance are left out.  lum = 0.2126 r + 0.7152 g + 0.0722 b of m_emissiveColor * m_intensity;
+ *     entry k is chosen with probability A_k lum_k / S, S = sum_k A_k lum_k, so pdf_A(g) = lum_g / S per unit area on geometry g
+ *     (0 for geometries not in the table).
+ *   Light sample, at a diffuse hit x of segment b < bounces - 1 (beta already holds this hit's albedo; n^ = the unit geometric
+ *     normal flipped against the incoming ray, as scatter uses it):
+ *       (r0, r1) = Philox(gpix, s << 8 | b, key ^ 0x6A09E667):  k = floor(r0 * n / 2^32); if !((r1 >> 8) / 2^24 < alias_probability_k)
+ *                                                                k = alias_k
+ *       (q0, q1) = Philox(gpix, s << 8 | b, key ^ 0xBB67AE85):  u = (q0 >> 8) / 2^24, v = (q1 >> 8) / 2^24
+ *       y = v0 + u e1 + v e2 (plane);  y = v0 + sqrt(u)(1 - v) e1 + sqrt(u) v e2 (triangle)
+ *       w = unit(y - x), d2 = |y - x|^2, cos_x = n^ . w, cos_y = |n_y . w|
+ *       if cos_x > 0 and cos_y > 0: a shadow ray from x + 1e-4 n^ along w; the sample is visible iff the ray's closest hit is the
+ *       sampled primitive (same geometry; same triangle for meshes).  Then
+ *         pdf_l = pdf_A(g) d2 / cos_y,  pdf_b = cos_x / pi,  w_l = pdf_l^2 / (pdf_l^2 + pdf_b^2)
+ *         L += beta Le (cos_x / pi) w_l / pdf_l
+ *   BSDF-sampled emitter hits: L += beta Le after the camera ray or a mirror / glass bounce; after a diffuse bounce
+ *     L += beta Le w_b, w_b = pdf_b^2 / (pdf_b^2 + pdf_l^2), pdf_b = cos / pi of the sampled direction at the previous vertex,
+ *     pdf_l = pdf_A(hit geometry) t^2 / |n . w| (t the hit distance); pdf_A = 0 (weight 1) for geometries not in the table.
+ *   No light sample on the last segment, so the mode's expectation is FF_SHADE_DIFFUSE_PATH's at the same bounces.  With an empty
+ *   table every sample is FF_SHADE_DIFFUSE_PATH's bit for bit.  Results do not depend on the lane, spp_per_launch, tile or strip.
+ * Geometric normals only (smooth-normal NEE is not offered).  ff_render, ff_render_tile, ff_render_strips, ff_render_progressive
+ * and the pixel-buffer twins render it; ff_render_distributed and ff_multi_render* return FF_ERR_UNSUPPORTED, and so does a state
+ * whose scene came from ff_multi_upload_scene.  FfStats: rays_traced counts extension and shadow rays, kernel_ms / kernel_launches
+ * cover the NEE kernel launches and the combine pass, rays_answered and rays_cut_short are 0. */
+
+/* Host-only: the light table FF_SHADE_DIFFUSE_PATH_NEE samples for a host scene, as ff_upload_scene builds it (in double, stored as
+ * float).  Writes up to max_entries entries (may be 0 with out_entries NULL) and, if out_pdf_area is not NULL, n floats: pdf_A per
+ * caller geometry (0 outside the table).  Returns the number of entries, or minus an FfStatus.  Needs no GPU. */
+FF_API int ff_light_table(const FfGeometry* host_geometries, int n, FfLightEntry* out_entries, int max_entries, float* out_pdf_area);
+
+/* Host-only: FF_OK if every render entry point would accept `params` (sizes, bounces, spp, modes), else FF_ERR_INVALID_ARG. */
+FF_API int ff_check_render_params(const FfRenderParams* params);
+
 /* ---- G-buffer and denoiser (no counterpart in the reference) ----------------------------- */
 
 /* What every pixel's primary ray (kernel.cu:197-205) hits: I = intersectRays (kernel.cu:127-176) for that ray, the FfIntersect

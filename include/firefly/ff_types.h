@@ -135,8 +135,10 @@ typedef enum FfTraceMode {
 typedef enum FfShadeMode {
     FF_SHADE_NORMAL_DEBUG = 0, /* kernel.cu:178-184: colour = abs(world normal); bounces/spp forced to 1 */
     FF_SHADE_DIFFUSE_PATH = 1, /* N-bounce integrator with the dormant BXDF semantics, utilities.h:90-138 */
-    FF_SHADE_DIFFUSE_PATH_SMOOTH = 2 /* the same, shading triangles with the interpolated vertex normals Triangle carries
-                                      * (utilities.h:163-170) through the barycentrics of kernel.cu:80-81 */
+    FF_SHADE_DIFFUSE_PATH_SMOOTH = 2, /* the same, shading triangles with the interpolated vertex normals Triangle carries
+                                       * (utilities.h:163-170) through the barycentrics of kernel.cu:80-81 */
+    FF_SHADE_DIFFUSE_PATH_NEE = 3 /* FF_SHADE_DIFFUSE_PATH's expectation with next-event estimation and multiple importance
+                                   * sampling at diffuse vertices (lower variance); the estimator is in ff_api.h */
 } FfShadeMode;
 
 typedef enum FfGridMode {
@@ -204,6 +206,20 @@ typedef struct FfBuildStats {
     double   copy_ms;          /* of which: host-to-device copies of the caller's triangles */
     double   build_ms;         /* of which: tree construction / refit (host builder: on the CPU; device builder: kernels, synchronised) */
 } FfBuildStats;
+
+/* One entry of the light table FF_SHADE_DIFFUSE_PATH_NEE samples (ff_light_table): an emitting plane (the world image of its unit
+ * quad) or one triangle of an emitting mesh, in world space.  A point of the entry is v0 + u e1 + v e2 with (u, v) in the unit square
+ * (plane) or the triangle u, v >= 0, u + v <= 1. */
+typedef struct FfLightEntry {
+    int32_t geometry;          /* the caller's geometry index */
+    int32_t primitive;         /* triangle index of a mesh, -1 for a plane */
+    float   area;              /* world area */
+    float   probability;       /* selection probability: area * luminance / sum over all entries */
+    FfVec3  v0, e1, e2;        /* corner / first vertex and the two edges from it */
+    FfVec3  normal;            /* unit normal, e1 x e2 / |e1 x e2| */
+    float   alias_probability; /* Vose alias table: entry k = floor(u0 * n) is kept if u1 < alias_probability, else `alias` is taken */
+    int32_t alias;
+} FfLightEntry;                /* 72 bytes */
 
 /* Filled by ff_scene_info(): what ff_upload_scene would build for a host scene (no GPU needed). */
 typedef struct FfSceneInfo {
