@@ -117,12 +117,12 @@ __global__ __launch_bounds__(256) void taa_kernel(const TaaArgs a, const float* 
     const float hx = (float)x + mx, hy = (float)y + my;
     valid = valid && hx >= 0.f && hx <= (float)(W - 1) && hy >= 0.f && hy <= (float)(H - 1);
     float len = 1.f, orr = cr, og = cg, ob = cb;
+    float hr = 0.f, hg = 0.f, hb = 0.f;
     if (valid) {
         const float4* __restrict__ prev = a.hist[1 - a.cur];
         const float flx = floorf(hx), fly = floorf(hy);
         const int x0 = (int)flx, y0 = (int)fly;
         const float ttx = hx - flx, tty = hy - fly;
-        float hr = 0.f, hg = 0.f, hb = 0.f;
         if (a.bilinear) {
             const float wx[2] = { 1.f - ttx, ttx }, wy[2] = { 1.f - tty, tty };
 #pragma unroll
@@ -154,17 +154,26 @@ __global__ __launch_bounds__(256) void taa_kernel(const TaaArgs a, const float* 
                 }
             }
         }
+        // a resampled history that is not finite is no history (ff_api.h): a NaN or Inf stored by an earlier call would otherwise
+        // stay (Catmull-Rom's zero weights at rest multiply it: 0 * NaN = NaN) or turn into the clamp box's bound
+        valid = isfinite(hr) && isfinite(hg) && isfinite(hb);
+    }
+    if (valid) {
         const int nx = min((int)floorf(hx + 0.5f), W - 1), ny = min((int)floorf(hy + 0.5f), H - 1);
-        const float len_h = prev[(size_t)ny * (size_t)W + (size_t)nx].w;
+        const float len_h = a.hist[1 - a.cur][(size_t)ny * (size_t)W + (size_t)nx].w;
         if (a.clamp) {
-            // the 3x3 neighbourhood of the current frame in YCoCg: mean, standard deviation, min and max per channel
+            // the 3x3 neighbourhood of the current frame in YCoCg: mean, standard deviation, min and max per channel over its n
+            // finite samples (a NaN or Inf sample would make every neighbour's box, and so its output, non-finite)
             float s1[3] = { 0.f, 0.f, 0.f }, s2[3] = { 0.f, 0.f, 0.f };
             float lo[3] = { INFINITY, INFINITY, INFINITY }, hi[3] = { -INFINITY, -INFINITY, -INFINITY };
+            int n = 0;
 #pragma unroll
             for (int dy = 0; dy < 3; ++dy) {
 #pragma unroll
                 for (int dx = 0; dx < 3; ++dx) {
                     const float r = s_c[0][ty + dy][tx + dx], g = s_c[1][ty + dy][tx + dx], b = s_c[2][ty + dy][tx + dx];
+                    if (!(isfinite(r) && isfinite(g) && isfinite(b))) continue;
+                    ++n;
                     const float q[3] = { (0.25f * r + 0.5f * g) + 0.25f * b, 0.5f * r - 0.5f * b, (-0.25f * r + 0.5f * g) - 0.25f * b };
 #pragma unroll
                     for (int ch = 0; ch < 3; ++ch) {
@@ -175,11 +184,12 @@ __global__ __launch_bounds__(256) void taa_kernel(const TaaArgs a, const float* 
                     }
                 }
             }
+            const float inv_n = n == 9 ? 1.f / 9.f : 1.f / (float)n; // (all nine finite: the constant, as before)
             float h[3] = { (0.25f * hr + 0.5f * hg) + 0.25f * hb, 0.5f * hr - 0.5f * hb, (-0.25f * hr + 0.5f * hg) - 0.25f * hb };
 #pragma unroll
             for (int ch = 0; ch < 3; ++ch) {
-                const float mu = s1[ch] * (1.f / 9.f);
-                const float sigma = sqrtf(fmaxf(0.f, s2[ch] * (1.f / 9.f) - mu * mu));
+                const float mu = s1[ch] * inv_n;
+                const float sigma = sqrtf(fmaxf(0.f, s2[ch] * inv_n - mu * mu));
                 const float bl = fmaxf(lo[ch], mu - a.gamma * sigma), bh = fminf(hi[ch], mu + a.gamma * sigma);
                 h[ch] = fminf(fmaxf(h[ch], bl), bh);
             }

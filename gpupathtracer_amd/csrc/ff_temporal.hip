@@ -18,6 +18,8 @@ __device__ __forceinline__ float dot3(float ax, float ay, float az, float bx, fl
 
 __device__ __forceinline__ float luminance(float r, float g, float b) { return (0.2126f * r + 0.7152f * g) + 0.0722f * b; }
 
+__device__ __forceinline__ bool finite3(float a, float b, float c) { return isfinite(a) && isfinite(b) && isfinite(c); }
+
 constexpr int kTile = 16;            // pass workgroups: 16 x 16 pixels, as ff_denoise's
 constexpr float kPlaneEps = 1e-30f;  // as ff_denoise: |x_q - x_p|^2 = 0 for coincident points
 constexpr float kLumEps = 1e-30f;    // keeps sigma_l sqrt(g) = 0 finite
@@ -116,6 +118,9 @@ __global__ __launch_bounds__(256) void temporal_reproject_kernel(const TemporalB
                 if (!(fabsf(dot3(hnx, hny, hnz, gq.x - xh, gq.y - yh, gq.z - zh)) <= plane_lim)) continue;
                 const float4 cq = b.col[prev][j];
                 const float4 mq = b.mom[prev][j];
+                // a stored value that is not finite is no history (ff_api.h): one NaN or Inf sample would otherwise stay in the
+                // blend for good at rest and spread through the bilinear taps under motion
+                if (!(finite3(cq.x, cq.y, cq.z) && finite3(mq.x, mq.y, mq.z))) continue;
                 wsum += w;
                 hx += w * cq.x;
                 hy += w * cq.y;

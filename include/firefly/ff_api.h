@@ -364,7 +364,10 @@ FF_API void ff_denoise_params_init(FfDenoiseParams* p);
  *                     taps outside the image, not filterable, (FF_DENOISE_SAME_GEOMETRY) on another geometry or with
  *                     w_c w_n w_x < e^-30 weigh 0
  *   output          = c * albedo after the last pass (where it was divided); rgb8 = trunc(clamp(v * 255)) as ff_render's.
- * iterations = 0 copies every pixel through.  Scaling all radiance by k scales the output by k.  rgb8 (W*H*3 bytes) and
+ * iterations = 0 copies every pixel through.  Scaling all radiance by k scales the output by k.
+ * Non-finite input (the rule of all three image filters): a NaN or +-Inf radiance value may make its own pixel's output
+ * non-finite in that call; every other output of the call stays finite.  Here every other pixel's output is bit for bit what
+ * it is when the non-finite pixel's ids mark a miss: its neighbours skip it, as its exponent is not <= 30.  rgb8 (W*H*3 bytes) and
  * radiance_out (W*H*3 floats) may each be NULL; radiance_out may alias radiance_in.  Synchronous; FfStats keeps describing
  * the last frame. */
 FF_API int ff_denoise(FfState* state, int width, int height, const FfDenoiseParams* dn,
@@ -391,7 +394,8 @@ FF_API void ff_temporal_params_init(FfTemporalParams* p);
  *             call's and g not moved: fx = x, fy = y exactly (the one tap is p itself, weight 1)
  *   taps      (floor(fx) + {0,1}, floor(fy) + {0,1}) with bilinear weights w_q; a tap counts when it lies in the previous image,
  *             has p's class there (same geometry, filterable), dot(n^, n_q) >= reuse_normal, |n^.(x_q - x^)| <= reuse_plane *
- *             |x^ - previous eye|, g's mesh was not replaced by ff_update_mesh since the previous call, and w_q > 0
+ *             |x^ - previous eye|, g's mesh was not replaced by ff_update_mesh since the previous call, w_q > 0 and its stored
+ *             colour and moments are all finite
  *   history   W = sum w_q over the taps that count.  W >= 1e-3: h = sum w_q h_q / W for the colour history, both moments and the
  *             length; len = len_h + 1, alpha = 1 / min(len, max_history), acc = h + alpha (cur - h) for colour c and moments
  *             (l, l^2), l = 0.2126 r + 0.7152 g + 0.0722 b of c.  Otherwise len = 1, acc = cur.
@@ -408,7 +412,8 @@ FF_API void ff_temporal_params_init(FfTemporalParams* p);
  * History is dropped by ff_temporal_reset, the first call, a change of width or height and ff_upload_scene; ff_update_mesh(g)
  * drops geometry g's only; ff_update_transforms moves it with its geometry.  The call leaves FfStats, the stored primary hits
  * and their key, the cull mask, ff_denoise's buffers and the progressive sum as they were.  Buffers as in ff_denoise
- * (radiance_out may alias radiance_in).  FF_ERR_NO_SCENE without a scene.  Synchronous.
+ * (radiance_out may alias radiance_in).  FF_ERR_NO_SCENE without a scene.  Synchronous.  Non-finite radiance: ff_denoise's rule
+ * (its own pixel only); such a pixel's history is not reused, so the next call starts it afresh.
  * The pixel jitter (ff_set_pixel_jitter) is not seen here: the previous camera's matrix is the unjittered ff_camera_ray_matrix
  * and "at rest" means FfCamera bitwise equal, so a jittered sequence at rest accumulates each pixel's jittered samples like a
  * progressive mean. */
@@ -445,11 +450,12 @@ FF_API void ff_taa_params_init(FfTaaParams* p);
  *             0 <= h.y <= H-1 and g's mesh was not replaced by ff_update_mesh since the previous call.  Colour: the 4x4
  *             Catmull-Rom sum around floor(h), taps clamped into the image, t = h - floor(h) per axis, weights
  *             ((-t^3 + 2t^2 - t)/2, (3t^3 - 5t^2 + 2)/2, (-3t^3 + 4t^2 + t)/2, (t^3 - t^2)/2) for floor(h) - 1 .. floor(h) + 2,
- *             not renormalised (FF_TAA_BILINEAR: the 2x2 taps floor(h) + {0, 1} with weights (1 - t, t)).  len_h: the
+ *             not renormalised (FF_TAA_BILINEAR: the 2x2 taps floor(h) + {0, 1} with weights (1 - t, t)).  A resampled colour
+ *             that is not finite (a zero weight times a stored NaN included) is no history: invalid.  len_h: the
  *             history length at the nearest tap floor(h + 0.5).  m = 0 gives t = 0: exactly the pixel's own history
  *   clamp     (not with FF_TAA_NO_CLAMP) in YCoCg, Y = r/4 + g/2 + b/4, Co = r/2 - b/2, Cg = -r/4 + g/2 - b/4: over the 3x3
  *             neighbourhood of radiance_in (coordinates clamped at the borders) the mean mu, sigma = sqrt(max(0, E[c^2] - mu^2))
- *             and min / max per channel; the history is clamped per channel to [max(min, mu - gamma sigma),
+ *             and min / max per channel, over the samples whose r, g, b are all finite; the history is clamped per channel to [max(min, mu - gamma sigma),
  *             min(max, mu + gamma sigma)] and converted back (r = Y + Co - Cg, g = Y + Cg, b = Y - Co - Cg)
  *   blend     valid history: len = min(len_h + 1, 4096), alpha = max(alpha_min, 1 / len), o = h + alpha (c - h) in RGB.
  *             Otherwise len = 1 and o = c
@@ -458,7 +464,8 @@ FF_API void ff_taa_params_init(FfTaaParams* p);
  * drops geometry g's only; ff_update_transforms moves it with its geometry.  The call leaves FfStats, the stored primary hits
  * and their key, the cull mask, ff_denoise's buffers, the temporal denoiser's history and the progressive sum as they were.
  * Buffers as in ff_denoise (radiance_out may alias radiance_in).  FF_ERR_NO_SCENE without a scene; FF_ERR_INVALID_ARG for
- * alpha_min outside (0, 1], gamma <= 0 or NaN, unknown flags or a nonzero `reserved`.  Synchronous. */
+ * alpha_min outside (0, 1], gamma <= 0 or NaN, unknown flags or a nonzero `reserved`.  Synchronous.  Non-finite radiance:
+ * ff_denoise's rule (its own pixel only; the next call finds no valid history wherever the resampling reads it). */
 FF_API int ff_taa(FfState* state, const FfCamera* camera, int width, int height, const FfTaaParams* p, const float* radiance_in,
                   const float* position, const int32_t* ids, int inputs_on_device, void* rgb8, int rgb8_on_device, float* radiance_out,
                   int radiance_out_on_device);

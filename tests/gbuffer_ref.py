@@ -79,7 +79,13 @@ def _shift(a, oy, ox, fill):
 
 
 def denoise_ref(radiance, gbuffer, iterations, sigma_color, sigma_normal, sigma_plane, flags):
-    """ff_denoise in float64: returns the output radiance [H,W,3]."""
+    """ff_denoise in float64: returns the output radiance [H,W,3].  A tap that weighs 0 adds nothing, not 0 * its colour: a
+    NaN or Inf pixel stays in its own output (ff_api.h's rule for non-finite input)."""
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        return _denoise_ref(radiance, gbuffer, iterations, sigma_color, sigma_normal, sigma_plane, flags)
+
+
+def _denoise_ref(radiance, gbuffer, iterations, sigma_color, sigma_normal, sigma_plane, flags):
     r = np.asarray(radiance, dtype=np.float64)
     ids = np.asarray(gbuffer["ids"])
     filt = filterable(ids)
@@ -119,9 +125,10 @@ def denoise_ref(radiance, gbuffer, iterations, sigma_color, sigma_normal, sigma_
                 pd = (n * v).sum(-1)
                 a_x = pd * pd / (sigma_plane ** 2 * (v * v).sum(-1) + PLANE_EPS)
                 e = a_c + a_n + a_x
-                w = np.where(ok & (e <= MAX_EXPONENT), B3[dx + 2] * B3[dy + 2] * np.exp(-np.minimum(e, MAX_EXPONENT)), 0.0)
+                take = ok & (e <= MAX_EXPONENT)
+                w = np.where(take, B3[dx + 2] * B3[dy + 2] * np.exp(-np.minimum(e, MAX_EXPONENT)), 0.0)
                 wsum += w
-                acc += w[..., None] * dc
+                acc += np.where(take[..., None], w[..., None] * dc, 0.0)
         c = np.where(filt[..., None], c - acc / wsum[..., None], c)
     if demod:
         c = np.where(div, c * a, c)

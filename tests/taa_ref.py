@@ -6,6 +6,9 @@ resampling, the YCoCg neighbourhood clamp and the blend.  It keeps the history b
 output it reports, per pixel, whether a validity bound or the nearest-tap decision floor(h + 0.5) was within 1e-5 (relative) of its threshold: such
 pixels may legitimately decide the other way in float32.  `tainted` adds every pixel whose history reads one of them with a
 nonzero weight, across calls.
+
+Non-finite input follows ff_api.h: the clamp box is taken over the finite samples of the 3x3 neighbourhood, and a resampled
+history that is not finite (a zero weight times a stored NaN included) is not valid.
 """
 import numpy as np
 
@@ -37,14 +40,18 @@ def _near(v, at):
 
 
 def neighbourhood_box(c, gamma):
-    """(lo, hi) per pixel and YCoCg channel: the 3x3 clamp box of ff_taa over the image c [H,W,3] (borders clamped)."""
-    q = c @ YCOCG.T
+    """(lo, hi) per pixel and YCoCg channel: the 3x3 clamp box of ff_taa over the image c [H,W,3] (borders clamped), over the
+    samples whose r, g, b are all finite."""
     H, W = c.shape[:2]
-    pad = np.pad(q, ((1, 1), (1, 1), (0, 0)), mode="edge")
-    taps = np.stack([pad[dy:dy + H, dx:dx + W] for dy in range(3) for dx in range(3)])
-    mu = taps.mean(0)
-    sigma = np.sqrt(np.maximum(0.0, (taps * taps).mean(0) - mu * mu))
-    return np.maximum(taps.min(0), mu - gamma * sigma), np.minimum(taps.max(0), mu + gamma * sigma)
+    pad = np.pad(c, ((1, 1), (1, 1), (0, 0)), mode="edge")
+    rgb = np.stack([pad[dy:dy + H, dx:dx + W] for dy in range(3) for dx in range(3)])
+    fin = np.isfinite(rgb).all(-1, keepdims=True)
+    taps = np.where(fin, rgb, 0.0) @ YCOCG.T
+    n = fin.sum(0)
+    mu = taps.sum(0) / n
+    sigma = np.sqrt(np.fmax(0.0, (taps * taps).sum(0) / n - mu * mu))
+    lo, hi = np.where(fin, taps, np.inf).min(0), np.where(fin, taps, -np.inf).max(0)
+    return np.fmax(lo, mu - gamma * sigma), np.fmin(hi, mu + gamma * sigma)
 
 
 class TaaRef:
@@ -61,6 +68,10 @@ class TaaRef:
         temporal_ref.scene_models() of the scene as it is now; p: an FfTaaParams or a dict of its fields; replaced: geometries
         whose mesh ff_update_mesh replaced since the last call.  Returns a dict: out [H,W,3] float64, motion [H,W,2],
         length [H,W], valid [H,W] bool, near [H,W] bool, tainted [H,W] bool."""
+        with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+            return self._step(radiance, gbuffer, camera, models, p, replaced)
+
+    def _step(self, radiance, gbuffer, camera, models, p, replaced):
         p = _params(p)
         c = np.asarray(radiance, dtype=np.float32).astype(np.float64)
         H, W = c.shape[:2]
@@ -132,6 +143,7 @@ class TaaRef:
                     w = wy[..., r] * wx[..., k]
                     hist += w[..., None] * prev["hist"][jy, jx]
                     taint |= valid & (w != 0) & prev["taint"][jy, jx]
+            valid &= np.isfinite(hist).all(-1)
             ny = np.clip(np.floor(vy + 0.5), 0, H - 1).astype(int)
             nx = np.clip(np.floor(vx + 0.5), 0, W - 1).astype(int)
             len_h = prev["length"][ny, nx]

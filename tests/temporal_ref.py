@@ -7,6 +7,9 @@ history between calls as the state does.  Besides the output it reports, per pix
 was within 1e-5 (relative) of its threshold: such pixels may legitimately decide the other way in float32.  `tainted` adds every
 pixel whose result reads one of them with a nonzero weight: a tap of the history (across calls), of the spatial variance or of
 a pass.
+
+Non-finite input follows ff_api.h: a tap whose stored colour or moments are not all finite is no history, a tap that weighs 0
+adds nothing (not 0 * its value), and max(0, v) is fmax (a NaN v gives 0), as the kernels compute it.
 """
 import ctypes as C
 
@@ -67,6 +70,10 @@ class TemporalRef:
         """radiance [H,W,3]; gbuffer: ff_gbuffer's dict for `camera`; models: scene_models() of the scene as it is now; tp: an
         FfTemporalParams or a dict of its fields; replaced: geometries whose mesh ff_update_mesh replaced since the last call.
         Returns a dict: out [H,W,3] float64, motion [H,W,2], length [H,W], near [H,W] bool, tainted [H,W] bool."""
+        with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+            return self._step(radiance, gbuffer, camera, models, tp, replaced)
+
+    def _step(self, radiance, gbuffer, camera, models, tp, replaced):
         p = _params(tp)
         rad = np.asarray(radiance, dtype=np.float64)
         H, W = rad.shape[:2]
@@ -121,8 +128,9 @@ class TemporalRef:
             fx = np.where(rest, xs, fx)
             fy = np.where(rest, ys, fy)
             seen |= rest
-            motion = np.where((hit & seen)[..., None], np.stack([fx - xs, fy - ys], -1), 0.0)
-            cand = filt & seen & ~rep & (fx > -1) & (fx < W) & (fy > -1) & (fy < H)
+            known = geom < len(models)  # (ids that name no geometry of the scene have no history and no motion)
+            motion = np.where((hit & known & seen)[..., None], np.stack([fx - xs, fy - ys], -1), 0.0)
+            cand = filt & known & seen & ~rep & (fx > -1) & (fx < W) & (fy > -1) & (fy < H)
             cfx, cfy = np.where(cand, fx, 0.0), np.where(cand, fy, 0.0)
             x0, y0 = np.floor(cfx), np.floor(cfy)
             ax, ay = cfx - x0, cfy - y0
@@ -139,13 +147,17 @@ class TemporalRef:
                 same = inside & (prev["cls"][jy, jx] == cls)
                 dn = (nh * prev["n"][jy, jx]).sum(-1)
                 pd = np.abs((nh * (prev["x"][jy, jx] - xh)).sum(-1))
-                ok = same & (dn >= rn) & (pd <= lim)
-                near |= same & ((np.abs(dn - rn) <= NEAR * max(abs(rn), 1e-30)) | (np.abs(pd - lim) <= NEAR * lim))
+                finite = np.isfinite(prev["col"][jy, jx]).all(-1) & np.isfinite(prev["mom"][jy, jx]).all(-1)
+                ok = same & (dn >= rn) & (pd <= lim) & finite
+                # (pd's float32 error is of the order of the coordinates' rounding, so the band around lim is at least 1e-7 of the
+                # distance: with reuse_plane 0, lim = 0 and a pd of 0 in one precision may be a few ulps in the other)
+                plane_band = NEAR * np.maximum(lim, 1e-2 * np.sqrt(((xh - prev["eye"]) ** 2).sum(-1)))
+                near |= same & ((np.abs(dn - rn) <= NEAR * max(abs(rn), 1e-30)) | (np.abs(pd - lim) <= plane_band))
                 w = np.where(ok, wt, 0.0)
                 inherited |= ok & prev["taint"][jy, jx]
                 wsum += w
-                hc += w[..., None] * prev["col"][jy, jx]
-                hm += w[..., None] * prev["mom"][jy, jx]
+                hc += np.where(ok[..., None], w[..., None] * prev["col"][jy, jx], 0.0)
+                hm += np.where(ok[..., None], w[..., None] * prev["mom"][jy, jx], 0.0)
             near |= (wsum > 0) & (np.abs(wsum - MIN_HISTORY_WEIGHT) <= NEAR * MIN_HISTORY_WEIGHT)
         have = wsum >= MIN_HISTORY_WEIGHT
         sw = np.where(have, wsum, 1.0)[..., None]
@@ -161,7 +173,7 @@ class TemporalRef:
         c = acc
         taint = near | inherited
         if p["iterations"] > 0:
-            var = np.maximum(0.0, m2 - m1 * m1)
+            var = np.fmax(0.0, m2 - m1 * m1)
             short = filt & (length < p["variance_history"])
             if short.any():
                 inv_sn = 1.0 / np.float64(np.float32(p["sigma_normal"]))
@@ -178,13 +190,14 @@ class TemporalRef:
                         pd = (n * v).sum(-1)
                         a_x = pd * pd / (sp2 * (v * v).sum(-1) + PLANE_EPS)
                         e = a_n + a_x
-                        w = np.where(ok & (e <= MAX_EXPONENT), np.exp(-np.minimum(e, MAX_EXPONENT)), 0.0)
+                        take = ok & (e <= MAX_EXPONENT)
+                        w = np.where(take, np.exp(-np.minimum(e, MAX_EXPONENT)), 0.0)
                         ws += w
                         taint = taint | (short & (w > 0) & _shift(near | inherited, dy, dx, False))
-                        s1 += w * _shift(m1, dy, dx, 0.0)
-                        s2 += w * _shift(m2, dy, dx, 0.0)
+                        s1 += np.where(take, w * _shift(m1, dy, dx, 0.0), 0.0)
+                        s2 += np.where(take, w * _shift(m2, dy, dx, 0.0), 0.0)
                 mu1, mu2 = s1 / ws, s2 / ws
-                spatial = np.maximum(0.0, mu2 - mu1 * mu1) * 4.0 / np.where(length > 0, length, 1.0)
+                spatial = np.fmax(0.0, mu2 - mu1 * mu1) * 4.0 / np.where(length > 0, length, 1.0)
                 var = np.where(short, spatial, var)
             var = np.where(filt, var, 0.0)
             c, var, fed, taint = atrous_passes(c, var, n, x, cls, filt, p, same_geometry, taint)
@@ -244,11 +257,12 @@ def atrous_passes(c, var, n, x, cls, filt, p, same_geometry, taint):
                 pd = (n * v).sum(-1)
                 a_x = pd * pd / (sp2 * (v * v).sum(-1) + PLANE_EPS)
                 e = a_l + a_n + a_x
-                w = np.where(ok & (e <= MAX_EXPONENT), B3[dx + 2] * B3[dy + 2] * np.exp(-np.minimum(e, MAX_EXPONENT)), 0.0)
+                take = ok & (e <= MAX_EXPONENT)
+                w = np.where(take, B3[dx + 2] * B3[dy + 2] * np.exp(-np.minimum(e, MAX_EXPONENT)), 0.0)
                 wsum += w
                 spread |= (w > 0) & _shift(taint, oy, ox, False)
-                vsum += w * w * _shift(var, oy, ox, 0.0)
-                acc += w[..., None] * (c - cq)
+                vsum += np.where(take, w * w * _shift(var, oy, ox, 0.0), 0.0)
+                acc += np.where(take[..., None], w[..., None] * (c - cq), 0.0)
         c = np.where(filt[..., None], c - acc / wsum[..., None], c)
         var = np.where(filt, vsum / (wsum * wsum), var)
         taint = spread
