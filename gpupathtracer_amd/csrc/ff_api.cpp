@@ -296,6 +296,10 @@ int render_enqueue(FfState* s, const FfCamera* camera, const FfRenderParams* prm
     if (local_pixels == 0) return FF_OK;
 
     const bool debug = prm->shade_mode == FF_SHADE_NORMAL_DEBUG;
+    const bool env = s->env_set && !debug; // (FF_SHADE_NORMAL_DEBUG ignores the environment)
+    if (env && prm->shade_mode == FF_SHADE_DIFFUSE_PATH_SMOOTH)
+        return fail(FF_ERR_UNSUPPORTED, "FF_SHADE_DIFFUSE_PATH_SMOOTH does not render under an environment light (ff_set_environment); "
+                    "clear it or use FF_SHADE_DIFFUSE_PATH / FF_SHADE_DIFFUSE_PATH_NEE");
     const int spp = debug ? 1 : prm->spp;
     const int bounces = debug ? 1 : prm->bounces;
     // Samples are accumulated in blocks (a multiple of 64, at most 16 blocks per pixel up to 1024 spp and beyond): a
@@ -384,8 +388,9 @@ int render_enqueue(FfState* s, const FfCamera* camera, const FfRenderParams* prm
     k.top_lds_count = s->top_lds_count;
     k.num_scan = s->num_scan;
     k.walls = s->walls;
-    if (prm->shade_mode == FF_SHADE_DIFFUSE_PATH_NEE) {
-        // (its own kernels: the rest of this function prepares the mega-kernels' frame)
+    if (prm->shade_mode == FF_SHADE_DIFFUSE_PATH_NEE || env) {
+        // (its own kernels: the rest of this function prepares the mega-kernels' frame; under an environment, FF_SHADE_DIFFUSE_PATH
+        // runs there too, with no light table)
         k.rgb8 = rgb8_dev;
         k.radiance = radiance_dev;
         return enqueue_nee(s, k, prm, launches, blocks_per_launch, local_pixels);
@@ -854,6 +859,7 @@ int ff_destroy(FfState* s)
     if (s->d_taa_geoms) (void)hipFree(s->d_taa_geoms);
     if (s->d_nee_lights) (void)hipFree(s->d_nee_lights);
     if (s->d_nee_pdf) (void)hipFree(s->d_nee_pdf);
+    env_release(s);
     free_build_scratch(s->scratch);
     if (s->d_blocksums) (void)hipFree(s->d_blocksums);
     if (s->d_rgb8) (void)hipFree(s->d_rgb8);

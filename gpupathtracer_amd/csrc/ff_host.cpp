@@ -1,6 +1,7 @@
 // ff_host.cpp — host-side pieces of the ABI that need no GPU: error strings, the reference's struct
 // constructors (Geometry, Camera, BXDF) restated with glm's operation order, and the OBJ reader.
 #include <cerrno>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -314,6 +315,9 @@ struct FfSceneFile {
     std::vector<FfTriangle*> meshes;              // malloc'ed by ff_load_obj
     std::vector<std::pair<std::string, FfBXDF*>> bxdfs; // stable addresses
     FfCamera camera;                               // width/height filled per request
+    bool has_env = false;                          // an environment statement: the .hdr path (resolved), intensity, rotation in degrees
+    std::string env_path;
+    float env_intensity = 1.f, env_rotation = 0.f;
     ~FfSceneFile()
     {
         for (FfTriangle* t : meshes) std::free(t);
@@ -450,6 +454,23 @@ int ff_scene_file_load(const char* path, FfSceneFile** out_scene)
             ff_geometry_init(&g, is_mesh ? FF_GEOM_TRIANGLEMESH : (is_sphere ? FF_GEOM_SPHERE : FF_GEOM_PLANE), pos, rot, scl, tris, ntris, radius);
             g.m_bxdf = bx;
             sc->geometries.push_back(g);
+        } else if (tok[0] == "environment") {
+            if (sc->has_env) { bad("a second environment statement"); break; }
+            if (tok.size() < 2) { bad("environment needs an .hdr path"); break; }
+            sc->env_path = (!tok[1].empty() && tok[1][0] == '/') ? tok[1] : dir + tok[1];
+            i = 2;
+            while (status == FF_OK && i < tok.size()) {
+                const std::string key = tok[i++];
+                float v[1];
+                if (key == "intensity") {
+                    if (!read_floats(tok, i, 1, v) || !(v[0] >= 0.f) || !std::isfinite(v[0])) bad("intensity needs a finite number >= 0");
+                    else sc->env_intensity = v[0];
+                } else if (key == "rotation") {
+                    if (!read_floats(tok, i, 1, v) || !std::isfinite(v[0])) bad("rotation needs a finite number");
+                    else sc->env_rotation = v[0];
+                } else bad("unknown environment key");
+            }
+            sc->has_env = true;
         } else {
             bad("unknown statement");
         }
@@ -482,5 +503,15 @@ int ff_scene_file_camera(const FfSceneFile* scene, int width, int height, FfCame
 }
 
 void ff_scene_file_free(FfSceneFile* scene) { delete scene; }
+
+int ff_scene_file_environment(const FfSceneFile* scene, const char** out_path, float* out_intensity, float* out_rotation_deg)
+{
+    ff::clear_error();
+    if (!scene || !scene->has_env) return 0;
+    if (out_path) *out_path = scene->env_path.c_str();
+    if (out_intensity) *out_intensity = scene->env_intensity;
+    if (out_rotation_deg) *out_rotation_deg = scene->env_rotation;
+    return 1;
+}
 
 } // extern "C"

@@ -159,7 +159,17 @@ struct NeeParams {
     int num_lights;
     const float* light_pdf; // per record (processing order): pdf per unit area of a light sample on it; 0 for geometries not in the table
     unsigned items;         // items of this launch: pix_items x (block_end - block_begin)
+    // Environment light (nee_path_kernel<..., ENV = 1> only; ff_env.cpp builds the table, ff_api.h spells out the estimator)
+    const float4* env_texels; // W x H, row 0 = +Y: {intensity x rgb, pdf_env per steradian (p_rc / Omega_rc; 0 if the map is black)}
+    const float2* env_alias;  // W x H: {alias acceptance probability, alias texel (int bits)}
+    const float* env_z;       // H + 1: cos(pi r / H), the rows' bounds in z = cos(theta)
+    int env_w, env_h;
+    float env_rotation;       // radians, in [0, 2 pi)
+    float p_env;              // probability of choosing the environment for a light sample: 0, 1/2 or 1
+    float p_area;             // 1 - p_env: the area lights' share
 };
+// key ^ this: the choice between the environment and the light table when both are there (first output, u24 < p_env: environment)
+constexpr unsigned kEnvKeyChoose = 0x3C6EF372u;
 
 // LDS bytes the BVH kernels need for (lds_nodes, stack_depth).
 size_t bvh_lds_bytes(int lds_nodes, int stack_depth, int block_threads, int num_geoms);
@@ -190,8 +200,9 @@ hipError_t launch_deinterleave(const void* src, void* dst, int width, int height
 // image order; rgb8 / radiance are the full-frame outputs (either may be null).
 hipError_t launch_unpack_strips(const void* src, unsigned char* rgb8, float* radiance, int width, int height, int strip_rows, int num_parts,
                                 hipStream_t stream);
-// One launch of the NEE path kernel (grid_blocks workgroups of kBlockThreads, persistent over np.items).
-hipError_t launch_nee(const NeeParams& np, int trace_mode, int grid_blocks, hipStream_t stream, const char** kernel_name);
+// One launch of the NEE path kernel (grid_blocks workgroups of kBlockThreads, persistent over np.items); env: the instantiation
+// with the environment light (np.env_*).
+hipError_t launch_nee(const NeeParams& np, int trace_mode, bool env, int grid_blocks, hipStream_t stream, const char** kernel_name);
 hipError_t prepare_kernels(); // one-time function attributes (dynamic LDS limit)
 
 } // namespace ff

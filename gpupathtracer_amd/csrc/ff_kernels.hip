@@ -3119,7 +3119,22 @@ __global__ void unpack_strips_kernel(const unsigned char* __restrict__ src, unsi
 // every sum is FF_SHADE_DIFFUSE_PATH's bit for bit.  Kept apart from trace_bvh_kernel, which it leaves as it was.
 __device__ __forceinline__ float nee_u24(unsigned r) { return (float)(r >> 8) * 5.9604644775390625e-08f; }
 
-template <int MODE, int BIG = 0>
+// The environment texel direction d falls in (ff_api.h): phi = atan2(d.x, -d.z) - rotation wrapped to [0, 2 pi), theta = acos(d.y),
+// nearest texel.  Returns {intensity x rgb, pdf_env}: one 16-byte load.
+__device__ __forceinline__ float4 env_lookup(const NeeParams& np, float dx, float dy, float dz)
+{
+    constexpr float kTwoPi = 6.28318530717958648f, kInvTwoPi = 0.15915494309189535f, kInvPi = 0.31830988618379067f;
+    float phi = atan2f(dx, -dz) - np.env_rotation;
+    if (phi < 0.f) phi = phi + kTwoPi;
+    if (phi < 0.f) phi = phi + kTwoPi;
+    const float theta = acosf(fminf(fmaxf(dy, -1.f), 1.f));
+    const int c = min(max((int)((phi * kInvTwoPi) * (float)np.env_w), 0), np.env_w - 1);
+    const int r = min(max((int)((theta * kInvPi) * (float)np.env_h), 0), np.env_h - 1);
+    return np.env_texels[r * np.env_w + c];
+}
+
+// ENV = 1: the environment is one more light of the MIS estimator (ff_api.h).  ENV = 0 compiles to the kernel without it.
+template <int MODE, int BIG = 0, int ENV = 0>
 __global__ __launch_bounds__(kBlockThreads) void nee_path_kernel(const NeeParams np)
 {
     const KParams& p = np.k;
@@ -3203,13 +3218,15 @@ __global__ __launch_bounds__(kBlockThreads) void nee_path_kernel(const NeeParams
                 // BSDF-sampled emitter hit: weight 1 after the camera or a specular bounce and for emitters the table leaves out
                 const float4 emission = mat_f4(M, 13);
                 float cx = P.bx * emission.x, cy = P.by * emission.y, cz = P.bz * emission.z;
-                const float area_pdf = np.light_pdf[best.geom];
+                // (FF_SHADE_DIFFUSE_PATH under an environment runs here with no light table: weight 1)
+                const float area_pdf = (ENV && np.num_lights == 0) ? 0.f : np.light_pdf[best.geom];
                 if (prev_pdf > 0.f && area_pdf > 0.f) {
                     float nx, ny, nz;
                     world_normal(M, best, false, nx, ny, nz);
                     const float ninv = ieee_rcp(ieee_sqrt(dot3(nx, ny, nz, nx, ny, nz)));
                     const float cos_y = fabsf(dot3(nx * ninv, ny * ninv, nz * ninv, P.ray.dx, P.ray.dy, P.ray.dz));
-                    const float pl = area_pdf * (best.dist * best.dist) / cos_y;
+                    float pl = area_pdf * (best.dist * best.dist) / cos_y;
+                    if (ENV) pl = pl * np.p_area;
                     const float pb2 = prev_pdf * prev_pdf;
                     const float w = pb2 / (pb2 + pl * pl);
                     cx = cx * w;
@@ -3229,6 +3246,21 @@ __global__ __launch_bounds__(kBlockThreads) void nee_path_kernel(const NeeParams
                 }
                 goes_on = P.b != p.bounces - 1;
             }
+        } else if (ENV) {
+            // BSDF-sampled miss: the environment's radiance, weight 1 after the camera or a specular bounce
+            const float4 le = env_lookup(np, P.ray.dx, P.ray.dy, P.ray.dz);
+            float cx = P.bx * le.x, cy = P.by * le.y, cz = P.bz * le.z;
+            const float pl = np.p_env * le.w;
+            if (prev_pdf > 0.f && pl > 0.f) {
+                const float pb2 = prev_pdf * prev_pdf;
+                const float w = pb2 / (pb2 + pl * pl);
+                cx = cx * w;
+                cy = cy * w;
+                cz = cz * w;
+            }
+            Lx = Lx + cx;
+            Ly = Ly + cy;
+            Lz = Lz + cz;
         }
         if (goes_on) {
             const int bxdf = mat_bxdf(M);
@@ -3242,50 +3274,97 @@ __global__ __launch_bounds__(kBlockThreads) void nee_path_kernel(const NeeParams
                 ux = nx * ninv; uy = ny * ninv; uz = nz * ninv;
                 if (dot3(ux, uy, uz, P.ray.dx, P.ray.dy, P.ray.dz) > 0.0f) { ux = -ux; uy = -uy; uz = -uz; }
             }
-            if (diffuse && np.num_lights > 0) {
+            if (diffuse && (np.num_lights > 0 || (ENV && np.p_env > 0.f))) {
                 // light sample: primitive by the alias table, point uniform on it (keys in ff_api.h)
                 const unsigned gpix = (P.gxy >> 16) * (unsigned)p.width + (P.gxy & 0xFFFFu);
                 const unsigned ctr = ((unsigned)P.s << 8) | ((unsigned)P.b & 0xFFu);
                 unsigned r0, r1, q0, q1;
                 philox2x32_10(gpix, ctr, p.key ^ kNeeKeySelect, r0, r1);
                 philox2x32_10(gpix, ctr, p.key ^ kNeeKeyPoint, q0, q1);
-                int e = (int)(((unsigned long long)r0 * (unsigned long long)np.num_lights) >> 32);
-                const float4 a0 = np.lights[5 * e + 3];
-                if (!(nee_u24(r1) < a0.w)) e = __float_as_int(np.lights[5 * e + 2].w);
-                const float4 v0 = np.lights[5 * e], ea = np.lights[5 * e + 1], eb = np.lights[5 * e + 2], nrm = np.lights[5 * e + 3], ex = np.lights[5 * e + 4];
-                const int prim = __float_as_int(ea.w);
-                float su = nee_u24(q0), sv = nee_u24(q1);
-                if (prim >= 0) { // triangle: the square-root warp
-                    const float r = ieee_sqrt(su);
-                    su = r * (1.0f - sv);
-                    sv = r * sv;
+                bool env_pick = false;
+                if (ENV) {
+                    // the environment or the light table (a stream of its own, drawn only when both are there)
+                    env_pick = np.p_env >= 1.f;
+                    if (np.p_env > 0.f && np.p_env < 1.f) {
+                        unsigned c0, c1;
+                        philox2x32_10(gpix, ctr, p.key ^ kEnvKeyChoose, c0, c1);
+                        env_pick = nee_u24(c0) < np.p_env;
+                    }
                 }
-                const float yx = v0.x + (su * ea.x + sv * eb.x), yy = v0.y + (su * ea.y + sv * eb.y), yz = v0.z + (su * ea.z + sv * eb.z);
-                const float dx = yx - best.px, dy = yy - best.py, dz = yz - best.pz;
-                const float d2 = dot3(dx, dy, dz, dx, dy, dz);
-                const float dinv = ieee_rcp(ieee_sqrt(d2));
-                const float wx = dx * dinv, wy = dy * dinv, wz = dz * dinv;
-                const float cos_x = dot3(ux, uy, uz, wx, wy, wz);
-                const float cos_y = fabsf(dot3(nrm.x, nrm.y, nrm.z, wx, wy, wz));
-                if (cos_x > 0.f && cos_y > 0.f && d2 > 0.f) {
-                    const int g = __float_as_int(v0.w);
-                    const float4 le = reinterpret_cast<const float4*>(p.geoms + g)[13];
-                    const float pl = ex.x * d2 / cos_y;
-                    const float pb = cos_x * kInvPi;
-                    const float pl2 = pl * pl;
-                    const float f = (pb * (pl2 / (pl2 + pb * pb))) / pl; // (cos_x / pi) * w_l / pdf_l
-                    scx = (P.bx * le.x) * f;
-                    scy = (P.by * le.y) * f;
-                    scz = (P.bz * le.z) * f;
-                    sgeom = g;
-                    sprim = prim;
-                    sray.ox = best.px + ux * kRayEps;
-                    sray.oy = best.py + uy * kRayEps;
-                    sray.oz = best.pz + uz * kRayEps;
-                    sray.dx = wx;
-                    sray.dy = wy;
-                    sray.dz = wz;
-                    shadow = true;
+                if (ENV && env_pick) {
+                    // environment sample: texel by the alias table, direction uniform in solid angle within it
+                    int e = (int)(((unsigned long long)r0 * (unsigned long long)(np.env_w * np.env_h)) >> 32);
+                    const float2 al = np.env_alias[e];
+                    if (!(nee_u24(r1) < al.x)) e = __float_as_int(al.y);
+                    const float4 le = np.env_texels[e];
+                    const int row = e / np.env_w, col = e - row * np.env_w;
+                    const float z0 = np.env_z[row], z1 = np.env_z[row + 1];
+                    const float wy = z0 + nee_u24(q0) * (z1 - z0);
+                    // phi / pi = (c + v) 2 / W + rotation / pi, in [0, 4): sincospi needs no long argument reduction
+                    const float phi_pi = ((float)col + nee_u24(q1)) * (2.0f / (float)np.env_w) + np.env_rotation * kInvPi;
+                    const float st = ieee_sqrt(fmaxf(0.f, 1.0f - wy * wy));
+                    float sp, cp;
+                    sincospif(phi_pi, &sp, &cp);
+                    const float wx = st * sp, wz = -(st * cp);
+                    const float cos_x = dot3(ux, uy, uz, wx, wy, wz);
+                    const float pl = np.p_env * le.w;
+                    if (cos_x > 0.f && pl > 0.f) {
+                        const float pb = cos_x * kInvPi;
+                        const float pl2 = pl * pl;
+                        const float f = (pb * (pl2 / (pl2 + pb * pb))) / pl; // (cos_x / pi) * w_l / pdf_l
+                        scx = (P.bx * le.x) * f;
+                        scy = (P.by * le.y) * f;
+                        scz = (P.bz * le.z) * f;
+                        sgeom = -1; // visible iff the shadow ray hits nothing
+                        sprim = -1;
+                        sray.ox = best.px + ux * kRayEps;
+                        sray.oy = best.py + uy * kRayEps;
+                        sray.oz = best.pz + uz * kRayEps;
+                        sray.dx = wx;
+                        sray.dy = wy;
+                        sray.dz = wz;
+                        shadow = true;
+                    }
+                } else {
+                    int e = (int)(((unsigned long long)r0 * (unsigned long long)np.num_lights) >> 32);
+                    const float4 a0 = np.lights[5 * e + 3];
+                    if (!(nee_u24(r1) < a0.w)) e = __float_as_int(np.lights[5 * e + 2].w);
+                    const float4 v0 = np.lights[5 * e], ea = np.lights[5 * e + 1], eb = np.lights[5 * e + 2], nrm = np.lights[5 * e + 3], ex = np.lights[5 * e + 4];
+                    const int prim = __float_as_int(ea.w);
+                    float su = nee_u24(q0), sv = nee_u24(q1);
+                    if (prim >= 0) { // triangle: the square-root warp
+                        const float r = ieee_sqrt(su);
+                        su = r * (1.0f - sv);
+                        sv = r * sv;
+                    }
+                    const float yx = v0.x + (su * ea.x + sv * eb.x), yy = v0.y + (su * ea.y + sv * eb.y), yz = v0.z + (su * ea.z + sv * eb.z);
+                    const float dx = yx - best.px, dy = yy - best.py, dz = yz - best.pz;
+                    const float d2 = dot3(dx, dy, dz, dx, dy, dz);
+                    const float dinv = ieee_rcp(ieee_sqrt(d2));
+                    const float wx = dx * dinv, wy = dy * dinv, wz = dz * dinv;
+                    const float cos_x = dot3(ux, uy, uz, wx, wy, wz);
+                    const float cos_y = fabsf(dot3(nrm.x, nrm.y, nrm.z, wx, wy, wz));
+                    if (cos_x > 0.f && cos_y > 0.f && d2 > 0.f) {
+                        const int g = __float_as_int(v0.w);
+                        const float4 le = reinterpret_cast<const float4*>(p.geoms + g)[13];
+                        float pl = ex.x * d2 / cos_y;
+                        if (ENV) pl = pl * np.p_area;
+                        const float pb = cos_x * kInvPi;
+                        const float pl2 = pl * pl;
+                        const float f = (pb * (pl2 / (pl2 + pb * pb))) / pl; // (cos_x / pi) * w_l / pdf_l
+                        scx = (P.bx * le.x) * f;
+                        scy = (P.by * le.y) * f;
+                        scz = (P.bz * le.z) * f;
+                        sgeom = g;
+                        sprim = prim;
+                        sray.ox = best.px + ux * kRayEps;
+                        sray.oy = best.py + uy * kRayEps;
+                        sray.oz = best.pz + uz * kRayEps;
+                        sray.dx = wx;
+                        sray.dy = wy;
+                        sray.dz = wz;
+                        shadow = true;
+                    }
                 }
             }
             scatter<true>(p, best, M, P);
@@ -3382,6 +3461,9 @@ hipError_t prepare_kernels()
     FF_SET_LDS((nee_path_kernel<FF_TRACE_BVH>))
     FF_SET_LDS((nee_path_kernel<FF_TRACE_BVH, 1>))
     FF_SET_LDS((nee_path_kernel<FF_TRACE_BVH, 2>))
+    FF_SET_LDS((nee_path_kernel<FF_TRACE_BVH, 0, 1>))
+    FF_SET_LDS((nee_path_kernel<FF_TRACE_BVH, 1, 1>))
+    FF_SET_LDS((nee_path_kernel<FF_TRACE_BVH, 2, 1>))
 #undef FF_SET_LDS
     return hipSuccess;
 }
@@ -3507,7 +3589,7 @@ hipError_t launch_ray_batch(const RayBatchParams& p, int trace_mode, hipStream_t
     return hipGetLastError();
 }
 
-hipError_t launch_nee(const NeeParams& np, int trace_mode, int grid_blocks, hipStream_t stream, const char** kernel_name)
+hipError_t launch_nee(const NeeParams& np, int trace_mode, bool env, int grid_blocks, hipStream_t stream, const char** kernel_name)
 {
     if (np.items == 0u) return hipSuccess;
     const KParams& p = np.k;
@@ -3516,7 +3598,13 @@ hipError_t launch_nee(const NeeParams& np, int trace_mode, int grid_blocks, hipS
                                                   : (size_t)kBruteBatchTris * sizeof(TriRecord);
     const dim3 grid(grid_blocks), block(kBlockThreads);
     const char* name;
-    if (trace_mode == FF_TRACE_BVH && big == 1) { hipLaunchKernelGGL((nee_path_kernel<FF_TRACE_BVH, 1>), grid, block, lds, stream, np); name = "nee_path_kernel<1, 1>"; }
+    if (env) {
+        if (trace_mode == FF_TRACE_BVH && big == 1) { hipLaunchKernelGGL((nee_path_kernel<FF_TRACE_BVH, 1, 1>), grid, block, lds, stream, np); name = "nee_path_kernel<1, 1, 1>"; }
+        else if (trace_mode == FF_TRACE_BVH && big == 2) { hipLaunchKernelGGL((nee_path_kernel<FF_TRACE_BVH, 2, 1>), grid, block, lds, stream, np); name = "nee_path_kernel<1, 2, 1>"; }
+        else if (trace_mode == FF_TRACE_BVH) { hipLaunchKernelGGL((nee_path_kernel<FF_TRACE_BVH, 0, 1>), grid, block, lds, stream, np); name = "nee_path_kernel<1, 0, 1>"; }
+        else { hipLaunchKernelGGL((nee_path_kernel<FF_TRACE_BRUTE_FORCE, 0, 1>), grid, block, lds, stream, np); name = "nee_path_kernel<0, 0, 1>"; }
+    }
+    else if (trace_mode == FF_TRACE_BVH && big == 1) { hipLaunchKernelGGL((nee_path_kernel<FF_TRACE_BVH, 1>), grid, block, lds, stream, np); name = "nee_path_kernel<1, 1>"; }
     else if (trace_mode == FF_TRACE_BVH && big == 2) { hipLaunchKernelGGL((nee_path_kernel<FF_TRACE_BVH, 2>), grid, block, lds, stream, np); name = "nee_path_kernel<1, 2>"; }
     else if (trace_mode == FF_TRACE_BVH) { hipLaunchKernelGGL((nee_path_kernel<FF_TRACE_BVH>), grid, block, lds, stream, np); name = "nee_path_kernel<1, 0>"; }
     else { hipLaunchKernelGGL((nee_path_kernel<FF_TRACE_BRUTE_FORCE>), grid, block, lds, stream, np); name = "nee_path_kernel<0, 0>"; }

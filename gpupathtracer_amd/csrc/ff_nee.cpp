@@ -234,8 +234,11 @@ int nee_rebuild(FfState* s)
 // stored primary hits, keys and cull mask are neither used nor touched: the next FF_SHADE_DIFFUSE_PATH frame finds them as they were.
 int enqueue_nee(FfState* s, KParams& k, const FfRenderParams* prm, int launches, int blocks_per_launch, size_t local_pixels)
 {
-    if (!s->nee_valid)
+    if (!s->nee_valid) {
+        if (s->env_set)
+            return fail(FF_ERR_UNSUPPORTED, "an environment light needs a scene uploaded with ff_upload_scene (this one has no light table)");
         return fail(FF_ERR_UNSUPPORTED, "FF_SHADE_DIFFUSE_PATH_NEE needs a scene uploaded with ff_upload_scene (this one has no light table)");
+    }
     hipStream_t st = s->stream;
     k.tail_block = -1;
     k.cull_mask = nullptr;
@@ -269,6 +272,19 @@ int enqueue_nee(FfState* s, KParams& k, const FfRenderParams* prm, int launches,
     np.lights = s->d_nee_lights;
     np.num_lights = s->nee_num_lights;
     np.light_pdf = s->d_nee_pdf;
+    const bool env = s->env_set; // (render_enqueue sends FF_SHADE_NORMAL_DEBUG elsewhere)
+    if (env) {
+        // the environment as one more light (ff_api.h): FF_SHADE_DIFFUSE_PATH samples no light at all, so p_env = 0 there
+        if (prm->shade_mode != FF_SHADE_DIFFUSE_PATH_NEE) np.num_lights = 0;
+        np.env_texels = s->d_env_texels;
+        np.env_alias = s->d_env_alias;
+        np.env_z = s->d_env_z;
+        np.env_w = s->env_w;
+        np.env_h = s->env_h;
+        np.env_rotation = s->env_rotation;
+        np.p_env = (prm->shade_mode != FF_SHADE_DIFFUSE_PATH_NEE || !s->env_sampled) ? 0.f : (np.num_lights > 0 ? 0.5f : 1.f);
+        np.p_area = 1.f - np.p_env;
+    }
     FF_HIP(hipMemsetAsync(s->d_counters, 0, (size_t)kCounterWords * sizeof(unsigned long long), st));
     FF_HIP(hipEventRecord(s->ev_begin, st));
     for (int l = 0; l < launches; ++l) {
@@ -278,7 +294,7 @@ int enqueue_nee(FfState* s, KParams& k, const FfRenderParams* prm, int launches,
         k.total_items = k.pix_items * k.whole_blocks;
         np.k = k;
         np.items = k.total_items;
-        FF_HIP(launch_nee(np, prm->trace_mode, grid, st, &s->last_kernel_name));
+        FF_HIP(launch_nee(np, prm->trace_mode, env, grid, st, &s->last_kernel_name));
     }
     FF_HIP(launch_combine(k, st));
     FF_HIP(hipEventRecord(s->ev_end, st));

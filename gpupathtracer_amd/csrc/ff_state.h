@@ -135,6 +135,18 @@ struct FfState {
     size_t nee_lights_bytes = 0;
     float* d_nee_pdf = nullptr;        // ff::NeeParams::light_pdf
     size_t nee_pdf_bytes = 0;
+    // Environment light (ff_env.cpp, ff_set_environment): belongs to the state, so it outlives uploads and updates of the scene.
+    // While it is set, FF_SHADE_DIFFUSE_PATH and FF_SHADE_DIFFUSE_PATH_NEE frames run nee_path_kernel<..., ENV = 1>.
+    bool env_set = false;
+    bool env_sampled = false;          // the map's total luminance is positive (else its table is empty: no environment light samples)
+    int env_w = 0, env_h = 0;
+    float env_rotation = 0.f;          // radians, in [0, 2 pi)
+    float4* d_env_texels = nullptr;    // ff::NeeParams::env_texels
+    size_t env_texels_bytes = 0;
+    float2* d_env_alias = nullptr;     // ff::NeeParams::env_alias
+    size_t env_alias_bytes = 0;
+    float* d_env_z = nullptr;          // ff::NeeParams::env_z
+    size_t env_z_bytes = 0;
     // temporal anti-aliasing (ff_taa, ff_taa.hip): two history buffers of one float4 per pixel {rgb, len} that swap by index, then
     // the motion (float2 per pixel).  taa_cur: the buffer the last call wrote.  The history describes the camera, image size and
     // per-geometry model matrices of that call; taa_replaced marks the meshes ff_update_mesh changed since.
@@ -234,6 +246,8 @@ void nee_capture(FfState* s, const FfGeometry* g, int n, bool upload);
 void nee_replace_mesh(FfState* s, int geometry_index, const FfTriangle* tris, int count);
 int nee_rebuild(FfState* s);
 int enqueue_nee(FfState* s, KParams& k, const FfRenderParams* prm, int launches, int blocks_per_launch, size_t local_pixels);
+// Environment light (ff_env.cpp): frees the state's device table (ff_destroy).
+void env_release(FfState* s);
 
 // ff_upload_scene for a scene already compiled on the host (ff_api.cpp).
 int upload_compiled_scene(FfState* s, const CompiledScene& cs, double build_ms);

@@ -31,6 +31,7 @@ EXPORTS = [
     "ff_camera_ray_matrix_jittered", "ff_set_pixel_jitter", "ff_multi_set_pixel_jitter", "ff_jitter_sequence",
     "ff_taa_params_init", "ff_taa", "ff_taa_reset", "ff_taa_history",
     "ff_light_table", "ff_check_render_params",
+    "ff_set_environment", "ff_environment_table", "ff_load_hdr", "ff_free_hdr", "ff_scene_file_environment",
 ]
 DIST_ID_BYTES = 128
 
@@ -164,6 +165,12 @@ def load():
     lib.ff_jitter_sequence.argtypes = [i32, i32, P(C.c_float), P(C.c_float)]
     lib.ff_light_table.argtypes = [P(T.FfGeometry), i32, P(T.FfLightEntry), i32, P(C.c_float)]
     lib.ff_check_render_params.argtypes = [P(T.FfRenderParams)]
+    lib.ff_set_environment.argtypes = [vp, vp, i32, i32, f32, f32]
+    lib.ff_environment_table.argtypes = [vp, i32, i32, vp, vp, vp, vp]
+    lib.ff_load_hdr.argtypes = [C.c_char_p, P(P(C.c_float)), P(i32), P(i32)]
+    lib.ff_free_hdr.argtypes = [P(C.c_float)]
+    lib.ff_free_hdr.restype = None
+    lib.ff_scene_file_environment.argtypes = [vp, P(C.c_char_p), P(C.c_float), P(C.c_float)]
     lib.ff_taa_params_init.argtypes = [P(T.FfTaaParams)]
     lib.ff_taa_params_init.restype = None
     lib.ff_taa.argtypes = [vp, P(T.FfCamera), i32, i32, P(T.FfTaaParams), vp, vp, vp, i32, vp, i32, vp, i32]
@@ -215,6 +222,13 @@ class SceneFile:
         return int(sum(self.geometries[i].m_numberOfTriangles for i in range(self._count)
                        if self.geometries[i].m_geometryType == T.GEOM_TRIANGLEMESH))
 
+    def environment(self):
+        """The file's environment statement as (resolved .hdr path, intensity, rotation in degrees), or None."""
+        path, inten, rot = C.c_char_p(), C.c_float(0.0), C.c_float(0.0)
+        if self._lib.ff_scene_file_environment(self._handle, C.byref(path), C.byref(inten), C.byref(rot)) == 0:
+            return None
+        return os.fsdecode(path.value), float(inten.value), float(rot.value)
+
     def camera(self, width, height):
         cam = T.FfCamera()
         check(self._lib.ff_scene_file_camera(self._handle, width, height, C.byref(cam)))
@@ -260,6 +274,37 @@ def light_table(scene):
     entries.update({name: np.array([getattr(r, name) for r in rows], dtype=np.float32) for name in ("area", "probability", "alias_probability")})
     entries.update({name: vec(name) for name in ("v0", "e1", "e2", "normal")})
     return entries, pdf[:n]
+
+
+def _env_map(rgb):
+    a = np.ascontiguousarray(rgb, dtype=np.float32)
+    if a.ndim != 3 or a.shape[2] != 3:
+        raise ValueError(f"an environment map is an [H, W, 3] array (got shape {a.shape})")
+    return a
+
+
+def environment_table(rgb):
+    """The sampling table ff_set_environment builds for an [H, W, 3] map (host-only, ff_environment_table): a dict of [H, W] arrays -
+    probability (float32), alias_probability (float32), alias (int32, flat texel index r * W + c) and pdf (float32, per steradian)."""
+    a = _env_map(rgb)
+    h, w = a.shape[:2]
+    out = {"probability": np.zeros((h, w), np.float32), "alias_probability": np.zeros((h, w), np.float32),
+           "alias": np.zeros((h, w), np.int32), "pdf": np.zeros((h, w), np.float32)}
+    check(load().ff_environment_table(a.ctypes.data, w, h, out["probability"].ctypes.data, out["alias_probability"].ctypes.data,
+                                      out["alias"].ctypes.data, out["pdf"].ctypes.data))
+    return out
+
+
+def load_hdr(path):
+    """A Radiance RGBE .hdr file (ff_load_hdr) -> float32 [H, W, 3], row 0 the top."""
+    lib = load()
+    ptr = C.POINTER(C.c_float)()
+    w, h = C.c_int(0), C.c_int(0)
+    check(lib.ff_load_hdr(os.fsencode(path), C.byref(ptr), C.byref(w), C.byref(h)))
+    try:
+        return np.ctypeslib.as_array(ptr, shape=(h.value * w.value * 3,)).reshape(h.value, w.value, 3).copy()
+    finally:
+        lib.ff_free_hdr(ptr)
 
 
 def check_render_params(params):
@@ -356,6 +401,15 @@ class Tracer:
     def upload_scene(self, scene):
         """scene: gpupathtracer_amd.scenes.Scene"""
         check(self._lib.ff_upload_scene(self._state, scene.geometries, len(scene)))
+
+    def set_environment(self, rgb, intensity=1.0, rotation_deg=0.0):
+        """Light the scene with an [H, W, 3] environment map (row 0 the top, +Y), `intensity` times its texels, turned by
+        `rotation_deg` about +Y (ff_set_environment).  It stays until clear_environment(), across scene uploads."""
+        a = _env_map(rgb)
+        check(self._lib.ff_set_environment(self._state, a.ctypes.data, a.shape[1], a.shape[0], float(intensity), float(rotation_deg)))
+
+    def clear_environment(self):
+        check(self._lib.ff_set_environment(self._state, None, 0, 0, 0.0, 0.0))
 
     def set_builder(self, builder):
         """T.BUILD_HOST_SAH (default) or T.BUILD_GPU_LBVH for the following upload_scene calls."""

@@ -231,3 +231,44 @@ def sphere_stress_scene(levels=5, base=None):
     s = Scene()
     s.add_mesh(subdivide_sphere(base, levels), (0, 0, 0), (0, 0, 0), (2, 2, 2), make_bxdf(T.BXDF_DIFFUSE, albedo=(0.75, 0.75, 0.75)))
     return _box(s).finalize()
+
+
+def env_directions(width, height):
+    """Unit directions of the texel centres of a width x height environment map at rotation 0 (ff_api.h's mapping): [H, W, 3]."""
+    theta = (np.arange(height, dtype=np.float64) + 0.5) * (np.pi / height)
+    phi = (np.arange(width, dtype=np.float64) + 0.5) * (2.0 * np.pi / width)
+    st, ct = np.sin(theta)[:, None], np.cos(theta)[:, None]
+    return np.stack(np.broadcast_arrays(st * np.sin(phi)[None, :], ct, -st * np.cos(phi)[None, :]), -1)
+
+
+def sun_sky_map(width, height, sun_dir=(0.35, 0.75, -0.55), sun_radius_deg=1.5, sun_radiance=(1.0, 0.92, 0.8), sun_intensity=5000.0,
+                zenith=(0.22, 0.42, 1.0), horizon=(0.85, 0.9, 1.0), ground=(0.25, 0.22, 0.2)):
+    """A deterministic environment map (float32 [H, W, 3], row 0 the top): a smooth sky from `horizon` to `zenith` above a dim
+    `ground`, and one small sun disc of `sun_intensity` x `sun_radiance` around `sun_dir` (at least the texel sun_dir falls in)."""
+    d = env_directions(width, height)
+    y = d[..., 1:2]
+    up = np.clip(y, 0.0, 1.0) ** 0.5
+    sky = np.asarray(horizon) * (1.0 - up) + np.asarray(zenith) * up
+    blend = np.clip(y / 0.05 + 1.0, 0.0, 1.0)  # (smooth into the ground over 3 degrees below the horizon)
+    out = np.asarray(ground) * (1.0 - blend) + sky * blend
+    s = np.asarray(sun_dir, np.float64)
+    s = s / np.linalg.norm(s)
+    disc = np.sum(d * s, -1) >= np.cos(np.radians(sun_radius_deg))
+    phi = np.arctan2(s[0], -s[2]) % (2.0 * np.pi)
+    r = min(int(np.arccos(np.clip(s[1], -1.0, 1.0)) / np.pi * height), height - 1)
+    c = min(int(phi / (2.0 * np.pi) * width), width - 1)
+    disc[r, c] = True
+    out[disc] = np.asarray(sun_radiance) * sun_intensity
+    return out.astype(np.float32)
+
+
+def open_floor_scene(area_light=False, wahoo=None):
+    """An open scene for environment lighting: wahoo.obj (scale 0.28) on a large grey floor plane, nothing else (no walls, no
+    ceiling).  area_light: an emitting plane above it as well, facing down."""
+    wahoo = load_mesh("wahoo") if wahoo is None else wahoo
+    s = Scene()
+    s.add_mesh(wahoo, (0, -2.4, 0), (0, 0, 0), (0.28, 0.28, 0.28), make_bxdf(T.BXDF_DIFFUSE, albedo=(0.8, 0.3, 0.2)))
+    s.add_plane((0, -2.5, 0), (90, 0, 0), (40, 40, 40), make_bxdf(T.BXDF_DIFFUSE, albedo=(0.6, 0.6, 0.6)))
+    if area_light:
+        s.add_plane((1.0, 0.5, 0.5), (90, 0, 0), (1.5, 1.5, 1.5), make_bxdf(T.BXDF_EMITTER, emissive=(1.0, 0.9, 0.8), intensity=4.0))
+    return s.finalize()

@@ -327,6 +327,56 @@ FF_API int ff_light_table(const FfGeometry* host_geometries, int n, FfLightEntry
 /* Host-only: FF_OK if every render entry point would accept `params` (sizes, bounces, spp, modes), else FF_ERR_INVALID_ARG. */
 FF_API int ff_check_render_params(const FfRenderParams* params);
 
+/* ---- environment light (no counterpart in the reference) ----------------------------------------- */
+
+/* A map of W x H linear RGB texels (row 0 the top, +Y) around the scene: what a ray that leaves the scene sees, times `intensity`.
+ *   Mapping of a unit direction d: phi = atan2(d.x, -d.z) - rotation, wrapped to [0, 2 pi); theta = acos(clamp(d.y, -1, 1));
+ *     column c = min(floor(phi / 2 pi * W), W - 1), row r = min(floor(theta / pi * H), H - 1); nearest texel, so the radiance
+ *     Le = intensity * texel (in float) is constant over texel (r, c), which covers the solid angle
+ *     Omega_rc = (2 pi / W)(cos(pi r / H) - cos(pi (r + 1) / H)).
+ *   Table (ff_environment_table; built in double): w_rc = lum_rc Omega_rc (lum = 0.2126 r + 0.7152 g + 0.0722 b of the texel),
+ *     p_rc = w_rc / sum, a Vose alias table over the W H texels (index k = r W + c), pdf_env = p_rc / Omega_rc per steradian.
+ *     A map of zero total luminance has an empty table: it is never sampled, and pdf_env = 0.
+ *   With an environment set, FF_SHADE_DIFFUSE_PATH and FF_SHADE_DIFFUSE_PATH_NEE add, on every segment including the last, for a
+ *   ray that hits nothing:  L += beta Le(w) w_b, where w_b = 1 after the camera ray or a mirror / glass bounce and always in
+ *   FF_SHADE_DIFFUSE_PATH, and w_b = pdf_b^2 / (pdf_b^2 + (p_env pdf_env(w))^2) after a diffuse bounce in FF_SHADE_DIFFUSE_PATH_NEE.
+ *   FF_SHADE_DIFFUSE_PATH_NEE's light sample (the block above) then chooses between the environment and the light table:
+ *       p_env = 1/2 with a non-empty light table, 1 without one, 0 if the environment's table is empty;
+ *       if 0 < p_env < 1: (c0, c1) = Philox(gpix, s << 8 | b, key ^ 0x3C6EF372), the environment iff (c0 >> 8) / 2^24 < p_env.
+ *     The light table's branch is the one above with pdf_l = (1 - p_env) pdf_A(g) d2 / cos_y, and so is the weight of a
+ *     BSDF-sampled emitter hit.  The environment's branch, with the same (r0, r1) and (q0, q1):
+ *       k = floor(r0 * W H / 2^32); if !((r1 >> 8) / 2^24 < alias_probability_k) k = alias_k; r = k / W, c = k % W
+ *       z = z_r + u (z_{r+1} - z_r), z_r = cos(pi r / H) (stored as float);  phi = (c + v) 2 pi / W + rotation
+ *       w = (sqrt(1 - z^2) sin phi, z, -sqrt(1 - z^2) cos phi),  cos_x = n^ . w
+ *       if cos_x > 0 and pdf_env_k > 0: a shadow ray from x + 1e-4 n^ along w, visible iff it hits nothing.  Then
+ *         pdf_l = p_env pdf_env_k,  pdf_b = cos_x / pi,  w_l = pdf_l^2 / (pdf_l^2 + pdf_b^2),  L += beta Le_k (cos_x / pi) w_l / pdf_l
+ *   Without an environment no frame changes, and no random number is drawn for it.  With an all-zero map every frame is the frame
+ *   without an environment bit for bit.  Results do not depend on the lane, spp_per_launch, tile or strip.
+ * FF_SHADE_NORMAL_DEBUG ignores the environment; FF_SHADE_DIFFUSE_PATH_SMOOTH returns FF_ERR_UNSUPPORTED while one is set, and so do
+ * ff_render_distributed, ff_multi_render*, and a state whose scene came from ff_multi_upload_scene, for FF_SHADE_DIFFUSE_PATH and
+ * FF_SHADE_DIFFUSE_PATH_NEE frames.  ff_gbuffer does not see it (a miss stays a miss).  FfStats.rays_traced counts the shadow rays.
+ * The environment belongs to the state: it stays through ff_upload_scene and the update calls, until it is replaced, cleared or
+ * the state is destroyed. */
+
+/* Sets the state's environment (copied to the device): `rgb` is height rows of width RGB floats; rgb == NULL clears it.
+ * FF_ERR_INVALID_ARG for a size below 1x1 or above 2^26 texels, a negative or non-finite texel, a negative or non-finite
+ * intensity, a non-finite rotation.  rotation_deg turns the map about world +Y (see the mapping above). */
+FF_API int ff_set_environment(FfState* state, const float* rgb, int width, int height, float intensity, float rotation_deg);
+
+/* Host-only: the table ff_set_environment builds for the map, W H entries each (any output may be NULL): probability p_rc,
+ * alias_probability, alias, pdf_env.  An all-zero map gives p = 0, alias_probability = 1, alias = itself and pdf = 0.
+ * FF_ERR_INVALID_ARG as ff_set_environment. */
+FF_API int ff_environment_table(const float* rgb, int width, int height, float* out_probability, float* out_alias_probability, int* out_alias,
+                                float* out_pdf);
+
+/* Reads a Radiance RGBE (.hdr) file: a "#?" signature, header lines up to an empty line (FORMAT=32-bit_rle_rgbe or none), the
+ * resolution line "-Y h +X w" (other orientations are not supported), then h scanlines, each flat (w RGBE quadruples) or
+ * new-style run-length encoded (2 2 w>>8 w&255, then the four channels as runs).  Texel = (R, G, B) * 2^(E - 136) (0 if E = 0),
+ * row 0 the top.  *out_rgb is malloc'ed (h rows of w RGB floats); release with ff_free_hdr.  FF_ERR_IO for a file that cannot be
+ * opened or ends early, FF_ERR_INVALID_ARG for a malformed or unsupported one. */
+FF_API int ff_load_hdr(const char* path, float** out_rgb, int* out_width, int* out_height);
+FF_API void ff_free_hdr(float* rgb);
+
 /* ---- G-buffer and denoiser (no counterpart in the reference) ----------------------------- */
 
 /* What every pixel's primary ray (kernel.cu:197-205) hits: I = intersectRays (kernel.cu:127-176) for that ray, the FfIntersect
@@ -530,6 +580,8 @@ FF_API void ff_free_triangles(FfTriangle* triangles);
  *   mesh FILE.obj [position X Y Z] [rotation X Y Z] [scale X Y Z] bxdf NAME (path relative to the scene file)
  *   plane [position X Y Z] [rotation X Y Z] [scale X Y Z] bxdf NAME
  *   sphere radius R [position X Y Z] [rotation X Y Z] [scale X Y Z] bxdf NAME
+ *   environment FILE.hdr [intensity I] [rotation DEG]                       (at most one; path relative to the scene file;
+ *                                                                             intensity 1 and rotation 0 by default)
  *
  * Geometries keep file order (it is the reference's iteration order, kernel.cu:133).  The returned object owns the
  * triangles and BXDFs its FfGeometry array points to. */
@@ -539,6 +591,9 @@ FF_API const FfGeometry* ff_scene_file_geometries(const FfSceneFile* scene, int*
 /* Camera of the file for a width x height image (UpdateBasisAxis applied). */
 FF_API int ff_scene_file_camera(const FfSceneFile* scene, int width, int height, FfCamera* out_camera);
 FF_API void ff_scene_file_free(FfSceneFile* scene);
+/* The file's environment statement: 1 with the resolved path (owned by the scene), intensity and rotation in degrees; 0 if the
+ * file has none (the outputs are left alone).  Loading the map and ff_set_environment are the caller's. */
+FF_API int ff_scene_file_environment(const FfSceneFile* scene, const char** out_path, float* out_intensity, float* out_rotation_deg);
 
 #ifdef __cplusplus
 } /* extern "C" */
