@@ -78,6 +78,28 @@ int ensure_bytes(void** ptr, size_t* cap, size_t need)
     return FF_OK;
 }
 
+// The registered pixel buffer, mapped for writing: the device pointer of at least need_bytes.  A mapping that gives no such
+// pointer is undone here, so the caller unmaps (unmap_pbo) exactly when this returned FF_OK.
+int map_pbo(FfState* s, size_t need_bytes, void** out_ptr)
+{
+    size_t nbytes = 0;
+    FF_HIP(hipGraphicsMapResources(1, &s->pbo_resource, s->stream));
+    hipError_t e = hipGraphicsResourceGetMappedPointer(out_ptr, &nbytes, s->pbo_resource);
+    if (e == hipSuccess && nbytes < need_bytes) e = hipErrorInvalidValue;
+    if (e == hipSuccess) return FF_OK;
+    const int st = fail(FF_ERR_HIP, "mapping the pixel buffer failed: %s", hipGetErrorString(e));
+    (void)hipGraphicsUnmapResources(1, &s->pbo_resource, s->stream);
+    return st;
+}
+
+// ... and unmapped; status: what the work in between returned (it is kept; a failing unmap shows only after a success).
+int unmap_pbo(FfState* s, int status)
+{
+    const hipError_t ue = hipGraphicsUnmapResources(1, &s->pbo_resource, s->stream);
+    if (status == FF_OK && ue != hipSuccess) return fail(FF_ERR_HIP, "hipGraphicsUnmapResources failed: %s", hipGetErrorString(ue));
+    return status;
+}
+
 } // namespace ff
 
 namespace {
@@ -860,6 +882,7 @@ int ff_destroy(FfState* s)
     if (s->d_nee_lights) (void)hipFree(s->d_nee_lights);
     if (s->d_nee_pdf) (void)hipFree(s->d_nee_pdf);
     env_release(s);
+    display_release(s);
     free_build_scratch(s->scratch);
     if (s->d_blocksums) (void)hipFree(s->d_blocksums);
     if (s->d_rgb8) (void)hipFree(s->d_rgb8);
@@ -1611,17 +1634,11 @@ int ff_render_to_pbo(FfState* s, const FfCamera* camera, const FfRenderParams* p
     FF_HIP(hipSetDevice(s->device));
     // kernel.cu:335-344
     void* dptr = nullptr;
-    size_t nbytes = 0;
-    FF_HIP(hipGraphicsMapResources(1, &s->pbo_resource, s->stream));                 // :338
-    hipError_t e = hipGraphicsResourceGetMappedPointer(&dptr, &nbytes, s->pbo_resource); // :339
-    if (e == hipSuccess && nbytes < (size_t)params->width * (size_t)params->height * 3) e = hipErrorInvalidValue;
-    if (e == hipSuccess) {
+    st = map_pbo(s, (size_t)params->width * (size_t)params->height * 3, &dptr); // :338-339
+    if (st == FF_OK) {
         st = render_local(s, camera, params, params->height, 0, 1, params->height, (unsigned char*)dptr, nullptr); // :340-342
-    } else {
-        st = fail(FF_ERR_HIP, "mapping the pixel buffer failed: %s", hipGetErrorString(e));
+        st = unmap_pbo(s, st);                                                                                       // :344
     }
-    hipError_t ue = hipGraphicsUnmapResources(1, &s->pbo_resource, s->stream);       // :344
-    if (st == FF_OK && ue != hipSuccess) st = fail(FF_ERR_HIP, "hipGraphicsUnmapResources failed: %s", hipGetErrorString(ue));
     s->stats.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return st;
 }
@@ -1704,14 +1721,8 @@ int ff_render_to_pbo_progressive(FfState* s, const FfCamera* camera, const FfRen
                     s->pbo_width, s->pbo_height);
     FF_HIP(hipSetDevice(s->device));
     void* dptr = nullptr;
-    size_t nbytes = 0;
-    FF_HIP(hipGraphicsMapResources(1, &s->pbo_resource, s->stream));
-    hipError_t e = hipGraphicsResourceGetMappedPointer(&dptr, &nbytes, s->pbo_resource);
-    if (e == hipSuccess && nbytes < (size_t)params->width * (size_t)params->height * 3) e = hipErrorInvalidValue;
-    if (e == hipSuccess) st = progressive_frame(s, camera, params, frame_index, (unsigned char*)dptr, nullptr);
-    else st = fail(FF_ERR_HIP, "mapping the pixel buffer failed: %s", hipGetErrorString(e));
-    hipError_t ue = hipGraphicsUnmapResources(1, &s->pbo_resource, s->stream);
-    if (st == FF_OK && ue != hipSuccess) st = fail(FF_ERR_HIP, "hipGraphicsUnmapResources failed: %s", hipGetErrorString(ue));
+    st = map_pbo(s, (size_t)params->width * (size_t)params->height * 3, &dptr);
+    if (st == FF_OK) st = unmap_pbo(s, progressive_frame(s, camera, params, frame_index, (unsigned char*)dptr, nullptr));
     s->stats.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return st;
 }

@@ -37,7 +37,7 @@ extern "C" {
 
 const char* ff_last_error(void) { return ff::g_last_error.c_str(); }
 
-int ff_version(void) { return 100; /* 0.1.0 */ }
+int ff_version(void) { return 200; /* 0.2.0 */ }
 
 void ff_bxdf_init(FfBXDF* b)
 {

@@ -160,6 +160,17 @@ struct FfState {
     FfCamera taa_camera = {};
     std::vector<float> taa_model;
     std::vector<unsigned char> taa_has_model, taa_replaced;
+    // display transform (ff_display, ff_display.hip): the adapted exposure, the last call's results (ff_display_state) and the
+    // device buffers - 256 histogram counters and the 255 sRGB thresholds in d_disp_const, the bloom pyramid ({rgb, 0} float4 per
+    // texel, levels 1 .. n one after another) and the staging of host buffers in d_disp_work.  Not reset by uploads.
+    void* d_disp_const = nullptr;
+    size_t disp_const_bytes = 0;
+    void* d_disp_work = nullptr;
+    size_t disp_work_bytes = 0;
+    bool disp_has_prev = false, disp_called = false;
+    float disp_prev_exposure = 0.f;           // E of the last automatic call (the next one adapts from it)
+    float disp_exposure = 0.f, disp_target = 0.f;
+    uint32_t disp_histogram[256] = {};
     unsigned* d_queue = nullptr;               // work-queue counter: lives right behind the counters (one memset clears both)
     unsigned long long* d_counters = nullptr;  // 28 counters + 4 queue words
     unsigned long long* h_counters = nullptr;  // pinned mirror for the per-frame read-back
@@ -248,6 +259,12 @@ int nee_rebuild(FfState* s);
 int enqueue_nee(FfState* s, KParams& k, const FfRenderParams* prm, int launches, int blocks_per_launch, size_t local_pixels);
 // Environment light (ff_env.cpp): frees the state's device table (ff_destroy).
 void env_release(FfState* s);
+// Display transform (ff_display_api.cpp): frees the state's device buffers (ff_destroy).
+void display_release(FfState* s);
+// The pixel buffer registered with ff_register_gl_pbo, mapped on the state's stream (kernel.cu:338-339) and unmapped again
+// (kernel.cu:344): what ff_render_to_pbo and ff_display_to_pbo write.  need_bytes: the least size the mapping must have.
+int map_pbo(FfState* s, size_t need_bytes, void** out_ptr);
+int unmap_pbo(FfState* s, int status);
 
 // ff_upload_scene for a scene already compiled on the host (ff_api.cpp).
 int upload_compiled_scene(FfState* s, const CompiledScene& cs, double build_ms);

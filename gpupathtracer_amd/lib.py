@@ -32,6 +32,8 @@ EXPORTS = [
     "ff_taa_params_init", "ff_taa", "ff_taa_reset", "ff_taa_history",
     "ff_light_table", "ff_check_render_params",
     "ff_set_environment", "ff_environment_table", "ff_load_hdr", "ff_free_hdr", "ff_scene_file_environment",
+    "ff_display_params_init", "ff_display", "ff_display_to_pbo", "ff_display_reset", "ff_display_state",
+    "ff_srgb_thresholds", "ff_display_curve", "ff_display_exposure", "ff_save_hdr",
 ]
 DIST_ID_BYTES = 128
 
@@ -176,6 +178,17 @@ def load():
     lib.ff_taa.argtypes = [vp, P(T.FfCamera), i32, i32, P(T.FfTaaParams), vp, vp, vp, i32, vp, i32, vp, i32]
     lib.ff_taa_reset.argtypes = [vp]
     lib.ff_taa_history.argtypes = [vp, vp, vp, i32]
+    # display transform
+    lib.ff_display_params_init.argtypes = [P(T.FfDisplayParams)]
+    lib.ff_display_params_init.restype = None
+    lib.ff_display.argtypes = [vp, i32, i32, P(T.FfDisplayParams), vp, i32, vp, i32, vp, i32]
+    lib.ff_display_to_pbo.argtypes = [vp, i32, i32, P(T.FfDisplayParams), vp, i32]
+    lib.ff_display_reset.argtypes = [vp]
+    lib.ff_display_state.argtypes = [vp, P(f32), P(f32), vp]
+    lib.ff_srgb_thresholds.argtypes = [vp]
+    lib.ff_display_curve.argtypes = [P(T.FfDisplayParams), vp, i32, vp, vp]
+    lib.ff_display_exposure.argtypes = [P(T.FfDisplayParams), vp, f32, P(f32), P(f32)]
+    lib.ff_save_hdr.argtypes = [C.c_char_p, vp, i32, i32]
     _lib = real
     return real
 
@@ -307,6 +320,14 @@ def load_hdr(path):
         lib.ff_free_hdr(ptr)
 
 
+def save_hdr(path, rgb):
+    """float32 [H, W, 3] (finite, >= 0) -> a Radiance RGBE .hdr file with flat scanlines (ff_save_hdr), row 0 the top."""
+    a = np.ascontiguousarray(rgb, dtype=np.float32)
+    if a.ndim != 3 or a.shape[2] != 3:
+        raise ValueError("an image is [H, W, 3]")
+    check(load().ff_save_hdr(os.fsencode(path), a.ctypes.data, a.shape[1], a.shape[0]))
+
+
 def check_render_params(params):
     """ff_check_render_params: the status every render entry point's parameter check gives `params` (host-only)."""
     return load().ff_check_render_params(C.byref(params))
@@ -348,6 +369,43 @@ def taa_params(**overrides):
             raise TypeError(f"FfTaaParams has no field {name!r}")
         setattr(p, name, value)
     return p
+
+
+def display_params(**overrides):
+    """ff_display_params_init's defaults with the given fields replaced (any FfDisplayParams field)."""
+    p = T.FfDisplayParams()
+    load().ff_display_params_init(C.byref(p))
+    for name, value in overrides.items():
+        if name not in dict(T.FfDisplayParams._fields_):
+            raise TypeError(f"FfDisplayParams has no field {name!r}")
+        setattr(p, name, value)
+    return p
+
+
+def srgb_thresholds():
+    """ff_srgb_thresholds: T_1 .. T_255 of FF_ENCODE_SRGB, float32 [255]."""
+    out = np.zeros(255, dtype=np.float32)
+    check(load().ff_srgb_thresholds(out.ctypes.data))
+    return out
+
+
+def display_curve(p, exposed):
+    """ff_display_curve: tone curve and encoding of p for exposed values of any shape -> (y float32, bytes uint8), same shape."""
+    e = np.ascontiguousarray(exposed, dtype=np.float32)
+    y = np.zeros(e.shape, dtype=np.float32)
+    b = np.zeros(e.shape, dtype=np.uint8)
+    check(load().ff_display_curve(C.byref(p), e.ctypes.data, e.size, y.ctypes.data, b.ctypes.data))
+    return y, b
+
+
+def display_exposure(p, histogram, previous_exposure=0.0):
+    """ff_display_exposure: (target, exposure) of a 256-bin histogram; previous_exposure <= 0: there is none."""
+    h = np.ascontiguousarray(histogram, dtype=np.uint32)
+    if h.shape != (T.DISPLAY_BINS,):
+        raise ValueError("the histogram has 256 bins")
+    target, exposure = C.c_float(), C.c_float()
+    check(load().ff_display_exposure(C.byref(p), h.ctypes.data, previous_exposure, C.byref(target), C.byref(exposure)))
+    return target.value, exposure.value
 
 
 def jitter_sequence(index, period=16):
@@ -627,6 +685,43 @@ class Tracer:
         length = np.zeros((h, w), dtype=np.float32)
         check(self._lib.ff_taa_history(self._state, motion.ctypes.data if h * w else None, length.ctypes.data if h * w else None, 0))
         return motion, length
+
+    def display(self, radiance, p=None, want_rgb8=True, want_out=True):
+        """ff_display of host radiance [H,W,3] -> (rgb8 [H,W,3] uint8, display_out [H,W,3] float32: the curve's output in [0, 1]);
+        the adapted exposure stays in the state."""
+        rad = np.ascontiguousarray(radiance, dtype=np.float32)
+        if rad.ndim != 3 or rad.shape[2] != 3:
+            raise ValueError("display: radiance must be [H,W,3]")
+        h, w = rad.shape[:2]
+        p = p if p is not None else display_params()
+        rgb8 = np.zeros((h, w, 3), dtype=np.uint8) if want_rgb8 else None
+        out = np.zeros((h, w, 3), dtype=np.float32) if want_out else None
+        check(self._lib.ff_display(self._state, w, h, C.byref(p), rad.ctypes.data, 0, rgb8.ctypes.data if want_rgb8 else None, 0,
+                                   out.ctypes.data if want_out else None, 0))
+        return rgb8, out
+
+    def display_device(self, width, height, radiance_ptr, p=None, rgb8_ptr=None, display_out_ptr=None):
+        """ff_display on DEVICE buffers (raw pointers); display_out_ptr may equal radiance_ptr."""
+        p = p if p is not None else display_params()
+        vp = lambda q: C.c_void_p(q) if q else None  # noqa: E731
+        check(self._lib.ff_display(self._state, width, height, C.byref(p), vp(radiance_ptr), 1, vp(rgb8_ptr), 1, vp(display_out_ptr), 1))
+
+    def display_to_pbo(self, radiance, p=None):
+        """ff_display_to_pbo of host radiance [H,W,3] into the buffer registered with ff_register_gl_pbo."""
+        rad = np.ascontiguousarray(radiance, dtype=np.float32)
+        p = p if p is not None else display_params()
+        check(self._lib.ff_display_to_pbo(self._state, rad.shape[1], rad.shape[0], C.byref(p), rad.ctypes.data, 0))
+
+    def display_reset(self):
+        """Forget the adapted exposure (ff_display_reset)."""
+        check(self._lib.ff_display_reset(self._state))
+
+    def display_state(self):
+        """The last display call's (exposure, target, histogram uint32 [256])."""
+        e, t = C.c_float(), C.c_float()
+        hist = np.zeros(T.DISPLAY_BINS, dtype=np.uint32)
+        check(self._lib.ff_display_state(self._state, C.byref(e), C.byref(t), hist.ctypes.data))
+        return e.value, t.value, hist
 
     def strips_local_rows(self, height, strip_rows, part, num_parts):
         return self._lib.ff_strips_local_rows(height, strip_rows, part, num_parts)

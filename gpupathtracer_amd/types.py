@@ -146,6 +146,22 @@ class FfTaaParams(C.Structure):
 TAA_PARAMS_BYTES = 16
 TAA_BILINEAR, TAA_NO_CLAMP = 1, 2
 
+
+class FfDisplayParams(C.Structure):
+    _fields_ = [
+        ("curve", C.c_int32), ("encoding", C.c_int32), ("flags", C.c_int32), ("exposure", C.c_float), ("white", C.c_float), ("key", C.c_float),
+        ("low_percentile", C.c_float), ("high_percentile", C.c_float), ("min_exposure", C.c_float), ("max_exposure", C.c_float),
+        ("adapt_darken", C.c_float), ("adapt_brighten", C.c_float), ("dt", C.c_float), ("bloom_threshold", C.c_float),
+        ("bloom_strength", C.c_float), ("bloom_levels", C.c_int32),
+    ]
+
+
+DISPLAY_PARAMS_BYTES = 64
+CURVE_CLAMP, CURVE_REINHARD, CURVE_ACES = 0, 1, 2
+ENCODE_LINEAR, ENCODE_SRGB = 0, 1
+DISPLAY_AUTO_EXPOSURE, DISPLAY_BLOOM = 1, 2
+DISPLAY_BINS = 256  # ff_display's luminance histogram: 8 bins per stop from 2^-16 up
+
 BUILD_HOST_SAH, BUILD_GPU_LBVH, BUILD_GPU_PLOC = 0, 1, 2
 UPDATE_REFIT, UPDATE_REBUILD = 0, 1
 

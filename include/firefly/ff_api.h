@@ -527,6 +527,82 @@ FF_API int ff_taa_reset(FfState* state);
  * length (W*H floats).  Either may be NULL.  FF_ERR_INVALID_ARG when no call was made since the last reset. */
 FF_API int ff_taa_history(FfState* state, float* motion, float* length, int on_device);
 
+/* ---- display transform (exposure, bloom, tone curve, sRGB) ------------------------------------- */
+
+/* Defaults: ACES, SRGB, flags 0, exposure 1, white 4, key 0.18, percentiles 0.5 / 0.95, min_exposure 2^-10, max_exposure 2^10,
+ * adapt_darken 3, adapt_brighten 1, dt 0, bloom_threshold 1, bloom_strength 0.05, bloom_levels 5. */
+FF_API void ff_display_params_init(FfDisplayParams* p);
+
+/* The last stage of render -> ff_gbuffer -> ff_denoise_temporal -> ff_taa: turns W x H float3 radiance into the uchar3 buffer a
+ * viewer uploads.  A pure image operation like ff_denoise: no scene is read and none is needed.  All per-pixel arithmetic is
+ * float32, every formula evaluated left to right as written with the parentheses shown, no fused multiply-add; bits(l) is a
+ * float's 32-bit pattern.  In the order it is evaluated:
+ *   1 histogram  (only with FF_DISPLAY_AUTO_EXPOSURE; otherwise all 256 counts are 0)  l = (0.2126 r + 0.7152 g) + 0.0722 b of the
+ *                input pixel.  A pixel is counted when r, g, b are all finite and l >= 2^-16; its bin is
+ *                min((bits(l) >> 20) - 888, 255): 8 bins per stop from 2^-16 up (exponent and three mantissa bits), the top bin
+ *                open-ended.  Counts are integers: the histogram does not depend on the order of the adds
+ *   2 exposure   (host, double; ff_display_exposure is this step alone)  N = sum n_b.  low_percentile * N of mass is removed from
+ *                bin 0 upward and (1 - high_percentile) * N from bin 255 downward, each bin giving min(what it holds, what is
+ *                still to remove), the bottom first; with the remaining n'_b: S = sum n'_b and M = (sum n'_b L_b) / S, both sums
+ *                from bin 0 upward, L_b = (b + 0.5) / 8 - 16; target = clamp(key / 2^M, min_exposure, max_exposure) * exposure.
+ *                N = 0 or S <= 0: target = the previous exposure, or `exposure` if there is none.  No previous exposure (first
+ *                call, ff_display_reset) or dt <= 0: E = target.  Otherwise rate = adapt_darken if target < E_prev else
+ *                adapt_brighten and E = E_prev * 2^((log2 target - log2 E_prev) * (1 - exp(-dt * rate))).  E and target are
+ *                rounded to float once, at the end; E becomes the next call's E_prev.  Without AUTO_EXPOSURE: E = target =
+ *                exposure, and the stored previous exposure is left alone
+ *   3 exposed    e = c * E per channel.  A pixel with a non-finite channel may spoil only itself: in steps 1 and 4 it counts as
+ *                black; in step 5 its channels map NaN -> 0, -Inf -> 0, +Inf -> 1 (its finite channels go the ordinary way)
+ *   4 bloom      (only with FF_DISPLAY_BLOOM)  bright pass at full resolution: le = the luminance of e as in step 1,
+ *                k = max(le - bloom_threshold, 0) / max(le, 1e-30), B_0 = e * k.  Level j = 1 .. n = bloom_levels has size
+ *                (ceil(W_{j-1} / 2), ceil(H_{j-1} / 2)) and D_j(x, y) = ((D_{j-1}(2x, 2y) + D_{j-1}(2x+1, 2y)) + (D_{j-1}(2x, 2y+1)
+ *                + D_{j-1}(2x+1, 2y+1))) * 0.25 with coordinates clamped into level j-1 (D_0 = B_0).  Back up: U_n = D_n;
+ *                U_j = D_j + up(U_{j+1}) for j = n-1 .. 1, where up(S)(x, y) is the bilinear sample of S at ((x + 0.5) / 2 - 0.5,
+ *                (y + 0.5) / 2 - 0.5): taps x0 = (x - 1) >> 1 (arithmetic shift) and x0 + 1, clamped into S, with weights
+ *                (wx0, wx1) = (0.25, 0.75) for even x and (0.75, 0.25) for odd x, the same in y, rows combined first:
+ *                (S00 wx0 + S10 wx1) wy0 + (S01 wx0 + S11 wx1) wy1.  e' = e + up(U_1) * (bloom_strength / n), the quotient formed
+ *                once in float.  Without the flag e' = e
+ *   5 curve      x = max(e', 0) (NaN: 0); REINHARD: w2 = white * white, y = (x * (1 + x / w2)) / (1 + x); ACES: y = (x * (2.51 x +
+ *                0.03)) / (x * (2.43 x + 0.59) + 0.14); CLAMP: y = x.  A quotient that comes out NaN (Inf / Inf) is 1.  Then
+ *                y = min(max(y, 0), 1): this is display_out
+ *   6 encoding   LINEAR: byte = trunc(y * 255) (255 for y = 1), the rule of every rgb8 output here.  SRGB: T_b = float(eotf((b -
+ *                0.5) / 255)), eotf(s) = s / 12.92 for s <= 0.04045, else ((s + 0.055) / 1.055)^2.4, in double on the host,
+ *                b = 1 .. 255 (ff_srgb_thresholds); the byte is the number of thresholds <= y: round(255 oetf(y)), correctly rounded.
+ * rgb8 (W*H*3 bytes) and display_out (W*H*3 floats) may each be NULL; display_out may alias radiance_in.  Width and height are
+ * 1 .. 65535.  Synchronous; all launches go to the state's stream.  The call leaves FfStats, the stored primary hits and their
+ * key, the three filters' histories and the progressive sum as they were; its own state is the adapted exposure, the last
+ * histogram and its scratch buffers (allocated on first use, regrown for a larger size, freed by ff_destroy), and
+ * ff_upload_scene does not reset it.  FF_ERR_INVALID_ARG, with a message that names the field, for a NULL state / params /
+ * input, a bad size, an unknown curve / encoding / flag bit, and every range in FfDisplayParams' comments (every float must be
+ * finite), all checked before any device work. */
+FF_API int ff_display(FfState* state, int width, int height, const FfDisplayParams* p, const float* radiance_in, int input_on_device,
+                      void* rgb8, int rgb8_on_device, float* display_out, int display_out_on_device);
+
+/* ff_display into the buffer registered with ff_register_gl_pbo (map, ff_display with a device rgb8, unmap).
+ * FF_ERR_GL_UNAVAILABLE when none is registered, FF_ERR_INVALID_ARG when the size differs from the registration. */
+FF_API int ff_display_to_pbo(FfState* state, int width, int height, const FfDisplayParams* p, const float* radiance_in, int input_on_device);
+
+/* Forgets the adapted exposure: the next automatic call takes its target at once. */
+FF_API int ff_display_reset(FfState* state);
+
+/* The last ff_display call's E, target and histogram (256 counts); any may be NULL.  FF_ERR_INVALID_ARG before the first call. */
+FF_API int ff_display_state(FfState* state, float* out_exposure, float* out_target, uint32_t* out_histogram256);
+
+/* Host-only pieces of the operator (no GPU, no state). */
+/* T_1 .. T_255 of step 6. */
+FF_API int ff_srgb_thresholds(float* out255);
+/* Steps 5 and 6 for n values of e' (p's curve, white and encoding); out_y and out_bytes may each be NULL. */
+FF_API int ff_display_curve(const FfDisplayParams* p, const float* exposed, int n, float* out_y, unsigned char* out_bytes);
+/* Step 2 for a histogram of 256 counts; previous_exposure <= 0: there is none.  Either output may be NULL. */
+FF_API int ff_display_exposure(const FfDisplayParams* p, const uint32_t* histogram256, float previous_exposure, float* out_target,
+                               float* out_exposure);
+
+/* The writer twin of ff_load_hdr: flat (not run-length encoded) scanlines, header "#?RADIANCE", "FORMAT=32-bit_rle_rgbe",
+ * "-Y h +X w".  Texel, in float: m = max(r, g, b); m < 1e-32: (0, 0, 0, 0); else frexp(m) = (f, e), scale = (f * 256) / m, channel
+ * byte = min(trunc(c * scale), 255), exponent byte e + 128.  FF_ERR_INVALID_ARG for a negative or non-finite value or one of
+ * 2^127 and more (no exponent byte), FF_ERR_IO when the file cannot be written.  What ff_load_hdr reads back saves to the same
+ * bytes again. */
+FF_API int ff_save_hdr(const char* path, const float* rgb, int width, int height);
+
 /* saveToPPM (utilities.h:842-856) for the 8-bit framebuffer: P3 text, one "r g b" line per pixel, top row first. */
 FF_API int ff_save_ppm(const char* path, const unsigned char* rgb8, int width, int height);
 

@@ -276,6 +276,29 @@ typedef struct FfTaaParams {
     int32_t reserved;   /* 0 */
 } FfTaaParams;          /* 16 bytes */
 
+/* ff_display: the display transform, W x H float3 radiance -> 8-bit RGB (exposure, bloom, tone curve, encoding).
+ * ff_display_params_init gives the defaults; the formulas are in ff_api.h. */
+#define FF_CURVE_CLAMP     0   /* y = x */
+#define FF_CURVE_REINHARD  1   /* y = x (1 + x / white^2) / (1 + x) */
+#define FF_CURVE_ACES      2   /* y = x (2.51 x + 0.03) / (x (2.43 x + 0.59) + 0.14)   (Narkowicz 2015) */
+#define FF_ENCODE_LINEAR   0   /* byte = trunc(clamp(y) * 255): ff_render's quantisation, bit for bit */
+#define FF_ENCODE_SRGB     1   /* byte = #{ b in 1..255 : T_b <= y } (ff_srgb_thresholds) */
+#define FF_DISPLAY_AUTO_EXPOSURE 1
+#define FF_DISPLAY_BLOOM         2
+typedef struct FfDisplayParams {
+    int32_t curve, encoding, flags; /* FF_CURVE_*, FF_ENCODE_*, FF_DISPLAY_* bits */
+    float   exposure;          /* > 0.  Without AUTO_EXPOSURE the multiplier itself; with it, a compensation factor on the target */
+    float   white;             /* > 0, REINHARD's white point */
+    float   key;               /* > 0, auto: the luminance the scene's average is mapped to */
+    float   low_percentile, high_percentile; /* 0 <= low < high <= 1: the share of the histogram's mass that is averaged */
+    float   min_exposure, max_exposure;      /* 0 < min <= max: clamp of the automatic target (before compensation) */
+    float   adapt_darken, adapt_brighten;    /* >= 0, per second: speed when the exposure has to fall / to rise */
+    float   dt;                /* seconds since the previous call; <= 0: no adaptation, the target is taken at once */
+    float   bloom_threshold;   /* >= 0, on exposed luminance */
+    float   bloom_strength;    /* >= 0 */
+    int32_t bloom_levels;      /* 1..8 */
+} FfDisplayParams;             /* 64 bytes; every float must be finite */
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif
@@ -287,6 +310,7 @@ static_assert(sizeof(FfGeometry) == 208, "Geometry layout must match utilities.h
 static_assert(sizeof(FfRay) == 24, "Ray layout must match utilities.h:257-267");
 static_assert(sizeof(FfIntersect) == 40, "Intersect layout must match utilities.h:57-66");
 static_assert(sizeof(FfCamera) == 108, "Camera layout must match utilities.h:269-291");
+static_assert(sizeof(FfDisplayParams) == 64, "FfDisplayParams is 64 bytes");
 #else
 _Static_assert(sizeof(FfBXDF) == 60, "BXDF layout");
 _Static_assert(sizeof(FfTriangle) == 96, "Triangle layout");
@@ -294,6 +318,7 @@ _Static_assert(sizeof(FfGeometry) == 208, "Geometry layout");
 _Static_assert(sizeof(FfRay) == 24, "Ray layout");
 _Static_assert(sizeof(FfIntersect) == 40, "Intersect layout");
 _Static_assert(sizeof(FfCamera) == 108, "Camera layout");
+_Static_assert(sizeof(FfDisplayParams) == 64, "FfDisplayParams layout");
 #endif
 
 #endif /* FIREFLY_FF_TYPES_H */
