@@ -513,6 +513,20 @@ int render_enqueue(FfState* s, const FfCamera* camera, const FfRenderParams* prm
         const int cst = ensure_bytes((void**)&s->d_primary_cache, &s->primary_cache_bytes, (size_t)3 * (size_t)k.pix_items * sizeof(float4));
         if (cst != FF_OK) return cst;
     }
+    // Start records: diffuse scenes of up to 32 geometries (the instantiation without the extras) on the lane-owned kernel start every
+    // sample from the pre-pass's SHADED hit (trace_bvh_kernel<..., START>).  The class of a pixel depends on the bounce count and the
+    // shade mode, so the kept records serve only a frame that agrees in both; the raw hits are written and kept as before (the job-pool
+    // kernel, ff_gbuffer and FF_NO_START_RECORDS read them).
+    const bool use_start = reuse && !pool && !s->sw.no_start_records && s->num_geoms <= kChunkGeometries && k.num_planes == k.num_quads &&
+                           k.has_specular == 0 && k.trinormals == nullptr;
+    bool start_kept = true;
+    if (use_start) {
+        const size_t need = (size_t)2 * (size_t)k.pix_items * sizeof(float4);
+        if (s->start_records_bytes < need) s->primary_has_start = false; // (the buffer is about to move)
+        const int sst = ensure_bytes((void**)&s->d_start_records, &s->start_records_bytes, need);
+        if (sst != FF_OK) return sst;
+        start_kept = s->primary_has_start && s->start_bounces == bounces && s->start_shade == prm->shade_mode;
+    }
     k.park = nullptr;
     if (pool) {
         // where a lane's own path and query state waits between setup passes (trace_pool_kernel): 7 x 16 bytes per thread of the launch
@@ -630,7 +644,7 @@ int render_enqueue(FfState* s, const FfCamera* camera, const FfRenderParams* prm
     const bool exact_cull = reuse && !s->sw.no_primary_cull && num_blocks - (tail_mode ? tail_blocks : 0) > 0;
     // Can this frame start from the hits (and the mask) the last one stored?  Same camera, same pixel mapping, no change of the scene
     // since (every upload / update clears primary_valid), and a mask there if this frame wants one.
-    const bool kept = reuse && hits_kept && (!(cull || exact_cull) || s->primary_has_mask);
+    const bool kept = reuse && hits_kept && (!(cull || exact_cull) || s->primary_has_mask) && start_kept;
     s->pending_mask_reused = s->pending_mask_built = false;
     if (cull || exact_cull) {
         const size_t mask_bytes = ((size_t)k.pix_items / 64 + 2) * sizeof(unsigned long long);
@@ -649,6 +663,8 @@ int render_enqueue(FfState* s, const FfCamera* camera, const FfRenderParams* prm
         s->pending_culled_rays_per_pixel = (unsigned)(spp - (tail_mode ? tail_n : 0));
     }
     if (reuse && kept) k.primary_hits = s->d_primary_cache;
+    k.start_records = use_start ? s->d_start_records : nullptr;
+    k.start_bounces = bounces;
     if (reuse && !kept) {
         // The pre-pass: the same persistent kernel, one item per pixel, one primary ray each, the hit stored per pixel (settle_hit).  Its
         // rays are not path segments of the frame: the kernel does not count them, and the work queue starts from zero again behind it.  (Always the lane-
@@ -678,6 +694,9 @@ int render_enqueue(FfState* s, const FfCamera* camera, const FfRenderParams* prm
         s->primary_key = key;
         s->primary_valid = true;
         s->primary_has_mask = cull || exact_cull;
+        s->primary_has_start = use_start;
+        s->start_bounces = bounces;
+        s->start_shade = prm->shade_mode;
     }
     for (int l = 0; l < launches; ++l) {
         k.block_begin = l * blocks_per_launch;
@@ -692,7 +711,7 @@ int render_enqueue(FfState* s, const FfCamera* camera, const FfRenderParams* prm
             k.total_items = k.tail_first_item + k.pix_items * groups;
         }
         if (l > 0) FF_HIP(hipMemsetAsync(s->d_queue, 0, (size_t)k.queue_counters * kQueueStride * sizeof(unsigned), st));
-        FF_HIP(launch_trace(k, prm->trace_mode, s->collect_stats, grid, block_threads, st, &s->last_kernel_name, pool));
+        FF_HIP(launch_trace(k, prm->trace_mode, s->collect_stats, grid, block_threads, st, &s->last_kernel_name, pool, /*prepass=*/false, /*start=*/use_start));
     }
     FF_HIP(launch_combine(k, st));
     FF_HIP(hipEventRecord(s->ev_end, st));
@@ -771,6 +790,7 @@ void read_switches(FfState* s)
     w.no_primary_cull = std::getenv("FF_NO_PRIMARY_CULL") != nullptr;
     w.no_primary_reuse = std::getenv("FF_NO_PRIMARY_REUSE") != nullptr;
     w.no_primary_cache = std::getenv("FF_NO_PRIMARY_CACHE") != nullptr;
+    w.no_start_records = std::getenv("FF_NO_START_RECORDS") != nullptr;
     if (const char* e = std::getenv("FF_TAIL_BLOCKS")) w.tail_blocks = std::max(1, std::min(3, std::atoi(e)));
     if (const char* e = std::getenv("FF_REUSE_MIN_SPP")) w.reuse_min_spp = std::max(1, std::atoi(e));
     if (const char* e = std::getenv("FF_REUSE_QUORUM")) w.reuse_quorum = std::max(1, std::min(65, std::atoi(e)));
@@ -868,6 +888,7 @@ int ff_destroy(FfState* s)
     if (s->d_stack_spill) (void)hipFree(s->d_stack_spill);
     if (s->d_cull_mask) (void)hipFree(s->d_cull_mask);
     if (s->d_primary_cache) (void)hipFree(s->d_primary_cache);
+    if (s->d_start_records) (void)hipFree(s->d_start_records);
     if (s->d_park) (void)hipFree(s->d_park);
     if (s->d_accum) (void)hipFree(s->d_accum);
     if (s->d_frame) (void)hipFree(s->d_frame);

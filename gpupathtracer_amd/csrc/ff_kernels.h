@@ -109,6 +109,13 @@ struct KParams {
     // wall clock (100 MHz ticks since the first wave started; counters[27] holds that epoch), kTimelineBuckets buckets
     unsigned* timeline;
     unsigned timeline_ticks;
+    // Start records (trace_bvh_kernel<..., START = true>): 2 float4 per pixel item, [2][pix_items] - the stored hit shaded once by the
+    // pre-pass, which writes them next to the hits when this is set: {origin of the second segment, class << 24 | geometry} {flipped
+    // unit world normal, 0} for a diffuse first hit of a path that goes on; {0, 0, 0, class} {the sample's radiance, 0} for a pixel
+    // whose path ends at its first hit.  start_bounces: the frame's bounce count (the pre-pass itself runs with bounces = 1).
+    // (at the end: the kernels without START read everything above at the offsets they always had)
+    float4* start_records;
+    int start_bounces;
 };
 // The ray count of a launch is added up in kRaySlots 64-bit slots of the counter block, kRaySlotStride words apart, from slot
 // kRaySlotFirst on (the first 256 bytes hold the named counters): counters[kRaySlotStride * (kRaySlotFirst + j)].
@@ -179,10 +186,12 @@ int max_lds_nodes(int stack_depth, int block_threads, int num_geoms, size_t rese
 size_t pool_lds_bytes(int block_threads);
 
 // block_threads: 512 or 1024 for the BVH kernel; the brute-force kernel always runs 512.
-// *kernel_name (optional) receives the name of the instantiation launched, as rocprofv3 prints it.
+// *kernel_name (optional) receives the name of the instantiation launched, as rocprofv3 prints it - except that the instantiations
+// without START are named by their first five parameters, as before START existed (a profiler appends ", false").
 // pool: the job-pool kernel (scenes of up to kChunkGeometries geometries; the LDS layout must have left pool_lds_bytes free).
+// start: the instantiation that runs on KParams::start_records (diffuse scenes of up to kChunkGeometries geometries, not the pool).
 hipError_t launch_trace(const KParams& p, int trace_mode, bool collect_stats, int grid_blocks, int block_threads, hipStream_t stream,
-                        const char** kernel_name = nullptr, bool pool = false, bool prepass = false);
+                        const char** kernel_name = nullptr, bool pool = false, bool prepass = false, bool start = false);
 // Sums every pixel's sample blocks in order, scales by 1/spp and writes radiance / rgb8 (row-major, coalesced).
 hipError_t launch_combine(const KParams& p, hipStream_t stream);
 // Fills mask[pix_items / 64] (see KParams::cull_mask) and zeroes the block sums of the culled pixels.

@@ -310,6 +310,12 @@ constexpr int kPackedEntry = 0x40000000;                  // stack entry that na
 constexpr unsigned kItemPixelMask = 0x1FFFFFFu;           // Path::item: the pixel item number (the host keeps pix_items below 2^25) ...
 constexpr int kItemBlockShift = 25;                       // ... the sample block above it (at most 16 blocks per pixel) ...
 constexpr unsigned kItemTail = 0x80000000u;               // ... and the sign bit for tail items
+// Start records (KParams::start_records): the class of a pixel sits above the geometry index in word 3 of quarter 0
+constexpr int kStartClassShift = 24;
+constexpr unsigned kStartGeomMask = 0xFFFFFFu;
+constexpr unsigned kStartGoesOn = 1u;  // a diffuse surface and more than one bounce: {second segment's origin, class | geometry} {flipped unit world normal, 0}
+constexpr unsigned kStartEnds = 2u;    // the path ends at the first hit (an emitter, nothing in view, a one-bounce frame): {0, 0, 0, class} {the sample's radiance, 0}
+constexpr unsigned kStartGeneral = 3u; // anything else (MIRROR / GLASS at the first hit): the raw hit serves
 
 struct LdsBase {
     int node_cap;   // LDS node slots: quarter k of LDS node j lives at uint4 index k * node_cap + j
@@ -1631,9 +1637,13 @@ __device__ __forceinline__ WaveQueue make_wave_queue(const KParams& p)
 // reference's default camera 191 ms instead of 84.)
 // Called by ALL lanes of the wave (Q must stay wave-uniform); `need` marks the lanes that want a pixel.  Returns false for lanes
 // that did not ask or saw the end of the queue.
-__device__ __forceinline__ bool acquire_pixel(const KParams& p, int lane, Path& P, WaveQueue& Q, bool need, unsigned& rays)
+// START (trace_bvh_kernel on start records): a pixel whose path ends at its first hit (kStartEnds) never reaches the caller - its
+// item is answered here from the record's constant radiance, its rays counted (`answered`: wave-uniform, like Counters::reused).
+template <bool START = false>
+__device__ __forceinline__ bool acquire_pixel(const KParams& p, int lane, Path& P, WaveQueue& Q, bool need, unsigned& rays, unsigned* answered = nullptr)
 {
     bool got = false, exhausted = !need;
+    unsigned ended = 0u; // START: samples of kStartEnds items this lane answered
     for (;;) {
         const bool want = !got && !exhausted;
         const unsigned long long m = __ballot(want);
@@ -1718,6 +1728,33 @@ __device__ __forceinline__ bool acquire_pixel(const KParams& p, int lane, Path& 
                 const int gy = p.y0 + (strip * p.num_parts + p.part) * p.strip_rows + (ly - strip * p.strip_rows);
                 const int gx = p.x0 + lx;
                 if (lx < p.local_width && gx < p.xlim && ly < p.local_rows && gy < p.ylim) {
+                    if constexpr (START) {
+                        if (((unsigned)__float_as_int(p.start_records[pitem].w) >> kStartClassShift) == kStartEnds) {
+                            // Every sample of this pixel ends at the first hit with the same radiance (an emitter, nothing, a one-bounce
+                            // frame): the item is the sum a lane would have kept - n sequential additions from zero - or, for a tail
+                            // item, the constant stored per sample.  Each sample is a path segment answered without a traversal.
+                            const float4 l = p.start_records[p.pix_items + pitem];
+                            int n;
+                            if (tail) {
+                                const int s0 = p.tail_block * p.block_spp + p.tail_start[blk];
+                                n = min(p.spp_total, p.tail_block * p.block_spp + p.tail_start[blk + 1]) - s0;
+                                for (int i = 0; i < n; ++i) p.tail_samples[(size_t)(p.tail_start[blk] + i) * p.pix_items + pitem] = make_float4(l.x, l.y, l.z, 0.f);
+                            } else {
+                                const int block = p.block_begin + (int)blk;
+                                n = min(p.spp_total, (block + 1) * p.block_spp) - block * p.block_spp;
+                                float ax = 0.f, ay = 0.f, az = 0.f;
+                                for (int i = 0; i < n; ++i) {
+                                    ax = ax + l.x;
+                                    ay = ay + l.y;
+                                    az = az + l.z;
+                                }
+                                p.blocksums[(size_t)pitem * p.num_blocks + block] = make_float4(ax, ay, az, 0.f);
+                            }
+                            rays += (unsigned)max(n, 0);
+                            ended += (unsigned)max(n, 0);
+                            continue;
+                        }
+                    }
                     got = true;
                     P.gxy = (unsigned)gx | ((unsigned)gy << 16);
                     if (tail) {
@@ -1732,10 +1769,12 @@ __device__ __forceinline__ bool acquire_pixel(const KParams& p, int lane, Path& 
                         P.send = min(p.spp_total, P.s + p.block_spp);
                     }
                     P.ax = P.ay = P.az = 0.f;
-                    primary_ray(p, P.gxy, P.ray); // once per (pixel, block); its samples reuse the direction
-                    P.pdx = P.ray.dx;
-                    P.pdy = P.ray.dy;
-                    P.pdz = P.ray.dz;
+                    if constexpr (!START) { // (a start record holds what the primary ray was needed for)
+                        primary_ray(p, P.gxy, P.ray); // once per (pixel, block); its samples reuse the direction
+                        P.pdx = P.ray.dx;
+                        P.pdy = P.ray.dy;
+                        P.pdz = P.ray.dz;
+                    }
                     start_sample(p, P);
                     // A camera outside the scene (the reference's default one looks at its box from 12.5 units away: 96 % of the
                     // frame is background): a pixel whose primary ray misses the padded box around ALL geometries has no hit in any
@@ -1745,6 +1784,9 @@ __device__ __forceinline__ bool acquire_pixel(const KParams& p, int lane, Path& 
                 }
             }
         }
+    }
+    if constexpr (START) {
+        if (__ballot(ended != 0u) != 0ull) *answered += (unsigned)wave_sum((unsigned long long)ended);
     }
     return got;
 }
@@ -1766,6 +1808,38 @@ __device__ __forceinline__ int settle_hit(const KParams& p, const Best& best, bo
         out[0] = make_float4(best.dist, best.px, best.py, best.pz);
         out[p.pix_items] = make_float4(best.cx, best.cy, best.cz, __int_as_float(hit ? best.geom : -1));
         out[2 * (size_t)p.pix_items] = make_float4(__int_as_float(best.rec), 0.f, 0.f, 0.f);
+        if (p.start_records != nullptr) {
+            // ... and the start record: what settle_hit and scatter below compute from this hit for EVERY sample of the pixel, computed
+            // once - the same operations in the same order on the same operands (the throughput is 1, the direction the primary ray's).
+            unsigned cls = kStartEnds;
+            float4 q0 = make_float4(0.f, 0.f, 0.f, 0.f), q1 = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (hit) {
+                const int bxdf = mat_bxdf(M);
+                if (bxdf == FF_BXDF_EMITTER) {
+                    const float4 emission = mat_f4(M, 13);
+                    q1.x = 0.f + P.bx * emission.x;
+                    q1.y = 0.f + P.by * emission.y;
+                    q1.z = 0.f + P.bz * emission.z;
+                } else if (SPECULAR && (bxdf == FF_BXDF_MIRROR || bxdf == FF_BXDF_GLASS)) {
+                    cls = kStartGeneral;
+                } else if (p.start_bounces > 1) {
+                    cls = kStartGoesOn;
+                    float nx, ny, nz;
+                    world_normal(M, best, false, nx, ny, nz);
+                    const float ninv = ieee_rcp(ieee_sqrt(dot3(nx, ny, nz, nx, ny, nz)));
+                    float ux = nx * ninv, uy = ny * ninv, uz = nz * ninv;
+                    if (dot3(ux, uy, uz, P.ray.dx, P.ray.dy, P.ray.dz) > 0.0f) { ux = -ux; uy = -uy; uz = -uz; }
+                    q0.x = best.px + ux * kRayEps;
+                    q0.y = best.py + uy * kRayEps;
+                    q0.z = best.pz + uz * kRayEps;
+                    q1.x = ux; q1.y = uy; q1.z = uz;
+                }
+            }
+            q0.w = __int_as_float((int)((cls << kStartClassShift) | ((unsigned)(hit ? best.geom : 0) & kStartGeomMask)));
+            float4* rec = p.start_records + ((unsigned)P.item & kItemPixelMask);
+            rec[0] = q0;
+            rec[p.pix_items] = q1;
+        }
         if (!hit && p.cull_mask_out != nullptr) {
             // Nothing in view: every sample of the pixel adds zero.  Its bit goes into the mask the work queue consults (acquire_pixel:
             // its whole-block items are dropped when they are decoded, their rays counted), its block sums are zeroed and it is counted -
@@ -1830,6 +1904,29 @@ __device__ __forceinline__ int settle_hit(const KParams& p, const Best& best, bo
     return kPixelDone;
 }
 
+// The two halves of a diffuse bounce: the cosine-weighted direction about +z from the sample's random numbers (they depend only on
+// pixel, sample, segment and seed), and that direction carried into the orthonormal basis about the unit normal u.
+__device__ __forceinline__ void diffuse_local_direction(const KParams& p, const Path& P, float& wlx, float& wly, float& wlz)
+{
+    unsigned r0, r1;
+    const unsigned gpix = (P.gxy >> 16) * (unsigned)p.width + (P.gxy & 0xFFFFu);
+    philox2x32_10(gpix, ((unsigned)P.s << 8) | ((unsigned)P.b & 0xFFu), p.key, r0, r1);
+    const float u1 = (float)(r0 >> 8) * 5.9604644775390625e-08f;
+    cosine_sample(u1, r1 >> 8, wlx, wly, wlz);
+}
+__device__ __forceinline__ void to_world_about(float ux, float uy, float uz, float wlx, float wly, float wlz, float& wox, float& woy, float& woz)
+{
+    // orthonormal basis (Duff et al. 2017)
+    const float sign = copysignf(1.0f, uz);
+    const float aa = -ieee_rcp(sign + uz); // -1 / x == -(1 / x)
+    const float bb = (ux * uy) * aa;
+    const float t0 = 1.0f + ((sign * ux) * ux) * aa, t1 = sign * bb, t2 = -sign * ux;
+    const float s0 = bb, s1 = sign + (uy * uy) * aa, s2 = -uy;
+    wox = (t0 * wlx + s0 * wly) + ux * wlz;
+    woy = (t1 * wlx + s1 * wly) + uy * wlz;
+    woz = (t2 * wlx + s2 * wly) + uz * wlz;
+}
+
 // The next ray of a path that goes on from `best` (settle_hit returned kGoesOn; the throughput already carries the surface's
 // albedo, glass excepted).  MIRROR: perfect reflection.  GLASS: smooth dielectric, Fresnel-weighted choice between reflection and
 // refraction (oracle/ff_oracle.c is the definition).  Everything else: cosine-weighted direction about the world normal.
@@ -1891,26 +1988,54 @@ __device__ __forceinline__ void scatter(const KParams& p, const Best& best, cons
         woy = P.ray.dy - k2 * uy;
         woz = P.ray.dz - k2 * uz;
     } else {
-        unsigned r0, r1;
-        const unsigned gpix = (P.gxy >> 16) * (unsigned)p.width + (P.gxy & 0xFFFFu);
-        philox2x32_10(gpix, ((unsigned)P.s << 8) | ((unsigned)P.b & 0xFFu), p.key, r0, r1);
-        const float u1 = (float)(r0 >> 8) * 5.9604644775390625e-08f;
         float wlx, wly, wlz;
-        cosine_sample(u1, r1 >> 8, wlx, wly, wlz);
-        // orthonormal basis (Duff et al. 2017)
-        const float sign = copysignf(1.0f, uz);
-        const float aa = -ieee_rcp(sign + uz); // -1 / x == -(1 / x)
-        const float bb = (ux * uy) * aa;
-        const float t0 = 1.0f + ((sign * ux) * ux) * aa, t1 = sign * bb, t2 = -sign * ux;
-        const float s0 = bb, s1 = sign + (uy * uy) * aa, s2 = -uy;
-        wox = (t0 * wlx + s0 * wly) + ux * wlz;
-        woy = (t1 * wlx + s1 * wly) + uy * wlz;
-        woz = (t2 * wlx + s2 * wly) + uz * wlz;
+        diffuse_local_direction(p, P, wlx, wly, wlz);
+        to_world_about(ux, uy, uz, wlx, wly, wlz, wox, woy, woz);
     }
     P.ray.ox = best.px + sx * kRayEps;
     P.ray.oy = best.py + sy * kRayEps;
     P.ray.oz = best.pz + sz * kRayEps;
     P.ray.dx = wox; // unit local direction in an orthonormal basis: used as is (|wo| = 1 +- 1e-6)
+    P.ray.dy = woy;
+    P.ray.dz = woz;
+    ++P.b;
+}
+
+// scatter for the kernel that runs on start records (diffuse scenes: SPECULAR = false).  Lanes in it go on either from the hit they
+// just traced (settle_hit returned kGoesOn) or, `from_rec`, from their pixel's start record {q0, q1}: a new sample whose first segment
+// the pre-pass answered and shaded.  For those the throughput, the normal, the flip and the origin come from the record; the random
+// numbers, the cosine sample, the basis and the direction are common code.  The record's quarters are first touched behind the
+// Philox rounds: the caller issued their loads just before, and the rounds cover the latency.
+__device__ __forceinline__ void scatter_start(const KParams& p, const Best& best, MaterialRef& M, Path& P, bool from_rec, const float4& q0, const float4& q1)
+{
+    float ux = 0.f, uy = 0.f, uz = 1.f, ox = 0.f, oy = 0.f, oz = 0.f;
+    if (!from_rec) {
+        float nx, ny, nz;
+        world_normal(M, best, false, nx, ny, nz);
+        const float ninv = ieee_rcp(ieee_sqrt(dot3(nx, ny, nz, nx, ny, nz)));
+        ux = nx * ninv; uy = ny * ninv; uz = nz * ninv;
+        if (dot3(ux, uy, uz, P.ray.dx, P.ray.dy, P.ray.dz) > 0.0f) { ux = -ux; uy = -uy; uz = -uz; }
+        ox = best.px + ux * kRayEps;
+        oy = best.py + uy * kRayEps;
+        oz = best.pz + uz * kRayEps;
+    }
+    float wlx, wly, wlz;
+    diffuse_local_direction(p, P, wlx, wly, wlz);
+    if (from_rec) {
+        M.g = (int)((unsigned)__float_as_int(q0.w) & kStartGeomMask);
+        const float4 albedo = mat_f4(M, 12);
+        P.bx = P.bx * albedo.x; // (1 * albedo: the expression settle_hit evaluates)
+        P.by = P.by * albedo.y;
+        P.bz = P.bz * albedo.z;
+        ux = q1.x; uy = q1.y; uz = q1.z;
+        ox = q0.x; oy = q0.y; oz = q0.z;
+    }
+    float wox, woy, woz;
+    to_world_about(ux, uy, uz, wlx, wly, wlz, wox, woy, woz);
+    P.ray.ox = ox;
+    P.ray.oy = oy;
+    P.ray.oz = oz;
+    P.ray.dx = wox;
     P.ray.dy = woy;
     P.ray.dz = woz;
     ++P.b;
@@ -1998,6 +2123,7 @@ __device__ __forceinline__ void init_path(Path& P)
 //   finish_segment  exact evaluation of the finished queries' winners (kernel.cu:110-125)
 //   settle_hit      does the path end here?  radiance, next sample, end of block; repeated for the lanes whose next sample starts
 //                   from the block's parked primary hit (every sample of a pixel starts with the same ray)
+//                   (START: once - a lane whose next sample starts loads its pixel's start record and joins scatter_start)
 //   scatter         normal, random numbers, next ray: once, for paths that go on from a traced hit and from a parked hit alike
 //   acquire_pixel   new (pixel, sample block) items for the lanes without work
 //   begin_segment   walls (wall table), other planes / spheres, candidate meshes; a last-bounce query that holds no emitter ends here
@@ -2011,9 +2137,13 @@ __device__ __forceinline__ void init_path(Path& P)
 // PREPASS = true is the instantiation that traces every pixel's primary ray once and stores its hit (settle_hit): the same loop on
 // one-ray items; a compile-time switch because its store / mask code inside the shading loop would cost the frame's own kernel
 // twenty spilled registers.
-template <bool STATS, int BLOCK, bool EXTRAS, int BIG = 0, bool PREPASS = false>
+// START = true (diffuse scenes of up to 32 geometries: EXTRAS = false, BIG = 0) is the instantiation that runs on the pre-pass's start
+// records instead of its raw hits: a sample starts inside the shading pass that ended the one before it, and the settle loop below
+// is not part of it; a template parameter and not a branch for the reason PREPASS is one.
+template <bool STATS, int BLOCK, bool EXTRAS, int BIG = 0, bool PREPASS = false, bool START = false>
 __global__ __launch_bounds__(BLOCK) void trace_bvh_kernel(const KParams p)
 {
+    static_assert(!START || (!EXTRAS && BIG == 0 && !PREPASS), "start records: the diffuse small-scene kernel only");
     const int tid = threadIdx.x;
     const int lane = tid & (kWave - 1);
     const LdsT<BIG> L = make_lds<BIG>(p.lds_nodes, p.stack_depth, BLOCK, tid, EXTRAS ? p.num_quads : 0x7fffffff, EXTRAS ? p.trinormals : nullptr,
@@ -2046,7 +2176,7 @@ __global__ __launch_bounds__(BLOCK) void trace_bvh_kernel(const KParams p)
     // stored by settle_hit) traces it ONCE per pixel; here every sample starts from the stored hit: no query, no traversal, no
     // resolution for the primary segment - one fifth of the headline frame's path segments.  (Rounds 3 kept the hit per lane and sample
     // block: one traced primary ray per 64 samples and 1.6 GB of parked hits written per 1080p frame.)
-    const bool reuse = !PREPASS && p.primary_hits != nullptr; // wave-uniform
+    const bool reuse = START || (!PREPASS && p.primary_hits != nullptr); // wave-uniform
     // (the address is formed where it is used - a few instructions - rather than held in registers through the loop)
     auto stored_hit = [&](int k) { return p.primary_hits + (size_t)k * p.pix_items + ((unsigned)P.item & kItemPixelMask); };
     // instrumented launches only: wave cycles per phase (s_memtime), [0] resolve [1] shade [2] acquire [3] begin [4] traverse
@@ -2091,61 +2221,97 @@ __global__ __launch_bounds__(BLOCK) void trace_bvh_kernel(const KParams p)
             finish_segment(L, p.tris, P.ray, S, best);
             hit = best.geom >= 0;
         }
-        // A lane that waits with a new sample (it starts from the pixel's stored primary hit, see below) joins this iteration's shading.
-        bool from_cache = setup && !inflight && active && P.b == 0 && reuse;
         if (STATS) t1 = __builtin_amdgcn_s_memtime();
-        // Shading in two steps (settle_hit / scatter).  A lane whose path ended and whose next sample starts with the parked hit
-        // settles again - at once if at least reuse_quorum lanes of the wave are in that position, else together with the next
-        // iteration's finished queries - until every settling lane has a path that goes on from a hit, a first-of-block primary ray
-        // to trace, a parked hit to wait with, or no work left.  Settling is cheap (a material lookup, a few multiplications); the
-        // expensive step - normal, random numbers, new direction - then runs ONCE, for the lanes that go on from the hit they just
-        // found and for those that go on from their parked primary hit alike.
-        bool settle_now = shade_now, goes_on = false;
-        for (;;) { // (every pass ends a sample of each lane in it: at most a block's samples)
-            if (from_cache) {
-                const float4 c0 = *stored_hit(0), c1 = *stored_hit(1), c2 = *stored_hit(2);
-                best.dist = c0.x; best.px = c0.y; best.py = c0.z; best.pz = c0.w;
-                best.cx = c1.x; best.cy = c1.y; best.cz = c1.z;
-                best.geom = __float_as_int(c1.w);
-                best.rec = __float_as_int(c2.x);
-                hit = best.geom >= 0;
-                cnt.rays += 1; // a path segment like any other, answered without a traversal (counted apart below)
-                settle_now = true;
-            }
-            {
-                const unsigned reused_now = (unsigned)__popcll(__ballot(from_cache));
-                cnt.reused += reused_now;
-                if (STATS && p.timeline) tl_count += reused_now; // (the launch timeline counts every path segment where it completes)
-            }
-            if (__ballot(settle_now) == 0ull) break;
-            bool waiting = false;
-            if (settle_now) {
-                MaterialRef M;
-                M.global = BIG == 2 ? p.geoms + (hit ? best.geom : 0) : nullptr;
-                M.geom_base = L.geom_base;
+        if constexpr (START) {
+            // Shading on start records.  Every sample of a pixel starts with the same ray, and the pre-pass has shaded its hit: a lane
+            // whose path ends here (settle_hit: kNewSample) - or that took a new item in the last iteration - has its next sample's
+            // first segment answered already.  It issues the loads of its pixel's record, counts the segment and joins THIS pass's
+            // scatter as a lane that goes on.  One settle, one scatter per iteration; no lane waits for a second trip.  (Pixels whose
+            // path ends at the first hit never get here: acquire_pixel answers their items.)
+            bool from_rec = setup && !inflight && active && P.b == 0;
+            bool goes_on = false;
+            MaterialRef M;
+            M.global = nullptr;
+            M.geom_base = L.geom_base;
+            M.g = 0;
+            if (shade_now) {
                 M.g = best.geom;
-                const int r = settle_hit<EXTRAS, PREPASS>(p, best, hit, M, P);
+                const int r = settle_hit<false, false>(p, best, hit, M, P);
                 inflight = false;
                 active = r != kPixelDone;
                 goes_on = r == kGoesOn;
-                waiting = r == kNewSample && reuse; // a new sample: it starts from the pixel's stored primary hit
+                from_rec = r == kNewSample;
             }
-            settle_now = false;
-            from_cache = waiting && __popcll(__ballot(waiting)) >= p.reuse_quorum;
-        }
-        if (goes_on) {
-            MaterialRef M;
-            M.global = BIG == 2 ? p.geoms + best.geom : nullptr;
-            M.geom_base = L.geom_base;
-            M.g = best.geom;
-            scatter<EXTRAS>(p, best, M, P);
+            float4 q0 = make_float4(0.f, 0.f, 0.f, 0.f), q1 = q0;
+            if (from_rec) {
+                const float4* rec = p.start_records + ((unsigned)P.item & kItemPixelMask);
+                q0 = rec[0];
+                q1 = rec[p.pix_items];
+                cnt.rays += 1; // a path segment like any other, answered without a traversal (counted apart below)
+                goes_on = true;
+            }
+            {
+                const unsigned reused_now = (unsigned)__popcll(__ballot(from_rec));
+                cnt.reused += reused_now;
+                if (STATS && p.timeline) tl_count += reused_now; // (the launch timeline counts every path segment where it completes)
+            }
+            if (goes_on) scatter_start(p, best, M, P, from_rec, q0, q1);
+        } else {
+            // A lane that waits with a new sample (it starts from the pixel's stored primary hit, see below) joins this iteration's shading.
+            bool from_cache = setup && !inflight && active && P.b == 0 && reuse;
+            // Shading in two steps (settle_hit / scatter).  A lane whose path ended and whose next sample starts with the parked hit
+            // settles again - at once if at least reuse_quorum lanes of the wave are in that position, else together with the next
+            // iteration's finished queries - until every settling lane has a path that goes on from a hit, a first-of-block primary ray
+            // to trace, a parked hit to wait with, or no work left.  Settling is cheap (a material lookup, a few multiplications); the
+            // expensive step - normal, random numbers, new direction - then runs ONCE, for the lanes that go on from the hit they just
+            // found and for those that go on from their parked primary hit alike.
+            bool settle_now = shade_now, goes_on = false;
+            for (;;) { // (every pass ends a sample of each lane in it: at most a block's samples)
+                if (from_cache) {
+                    const float4 c0 = *stored_hit(0), c1 = *stored_hit(1), c2 = *stored_hit(2);
+                    best.dist = c0.x; best.px = c0.y; best.py = c0.z; best.pz = c0.w;
+                    best.cx = c1.x; best.cy = c1.y; best.cz = c1.z;
+                    best.geom = __float_as_int(c1.w);
+                    best.rec = __float_as_int(c2.x);
+                    hit = best.geom >= 0;
+                    cnt.rays += 1; // a path segment like any other, answered without a traversal (counted apart below)
+                    settle_now = true;
+                }
+                {
+                    const unsigned reused_now = (unsigned)__popcll(__ballot(from_cache));
+                    cnt.reused += reused_now;
+                    if (STATS && p.timeline) tl_count += reused_now; // (the launch timeline counts every path segment where it completes)
+                }
+                if (__ballot(settle_now) == 0ull) break;
+                bool waiting = false;
+                if (settle_now) {
+                    MaterialRef M;
+                    M.global = BIG == 2 ? p.geoms + (hit ? best.geom : 0) : nullptr;
+                    M.geom_base = L.geom_base;
+                    M.g = best.geom;
+                    const int r = settle_hit<EXTRAS, PREPASS>(p, best, hit, M, P);
+                    inflight = false;
+                    active = r != kPixelDone;
+                    goes_on = r == kGoesOn;
+                    waiting = r == kNewSample && reuse; // a new sample: it starts from the pixel's stored primary hit
+                }
+                settle_now = false;
+                from_cache = waiting && __popcll(__ballot(waiting)) >= p.reuse_quorum;
+            }
+            if (goes_on) {
+                MaterialRef M;
+                M.global = BIG == 2 ? p.geoms + best.geom : nullptr;
+                M.geom_base = L.geom_base;
+                M.g = best.geom;
+                scatter<EXTRAS>(p, best, M, P);
+            }
         }
         if (STATS) t2 = __builtin_amdgcn_s_memtime();
         {
             const bool need = setup && !active && !exhausted;
             if (__ballot(need) != 0ull) {
                 const unsigned rays_before = cnt.rays;
-                const bool got = acquire_pixel(p, lane, P, Q, need, cnt.rays); // (all lanes call: the wave's chunk of the queue is wave state)
+                const bool got = acquire_pixel<START>(p, lane, P, Q, need, cnt.rays, &cnt.reused); // (all lanes call: the wave's chunk of the queue is wave state)
                 if (STATS && p.timeline) tl_count += (unsigned)wave_sum((unsigned long long)(cnt.rays - rays_before)); // (the rays of items dropped at the queue)
                 if (need) {
                     active = got;
@@ -3451,6 +3617,12 @@ hipError_t prepare_kernels()
     FF_SET_LDS((trace_bvh_kernel<false, 512, true, 2, true>))
     FF_SET_LDS((trace_bvh_kernel<false, 768, true, 2, true>))
     FF_SET_LDS((trace_bvh_kernel<false, 1024, true, 2, true>))
+    FF_SET_LDS((trace_bvh_kernel<false, 512, false, 0, false, true>))
+    FF_SET_LDS((trace_bvh_kernel<true, 512, false, 0, false, true>))
+    FF_SET_LDS((trace_bvh_kernel<false, 768, false, 0, false, true>))
+    FF_SET_LDS((trace_bvh_kernel<true, 768, false, 0, false, true>))
+    FF_SET_LDS((trace_bvh_kernel<false, 1024, false, 0, false, true>))
+    FF_SET_LDS((trace_bvh_kernel<true, 1024, false, 0, false, true>))
     FF_SET_LDS((trace_pool_kernel<false, 1024, false>))
     FF_SET_LDS((trace_pool_kernel<false, 1024, true>))
     FF_SET_LDS((trace_pool_kernel<true, 1024, false>))
@@ -3471,7 +3643,7 @@ hipError_t prepare_kernels()
 size_t pool_lds_bytes(int block_threads) { return (size_t)block_threads * 48 + (size_t)kPoolRing * 2 + 128; } // jobs, ring, [head, tail, -, -], the role's inputs, the workgroup's tallies
 
 hipError_t launch_trace(const KParams& p, int trace_mode, bool collect_stats, int grid_blocks, int block_threads, hipStream_t stream,
-                        const char** kernel_name, bool pool, bool prepass)
+                        const char** kernel_name, bool pool, bool prepass, bool start)
 {
     const dim3 grid(grid_blocks);
     const char* name = "";
@@ -3514,9 +3686,13 @@ hipError_t launch_trace(const KParams& p, int trace_mode, bool collect_stats, in
         const int big = p.num_geoms <= kChunkGeometries ? 0 : (p.num_geoms <= kMaxLdsRecords ? 1 : 2);
         const size_t lds = bvh_lds_bytes(p.lds_nodes, p.stack_depth, block_threads, big == 2 ? 0 : p.num_geoms);
         const bool spheres = p.num_planes > p.num_quads || p.has_specular != 0 || p.trinormals != nullptr; // any extra: the full kernel
+        if (start && (big != 0 || spheres || p.start_records == nullptr)) return hipErrorInvalidValue; // (the host asks for it on diffuse small scenes only)
 #define FF_LAUNCH_BVH(B)                                                                                                  \
     do {                                                                                                                  \
-        if (big == 1) {                                                                                                   \
+        if (start) {                                                                                                      \
+            if (collect_stats) { hipLaunchKernelGGL((trace_bvh_kernel<true, B, false, 0, false, true>), grid, block, lds, stream, p); name = "trace_bvh_kernel<true, " #B ", false, 0, false, true>"; } \
+            else { hipLaunchKernelGGL((trace_bvh_kernel<false, B, false, 0, false, true>), grid, block, lds, stream, p); name = "trace_bvh_kernel<false, " #B ", false, 0, false, true>"; } \
+        } else if (big == 1) {                                                                                                   \
             if (collect_stats) { hipLaunchKernelGGL((trace_bvh_kernel<true, B, true, 1>), grid, block, lds, stream, p); name = "trace_bvh_kernel<true, " #B ", true, 1, false>"; } \
             else { hipLaunchKernelGGL((trace_bvh_kernel<false, B, true, 1>), grid, block, lds, stream, p); name = "trace_bvh_kernel<false, " #B ", true, 1, false>"; } \
         } else if (big == 2) {                                                                                            \

@@ -37,6 +37,12 @@ struct FfState {
     size_t cull_mask_bytes = 0;
     float4* d_primary_cache = nullptr; // KParams::primary_cache
     size_t primary_cache_bytes = 0;
+    // The start records that go with the stored hits (KParams::start_records): kept under the same rule, and only for the bounce
+    // count and shade mode they were classified for
+    float4* d_start_records = nullptr;
+    size_t start_records_bytes = 0;
+    bool primary_has_start = false;
+    int start_bounces = 0, start_shade = 0;
     // The stored primary hits (and the mask of pixels that see nothing) belong to a camera, a pixel mapping and a scene: while those
     // stay what they were - a viewer that accumulates 1-spp frames with the camera at rest (kernel.cu:266,342) - the next frame starts
     // from them without a pre-pass.  primary_key: what they were computed for; any change of the scene clears primary_valid.
@@ -181,6 +187,7 @@ struct FfState {
     // getenv runs next to another thread's setenv.
     struct Switches {
         bool no_last_bounce_cut = false, no_primary_cull = false, no_primary_reuse = false; // per frame (render_enqueue)
+        bool no_start_records = false; // FF_NO_START_RECORDS: every sample starts from the pixel's raw stored hit (the kernel without START)
         bool no_primary_cache = false; // FF_NO_PRIMARY_CACHE: every frame runs its own pre-pass (the stored hits are not kept from frame to frame)
         int tail_blocks = 0;           // FF_TAIL_BLOCKS: how many of the frame's last sample blocks go out as short items (0: the library's choice)
         int reuse_min_spp = 2;         // FF_REUSE_MIN_SPP: frames of fewer samples per pixel trace their primary rays themselves unless the hits are there
