@@ -14,10 +14,7 @@
 // (the interop header relies on hip_runtime.h having been included first)
 #include <hip/hip_gl_interop.h>
 
-#include "ff_denoise.h"
 #include "ff_state.h"
-#include "ff_taa.h"
-#include "ff_temporal.h"
 
 using namespace ff;
 
@@ -302,6 +299,140 @@ int collapse_slot(FfState* s, size_t gi, bool with_info)
     return FF_OK;
 }
 
+// The camera and the pixel mapping of a frame part into `k`: strips of strip_rows rows dealt to num_parts parts, of which this is
+// `part` with local_rows rows, and the window [x0, x0 + win_w) x (y0 + ...) of the W x H image.  num_blocks: the sample blocks a
+// pixel item is queued for (the work queue counts items in 31 bits); who: the prefix of that error's text.
+int fill_frame_mapping(const FfState* s, KParams& k, const FfCamera* camera, int W, int H, int grid_mode, int strip_rows, int part, int num_parts,
+                       int local_rows, int x0, int y0, int win_w, int num_blocks, const char* who)
+{
+    FfMat4 cm;
+    ff_camera_ray_matrix_jittered(camera, s->jitter_x, s->jitter_y, &cm); // (the state's pixel jitter; 0 0: ff_camera_ray_matrix)
+    std::memcpy(k.cam_c0, &cm.m[0], 16);
+    std::memcpy(k.cam_c1, &cm.m[4], 16);
+    std::memcpy(k.cam_c2, &cm.m[8], 16);
+    std::memcpy(k.cam_c3, &cm.m[12], 16);
+    k.cam_pos[0] = camera->m_position.x;
+    k.cam_pos[1] = camera->m_position.y;
+    k.cam_pos[2] = camera->m_position.z;
+    k.far_clip = camera->m_farClip;
+    k.screen_w = camera->m_screenWidth;
+    k.screen_h = camera->m_screenHeight;
+    k.width = W;
+    k.height = H;
+    k.xlim = W;
+    k.ylim = H;
+    if (grid_mode == FF_GRID_REFERENCE_FLOOR) { // kernel.cu:306-309
+        k.xlim = (W / 16) * 16;
+        k.ylim = (H / 16) * 16;
+    }
+    k.strip_rows = strip_rows;
+    k.part = part;
+    k.num_parts = num_parts;
+    k.local_rows = local_rows;
+    k.x0 = x0;
+    k.y0 = y0;
+    k.local_width = win_w;
+    k.tiles_per_row = (win_w + 7) / 8;
+    const uint64_t tiles = (uint64_t)k.tiles_per_row * (uint64_t)((local_rows + 7) / 8);
+    if (tiles * 64 * (uint64_t)(num_blocks + 64) >= (1ull << 31)) return fail(FF_ERR_INVALID_ARG, "%simage too large for the work queue", who);
+    k.pix_items = (unsigned)(tiles * 64);
+    return FF_OK;
+}
+
+// The uploaded scene and its LDS layout (finalize_layout) into `k`.  smooth: the frame shades with vertex normals; lds_block_threads:
+// the BVH kernel's workgroup size, for FF_DEBUG_LDS_FILL (0: a brute-force frame, which has no such layout).
+void fill_scene(const FfState* s, KParams& k, bool smooth, int lds_block_threads)
+{
+    k.setup_threshold = s->setup_threshold;
+    k.leaf_threshold = s->leaf_threshold;
+    k.num_geoms = s->num_geoms;
+    k.num_planes = s->num_planes;
+    k.num_quads = s->num_quads;
+    k.has_specular = s->has_specular ? 1 : 0;
+    k.geoms = s->d_geoms;
+    k.tris = s->d_tris;
+    k.trinormals = smooth ? reinterpret_cast<const float4*>(s->d_normals) : nullptr;
+    k.nodes4 = s->d_nodes4;
+    if (s->sw.lds_fill && lds_block_threads > 0) {
+        const size_t bytes = bvh_lds_bytes(s->lds_cap, s->stack_lds_levels, lds_block_threads, lds_records(s)); // (the pool behind it is initialised by the kernel)
+        k.debug_lds_words = (unsigned)std::min<size_t>(s->sw.lds_fill_words, bytes / 4);
+        k.debug_lds_pattern = (unsigned)s->sw.lds_fill_pattern;
+    }
+    k.stack_depth = s->stack_lds_levels;
+    k.stack_spill = nullptr;
+    k.lds_nodes = s->lds_cap;
+    k.top_first = (int)s->node_capacity;
+    k.top_lds_first = 0;
+    k.top_lds_count = s->top_lds_count;
+    k.num_scan = s->num_scan;
+    k.walls = s->walls;
+}
+
+// The stack levels that did not get LDS (finalize_layout): one int per level and thread of the launch.
+int attach_stack_spill(FfState* s, KParams& k, int grid, int block_threads)
+{
+    if (s->stack_lds_levels >= s->stack_entries) return FF_OK;
+    const int st = ensure_bytes((void**)&s->d_stack_spill, &s->stack_spill_bytes,
+                                (size_t)(s->stack_entries - s->stack_lds_levels) * (size_t)grid * (size_t)block_threads * sizeof(int));
+    if (st == FF_OK) k.stack_spill = s->d_stack_spill;
+    return st;
+}
+
+// The work queue's counters for a launch of `grid` workgroups, and its as-asked tail zone: tail_per_wave items (FF_QUEUE_TAIL
+// overrides) for every wave that draws from a counter.
+void size_work_queue(const FfState* s, KParams& k, int grid, int block_threads, int tail_per_wave)
+{
+    k.queue_counters = std::min(kQueueCountersDefault, grid);
+    if (s->sw.queue_counters > 0) k.queue_counters = std::min(std::min(kQueueCounters, grid), s->sw.queue_counters);
+    const int waves_per_counter = (grid * (block_threads / 64) + k.queue_counters - 1) / k.queue_counters;
+    k.queue_tail_items = (unsigned)(waves_per_counter * (s->sw.queue_tail >= 0 ? s->sw.queue_tail : tail_per_wave));
+}
+
+// What stored primary hits were computed for: the camera and the pixel mapping in `k` (fill_frame_mapping), and whether the stored
+// normal is the interpolated one (the frame shades with vertex normals).  Compared bytewise.
+FfState::PrimaryKey primary_key(const KParams& k, bool smooth)
+{
+    FfState::PrimaryKey key;
+    std::memset(&key, 0, sizeof key);
+    std::memcpy(key.cam, k.cam_c0, 16 * sizeof(float));
+    std::memcpy(key.cam + 16, k.cam_pos, 3 * sizeof(float));
+    key.cam[19] = k.far_clip; key.cam[20] = k.screen_w; key.cam[21] = k.screen_h;
+    const int dims[12] = { k.width, k.height, k.xlim, k.ylim, k.strip_rows, k.part, k.num_parts, k.local_rows, k.x0, k.y0, k.local_width, smooth ? 1 : 0 };
+    std::memcpy(key.dims, dims, sizeof dims);
+    key.pix_items = k.pix_items;
+    return key;
+}
+
+// The pre-pass of a frame whose launch parameters are `k`: the same persistent kernel, one item per pixel, one primary ray each, the
+// hit stored per pixel in `hits` (settle_hit) and the pixels that hit nothing marked in mask_out (may be null).  Its rays are not path
+// segments of the frame: the kernel does not count them, and the work queue starts from zero again behind it.  (Always the lane-owned
+// kernel, never instrumented: the frame's own launches are what the statistics describe.)
+int enqueue_prepass(FfState* s, const KParams& k, float4* hits, unsigned long long* mask_out, int frame_blocks, int grid, int block_threads)
+{
+    KParams kp = k;
+    kp.shade_mode = kShadePrimaryPass;
+    kp.primary_hits = hits;
+    kp.bounces = 1;
+    kp.spp_total = 1;
+    kp.block_spp = 1;
+    kp.num_blocks = 1;
+    kp.block_begin = 0;
+    kp.block_end = 1;
+    kp.whole_blocks = 1u;
+    kp.total_items = kp.pix_items;
+    kp.tail_block = -1;
+    kp.cull_mask = nullptr; // (every pixel gets its stored hit: a culled pixel's tail items - its last block, traced sample by sample - read it too)
+    kp.cull_mask_out = mask_out;
+    kp.frame_blocks = frame_blocks;
+    kp.cut_last = 0;
+    kp.timeline = nullptr;
+    kp.queue_chunk = 32u;
+    if (s->sw.queue_chunk > 0) kp.queue_chunk = (unsigned)s->sw.queue_chunk;
+    FF_HIP(launch_trace(kp, FF_TRACE_BVH, false, grid, block_threads, s->stream, nullptr, false, /*prepass=*/true));
+    FF_HIP(hipMemsetAsync(s->d_queue, 0, (size_t)k.queue_counters * kQueueStride * sizeof(unsigned), s->stream));
+    return FF_OK;
+}
+
 } // namespace
 
 namespace ff {
@@ -335,37 +466,10 @@ int render_enqueue(FfState* s, const FfCamera* camera, const FfRenderParams* prm
 
     KParams k;
     std::memset(&k, 0, sizeof k);
-    FfMat4 cm;
-    ff_camera_ray_matrix_jittered(camera, s->jitter_x, s->jitter_y, &cm); // (the state's pixel jitter; 0 0: ff_camera_ray_matrix)
-    std::memcpy(k.cam_c0, &cm.m[0], 16);
-    std::memcpy(k.cam_c1, &cm.m[4], 16);
-    std::memcpy(k.cam_c2, &cm.m[8], 16);
-    std::memcpy(k.cam_c3, &cm.m[12], 16);
-    k.cam_pos[0] = camera->m_position.x;
-    k.cam_pos[1] = camera->m_position.y;
-    k.cam_pos[2] = camera->m_position.z;
-    k.far_clip = camera->m_farClip;
-    k.screen_w = camera->m_screenWidth;
-    k.screen_h = camera->m_screenHeight;
-    k.width = W;
-    k.height = H;
-    k.xlim = W;
-    k.ylim = H;
-    if (prm->grid_mode == FF_GRID_REFERENCE_FLOOR) { // kernel.cu:306-309
-        k.xlim = (W / 16) * 16;
-        k.ylim = (H / 16) * 16;
+    {
+        const int mst = fill_frame_mapping(s, k, camera, W, H, prm->grid_mode, strip_rows, part, num_parts, local_rows, x0, y0, win_w, num_blocks, "");
+        if (mst != FF_OK) return mst;
     }
-    k.strip_rows = strip_rows;
-    k.part = part;
-    k.num_parts = num_parts;
-    k.local_rows = local_rows;
-    k.x0 = x0;
-    k.y0 = y0;
-    k.local_width = win_w;
-    k.tiles_per_row = (win_w + 7) / 8;
-    const uint64_t tiles = (uint64_t)k.tiles_per_row * (uint64_t)((local_rows + 7) / 8);
-    if (tiles * 64 * (uint64_t)(num_blocks + 64) >= (1ull << 31)) return fail(FF_ERR_INVALID_ARG, "image too large for the work queue");
-    k.pix_items = (unsigned)(tiles * 64);
     k.bounces = bounces;
     k.spp_total = spp;
     k.block_spp = block_spp;
@@ -377,16 +481,6 @@ int render_enqueue(FfState* s, const FfCamera* camera, const FfRenderParams* prm
     k.blocksums = reinterpret_cast<float4*>(s->d_blocksums);
     k.key = (unsigned)prm->seed ^ (unsigned)(prm->seed >> 32);
     k.shade_mode = prm->shade_mode;
-    k.setup_threshold = s->setup_threshold;
-    k.leaf_threshold = s->leaf_threshold;
-    k.num_geoms = s->num_geoms;
-    k.num_planes = s->num_planes;
-    k.num_quads = s->num_quads;
-    k.has_specular = s->has_specular ? 1 : 0;
-    k.geoms = s->d_geoms;
-    k.tris = s->d_tris;
-    k.trinormals = prm->shade_mode == FF_SHADE_DIFFUSE_PATH_SMOOTH ? reinterpret_cast<const float4*>(s->d_normals) : nullptr;
-    k.nodes4 = s->d_nodes4;
     int block_threads = kBlockThreads;
     if (prm->trace_mode == FF_TRACE_BVH) {
         block_threads = s->scene_block_threads;
@@ -394,22 +488,7 @@ int render_enqueue(FfState* s, const FfCamera* camera, const FfRenderParams* prm
             return fail(FF_ERR_UNSUPPORTED, "4-wide BVH of depth %d does not fit the LDS traversal stack (512 threads x %d levels + %d geometry records > 160 KiB); "
                         "upload with FF_BUILD_HOST_SAH or render with FF_TRACE_BRUTE_FORCE", s->max_depth4, s->max_depth4 + 1, s->num_geoms);
     }
-    if (s->sw.lds_fill) {
-        const unsigned long words = s->sw.lds_fill_words, pattern = s->sw.lds_fill_pattern;
-        if (prm->trace_mode == FF_TRACE_BVH) {
-            const size_t bytes = bvh_lds_bytes(s->lds_cap, s->stack_lds_levels, block_threads, lds_records(s)); // (the pool behind it is initialised by the kernel)
-            k.debug_lds_words = (unsigned)std::min<size_t>(words, bytes / 4);
-            k.debug_lds_pattern = (unsigned)pattern;
-        }
-    }
-    k.stack_depth = s->stack_lds_levels;
-    k.stack_spill = nullptr;
-    k.lds_nodes = s->lds_cap;
-    k.top_first = (int)s->node_capacity;
-    k.top_lds_first = 0;
-    k.top_lds_count = s->top_lds_count;
-    k.num_scan = s->num_scan;
-    k.walls = s->walls;
+    fill_scene(s, k, prm->shade_mode == FF_SHADE_DIFFUSE_PATH_SMOOTH, prm->trace_mode == FF_TRACE_BVH ? block_threads : 0);
     if (prm->shade_mode == FF_SHADE_DIFFUSE_PATH_NEE || env) {
         // (its own kernels: the rest of this function prepares the mega-kernels' frame; under an environment, FF_SHADE_DIFFUSE_PATH
         // runs there too, with no light table)
@@ -491,17 +570,10 @@ int render_enqueue(FfState* s, const FfCamera* camera, const FfRenderParams* prm
     // or when the frame before it had the same key - the camera has come to rest, so this frame's pre-pass (-4 % for this frame) is
     // the last one; a one-off 1-spp frame traces its primary rays itself (profiles/r04_j_*).
     const bool reuse_possible = prm->trace_mode == FF_TRACE_BVH && !debug && !s->sw.no_primary_reuse;
+    // (the stored normal is the interpolated one when the frame shades with vertex normals: part of the key)
     FfState::PrimaryKey key;
     std::memset(&key, 0, sizeof key);
-    if (reuse_possible) {
-        std::memcpy(key.cam, k.cam_c0, 16 * sizeof(float));
-        std::memcpy(key.cam + 16, k.cam_pos, 3 * sizeof(float));
-        key.cam[19] = k.far_clip; key.cam[20] = k.screen_w; key.cam[21] = k.screen_h;
-        // (the stored normal is the interpolated one when the frame shades with vertex normals: part of the key)
-        const int dims[12] = { W, H, k.xlim, k.ylim, strip_rows, part, num_parts, local_rows, x0, y0, win_w, k.trinormals != nullptr ? 1 : 0 };
-        std::memcpy(key.dims, dims, sizeof dims);
-        key.pix_items = k.pix_items;
-    }
+    if (reuse_possible) key = primary_key(k, k.trinormals != nullptr);
     const bool keeping = reuse_possible && !s->sw.no_primary_cache;
     const bool hits_kept = keeping && s->primary_valid && std::memcmp(&key, &s->primary_key, sizeof key) == 0;
     const bool at_rest = keeping && s->last_key_valid && std::memcmp(&key, &s->last_key, sizeof key) == 0;
@@ -534,12 +606,9 @@ int render_enqueue(FfState* s, const FfCamera* camera, const FfRenderParams* prm
         if (pst != FF_OK) return pst;
         k.park = s->d_park;
     }
-    if (prm->trace_mode == FF_TRACE_BVH && s->stack_lds_levels < s->stack_entries) {
-        // the stack levels that did not get LDS (finalize_layout): one int per level and thread of the launch
-        const int st = ensure_bytes((void**)&s->d_stack_spill, &s->stack_spill_bytes,
-                                    (size_t)(s->stack_entries - s->stack_lds_levels) * (size_t)grid * (size_t)block_threads * sizeof(int));
+    if (prm->trace_mode == FF_TRACE_BVH) {
+        const int st = attach_stack_spill(s, k, grid, block_threads);
         if (st != FF_OK) return st;
-        k.stack_spill = s->d_stack_spill;
     }
 
     {
@@ -559,18 +628,12 @@ int render_enqueue(FfState* s, const FfCamera* camera, const FfRenderParams* prm
         // (the strips of a multi-GPU rank: 32; slowest of eight ranks 125.5 ms against 126.9 with 64 and 125.9 with 16)
         k.queue_chunk = samples_per_item >= 64 ? (num_parts > 1 ? 32u : 64u) : (unsigned)std::min(32, std::max(4, 64 / samples_per_item));
         if (s->sw.queue_chunk > 0) k.queue_chunk = (unsigned)s->sw.queue_chunk;
-        k.queue_counters = std::min(kQueueCountersDefault, grid);
-        if (s->sw.queue_counters > 0) k.queue_counters = std::min(std::min(kQueueCounters, grid), s->sw.queue_counters);
         // The last items of every counter's share go out exactly as asked for (acquire_pixel: no private stock at the end of a launch):
         // one per lane of the waves that draw from the counter where items are long (sample blocks), an eighth of that where they are
         // short (a 1-spp frame's paths: single-item requests cost an atomic each, which is what the chunks are there to avoid).
-        {
-            const int waves_per_counter = (grid * (block_threads / 64) + k.queue_counters - 1) / k.queue_counters;
-            // (measured on one box, profiles/r04_b_queue_tail.txt: long items 64 per wave; frames that drop most of their items at the
-            // queue - a camera outside the scene - lose with a long zone, every dropped item there being a request of its own: 8)
-            const int per_wave = s->sw.queue_tail >= 0 ? s->sw.queue_tail : (samples_per_item >= 16 && !cull ? 64 : 8);
-            k.queue_tail_items = (unsigned)(waves_per_counter * per_wave);
-        }
+        // (measured on one box, profiles/r04_b_queue_tail.txt: long items 64 per wave; frames that drop most of their items at the
+        // queue - a camera outside the scene - lose with a long zone, every dropped item there being a request of its own: 8)
+        size_work_queue(s, k, grid, block_threads, samples_per_item >= 16 && !cull ? 64 : 8);
     }
     hipStream_t st = s->stream;
     // cudaMemset(pbo, 0) of kernel.cu:340: untraced pixels read 0.  With the full grid the combine pass writes every pixel
@@ -666,30 +729,8 @@ int render_enqueue(FfState* s, const FfCamera* camera, const FfRenderParams* prm
     k.start_records = use_start ? s->d_start_records : nullptr;
     k.start_bounces = bounces;
     if (reuse && !kept) {
-        // The pre-pass: the same persistent kernel, one item per pixel, one primary ray each, the hit stored per pixel (settle_hit).  Its
-        // rays are not path segments of the frame: the kernel does not count them, and the work queue starts from zero again behind it.  (Always the lane-
-        // owned kernel, never instrumented: the frame's own launches are what the statistics describe.)
-        KParams kp = k;
-        kp.shade_mode = kShadePrimaryPass;
-        kp.primary_hits = s->d_primary_cache;
-        kp.bounces = 1;
-        kp.spp_total = 1;
-        kp.block_spp = 1;
-        kp.num_blocks = 1;
-        kp.block_begin = 0;
-        kp.block_end = 1;
-        kp.whole_blocks = 1u;
-        kp.total_items = kp.pix_items;
-        kp.tail_block = -1;
-        kp.cull_mask = nullptr; // (every pixel gets its stored hit: a culled pixel's tail items - its last block, traced sample by sample - read it too)
-        kp.cull_mask_out = exact_cull ? s->d_cull_mask : nullptr;
-        kp.frame_blocks = num_blocks;
-        kp.cut_last = 0;
-        kp.timeline = nullptr;
-        kp.queue_chunk = 32u;
-        if (s->sw.queue_chunk > 0) kp.queue_chunk = (unsigned)s->sw.queue_chunk;
-        FF_HIP(launch_trace(kp, FF_TRACE_BVH, false, grid, block_threads, st, nullptr, false, /*prepass=*/true));
-        FF_HIP(hipMemsetAsync(s->d_queue, 0, (size_t)k.queue_counters * kQueueStride * sizeof(unsigned), st));
+        const int pst = enqueue_prepass(s, k, s->d_primary_cache, exact_cull ? s->d_cull_mask : nullptr, num_blocks, grid, block_threads);
+        if (pst != FF_OK) return pst;
         k.primary_hits = s->d_primary_cache;
         s->primary_key = key;
         s->primary_valid = true;
@@ -724,6 +765,42 @@ int render_enqueue(FfState* s, const FfCamera* camera, const FfRenderParams* prm
     s->pending = true;
     s->pending_launches = launches;
     return FF_OK;
+}
+
+// (declared in ff_state.h)
+int frame_primary_hits(FfState* s, const FfCamera* camera, const FfRenderParams* params, PrimaryHits* out)
+{
+    const int W = params->width, H = params->height;
+    KParams k;
+    std::memset(&k, 0, sizeof k);
+    int st = fill_frame_mapping(s, k, camera, W, H, params->grid_mode, H, 0, 1, H, 0, 0, W, 1, "ff_gbuffer: ");
+    if (st != FF_OK) return st;
+    // The frame's stored hits serve if they were computed for this camera and pixel mapping: with either kind of stored normal, which
+    // the G-buffer's resolve does not read.
+    const size_t hits_bytes = (size_t)3 * (size_t)k.pix_items * sizeof(float4);
+    bool kept = false;
+    for (int smooth = 0; smooth < 2 && !kept; ++smooth) {
+        const FfState::PrimaryKey key = primary_key(k, smooth != 0);
+        kept = s->primary_valid && s->primary_cache_bytes >= hits_bytes && std::memcmp(&key, &s->primary_key, sizeof key) == 0;
+    }
+    *out = { s->d_primary_cache, !kept, k.pix_items, k.tiles_per_row, k.xlim, k.ylim };
+    if (kept) return FF_OK;
+    // a pre-pass of its own (geometric normals; the resolve recomputes a triangle's from its record anyway)
+    st = ensure_bytes((void**)&s->d_gb_hits, &s->gb_hits_bytes, hits_bytes);
+    if (st != FF_OK) return st;
+    out->hits = s->d_gb_hits;
+    const int block_threads = s->scene_block_threads;
+    const int grid = (int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)s->num_cus, ((uint64_t)k.pix_items + (uint64_t)block_threads - 1) / (uint64_t)block_threads));
+    fill_scene(s, k, false, block_threads);
+    st = attach_stack_spill(s, k, grid, block_threads);
+    if (st != FF_OK) return st;
+    k.reuse_quorum = s->sw.reuse_quorum;
+    k.queue = s->d_queue;
+    k.counters = s->d_counters;
+    k.timeline_ticks = 1;
+    size_work_queue(s, k, grid, block_threads, 8);
+    FF_HIP(hipMemsetAsync(s->d_counters, 0, (size_t)(1 + k.queue_counters) * kQueueStride * sizeof(unsigned), s->stream));
+    return enqueue_prepass(s, k, s->d_gb_hits, nullptr, 1, grid, block_threads);
 }
 
 int render_finish(FfState* s)
@@ -896,10 +973,7 @@ int ff_destroy(FfState* s)
     if (s->d_gb_hits) (void)hipFree(s->d_gb_hits);
     if (s->d_img_stage) (void)hipFree(s->d_img_stage);
     if (s->d_dn_work) (void)hipFree(s->d_dn_work);
-    if (s->d_tp_work) (void)hipFree(s->d_tp_work);
-    if (s->d_tp_geoms) (void)hipFree(s->d_tp_geoms);
-    if (s->d_taa_work) (void)hipFree(s->d_taa_work);
-    if (s->d_taa_geoms) (void)hipFree(s->d_taa_geoms);
+    for (ReprojectionHistory& h : s->history) h.release();
     if (s->d_nee_lights) (void)hipFree(s->d_nee_lights);
     if (s->d_nee_pdf) (void)hipFree(s->d_nee_pdf);
     env_release(s);
@@ -1091,8 +1165,7 @@ int ff_upload_scene(FfState* s, const FfGeometry* host_geometries, int n)
     clear_error();
     if (!s) return fail(FF_ERR_INVALID_ARG, "ff_upload_scene: state is null");
     s->primary_valid = s->last_key_valid = false; // (the stored primary hits belong to the scene that goes)
-    s->tp_valid = s->tp_last = false;             // (and so does the temporal history)
-    s->taa_valid = s->taa_last = false;           // (and the TAA history)
+    for (ReprojectionHistory& h : s->history) h.invalidate(); // (and so do the temporal denoiser's and the TAA history)
     const auto t_call = std::chrono::steady_clock::now();
     s->build_stats = FfBuildStats();
     const BvhBuildParams bp = default_bvh_params();
@@ -1217,8 +1290,7 @@ int upload_compiled_scene(FfState* s, const CompiledScene& cs, double build_ms)
 {
     const auto t_call = std::chrono::steady_clock::now();
     s->primary_valid = s->last_key_valid = false;
-    s->tp_valid = s->tp_last = false;
-    s->taa_valid = s->taa_last = false;
+    for (ReprojectionHistory& h : s->history) h.invalidate();
     s->nee_valid = false; // (no light table: FF_SHADE_DIFFUSE_PATH_NEE is not offered on a compiled upload)
     s->nee_geoms.clear();
     s->nee_tris.clear();
@@ -1300,8 +1372,7 @@ int ff_update_mesh(FfState* s, int geometry_index, const FfTriangle* triangles, 
     if (count != rec.tri_count || count <= 0) return fail(FF_ERR_INVALID_ARG, "ff_update_mesh: %d triangles, the uploaded mesh has %d", count, rec.tri_count);
     if (mode == FF_UPDATE_REBUILD && s->scene_builder == FF_BUILD_HOST_SAH)
         return fail(FF_ERR_UNSUPPORTED, "ff_update_mesh: rebuilding in place needs a scene uploaded with a device builder (host-built trees are packed)");
-    if ((size_t)geometry_index < s->tp_replaced.size()) s->tp_replaced[geometry_index] = 1; // (its temporal history restarts)
-    if ((size_t)geometry_index < s->taa_replaced.size()) s->taa_replaced[geometry_index] = 1; // (and its TAA history)
+    for (ReprojectionHistory& h : s->history) h.mark_replaced(geometry_index); // (the mesh's temporal and TAA histories restart)
     const auto t_call = std::chrono::steady_clock::now();
     FfBuildStats& bs = s->build_stats;
     bs.copy_ms = bs.build_ms = 0.0;
@@ -1748,601 +1819,7 @@ int ff_render_to_pbo_progressive(FfState* s, const FfCamera* camera, const FfRen
     return st;
 }
 
-// ---- G-buffer and denoiser (kernels in ff_denoise.hip) ---------------------
-
-namespace {
-
-// Host buffers of ff_gbuffer / ff_denoise go through one state-owned staging area: carve() hands out 16-byte aligned pieces.
-struct Carver {
-    char* base;
-    size_t used;
-    void* carve(size_t bytes)
-    {
-        void* p = base + used;
-        used += (bytes + 15) & ~(size_t)15;
-        return p;
-    }
-};
-
-size_t padded(size_t bytes) { return (bytes + 15) & ~(size_t)15; }
-
-// The primary-hit pre-pass of a whole W x H frame (render_enqueue's, with the pixel mapping of ff_render) into `hits`, on the
-// state's stream.  It writes nothing else of the state: not the stored hits of the frames or their key, not the cull mask; the
-// work-queue counters are zeroed behind it as after the frame's own pre-pass.
-int enqueue_gbuffer_prepass(FfState* s, KParams& k, float4* hits)
-{
-    const int block_threads = s->scene_block_threads;
-    int grid = s->num_cus;
-    const uint64_t max_useful = ((uint64_t)k.pix_items + (uint64_t)block_threads - 1) / (uint64_t)block_threads;
-    if ((uint64_t)grid > max_useful) grid = (int)max_useful;
-    if (grid < 1) grid = 1;
-    k.shade_mode = kShadePrimaryPass;
-    k.bounces = k.spp_total = k.block_spp = k.num_blocks = 1;
-    k.block_begin = 0;
-    k.block_end = 1;
-    k.whole_blocks = 1u;
-    k.total_items = k.pix_items;
-    k.frame_blocks = 1;
-    k.tail_block = -1;
-    k.setup_threshold = s->setup_threshold;
-    k.leaf_threshold = s->leaf_threshold;
-    k.num_geoms = s->num_geoms;
-    k.num_planes = s->num_planes;
-    k.num_quads = s->num_quads;
-    k.has_specular = s->has_specular ? 1 : 0;
-    k.geoms = s->d_geoms;
-    k.tris = s->d_tris;
-    k.trinormals = nullptr; // (geometric normals; the resolve recomputes a triangle's from its record anyway)
-    k.nodes4 = s->d_nodes4;
-    if (s->sw.lds_fill) {
-        const size_t bytes = bvh_lds_bytes(s->lds_cap, s->stack_lds_levels, block_threads, lds_records(s));
-        k.debug_lds_words = (unsigned)std::min<size_t>(s->sw.lds_fill_words, bytes / 4);
-        k.debug_lds_pattern = (unsigned)s->sw.lds_fill_pattern;
-    }
-    k.stack_depth = s->stack_lds_levels;
-    k.stack_spill = nullptr;
-    if (s->stack_lds_levels < s->stack_entries) {
-        const int st = ensure_bytes((void**)&s->d_stack_spill, &s->stack_spill_bytes,
-                                    (size_t)(s->stack_entries - s->stack_lds_levels) * (size_t)grid * (size_t)block_threads * sizeof(int));
-        if (st != FF_OK) return st;
-        k.stack_spill = s->d_stack_spill;
-    }
-    k.lds_nodes = s->lds_cap;
-    k.top_first = (int)s->node_capacity;
-    k.top_lds_first = 0;
-    k.top_lds_count = s->top_lds_count;
-    k.num_scan = s->num_scan;
-    k.walls = s->walls;
-    k.primary_hits = hits;
-    k.reuse_quorum = s->sw.reuse_quorum;
-    k.queue = s->d_queue;
-    k.counters = s->d_counters;
-    k.timeline_ticks = 1;
-    k.queue_chunk = s->sw.queue_chunk > 0 ? (unsigned)s->sw.queue_chunk : 32u;
-    k.queue_counters = std::min(kQueueCountersDefault, grid);
-    if (s->sw.queue_counters > 0) k.queue_counters = std::min(std::min(kQueueCounters, grid), s->sw.queue_counters);
-    const int waves_per_counter = (grid * (block_threads / 64) + k.queue_counters - 1) / k.queue_counters;
-    k.queue_tail_items = (unsigned)(waves_per_counter * (s->sw.queue_tail >= 0 ? s->sw.queue_tail : 8));
-    hipStream_t st = s->stream;
-    FF_HIP(hipMemsetAsync(s->d_counters, 0, (size_t)(1 + k.queue_counters) * kQueueStride * sizeof(unsigned), st));
-    FF_HIP(launch_trace(k, FF_TRACE_BVH, false, grid, block_threads, st, nullptr, false, /*prepass=*/true));
-    FF_HIP(hipMemsetAsync(s->d_queue, 0, (size_t)k.queue_counters * kQueueStride * sizeof(unsigned), st));
-    return FF_OK;
-}
-
-} // namespace
-
-int ff_gbuffer(FfState* s, const FfCamera* camera, const FfRenderParams* params, float* depth, float* position, float* normal, float* albedo,
-               int32_t* ids, int on_device)
-{
-    clear_error();
-    int st = check_render_call(s, camera, params, "ff_gbuffer");
-    if (st != FF_OK) return st;
-    if (s->scene_block_threads == 0)
-        return fail(FF_ERR_UNSUPPORTED, "ff_gbuffer: 4-wide BVH of depth %d does not fit the LDS traversal stack; upload with FF_BUILD_HOST_SAH", s->max_depth4);
-    FF_HIP(hipSetDevice(s->device));
-    const int W = params->width, H = params->height;
-    // the pixel mapping of a whole frame (ff_render: one part, strips of H rows, the window is the image)
-    KParams k;
-    std::memset(&k, 0, sizeof k);
-    FfMat4 cm;
-    ff_camera_ray_matrix_jittered(camera, s->jitter_x, s->jitter_y, &cm); // (the state's pixel jitter; 0 0: ff_camera_ray_matrix)
-    std::memcpy(k.cam_c0, &cm.m[0], 16);
-    std::memcpy(k.cam_c1, &cm.m[4], 16);
-    std::memcpy(k.cam_c2, &cm.m[8], 16);
-    std::memcpy(k.cam_c3, &cm.m[12], 16);
-    k.cam_pos[0] = camera->m_position.x;
-    k.cam_pos[1] = camera->m_position.y;
-    k.cam_pos[2] = camera->m_position.z;
-    k.far_clip = camera->m_farClip;
-    k.screen_w = camera->m_screenWidth;
-    k.screen_h = camera->m_screenHeight;
-    k.width = k.xlim = W;
-    k.height = k.ylim = H;
-    if (params->grid_mode == FF_GRID_REFERENCE_FLOOR) { // kernel.cu:306-309
-        k.xlim = (W / 16) * 16;
-        k.ylim = (H / 16) * 16;
-    }
-    k.strip_rows = H;
-    k.part = 0;
-    k.num_parts = 1;
-    k.local_rows = H;
-    k.local_width = W;
-    k.tiles_per_row = (W + 7) / 8;
-    const uint64_t tiles = (uint64_t)k.tiles_per_row * (uint64_t)((H + 7) / 8);
-    if (tiles * 64 * 65 >= (1ull << 31)) return fail(FF_ERR_INVALID_ARG, "ff_gbuffer: image too large for the work queue");
-    k.pix_items = (unsigned)(tiles * 64);
-    // The frame's stored hits serve if they were computed for this camera and pixel mapping (render_enqueue's key; the last dims
-    // entry says whether that frame shaded with vertex normals, which changes the stored normal but not what the resolve reads).
-    FfState::PrimaryKey key;
-    std::memset(&key, 0, sizeof key);
-    std::memcpy(key.cam, k.cam_c0, 16 * sizeof(float));
-    std::memcpy(key.cam + 16, k.cam_pos, 3 * sizeof(float));
-    key.cam[19] = k.far_clip; key.cam[20] = k.screen_w; key.cam[21] = k.screen_h;
-    const int dims[12] = { W, H, k.xlim, k.ylim, H, 0, 1, H, 0, 0, W, 0 };
-    std::memcpy(key.dims, dims, sizeof dims);
-    key.pix_items = k.pix_items;
-    const size_t hits_bytes = (size_t)3 * (size_t)k.pix_items * sizeof(float4);
-    bool kept = false;
-    for (int smooth = 0; smooth < 2 && !kept; ++smooth) {
-        key.dims[11] = smooth;
-        kept = s->primary_valid && s->primary_cache_bytes >= hits_bytes && std::memcmp(&key, &s->primary_key, sizeof key) == 0;
-    }
-    // outputs: the caller's device buffers, or the staging area and a copy back
-    const size_t px = (size_t)W * (size_t)H;
-    float* d_depth = depth;
-    float* d_pos = position;
-    float* d_nrm = normal;
-    float* d_alb = albedo;
-    int* d_ids = ids;
-    if (!on_device) {
-        const size_t need = (depth ? padded(px * 4) : 0) + (position ? padded(px * 12) : 0) + (normal ? padded(px * 12) : 0) +
-                            (albedo ? padded(px * 12) : 0) + (ids ? padded(px * 12) : 0);
-        if (need > 0) {
-            st = ensure_bytes(&s->d_img_stage, &s->img_stage_bytes, need);
-            if (st != FF_OK) return st;
-        }
-        Carver c = { (char*)s->d_img_stage, 0 };
-        d_depth = depth ? (float*)c.carve(px * 4) : nullptr;
-        d_pos = position ? (float*)c.carve(px * 12) : nullptr;
-        d_nrm = normal ? (float*)c.carve(px * 12) : nullptr;
-        d_alb = albedo ? (float*)c.carve(px * 12) : nullptr;
-        d_ids = ids ? (int*)c.carve(px * 12) : nullptr;
-    }
-    const float4* hits = s->d_primary_cache;
-    if (!kept) {
-        st = ensure_bytes((void**)&s->d_gb_hits, &s->gb_hits_bytes, hits_bytes);
-        if (st == FF_OK) st = enqueue_gbuffer_prepass(s, k, s->d_gb_hits);
-        if (st != FF_OK) return st;
-        hits = s->d_gb_hits;
-    }
-    GbufferResolveParams r;
-    r.hits = hits;
-    r.pix_items = k.pix_items;
-    r.tiles_per_row = k.tiles_per_row;
-    r.width = W;
-    r.height = H;
-    r.xlim = k.xlim;
-    r.ylim = k.ylim;
-    r.geoms = s->d_geoms;
-    r.tris = s->d_tris;
-    r.num_geoms = s->num_geoms;
-    r.num_tris = (long long)s->num_tris;
-    r.depth = d_depth;
-    r.position = d_pos;
-    r.normal = d_nrm;
-    r.albedo = d_alb;
-    r.ids = d_ids;
-    FF_HIP(launch_gbuffer_resolve(r, s->stream));
-    FF_HIP(hipStreamSynchronize(s->stream));
-    if (!kept) {
-        unsigned long long cut = 0;
-        FF_HIP(hipMemcpy(&cut, s->d_counters, sizeof cut, hipMemcpyDeviceToHost));
-        if (cut != 0) return fail(FF_ERR_HIP, "ff_gbuffer: the traversal loop guard cut %llu queries short (a malformed or absurdly deep tree)", cut);
-    }
-    if (!on_device) {
-        if (depth) FF_HIP(hipMemcpy(depth, d_depth, px * 4, hipMemcpyDeviceToHost));
-        if (position) FF_HIP(hipMemcpy(position, d_pos, px * 12, hipMemcpyDeviceToHost));
-        if (normal) FF_HIP(hipMemcpy(normal, d_nrm, px * 12, hipMemcpyDeviceToHost));
-        if (albedo) FF_HIP(hipMemcpy(albedo, d_alb, px * 12, hipMemcpyDeviceToHost));
-        if (ids) FF_HIP(hipMemcpy(ids, d_ids, px * 12, hipMemcpyDeviceToHost));
-    }
-    return FF_OK;
-}
-
-void ff_denoise_params_init(FfDenoiseParams* p)
-{
-    if (!p) return;
-    // (cornell_wahoo at the C2 pose, 320x180, 16 spp against 4 096 spp: the MSE falls to 0.32 of the raw frame's;
-    // sigma_color 1 / 2 / 4 / 8 leave 0.38 / 0.34 / 0.32 / 0.33; the other two sigmas move it by less than 0.002)
-    p->iterations = 5;
-    p->sigma_color = 4.0f;
-    p->sigma_normal = 0.1f;
-    p->sigma_plane = 0.1f;
-    p->flags = FF_DENOISE_SAME_GEOMETRY | FF_DENOISE_DEMODULATE_ALBEDO;
-}
-
-int ff_denoise(FfState* s, int width, int height, const FfDenoiseParams* dn, const float* radiance_in, const float* position, const float* normal,
-               const float* albedo, const int32_t* ids, int inputs_on_device, void* rgb8, int rgb8_on_device, float* radiance_out,
-               int radiance_out_on_device)
-{
-    clear_error();
-    if (!s) return fail(FF_ERR_INVALID_ARG, "ff_denoise: state is null");
-    if (!dn) return fail(FF_ERR_INVALID_ARG, "ff_denoise: params are null");
-    if (width <= 0 || height <= 0 || width > 65535 || height > 65535) return fail(FF_ERR_INVALID_ARG, "ff_denoise: image size %dx%d is invalid", width, height);
-    if (dn->iterations < 0 || dn->iterations > 10) return fail(FF_ERR_INVALID_ARG, "ff_denoise: iterations must be in 0..10 (got %d)", dn->iterations);
-    if (!(dn->sigma_color > 0.f && dn->sigma_normal > 0.f && dn->sigma_plane > 0.f) || !std::isfinite(dn->sigma_color) ||
-        !std::isfinite(dn->sigma_normal) || !std::isfinite(dn->sigma_plane))
-        return fail(FF_ERR_INVALID_ARG, "ff_denoise: the sigmas must be positive and finite");
-    if (dn->flags & ~(FF_DENOISE_SAME_GEOMETRY | FF_DENOISE_DEMODULATE_ALBEDO)) return fail(FF_ERR_INVALID_ARG, "ff_denoise: unknown flags 0x%x", dn->flags);
-    const int demod = (dn->flags & FF_DENOISE_DEMODULATE_ALBEDO) ? 1 : 0;
-    if (!radiance_in || !position || !normal || !ids || (demod && !albedo))
-        return fail(FF_ERR_INVALID_ARG, "ff_denoise: radiance, position, normal and ids are required (and albedo with FF_DENOISE_DEMODULATE_ALBEDO)");
-    FF_HIP(hipSetDevice(s->device));
-    const size_t px = (size_t)width * (size_t)height;
-    const bool filter = dn->iterations > 0;
-    // host buffers are staged: the inputs the call reads, the outputs it writes
-    const bool in_host = !inputs_on_device, rgb_host = rgb8 && !rgb8_on_device, out_host = radiance_out && !radiance_out_on_device;
-    const size_t need = (in_host ? padded(px * 12) * (filter ? 4 + demod : 1) : 0) + (rgb_host ? padded(px * 3) : 0) +
-                        (out_host ? padded(px * 12) : 0);
-    if (need > 0) {
-        const int st = ensure_bytes(&s->d_img_stage, &s->img_stage_bytes, need);
-        if (st != FF_OK) return st;
-    }
-    Carver c = { (char*)s->d_img_stage, 0 };
-    hipStream_t stream = s->stream;
-    auto stage_in = [&](const void* host, size_t bytes) -> const void* {
-        void* d = c.carve(bytes);
-        return hipMemcpyAsync(d, host, bytes, hipMemcpyHostToDevice, stream) == hipSuccess ? d : nullptr;
-    };
-    const float* d_rad = radiance_in;
-    const float* d_pos = position;
-    const float* d_nrm = normal;
-    const float* d_alb = demod ? albedo : nullptr;
-    const int* d_ids = ids;
-    if (in_host) {
-        d_rad = (const float*)stage_in(radiance_in, px * 12);
-        if (filter) {
-            d_pos = (const float*)stage_in(position, px * 12);
-            d_nrm = (const float*)stage_in(normal, px * 12);
-            if (demod) d_alb = (const float*)stage_in(albedo, px * 12);
-            d_ids = (const int*)stage_in(ids, px * 12);
-        }
-        if (!d_rad || (filter && (!d_pos || !d_nrm || !d_ids || (demod && !d_alb)))) return fail(FF_ERR_HIP, "ff_denoise: staging the inputs failed");
-    }
-    unsigned char* d_rgb8 = rgb_host ? (unsigned char*)c.carve(px * 3) : (unsigned char*)rgb8;
-    float* d_out = out_host ? (float*)c.carve(px * 12) : radiance_out;
-    DenoiseBuffers b;
-    b.width = width;
-    b.height = height;
-    b.guide_pos = b.guide_nrm = b.color[0] = b.color[1] = nullptr;
-    int src = -1;
-    if (filter) {
-        const int st = ensure_bytes((void**)&s->d_dn_work, &s->dn_work_bytes, 4 * px * sizeof(float4));
-        if (st != FF_OK) return st;
-        b.guide_pos = s->d_dn_work;
-        b.guide_nrm = s->d_dn_work + px;
-        b.color[0] = s->d_dn_work + 2 * px;
-        b.color[1] = s->d_dn_work + 3 * px;
-        FF_HIP(launch_denoise_pack(b, d_rad, d_pos, d_nrm, d_alb, d_ids, demod, stream));
-        src = 0;
-        const int same = (dn->flags & FF_DENOISE_SAME_GEOMETRY) ? 1 : 0;
-        for (int i = 0; i < dn->iterations; ++i) {
-            const double sigma_i = (double)dn->sigma_color * std::ldexp(1.0, -i); // halved every pass
-            FF_HIP(launch_denoise_pass(b, src, i, (float)(1.0 / (sigma_i * sigma_i)), (float)(1.0 / (double)dn->sigma_normal),
-                                       dn->sigma_plane * dn->sigma_plane, same, stream));
-            src = 1 - src;
-        }
-    }
-    FF_HIP(launch_denoise_finish(b, src, d_rad, d_alb, demod, d_rgb8, d_out, stream));
-    FF_HIP(hipStreamSynchronize(stream));
-    if (rgb_host) FF_HIP(hipMemcpy(rgb8, d_rgb8, px * 3, hipMemcpyDeviceToHost));
-    if (out_host) FF_HIP(hipMemcpy(radiance_out, d_out, px * 12, hipMemcpyDeviceToHost));
-    return FF_OK;
-}
-
-// ---- temporal denoiser (SVGF; kernels in ff_temporal.hip) ---------------------------------------------------------
-
-void ff_temporal_params_init(FfTemporalParams* p)
-{
-    if (!p) return;
-    // (the paper's values, with max_history chosen on the C2 scene's moving camera)
-    p->iterations = 5;
-    p->sigma_luminance = 4.0f;
-    p->sigma_normal = 0.1f;
-    p->sigma_plane = 0.1f;
-    p->flags = FF_DENOISE_SAME_GEOMETRY | FF_DENOISE_DEMODULATE_ALBEDO;
-    p->max_history = 16;
-    p->variance_history = 4;
-    p->feedback_pass = 0;
-    p->reuse_normal = 0.9f;
-    p->reuse_plane = 0.01f;
-}
-
-} // extern "C"
-
-namespace {
-
-// inverse of a 4x4 matrix in double (Gauss-Jordan with partial pivoting); column-major in and out.  False if singular.
-bool invert4(const double* m, double* out)
-{
-    double a[4][8];
-    for (int r = 0; r < 4; ++r)
-        for (int c = 0; c < 4; ++c) {
-            a[r][c] = m[c * 4 + r];
-            a[r][4 + c] = r == c ? 1.0 : 0.0;
-        }
-    for (int c = 0; c < 4; ++c) {
-        int piv = c;
-        for (int r = c + 1; r < 4; ++r)
-            if (std::fabs(a[r][c]) > std::fabs(a[piv][c])) piv = r;
-        if (a[piv][c] == 0.0) return false;
-        if (piv != c)
-            for (int k = 0; k < 8; ++k) std::swap(a[c][k], a[piv][k]);
-        const double d = a[c][c];
-        for (int k = 0; k < 8; ++k) a[c][k] /= d;
-        for (int r = 0; r < 4; ++r) {
-            if (r == c || a[r][c] == 0.0) continue;
-            const double f = a[r][c];
-            for (int k = 0; k < 8; ++k) a[r][k] -= f * a[c][k];
-        }
-    }
-    for (int r = 0; r < 4; ++r)
-        for (int c = 0; c < 4; ++c) out[c * 4 + r] = a[r][4 + c];
-    return true;
-}
-
-// the model matrix of a record as 12 floats (columns, xyz)
-void record_model(const GeomRecord& g, float* out12)
-{
-    const float* cols[4] = { g.mod_c0, g.mod_c1, g.mod_c2, g.mod_c3 };
-    for (int c = 0; c < 4; ++c)
-        for (int r = 0; r < 3; ++r) out12[c * 3 + r] = cols[c][r];
-}
-
-// The table row of one geometry: A = M_prev * inverse(M_cur) from the previous call's model matrix and this record's inverse model
-// matrix, composed in double; N = inverse(A)^T (3x3: the cofactors over the determinant).
-TemporalGeom temporal_row(const float* prev12, const GeomRecord& g, int flags)
-{
-    TemporalGeom row;
-    double A[3][4] = { { 1, 0, 0, 0 }, { 0, 1, 0, 0 }, { 0, 0, 1, 0 } };
-    if (flags & kTpMoved) {
-        const float* inv[4] = { g.inv_c0, g.inv_c1, g.inv_c2, g.inv_c3 };
-        for (int r = 0; r < 3; ++r)
-            for (int c = 0; c < 4; ++c) {
-                double v = c == 3 ? (double)prev12[9 + r] : 0.0;
-                for (int k = 0; k < 3; ++k) v += (double)prev12[k * 3 + r] * (double)inv[c][k];
-                A[r][c] = v;
-            }
-    }
-    double cof[3][3];
-    for (int r = 0; r < 3; ++r)
-        for (int c = 0; c < 3; ++c) {
-            const int r1 = (r + 1) % 3, r2 = (r + 2) % 3, c1 = (c + 1) % 3, c2 = (c + 2) % 3;
-            cof[r][c] = A[r1][c1] * A[r2][c2] - A[r1][c2] * A[r2][c1];
-        }
-    const double det = A[0][0] * cof[0][0] + A[0][1] * cof[0][1] + A[0][2] * cof[0][2];
-    const double id = det != 0.0 ? 1.0 / det : 0.0;
-    for (int r = 0; r < 3; ++r) {
-        row.a[r] = make_float4((float)A[r][0], (float)A[r][1], (float)A[r][2], (float)A[r][3]);
-        row.n[r] = make_float4((float)(cof[r][0] * id), (float)(cof[r][1] * id), (float)(cof[r][2] * id), 0.f);
-    }
-    std::memcpy(&row.n[0].w, &flags, sizeof flags);
-    return row;
-}
-
-// ff_denoise_temporal's history and working buffers: 10 float4 and one float2 per pixel (ff_state.h)
-TemporalBuffers temporal_buffers(FfState* s, int width, int height)
-{
-    const size_t px = (size_t)width * (size_t)height;
-    TemporalBuffers b;
-    b.width = width;
-    b.height = height;
-    float4* base = s->d_tp_work;
-    for (int k = 0; k < 2; ++k) {
-        b.pos[k] = base + (4 * k + 0) * px;
-        b.nrm[k] = base + (4 * k + 1) * px;
-        b.col[k] = base + (4 * k + 2) * px;
-        b.mom[k] = base + (4 * k + 3) * px;
-        b.work[k] = base + (8 + k) * px;
-    }
-    b.motion = (float2*)(base + 10 * px);
-    return b;
-}
-
-} // namespace
-
-extern "C" {
-
-int ff_denoise_temporal(FfState* s, const FfCamera* camera, int width, int height, const FfTemporalParams* tp, const float* radiance_in,
-                        const float* position, const float* normal, const float* albedo, const int32_t* ids, int inputs_on_device, void* rgb8,
-                        int rgb8_on_device, float* radiance_out, int radiance_out_on_device)
-{
-    clear_error();
-    if (!s) return fail(FF_ERR_INVALID_ARG, "ff_denoise_temporal: state is null");
-    if (!camera) return fail(FF_ERR_INVALID_ARG, "ff_denoise_temporal: camera is null");
-    if (!tp) return fail(FF_ERR_INVALID_ARG, "ff_denoise_temporal: params are null");
-    if (width <= 0 || height <= 0 || width > 65535 || height > 65535)
-        return fail(FF_ERR_INVALID_ARG, "ff_denoise_temporal: image size %dx%d is invalid", width, height);
-    if (tp->iterations < 0 || tp->iterations > 10) return fail(FF_ERR_INVALID_ARG, "ff_denoise_temporal: iterations must be in 0..10 (got %d)", tp->iterations);
-    if (tp->feedback_pass < -1 || tp->feedback_pass >= tp->iterations)
-        return fail(FF_ERR_INVALID_ARG, "ff_denoise_temporal: feedback_pass must be in -1..iterations-1 (got %d)", tp->feedback_pass);
-    if (tp->max_history < 1) return fail(FF_ERR_INVALID_ARG, "ff_denoise_temporal: max_history must be at least 1 (got %d)", tp->max_history);
-    if (tp->variance_history < 1) return fail(FF_ERR_INVALID_ARG, "ff_denoise_temporal: variance_history must be at least 1 (got %d)", tp->variance_history);
-    if (!(tp->sigma_luminance > 0.f && tp->sigma_normal > 0.f && tp->sigma_plane > 0.f) || !std::isfinite(tp->sigma_luminance) ||
-        !std::isfinite(tp->sigma_normal) || !std::isfinite(tp->sigma_plane))
-        return fail(FF_ERR_INVALID_ARG, "ff_denoise_temporal: the sigmas must be positive and finite");
-    if (!std::isfinite(tp->reuse_normal) || !(tp->reuse_plane >= 0.f) || !std::isfinite(tp->reuse_plane))
-        return fail(FF_ERR_INVALID_ARG, "ff_denoise_temporal: reuse_normal must be finite and reuse_plane finite and >= 0");
-    if (tp->flags & ~(FF_DENOISE_SAME_GEOMETRY | FF_DENOISE_DEMODULATE_ALBEDO))
-        return fail(FF_ERR_INVALID_ARG, "ff_denoise_temporal: unknown flags 0x%x", tp->flags);
-    const int demod = (tp->flags & FF_DENOISE_DEMODULATE_ALBEDO) ? 1 : 0;
-    if (!radiance_in || !position || !normal || !ids || (demod && !albedo))
-        return fail(FF_ERR_INVALID_ARG, "ff_denoise_temporal: radiance, position, normal and ids are required (and albedo with FF_DENOISE_DEMODULATE_ALBEDO)");
-    if (!s->has_scene) return fail(FF_ERR_NO_SCENE, "ff_denoise_temporal: no scene uploaded (the history follows its geometries)");
-    FF_HIP(hipSetDevice(s->device));
-    const size_t px = (size_t)width * (size_t)height;
-    // host buffers are staged, as in ff_denoise
-    const bool in_host = !inputs_on_device, rgb_host = rgb8 && !rgb8_on_device, out_host = radiance_out && !radiance_out_on_device;
-    const size_t need = (in_host ? padded(px * 12) * (4 + demod) : 0) + (rgb_host ? padded(px * 3) : 0) + (out_host ? padded(px * 12) : 0);
-    if (need > 0) {
-        const int st = ensure_bytes(&s->d_img_stage, &s->img_stage_bytes, need);
-        if (st != FF_OK) return st;
-    }
-    Carver c = { (char*)s->d_img_stage, 0 };
-    hipStream_t stream = s->stream;
-    auto stage_in = [&](const void* host, size_t bytes) -> const void* {
-        void* d = c.carve(bytes);
-        return hipMemcpyAsync(d, host, bytes, hipMemcpyHostToDevice, stream) == hipSuccess ? d : nullptr;
-    };
-    const float* d_rad = radiance_in;
-    const float* d_pos = position;
-    const float* d_nrm = normal;
-    const float* d_alb = demod ? albedo : nullptr;
-    const int* d_ids = ids;
-    if (in_host) {
-        d_rad = (const float*)stage_in(radiance_in, px * 12);
-        d_pos = (const float*)stage_in(position, px * 12);
-        d_nrm = (const float*)stage_in(normal, px * 12);
-        if (demod) d_alb = (const float*)stage_in(albedo, px * 12);
-        d_ids = (const int*)stage_in(ids, px * 12);
-        if (!d_rad || !d_pos || !d_nrm || !d_ids || (demod && !d_alb)) return fail(FF_ERR_HIP, "ff_denoise_temporal: staging the inputs failed");
-    }
-    unsigned char* d_rgb8 = rgb_host ? (unsigned char*)c.carve(px * 3) : (unsigned char*)rgb8;
-    float* d_out = out_host ? (float*)c.carve(px * 12) : radiance_out;
-    // history: kept only for the same image size (a new size, a reset or a new scene start afresh)
-    const bool has_history = s->tp_valid && width == s->tp_width && height == s->tp_height;
-    s->tp_valid = s->tp_last = false; // (from here on the history sets are being rewritten)
-    int st = ensure_bytes((void**)&s->d_tp_work, &s->tp_work_bytes, 10 * px * sizeof(float4) + px * sizeof(float2));
-    if (st != FF_OK) return st;
-    const TemporalBuffers b = temporal_buffers(s, width, height);
-    TemporalReproject r;
-    std::memset(&r, 0, sizeof r);
-    r.cur = has_history ? 1 - s->tp_cur : 0;
-    r.has_history = has_history ? 1 : 0;
-    // the per-geometry table, indexed by the caller's geometry index
-    int num = 0;
-    for (const GeomRecord& g : s->h_geoms) num = std::max(num, g.orig_index + 1);
-    s->h_tp_geoms.assign((size_t)num * sizeof(TemporalGeom), 0);
-    TemporalGeom* rows = (TemporalGeom*)s->h_tp_geoms.data();
-    for (const GeomRecord& g : s->h_geoms) {
-        const int o = g.orig_index;
-        if (o < 0) continue;
-        float cur12[12];
-        record_model(g, cur12);
-        int flags = 0;
-        const float* prev12 = cur12;
-        if (has_history && (size_t)o < s->tp_has_model.size() && s->tp_has_model[o]) {
-            prev12 = &s->tp_model[(size_t)o * 12];
-            if (std::memcmp(prev12, cur12, sizeof cur12) != 0) flags |= kTpMoved;
-        }
-        if ((size_t)o < s->tp_replaced.size() && s->tp_replaced[o]) flags |= kTpReplaced;
-        rows[o] = temporal_row(prev12, g, flags);
-    }
-    r.num_geoms = num;
-    if (num > 0) {
-        st = ensure_bytes(&s->d_tp_geoms, &s->tp_geoms_bytes, s->h_tp_geoms.size());
-        if (st != FF_OK) return st;
-        FF_HIP(hipMemcpyAsync(s->d_tp_geoms, s->h_tp_geoms.data(), s->h_tp_geoms.size(), hipMemcpyHostToDevice, stream));
-    }
-    r.geoms = (const TemporalGeom*)s->d_tp_geoms;
-    if (has_history) {
-        r.at_rest = std::memcmp(camera, &s->tp_camera, sizeof(FfCamera)) == 0 ? 1 : 0;
-        FfMat4 cm;
-        ff_camera_ray_matrix(&s->tp_camera, &cm);
-        double m[16], inv[16];
-        for (int k = 0; k < 16; ++k) m[k] = cm.m[k];
-        if (!invert4(m, inv)) return fail(FF_ERR_INVALID_ARG, "ff_denoise_temporal: the previous camera's ray matrix is singular");
-        for (int k = 0; k < 16; ++k) r.proj[k] = (float)inv[k];
-        r.eye[0] = s->tp_camera.m_position.x;
-        r.eye[1] = s->tp_camera.m_position.y;
-        r.eye[2] = s->tp_camera.m_position.z;
-        r.screen_w = s->tp_camera.m_screenWidth;
-        r.screen_h = s->tp_camera.m_screenHeight;
-    }
-    r.reuse_normal = tp->reuse_normal;
-    r.reuse_plane = tp->reuse_plane;
-    r.max_history = (float)tp->max_history;
-    r.variance_history = (float)tp->variance_history;
-    r.demodulate = demod;
-    r.feedback_unfiltered = tp->feedback_pass < 0 ? 1 : 0;
-    FF_HIP(launch_temporal_reproject(b, r, d_rad, d_pos, d_nrm, d_alb, d_ids, stream));
-    int src = 0;
-    if (tp->iterations > 0) {
-        const float inv_sigma_normal = (float)(1.0 / (double)tp->sigma_normal), sigma_plane2 = tp->sigma_plane * tp->sigma_plane;
-        FF_HIP(launch_temporal_variance(b, r.cur, r.variance_history, inv_sigma_normal, sigma_plane2, stream));
-        const int same = (tp->flags & FF_DENOISE_SAME_GEOMETRY) ? 1 : 0;
-        for (int i = 0; i < tp->iterations; ++i) {
-            FF_HIP(launch_temporal_pass(b, r.cur, src, i, tp->sigma_luminance, inv_sigma_normal, sigma_plane2, same,
-                                        i == tp->feedback_pass ? b.col[r.cur] : nullptr, stream));
-            src = 1 - src;
-        }
-    }
-    // output: ff_denoise's finish on the last colour buffer (the class in the guide's w decides what is copied through)
-    DenoiseBuffers fb;
-    fb.width = width;
-    fb.height = height;
-    fb.guide_pos = b.pos[r.cur];
-    fb.guide_nrm = b.nrm[r.cur];
-    fb.color[0] = b.work[src];
-    fb.color[1] = b.work[1 - src];
-    FF_HIP(launch_denoise_finish(fb, 0, d_rad, d_alb, demod, d_rgb8, d_out, stream));
-    FF_HIP(hipStreamSynchronize(stream));
-    // the history now describes this call
-    s->tp_valid = s->tp_last = true;
-    s->tp_cur = r.cur;
-    s->tp_width = width;
-    s->tp_height = height;
-    s->tp_camera = *camera;
-    s->tp_model.assign((size_t)num * 12, 0.f);
-    s->tp_has_model.assign((size_t)num, 0);
-    for (const GeomRecord& g : s->h_geoms) {
-        if (g.orig_index < 0) continue;
-        record_model(g, &s->tp_model[(size_t)g.orig_index * 12]);
-        s->tp_has_model[g.orig_index] = 1;
-    }
-    s->tp_replaced.assign((size_t)num, 0);
-    if (rgb_host) FF_HIP(hipMemcpy(rgb8, d_rgb8, px * 3, hipMemcpyDeviceToHost));
-    if (out_host) FF_HIP(hipMemcpy(radiance_out, d_out, px * 12, hipMemcpyDeviceToHost));
-    return FF_OK;
-}
-
-int ff_temporal_reset(FfState* s)
-{
-    clear_error();
-    if (!s) return fail(FF_ERR_INVALID_ARG, "ff_temporal_reset: state is null");
-    s->tp_valid = s->tp_last = false;
-    return FF_OK;
-}
-
-int ff_temporal_history(FfState* s, float* motion, float* length, int on_device)
-{
-    clear_error();
-    if (!s) return fail(FF_ERR_INVALID_ARG, "ff_temporal_history: state is null");
-    if (!s->tp_last) return fail(FF_ERR_INVALID_ARG, "ff_temporal_history: no ff_denoise_temporal call since the last reset");
-    if (!motion && !length) return FF_OK;
-    FF_HIP(hipSetDevice(s->device));
-    const size_t px = (size_t)s->tp_width * (size_t)s->tp_height;
-    const TemporalBuffers b = temporal_buffers(s, s->tp_width, s->tp_height);
-    float* d_motion = motion;
-    float* d_length = length;
-    if (!on_device) {
-        const int st = ensure_bytes(&s->d_img_stage, &s->img_stage_bytes, padded(px * 8) + padded(px * 4));
-        if (st != FF_OK) return st;
-        Carver c = { (char*)s->d_img_stage, 0 };
-        d_motion = motion ? (float*)c.carve(px * 8) : nullptr;
-        d_length = length ? (float*)c.carve(px * 4) : nullptr;
-    }
-    FF_HIP(launch_temporal_history(b, s->tp_cur, d_motion, d_length, s->stream));
-    FF_HIP(hipStreamSynchronize(s->stream));
-    if (!on_device) {
-        if (motion) FF_HIP(hipMemcpy(motion, d_motion, px * 8, hipMemcpyDeviceToHost));
-        if (length) FF_HIP(hipMemcpy(length, d_length, px * 4, hipMemcpyDeviceToHost));
-    }
-    return FF_OK;
-}
-
-// ---- sub-pixel jitter and temporal anti-aliasing (kernel in ff_taa.hip) ----------------------------------------------
+// ---- sub-pixel jitter of the primary rays (composed into the ray matrix by fill_frame_mapping) ------------------------
 
 int ff_set_pixel_jitter(FfState* s, float jx, float jy)
 {
@@ -2352,205 +1829,6 @@ int ff_set_pixel_jitter(FfState* s, float jx, float jy)
         return fail(FF_ERR_INVALID_ARG, "ff_set_pixel_jitter: the jitter must be finite and in [0, 1) (got %g %g)", (double)jx, (double)jy);
     s->jitter_x = jx;
     s->jitter_y = jy;
-    return FF_OK;
-}
-
-void ff_taa_params_init(FfTaaParams* p)
-{
-    if (!p) return;
-    // 
-    p->alpha_min = 0.1f;
-    p->gamma = 1.0f;
-    p->flags = 0;
-    p->reserved = 0;
-}
-
-} // extern "C"
-
-namespace {
-
-// ff_taa's history and motion: two float4 per pixel {rgb, len} and one float2 (ff_state.h)
-TaaArgs taa_buffers(FfState* s, int width, int height, int cur)
-{
-    const size_t px = (size_t)width * (size_t)height;
-    TaaArgs a;
-    std::memset(&a, 0, sizeof a);
-    a.width = width;
-    a.height = height;
-    a.cur = cur;
-    a.hist[0] = s->d_taa_work;
-    a.hist[1] = s->d_taa_work + px;
-    a.motion = (float2*)(s->d_taa_work + 2 * px);
-    return a;
-}
-
-// inverse(ff_camera_ray_matrix(c)) in double, rounded to float; false if singular
-bool inverse_ray_matrix(const FfCamera* c, float* out16, FfMat4* ray)
-{
-    ff_camera_ray_matrix(c, ray);
-    double m[16], inv[16];
-    for (int k = 0; k < 16; ++k) m[k] = ray->m[k];
-    if (!invert4(m, inv)) return false;
-    for (int k = 0; k < 16; ++k) out16[k] = (float)inv[k];
-    return true;
-}
-
-} // namespace
-
-extern "C" {
-
-int ff_taa(FfState* s, const FfCamera* camera, int width, int height, const FfTaaParams* p, const float* radiance_in, const float* position,
-           const int32_t* ids, int inputs_on_device, void* rgb8, int rgb8_on_device, float* radiance_out, int radiance_out_on_device)
-{
-    clear_error();
-    if (!s) return fail(FF_ERR_INVALID_ARG, "ff_taa: state is null");
-    if (!camera) return fail(FF_ERR_INVALID_ARG, "ff_taa: camera is null");
-    if (!p) return fail(FF_ERR_INVALID_ARG, "ff_taa: params are null");
-    if (width <= 0 || height <= 0 || width > 65535 || height > 65535)
-        return fail(FF_ERR_INVALID_ARG, "ff_taa: image size %dx%d is invalid", width, height);
-    if (!(p->alpha_min > 0.f && p->alpha_min <= 1.f)) return fail(FF_ERR_INVALID_ARG, "ff_taa: alpha_min must be in (0, 1] (got %g)", (double)p->alpha_min);
-    if (!(p->gamma > 0.f) || !std::isfinite(p->gamma)) return fail(FF_ERR_INVALID_ARG, "ff_taa: gamma must be positive and finite (got %g)", (double)p->gamma);
-    if (p->flags & ~(FF_TAA_BILINEAR | FF_TAA_NO_CLAMP)) return fail(FF_ERR_INVALID_ARG, "ff_taa: unknown flags 0x%x", p->flags);
-    if (p->reserved != 0) return fail(FF_ERR_INVALID_ARG, "ff_taa: reserved must be 0");
-    if (!radiance_in || !position || !ids) return fail(FF_ERR_INVALID_ARG, "ff_taa: radiance, position and ids are required");
-    if (!s->has_scene) return fail(FF_ERR_NO_SCENE, "ff_taa: no scene uploaded (the history follows its geometries)");
-    FF_HIP(hipSetDevice(s->device));
-    const size_t px = (size_t)width * (size_t)height;
-    // host buffers are staged, as in ff_denoise; a device radiance_out that overlaps radiance_in reads a copy of the input (the
-    // kernel's apron reads neighbours that another workgroup may already have written)
-    const bool in_host = !inputs_on_device, rgb_host = rgb8 && !rgb8_on_device, out_host = radiance_out && !radiance_out_on_device;
-    const char* rin = (const char*)radiance_in;
-    const char* rout = (const char*)radiance_out;
-    const bool alias = !in_host && !out_host && radiance_out && rin < rout + px * 12 && rout < rin + px * 12;
-    const size_t need = (in_host ? padded(px * 12) * 3 : 0) + (alias ? padded(px * 12) : 0) + (rgb_host ? padded(px * 3) : 0) +
-                        (out_host ? padded(px * 12) : 0);
-    if (need > 0) {
-        const int st = ensure_bytes(&s->d_img_stage, &s->img_stage_bytes, need);
-        if (st != FF_OK) return st;
-    }
-    Carver c = { (char*)s->d_img_stage, 0 };
-    hipStream_t stream = s->stream;
-    auto stage_in = [&](const void* src, size_t bytes, hipMemcpyKind kind) -> const void* {
-        void* d = c.carve(bytes);
-        return hipMemcpyAsync(d, src, bytes, kind, stream) == hipSuccess ? d : nullptr;
-    };
-    const float* d_rad = radiance_in;
-    const float* d_pos = position;
-    const int* d_ids = ids;
-    if (in_host) {
-        d_rad = (const float*)stage_in(radiance_in, px * 12, hipMemcpyHostToDevice);
-        d_pos = (const float*)stage_in(position, px * 12, hipMemcpyHostToDevice);
-        d_ids = (const int*)stage_in(ids, px * 12, hipMemcpyHostToDevice);
-        if (!d_rad || !d_pos || !d_ids) return fail(FF_ERR_HIP, "ff_taa: staging the inputs failed");
-    } else if (alias) {
-        d_rad = (const float*)stage_in(radiance_in, px * 12, hipMemcpyDeviceToDevice);
-        if (!d_rad) return fail(FF_ERR_HIP, "ff_taa: copying the input failed");
-    }
-    unsigned char* d_rgb8 = rgb_host ? (unsigned char*)c.carve(px * 3) : (unsigned char*)rgb8;
-    float* d_out = out_host ? (float*)c.carve(px * 12) : radiance_out;
-    // history: kept only for the same image size (a new size, a reset or a new scene start afresh)
-    const bool has_history = s->taa_valid && width == s->taa_width && height == s->taa_height;
-    s->taa_valid = s->taa_last = false; // (from here on the history is being rewritten)
-    int st = ensure_bytes((void**)&s->d_taa_work, &s->taa_work_bytes, 2 * px * sizeof(float4) + px * sizeof(float2));
-    if (st != FF_OK) return st;
-    TaaArgs a = taa_buffers(s, width, height, has_history ? 1 - s->taa_cur : 0);
-    a.has_history = has_history ? 1 : 0;
-    a.bilinear = (p->flags & FF_TAA_BILINEAR) ? 1 : 0;
-    a.clamp = (p->flags & FF_TAA_NO_CLAMP) ? 0 : 1;
-    a.alpha_min = p->alpha_min;
-    a.gamma = p->gamma;
-    FfMat4 cm;
-    if (!inverse_ray_matrix(camera, a.inv_cur, &cm)) return fail(FF_ERR_INVALID_ARG, "ff_taa: the camera's ray matrix is singular");
-    std::memcpy(a.ray, cm.m, sizeof a.ray);
-    a.far_clip = camera->m_farClip;
-    a.screen_w = camera->m_screenWidth;
-    a.screen_h = camera->m_screenHeight;
-    // the per-geometry table: ff_denoise_temporal's rows from the TAA history's model matrices
-    int num = 0;
-    for (const GeomRecord& g : s->h_geoms) num = std::max(num, g.orig_index + 1);
-    s->h_taa_geoms.assign((size_t)num * sizeof(TemporalGeom), 0);
-    TemporalGeom* rows = (TemporalGeom*)s->h_taa_geoms.data();
-    for (const GeomRecord& g : s->h_geoms) {
-        const int o = g.orig_index;
-        if (o < 0) continue;
-        float cur12[12];
-        record_model(g, cur12);
-        int flags = 0;
-        const float* prev12 = cur12;
-        if (has_history && (size_t)o < s->taa_has_model.size() && s->taa_has_model[o]) {
-            prev12 = &s->taa_model[(size_t)o * 12];
-            if (std::memcmp(prev12, cur12, sizeof cur12) != 0) flags |= kTpMoved;
-        }
-        if ((size_t)o < s->taa_replaced.size() && s->taa_replaced[o]) flags |= kTpReplaced;
-        rows[o] = temporal_row(prev12, g, flags);
-    }
-    a.num_geoms = num;
-    if (num > 0) {
-        st = ensure_bytes(&s->d_taa_geoms, &s->taa_geoms_bytes, s->h_taa_geoms.size());
-        if (st != FF_OK) return st;
-        FF_HIP(hipMemcpyAsync(s->d_taa_geoms, s->h_taa_geoms.data(), s->h_taa_geoms.size(), hipMemcpyHostToDevice, stream));
-    }
-    a.geoms = (const TemporalGeom*)s->d_taa_geoms;
-    if (has_history) {
-        a.cam_rest = std::memcmp(camera, &s->taa_camera, sizeof(FfCamera)) == 0 ? 1 : 0;
-        FfMat4 pm;
-        if (!inverse_ray_matrix(&s->taa_camera, a.inv_prev, &pm)) return fail(FF_ERR_INVALID_ARG, "ff_taa: the previous camera's ray matrix is singular");
-        a.prev_screen_w = s->taa_camera.m_screenWidth;
-        a.prev_screen_h = s->taa_camera.m_screenHeight;
-    }
-    FF_HIP(launch_taa(a, d_rad, d_pos, d_ids, d_rgb8, d_out, stream));
-    FF_HIP(hipStreamSynchronize(stream));
-    // the history now describes this call
-    s->taa_valid = s->taa_last = true;
-    s->taa_cur = a.cur;
-    s->taa_width = width;
-    s->taa_height = height;
-    s->taa_camera = *camera;
-    s->taa_model.assign((size_t)num * 12, 0.f);
-    s->taa_has_model.assign((size_t)num, 0);
-    for (const GeomRecord& g : s->h_geoms) {
-        if (g.orig_index < 0) continue;
-        record_model(g, &s->taa_model[(size_t)g.orig_index * 12]);
-        s->taa_has_model[g.orig_index] = 1;
-    }
-    s->taa_replaced.assign((size_t)num, 0);
-    if (rgb_host) FF_HIP(hipMemcpy(rgb8, d_rgb8, px * 3, hipMemcpyDeviceToHost));
-    if (out_host) FF_HIP(hipMemcpy(radiance_out, d_out, px * 12, hipMemcpyDeviceToHost));
-    return FF_OK;
-}
-
-int ff_taa_reset(FfState* s)
-{
-    clear_error();
-    if (!s) return fail(FF_ERR_INVALID_ARG, "ff_taa_reset: state is null");
-    s->taa_valid = s->taa_last = false;
-    return FF_OK;
-}
-
-int ff_taa_history(FfState* s, float* motion, float* length, int on_device)
-{
-    clear_error();
-    if (!s) return fail(FF_ERR_INVALID_ARG, "ff_taa_history: state is null");
-    if (!s->taa_last) return fail(FF_ERR_INVALID_ARG, "ff_taa_history: no ff_taa call since the last reset");
-    if (!motion && !length) return FF_OK;
-    FF_HIP(hipSetDevice(s->device));
-    const size_t px = (size_t)s->taa_width * (size_t)s->taa_height;
-    const TaaArgs a = taa_buffers(s, s->taa_width, s->taa_height, s->taa_cur);
-    float* d_motion = motion;
-    float* d_length = length;
-    if (!on_device) {
-        const int st = ensure_bytes(&s->d_img_stage, &s->img_stage_bytes, padded(px * 8) + padded(px * 4));
-        if (st != FF_OK) return st;
-        Carver c = { (char*)s->d_img_stage, 0 };
-        d_motion = motion ? (float*)c.carve(px * 8) : nullptr;
-        d_length = length ? (float*)c.carve(px * 4) : nullptr;
-    }
-    FF_HIP(launch_taa_history(a, d_motion, d_length, s->stream));
-    FF_HIP(hipStreamSynchronize(s->stream));
-    if (!on_device) {
-        if (motion) FF_HIP(hipMemcpy(motion, d_motion, px * 8, hipMemcpyDeviceToHost));
-        if (length) FF_HIP(hipMemcpy(length, d_length, px * 4, hipMemcpyDeviceToHost));
-    }
     return FF_OK;
 }
 

@@ -125,8 +125,6 @@ void curve_values(const FfDisplayParams& p, const float* exposed, int n, float* 
     }
 }
 
-size_t padded16(size_t bytes) { return (bytes + 15) & ~(size_t)15; }
-
 // The call behind ff_display and ff_display_to_pbo; the arguments are checked.
 int display_run(FfState* s, int width, int height, const FfDisplayParams* p, const float* radiance_in, int input_on_device, void* rgb8,
                 int rgb8_on_device, float* display_out, int display_out_on_device)
@@ -153,7 +151,7 @@ int display_run(FfState* s, int width, int height, const FfDisplayParams* p, con
     unsigned* d_counters = (unsigned*)s->d_disp_const;
     // the work buffer: the pyramid's levels, then the staging of host buffers (and the copy of an overlapping input)
     BloomLevel level[kDisplayMaxLevels + 1] = {};
-    size_t need = 0;
+    size_t need = 0, level_at[kDisplayMaxLevels + 1] = {};
     const int levels = bloom ? p->bloom_levels : 0;
     int lw = width, lh = height;
     for (int j = 1; j <= levels; ++j) {
@@ -161,34 +159,19 @@ int display_run(FfState* s, int width, int height, const FfDisplayParams* p, con
         lh = (lh + 1) / 2;
         level[j].w = lw;
         level[j].h = lh;
-        need += padded16((size_t)lw * (size_t)lh * sizeof(float4));
+        level_at[j] = need;
+        need += ((size_t)lw * (size_t)lh * sizeof(float4) + 15) & ~(size_t)15;
     }
-    const size_t pyramid_bytes = need;
-    need += (in_host || overlap ? padded16(px * 12) : 0) + (rgb_host ? padded16(px * 3) : 0) + (out_host ? padded16(px * 12) : 0);
-    if (need > 0) {
-        const int st = ensure_bytes(&s->d_disp_work, &s->disp_work_bytes, need);
-        if (st != FF_OK) return st;
-    }
-    char* base = (char*)s->d_disp_work;
-    size_t used = 0;
-    for (int j = 1; j <= levels; ++j) {
-        level[j].texels = (float4*)(base + used);
-        used += padded16((size_t)level[j].w * (size_t)level[j].h * sizeof(float4));
-    }
-    used = pyramid_bytes;
-    auto carve = [&](size_t bytes) {
-        void* q = base + used;
-        used += padded16(bytes);
-        return q;
-    };
     const float* d_in = radiance_in;
-    if (in_host || overlap) {
-        float* d = (float*)carve(px * 12);
-        FF_HIP(hipMemcpyAsync(d, radiance_in, px * 12, in_host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, stream));
-        d_in = d;
-    }
-    unsigned char* d_rgb8 = rgb_host ? (unsigned char*)carve(px * 3) : (unsigned char*)rgb8;
-    float* d_out = out_host ? (float*)carve(px * 12) : display_out;
+    unsigned char* d_rgb8 = (unsigned char*)rgb8;
+    float* d_out = display_out;
+    Staging stage(&s->d_disp_work, &s->disp_work_bytes, need);
+    if (in_host || overlap) stage.in(&d_in, radiance_in, px * 12, in_host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice);
+    if (rgb_host) stage.out(&d_rgb8, rgb8, px * 3);
+    if (out_host) stage.out(&d_out, display_out, px * 12);
+    const int sst = stage.commit(stream, nullptr);
+    if (sst != FF_OK) return sst;
+    for (int j = 1; j <= levels; ++j) level[j].texels = (float4*)((char*)s->d_disp_work + level_at[j]);
     // steps 1 and 2
     uint32_t hist[kDisplayBins] = {};
     if (automatic) {
@@ -223,8 +206,8 @@ int display_run(FfState* s, int width, int height, const FfDisplayParams* p, con
     }
     if (d_rgb8 || d_out) FF_HIP(launch_display(a, d_in, d_rgb8, d_out, stream));
     FF_HIP(hipStreamSynchronize(stream));
-    if (rgb_host) FF_HIP(hipMemcpy(rgb8, d_rgb8, px * 3, hipMemcpyDeviceToHost));
-    if (out_host) FF_HIP(hipMemcpy(display_out, d_out, px * 12, hipMemcpyDeviceToHost));
+    const int fst = stage.finish();
+    if (fst != FF_OK) return fst;
     // the state now describes this call
     if (automatic) {
         s->disp_has_prev = true;

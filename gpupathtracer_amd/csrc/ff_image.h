@@ -1,0 +1,83 @@
+// ff_image.h — what the image-space entry points (ff_image_api.cpp: ff_gbuffer, ff_denoise, ff_denoise_temporal, ff_taa;
+// ff_display_api.cpp) keep in the tracer state and share: the staging of host buffers and the reprojection history.  Nothing
+// here reaches a trace kernel.
+#pragma once
+
+#include <vector>
+
+#include <hip/hip_runtime.h>
+
+#include "ff_internal.h"
+
+namespace ff {
+
+struct TemporalGeom; // ff_temporal.h
+
+// Host buffers travel through a device buffer the state owns, in 16-byte aligned pieces from `first_byte` on.  The caller names
+// its pieces once - in(): copied to the device by commit(), out(): copied back by finish() - so the size of the buffer and every
+// piece's place in it come from the same list.  commit() grows the buffer, stores each piece's device address through the pointer
+// it was registered with and enqueues the copies in; finish() runs after the caller's synchronize.
+struct Staging {
+    Staging(void** buffer, size_t* capacity, size_t first_byte = 0) : buf(buffer), cap(capacity), used(first_byte) {}
+    template <class T>
+    void in(const T** dev, const void* src, size_t bytes, hipMemcpyKind kind = hipMemcpyHostToDevice) { add((void**)dev, src, nullptr, bytes, kind); }
+    template <class T>
+    void out(T** dev, void* host, size_t bytes) { add((void**)dev, nullptr, host, bytes, hipMemcpyDeviceToHost); }
+    int commit(hipStream_t stream, const char* copy_failed); // copy_failed: the error text of a failed copy in (null: the HIP call's)
+    int finish();
+
+private:
+    struct Piece {
+        void** dev;
+        const void* src;
+        void* host;
+        size_t offset, bytes;
+        hipMemcpyKind kind;
+    };
+    void add(void** dev, const void* src, void* host, size_t bytes, hipMemcpyKind kind)
+    {
+        pieces.push_back({ dev, src, host, used, bytes, kind });
+        used += (bytes + 15) & ~(size_t)15;
+    }
+    void** buf;
+    size_t* cap;
+    size_t used;
+    std::vector<Piece> pieces;
+};
+
+// What a filter that reprojects its last result (ff_denoise_temporal, ff_taa) remembers between calls: two history sets in
+// d_work that swap by index (`cur`: the one the last call wrote; the layout is the filter's own), and the camera, image size and
+// per-geometry model matrices (caller's order) of that call.  `replaced` marks the meshes ff_update_mesh changed since.
+struct ReprojectionHistory {
+    float4* d_work = nullptr;
+    size_t work_bytes = 0;
+    void* d_geoms = nullptr; // the per-geometry table (TemporalGeom rows)
+    size_t geoms_bytes = 0;
+    std::vector<unsigned char> h_geoms; // its host copy (kept alive until the upload has completed)
+    bool valid = false;                 // history to reproject from
+    bool last = false;                  // a call's motion and lengths are there to read (ff_temporal_history / ff_taa_history)
+    int cur = 0, width = 0, height = 0;
+    FfCamera camera = {};
+    std::vector<float> model; // 12 floats (model matrix columns, xyz) per caller geometry index
+    std::vector<unsigned char> has_model, replaced;
+
+    // One call of the filter: whether it reprojects, the set it writes, and the table (num rows on the device).
+    struct Frame {
+        bool has_history;
+        int cur, num;
+        const TemporalGeom* geoms;
+    };
+    // begin: the history is kept only for the same image size.  It is invalid from here until commit(), so a call that fails in
+    // between leaves none; sizes d_work, builds the table from the previous call's model matrices and uploads it on `stream`.
+    int begin(const std::vector<GeomRecord>& records, int w, int h, size_t work_bytes_needed, hipStream_t stream, Frame* out);
+    // commit: the history now describes this call.
+    void commit(const std::vector<GeomRecord>& records, const FfCamera* cam, int w, int h, const Frame& f);
+    void invalidate() { valid = last = false; }
+    void mark_replaced(int index)
+    {
+        if ((size_t)index < replaced.size()) replaced[index] = 1;
+    }
+    void release(); // frees the device buffers (ff_destroy)
+};
+
+} // namespace ff

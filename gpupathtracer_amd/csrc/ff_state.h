@@ -1,5 +1,6 @@
 // ff_state.h — the tracer state behind the opaque FfState handle and the internal render steps shared by the
-// translation units of the library (ff_api.cpp: single-device entry points; ff_dist.cpp: multi-GPU entry points).
+// translation units of the library (ff_api.cpp: single-device entry points; ff_dist.cpp: multi-GPU entry points;
+// ff_image_api.cpp and ff_display_api.cpp: the image-space entry points, whose own state is described in ff_image.h).
 #pragma once
 
 #include <vector>
@@ -7,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include "ff_build.h"
+#include "ff_image.h"
 #include "ff_internal.h"
 #include "ff_kernels.h"
 
@@ -105,29 +107,20 @@ struct FfState {
     float* d_mean = nullptr;
     size_t mean_bytes = 0;
     int accum_width = 0, accum_height = 0, accum_frames = 0;
-    // G-buffer and denoiser (ff_gbuffer / ff_denoise, ff_denoise.hip): ff_gbuffer's own primary hits ([3][pix_items] float4, never
-    // the frame's d_primary_cache), staging for host buffers, the filter's packed guides and its two colour buffers
+    // G-buffer and denoiser (ff_gbuffer / ff_denoise, ff_image_api.cpp, ff_denoise.hip): ff_gbuffer's own primary hits ([3][pix_items]
+    // float4, never the frame's d_primary_cache), staging for host buffers (ff::Staging), the filter's packed guides and its two
+    // colour buffers
     float4* d_gb_hits = nullptr;
     size_t gb_hits_bytes = 0;
     void* d_img_stage = nullptr;
     size_t img_stage_bytes = 0;
     float4* d_dn_work = nullptr; // 4 float4 per pixel: guide_pos, guide_nrm, colour 0, colour 1
     size_t dn_work_bytes = 0;
-    // temporal denoiser (ff_denoise_temporal, ff_temporal.hip): two history sets of 4 float4 per pixel (guide position and class,
-    // unit normal, colour history, moments {l, l^2, len}) that swap by index, then the two working colour buffers and the motion
-    // (float2 per pixel).  tp_cur: the set the last call wrote.  The history describes the camera, image size and per-geometry
-    // model matrices (caller's order) of that call; tp_replaced marks the meshes ff_update_mesh changed since.
-    float4* d_tp_work = nullptr;
-    size_t tp_work_bytes = 0;
-    void* d_tp_geoms = nullptr; // the per-geometry table (ff::TemporalGeom rows)
-    size_t tp_geoms_bytes = 0;
-    std::vector<unsigned char> h_tp_geoms; // its host copy (kept alive until the upload has completed)
-    bool tp_valid = false;                  // history to reproject from
-    bool tp_last = false;                   // a call's motion and lengths are there to read (ff_temporal_history)
-    int tp_cur = 0, tp_width = 0, tp_height = 0;
-    FfCamera tp_camera = {};
-    std::vector<float> tp_model;            // 12 floats (model matrix columns, xyz) per caller geometry index
-    std::vector<unsigned char> tp_has_model, tp_replaced;
+    // The reprojection histories (ff_image.h).  ff_denoise_temporal (ff_temporal.hip): two sets of 4 float4 per pixel (guide position
+    // and class, unit normal, colour history, moments {l, l^2, len}), then the two working colour buffers and the motion (float2 per
+    // pixel).  ff_taa (ff_taa.hip): two buffers of one float4 per pixel {rgb, len}, then the motion.
+    enum { kHistoryTemporal = 0, kHistoryTaa = 1 };
+    ff::ReprojectionHistory history[2];
     // sub-pixel jitter of the primary rays (ff_set_pixel_jitter): composed into the ray matrix of ff_render* and ff_gbuffer
     float jitter_x = 0.f, jitter_y = 0.f;
     // Next-event estimation (ff_nee.cpp): what the light table is built from - the uploaded geometries (caller order) with their
@@ -153,19 +146,6 @@ struct FfState {
     size_t env_alias_bytes = 0;
     float* d_env_z = nullptr;          // ff::NeeParams::env_z
     size_t env_z_bytes = 0;
-    // temporal anti-aliasing (ff_taa, ff_taa.hip): two history buffers of one float4 per pixel {rgb, len} that swap by index, then
-    // the motion (float2 per pixel).  taa_cur: the buffer the last call wrote.  The history describes the camera, image size and
-    // per-geometry model matrices of that call; taa_replaced marks the meshes ff_update_mesh changed since.
-    float4* d_taa_work = nullptr;
-    size_t taa_work_bytes = 0;
-    void* d_taa_geoms = nullptr; // the per-geometry table (ff::TemporalGeom rows, as the temporal denoiser's)
-    size_t taa_geoms_bytes = 0;
-    std::vector<unsigned char> h_taa_geoms;
-    bool taa_valid = false, taa_last = false;
-    int taa_cur = 0, taa_width = 0, taa_height = 0;
-    FfCamera taa_camera = {};
-    std::vector<float> taa_model;
-    std::vector<unsigned char> taa_has_model, taa_replaced;
     // display transform (ff_display, ff_display.hip): the adapted exposure, the last call's results (ff_display_state) and the
     // device buffers - 256 histogram counters and the 255 sRGB thresholds in d_disp_const, the bloom pyramid ({rgb, 0} float4 per
     // texel, levels 1 .. n one after another) and the staging of host buffers in d_disp_work.  Not reset by uploads.
@@ -255,6 +235,18 @@ int check_render_call(const FfState* s, const FfCamera* camera, const FfRenderPa
 int render_enqueue(FfState* s, const FfCamera* camera, const FfRenderParams* prm, int strip_rows, int part, int num_parts, int local_rows,
                    unsigned char* rgb8_dev, float* radiance_dev, int x0 = 0, int y0 = 0, int win_w = -1);
 int render_finish(FfState* s);
+
+// This camera's primary hits for a whole width x height frame (ff_render's pixel mapping: one part, strips of height rows, the
+// window is the image), for ff_gbuffer (ff_image_api.cpp): the hits the state keeps from its last frame if they were computed for
+// this camera and mapping, else a pre-pass into d_gb_hits on the state's stream (fresh; the work-queue counters are zeroed behind
+// it and the loop-guard counter is the caller's to read).  Nothing of the frame's state - stored hits, key, cull mask - is written.
+struct PrimaryHits {
+    const float4* hits;
+    bool fresh;
+    unsigned pix_items;
+    int tiles_per_row, xlim, ylim;
+};
+int frame_primary_hits(FfState* s, const FfCamera* camera, const FfRenderParams* params, PrimaryHits* out);
 
 void dist_release(FfState* s); // ff_dist.cpp: frees s->dist (called by ff_destroy)
 
