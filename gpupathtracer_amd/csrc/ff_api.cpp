@@ -26,6 +26,7 @@ void free_scene(FfState* s)
     if (s->d_geoms) (void)hipFree(s->d_geoms);
     if (s->d_tris) (void)hipFree(s->d_tris);
     if (s->d_normals) (void)hipFree(s->d_normals);
+    if (s->d_uvs) (void)hipFree(s->d_uvs);
     if (s->d_nodes) (void)hipFree(s->d_nodes);
     if (s->d_nodes4) (void)hipFree(s->d_nodes4);
     s->top_count = s->top_depth = 0;
@@ -38,6 +39,7 @@ void free_scene(FfState* s)
     s->d_geoms = nullptr;
     s->d_tris = nullptr;
     s->d_normals = nullptr;
+    s->d_uvs = nullptr;
     s->d_nodes = nullptr;
     s->d_parent = nullptr;
     s->d_role = nullptr;
@@ -453,6 +455,10 @@ int render_enqueue(FfState* s, const FfCamera* camera, const FfRenderParams* prm
     if (env && prm->shade_mode == FF_SHADE_DIFFUSE_PATH_SMOOTH)
         return fail(FF_ERR_UNSUPPORTED, "FF_SHADE_DIFFUSE_PATH_SMOOTH does not render under an environment light (ff_set_environment); "
                     "clear it or use FF_SHADE_DIFFUSE_PATH / FF_SHADE_DIFFUSE_PATH_NEE");
+    const bool tex = s->tex_bound > 0 && !debug; // (... and albedo textures)
+    if (tex && prm->shade_mode == FF_SHADE_DIFFUSE_PATH_SMOOTH)
+        return fail(FF_ERR_UNSUPPORTED, "FF_SHADE_DIFFUSE_PATH_SMOOTH does not render albedo textures (ff_set_albedo_texture); "
+                    "unbind them or use FF_SHADE_DIFFUSE_PATH / FF_SHADE_DIFFUSE_PATH_NEE");
     const int spp = debug ? 1 : prm->spp;
     const int bounces = debug ? 1 : prm->bounces;
     // Samples are accumulated in blocks (a multiple of 64, at most 16 blocks per pixel up to 1024 spp and beyond): a
@@ -489,9 +495,9 @@ int render_enqueue(FfState* s, const FfCamera* camera, const FfRenderParams* prm
                         "upload with FF_BUILD_HOST_SAH or render with FF_TRACE_BRUTE_FORCE", s->max_depth4, s->max_depth4 + 1, s->num_geoms);
     }
     fill_scene(s, k, prm->shade_mode == FF_SHADE_DIFFUSE_PATH_SMOOTH, prm->trace_mode == FF_TRACE_BVH ? block_threads : 0);
-    if (prm->shade_mode == FF_SHADE_DIFFUSE_PATH_NEE || env) {
-        // (its own kernels: the rest of this function prepares the mega-kernels' frame; under an environment, FF_SHADE_DIFFUSE_PATH
-        // runs there too, with no light table)
+    if (prm->shade_mode == FF_SHADE_DIFFUSE_PATH_NEE || env || tex) {
+        // (its own kernels: the rest of this function prepares the mega-kernels' frame; under an environment or with albedo textures
+        // bound, FF_SHADE_DIFFUSE_PATH runs there too, with no light table)
         k.rgb8 = rgb8_dev;
         k.radiance = radiance_dev;
         return enqueue_nee(s, k, prm, launches, blocks_per_launch, local_pixels);
@@ -977,6 +983,7 @@ int ff_destroy(FfState* s)
     if (s->d_nee_lights) (void)hipFree(s->d_nee_lights);
     if (s->d_nee_pdf) (void)hipFree(s->d_nee_pdf);
     env_release(s);
+    tex_release(s);
     display_release(s);
     free_build_scratch(s->scratch);
     if (s->d_blocksums) (void)hipFree(s->d_blocksums);
@@ -1032,8 +1039,9 @@ int place_single_leaf_mesh(FfState* s, const FfTriangle* tris, int count, const 
     std::vector<BvhNode> tn;
     std::vector<TriRecord> tt;
     std::vector<TriNormals> nn;
+    std::vector<TriUVs> uu;
     int depth = 0;
-    build_mesh_bvh(tris, count, bp, tn, tt, &depth, &nn);
+    build_mesh_bvh(tris, count, bp, tn, tt, &depth, &nn, &uu);
     for (BvhNode& nd : tn) {
         int* links[2] = { &nd.left, &nd.right };
         for (int* l : links) {
@@ -1048,6 +1056,7 @@ int place_single_leaf_mesh(FfState* s, const FfTriangle* tris, int count, const 
     FF_HIP(hipMemcpy(s->d_nodes + node_base, tn.data(), tn.size() * sizeof(BvhNode), hipMemcpyHostToDevice));
     FF_HIP(hipMemcpy(s->d_tris + tri_first, tt.data(), tt.size() * sizeof(TriRecord), hipMemcpyHostToDevice));
     FF_HIP(hipMemcpy(s->d_normals + tri_first, nn.data(), nn.size() * sizeof(TriNormals), hipMemcpyHostToDevice));
+    FF_HIP(hipMemcpy(s->d_uvs + tri_first, uu.data(), uu.size() * sizeof(TriUVs), hipMemcpyHostToDevice));
     *out_nodes = (int)tn.size();
     *out_depth = depth;
     return FF_OK;
@@ -1085,6 +1094,7 @@ int upload_with_device_builder(FfState* s, const FfGeometry* host_geometries, in
     FF_HIP(scene_alloc(s, (void**)&s->d_geoms, cs.geoms.size() * sizeof(GeomRecord)));
     FF_HIP(scene_alloc(s, (void**)&s->d_tris, (cs.total_tris ? (size_t)cs.total_tris : 1) * sizeof(TriRecord)));
     FF_HIP(scene_alloc(s, (void**)&s->d_normals, (cs.total_tris ? (size_t)cs.total_tris : 1) * sizeof(TriNormals)));
+    FF_HIP(hipMalloc((void**)&s->d_uvs, (cs.total_tris ? (size_t)cs.total_tris : 1) * sizeof(TriUVs)));
     FF_HIP(scene_alloc(s, (void**)&s->d_nodes, (node_cap ? node_cap : 1) * sizeof(BvhNode)));
     // (the kernels address a node by a 32-bit byte offset from the array's base)
     if ((uint64_t)(node_cap + cs.geoms.size() + 1) * sizeof(Bvh4Node) >= (1ull << 32))
@@ -1110,7 +1120,7 @@ int upload_with_device_builder(FfState* s, const FfGeometry* host_geometries, in
             if (st != FF_OK) return st;
             const auto t0 = std::chrono::steady_clock::now();
             MeshBuildInfo info;
-            st = gpu_build_mesh(s->stream, s->scratch, s->d_stage, r.tri_count, r.tri_first, node_base, device_leaf, s->d_tris, s->d_normals, s->d_nodes, &info,
+            st = gpu_build_mesh(s->stream, s->scratch, s->d_stage, r.tri_count, r.tri_first, node_base, device_leaf, s->d_tris, s->d_normals, s->d_uvs, s->d_nodes, &info,
                                 s->builder == FF_BUILD_GPU_PLOC);
             if (st != FF_OK) return st;
             FF_HIP(hipStreamSynchronize(s->stream));
@@ -1170,6 +1180,7 @@ int ff_upload_scene(FfState* s, const FfGeometry* host_geometries, int n)
     s->build_stats = FfBuildStats();
     const BvhBuildParams bp = default_bvh_params();
     s->nee_valid = false; // (the light table belongs to the scene that goes)
+    tex_drop_bindings(s); // (and so do the albedo-texture bindings; the textures stay)
     if (s->builder != FF_BUILD_HOST_SAH) {
         int st = upload_with_device_builder(s, host_geometries, n, bp);
         if (st == FF_OK) {
@@ -1224,6 +1235,8 @@ int upload_compiled(FfState* s, const CompiledScene& cs)
     FF_HIP(scene_alloc(s, (void**)&s->d_normals, tri_bytes));
     static_assert(sizeof(TriNormals) == sizeof(TriRecord), "parallel arrays of equal stride");
     if (!cs.normals.empty()) FF_HIP(hipMemcpy(s->d_normals, cs.normals.data(), cs.normals.size() * sizeof(TriNormals), hipMemcpyHostToDevice));
+    FF_HIP(hipMalloc((void**)&s->d_uvs, (cs.uvs.size() ? cs.uvs.size() : 1) * sizeof(TriUVs)));
+    if (!cs.uvs.empty()) FF_HIP(hipMemcpy(s->d_uvs, cs.uvs.data(), cs.uvs.size() * sizeof(TriUVs), hipMemcpyHostToDevice));
     FF_HIP(scene_alloc(s, (void**)&s->d_nodes, node_bytes));
     // (the kernels address a node by a 32-bit byte offset from the array's base)
     if ((uint64_t)(cs.nodes.size() + cs.geoms.size() + 1) * sizeof(Bvh4Node) >= (1ull << 32))
@@ -1292,6 +1305,7 @@ int upload_compiled_scene(FfState* s, const CompiledScene& cs, double build_ms)
     s->primary_valid = s->last_key_valid = false;
     for (ReprojectionHistory& h : s->history) h.invalidate();
     s->nee_valid = false; // (no light table: FF_SHADE_DIFFUSE_PATH_NEE is not offered on a compiled upload)
+    tex_drop_bindings(s);
     s->nee_geoms.clear();
     s->nee_tris.clear();
     s->build_stats = FfBuildStats();
@@ -1387,7 +1401,7 @@ int ff_update_mesh(FfState* s, int geometry_index, const FfTriangle* triangles, 
             st = place_single_leaf_mesh(s, triangles, count, bp, rec.tri_first, slot.node_first, &slot.node_count, &slot.depth);
         } else {
             MeshBuildInfo info = MeshBuildInfo();
-            st = gpu_build_mesh(s->stream, s->scratch, s->d_stage, count, rec.tri_first, slot.node_first, device_leaf_tris(bp), s->d_tris, s->d_normals, s->d_nodes, &info,
+            st = gpu_build_mesh(s->stream, s->scratch, s->d_stage, count, rec.tri_first, slot.node_first, device_leaf_tris(bp), s->d_tris, s->d_normals, s->d_uvs, s->d_nodes, &info,
                                 s->scene_builder == FF_BUILD_GPU_PLOC);
             if (st == FF_OK) {
                 slot.node_count = info.node_count;
@@ -1413,7 +1427,7 @@ int ff_update_mesh(FfState* s, int geometry_index, const FfTriangle* triangles, 
             slot.parents_linked = true;
         }
         st = gpu_refit_mesh(s->stream, s->scratch, s->d_stage, count, rec.tri_first, slot.node_first, slot.node_count, s->d_parent + slot.node_first, s->d_tris,
-                            s->d_normals, s->d_nodes);
+                            s->d_normals, s->d_uvs, s->d_nodes);
         if (st != FF_OK) return st;
         st = collapse_slot(s, (size_t)gi, /*with_info=*/false); // same topology: the boxes of the 4-wide nodes follow
         if (st != FF_OK) return st;

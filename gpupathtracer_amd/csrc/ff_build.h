@@ -38,7 +38,7 @@ inline size_t gpu_build_max_nodes(int tri_count) { return tri_count > 1 ? (size_
 // single leaf and are assembled on the host).  ploc = false: LBVH (Karras hierarchy on the Morton order); true: PLOC
 // (agglomerative clustering on the Morton order: slower to build, close to SAH quality).
 int gpu_build_mesh(hipStream_t stream, BuildScratch& scratch, const FfTriangle* d_src, int tri_count, int tri_first, int node_base, int max_leaf,
-                   TriRecord* d_tris, TriNormals* d_normals, BvhNode* d_nodes, MeshBuildInfo* out, bool ploc = false);
+                   TriRecord* d_tris, TriNormals* d_normals, TriUVs* d_uvs, BvhNode* d_nodes, MeshBuildInfo* out, bool ploc = false);
 
 // parent[n - node_first] = (parent node index << 1 | side) for every inner node n of the mesh, -1 for its root.
 int gpu_link_parents(hipStream_t stream, const BvhNode* d_nodes, int node_first, int node_count, int* d_parent);
@@ -48,7 +48,7 @@ int gpu_link_parents(hipStream_t stream, const BvhNode* d_nodes, int node_first,
 // boxes to the root.  Works on trees from either builder.  d_parent: from gpu_link_parents.  d_counters: node_count ints
 // of scratch.  Asynchronous on `stream`.
 int gpu_refit_mesh(hipStream_t stream, BuildScratch& scratch, const FfTriangle* d_src, int tri_count, int tri_first, int node_first, int node_count,
-                   const int* d_parent, TriRecord* d_tris, TriNormals* d_normals, BvhNode* d_nodes);
+                   const int* d_parent, TriRecord* d_tris, TriNormals* d_normals, TriUVs* d_uvs, BvhNode* d_nodes);
 
 // The 4-wide tree the trace kernels traverse, derived from one mesh's binary nodes [node_first, node_first + node_count)
 // (any builder; node numbers grow level by level, root first).  Which binary nodes become 4-wide nodes and which are absorbed

@@ -945,9 +945,16 @@ __device__ __forceinline__ void write_normals(TriNormals& n, const FfTriangle& t
     n.n2[0] = t.m_n2.x; n.n2[1] = t.m_n2.y; n.n2[2] = t.m_n2.z; n.pad2 = 0.f;
 }
 
+__device__ __forceinline__ void write_uvs(TriUVs& u, const FfTriangle& t)
+{
+    u.uv[0] = t.m_uv0.x; u.uv[1] = t.m_uv0.y;
+    u.uv[2] = t.m_uv1.x; u.uv[3] = t.m_uv1.y;
+    u.uv[4] = t.m_uv2.x; u.uv[5] = t.m_uv2.y;
+}
+
 __global__ __launch_bounds__(kBuildBlock) void records_kernel(const FfTriangle* __restrict__ src, const uint32_t* __restrict__ vals, int T, int tri_first,
                                                                const int* __restrict__ leaf_position, TriRecord* __restrict__ tris,
-                                                               TriNormals* __restrict__ normals)
+                                                               TriNormals* __restrict__ normals, TriUVs* __restrict__ uvs)
 {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= T) return;
@@ -959,12 +966,15 @@ __global__ __launch_bounds__(kBuildBlock) void records_kernel(const FfTriangle* 
     TriNormals n;
     write_normals(n, src[orig]);
     normals[dst] = n;
+    TriUVs u;
+    write_uvs(u, src[orig]);
+    uvs[dst] = u;
 }
 
 // ---- refit ------------------------------------------------------------------------------------------------------------
 
 __global__ __launch_bounds__(kBuildBlock) void refresh_records_kernel(const FfTriangle* __restrict__ src, int T, int tri_first, TriRecord* __restrict__ tris,
-                                                                       TriNormals* __restrict__ normals)
+                                                                       TriNormals* __restrict__ normals, TriUVs* __restrict__ uvs)
 {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= T) return;
@@ -976,6 +986,9 @@ __global__ __launch_bounds__(kBuildBlock) void refresh_records_kernel(const FfTr
     TriNormals n;
     write_normals(n, src[orig]);
     normals[tri_first + j] = n;
+    TriUVs u;
+    write_uvs(u, src[orig]);
+    uvs[tri_first + j] = u;
 }
 
 __global__ __launch_bounds__(kBuildBlock) void link_parents_kernel(const BvhNode* __restrict__ nodes, int node_first, int node_count, int* __restrict__ parent)
@@ -1388,7 +1401,7 @@ void free_build_scratch(BuildScratch& s)
 }
 
 int gpu_build_mesh(hipStream_t stream, BuildScratch& scratch, const FfTriangle* d_src, int T, int tri_first, int node_base, int max_leaf,
-                   TriRecord* d_tris, TriNormals* d_normals, BvhNode* d_nodes, MeshBuildInfo* out, bool ploc)
+                   TriRecord* d_tris, TriNormals* d_normals, TriUVs* d_uvs, BvhNode* d_nodes, MeshBuildInfo* out, bool ploc)
 {
     if (T <= max_leaf || T < 2) return fail(FF_ERR_INVALID_ARG, "gpu_build_mesh: %d triangles fit one leaf", T);
     if (max_leaf < 1 || max_leaf > 8) return fail(FF_ERR_INVALID_ARG, "max_leaf_tris must be 1..8");
@@ -1494,7 +1507,7 @@ int gpu_build_mesh(hipStream_t stream, BuildScratch& scratch, const FfTriangle* 
     rank_scatter_kernel<<<grid_for(emitted), kBuildBlock, 0, stream>>>(emitted, b.ids_out, b.new_index);
     emit_kernel<<<grid_for(emitted), kBuildBlock, 0, stream>>>(T, emitted, max_leaf, tri_first, node_base, b.bounds, b.ids_out, b.new_index, b.left, b.right,
                                                                b.first, b.last, b.boxes, leaf_position, d_nodes);
-    records_kernel<<<tri_grid, kBuildBlock, 0, stream>>>(d_src, b.vals_out, T, tri_first, leaf_position, d_tris, d_normals);
+    records_kernel<<<tri_grid, kBuildBlock, 0, stream>>>(d_src, b.vals_out, T, tri_first, leaf_position, d_tris, d_normals, d_uvs);
     FFB_HIP(hipGetLastError());
     out->root = node_base;
     out->node_count = emitted;
@@ -1571,7 +1584,7 @@ int gpu_link_parents(hipStream_t stream, const BvhNode* d_nodes, int node_first,
 }
 
 int gpu_refit_mesh(hipStream_t stream, BuildScratch& scratch, const FfTriangle* d_src, int T, int tri_first, int node_first, int node_count,
-                   const int* d_parent, TriRecord* d_tris, TriNormals* d_normals, BvhNode* d_nodes)
+                   const int* d_parent, TriRecord* d_tris, TriNormals* d_normals, TriUVs* d_uvs, BvhNode* d_nodes)
 {
     if (T <= 0 || node_count <= 0) return FF_OK;
     Carver probe(nullptr);
@@ -1586,7 +1599,7 @@ int gpu_refit_mesh(hipStream_t stream, BuildScratch& scratch, const FfTriangle* 
     FFB_HIP(hipMemsetAsync(arrivals, 0, (size_t)node_count * sizeof(int), stream));
     const int tri_grid = grid_for(T);
     bounds_kernel<<<tri_grid < 1024 ? tri_grid : 1024, kBuildBlock, 0, stream>>>(d_src, T, bounds);
-    refresh_records_kernel<<<tri_grid, kBuildBlock, 0, stream>>>(d_src, T, tri_first, d_tris, d_normals);
+    refresh_records_kernel<<<tri_grid, kBuildBlock, 0, stream>>>(d_src, T, tri_first, d_tris, d_normals, d_uvs);
     refit_kernel<<<grid_for(node_count), kBuildBlock, 0, stream>>>(d_src, d_tris, bounds, node_first, node_count, d_parent, d_nodes, arrivals);
     FFB_HIP(hipGetLastError());
     return FF_OK;

@@ -19,6 +19,10 @@ struct GbufferResolveParams {
     const TriRecord* tris;
     int num_geoms;
     long long num_tris;
+    // albedo textures (ff_texture.h; tex_bind null: none bound): a bound diffuse hit's albedo is m_albedo times the texel at its position
+    const TexBinding* tex_bind;
+    const TexDesc* tex_desc;
+    const TriUVs* uvs;
     // outputs, row-major, top row first (any may be null)
     float* depth;    // W*H
     float* position; // W*H*3

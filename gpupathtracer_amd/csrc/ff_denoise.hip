@@ -74,6 +74,16 @@ __global__ __launch_bounds__(256) void gbuffer_resolve_kernel(const GbufferResol
             ax = col[0];
             ay = col[1];
             az = col[2];
+            if (p.tex_bind && bxdf == FF_BXDF_DIFFUSE) {
+                // the integrator's lookup (nee_path_kernel): the same function of the same world point, so the same bits
+                float texel[3];
+                if (tex_albedo(p.tex_bind, p.tex_desc, p.uvs, g, rec, G.type, reinterpret_cast<const float*>(&G), reinterpret_cast<const float*>(p.tris), px, py, pz,
+                               texel)) {
+                    ax = ax * texel[0];
+                    ay = ay * texel[1];
+                    az = az * texel[2];
+                }
+            }
             geom = G.orig_index;
         }
     }

@@ -318,6 +318,10 @@ struct FfSceneFile {
     bool has_env = false;                          // an environment statement: the .hdr path (resolved), intensity, rotation in degrees
     std::string env_path;
     float env_intensity = 1.f, env_rotation = 0.f;
+    struct Texture { std::string name, path; int flags; };   // texture statements, file order
+    std::vector<Texture> textures;
+    struct AlbedoMap { int texture; float scale[2], offset[2]; }; // per geometry (texture < 0: none)
+    std::vector<AlbedoMap> albedo_maps;
     ~FfSceneFile()
     {
         for (FfTriangle* t : meshes) std::free(t);
@@ -433,6 +437,7 @@ int ff_scene_file_load(const char* path, FfSceneFile** out_scene)
             }
             FfVec3 pos{ 0, 0, 0 }, rot{ 0, 0, 0 }, scl{ 1, 1, 1 };
             FfBXDF* bx = nullptr;
+            FfSceneFile::AlbedoMap amap = { -1, { 1.f, 1.f }, { 0.f, 0.f } };
             while (status == FF_OK && i < tok.size()) {
                 const std::string key = tok[i++];
                 float v[3];
@@ -445,6 +450,18 @@ int ff_scene_file_load(const char* path, FfSceneFile** out_scene)
                     for (auto& b : sc->bxdfs) if (b.first == tok[i]) bx = b.second;
                     if (!bx) bad("bxdf name not defined above");
                     ++i;
+                } else if (key == "albedo_map") {
+                    // (a `scale U V` / `offset U V` right behind the name is the map's, not the geometry's)
+                    if (i >= tok.size()) { bad("albedo_map needs a texture name"); break; }
+                    for (size_t t = 0; t < sc->textures.size(); ++t) if (sc->textures[t].name == tok[i]) amap.texture = (int)t;
+                    if (amap.texture < 0) { bad("albedo_map names a texture not defined above"); break; }
+                    ++i;
+                    while (status == FF_OK && i < tok.size() && (tok[i] == "scale" || tok[i] == "offset")) {
+                        float* dst = tok[i] == "scale" ? amap.scale : amap.offset;
+                        ++i;
+                        if (!read_floats(tok, i, 2, v) || !std::isfinite(v[0]) || !std::isfinite(v[1])) bad("albedo_map scale / offset need 2 finite numbers");
+                        else { dst[0] = v[0]; dst[1] = v[1]; }
+                    }
                 } else bad("unknown geometry key");
             }
             if (status != FF_OK) break;
@@ -454,6 +471,26 @@ int ff_scene_file_load(const char* path, FfSceneFile** out_scene)
             ff_geometry_init(&g, is_mesh ? FF_GEOM_TRIANGLEMESH : (is_sphere ? FF_GEOM_SPHERE : FF_GEOM_PLANE), pos, rot, scl, tris, ntris, radius);
             g.m_bxdf = bx;
             sc->geometries.push_back(g);
+            sc->albedo_maps.push_back(amap);
+        } else if (tok[0] == "texture") {
+            if (tok.size() < 3) { bad("texture needs a name and an image path"); break; }
+            bool dup = false;
+            for (const auto& t : sc->textures) dup = dup || t.name == tok[1];
+            if (dup) { bad("a second texture of that name"); break; }
+            FfSceneFile::Texture t;
+            t.name = tok[1];
+            t.path = (!tok[2].empty() && tok[2][0] == '/') ? tok[2] : dir + tok[2];
+            const size_t dot = t.path.find_last_of('.');
+            const std::string ext = dot == std::string::npos ? std::string() : t.path.substr(dot);
+            if (ext != ".hdr" && ext != ".ppm") { bad("a texture is an .hdr or a .ppm file"); break; }
+            t.flags = 0;
+            for (i = 3; status == FF_OK && i < tok.size(); ++i) {
+                if (tok[i] == "srgb") t.flags |= FF_SCENE_TEX_SRGB;
+                else if (tok[i] == "clamp") t.flags |= FF_TEX_CLAMP;
+                else if (tok[i] == "nearest") t.flags |= FF_TEX_NEAREST;
+                else bad("unknown texture option");
+            }
+            if (status == FF_OK) sc->textures.push_back(t);
         } else if (tok[0] == "environment") {
             if (sc->has_env) { bad("a second environment statement"); break; }
             if (tok.size() < 2) { bad("environment needs an .hdr path"); break; }
@@ -511,6 +548,31 @@ int ff_scene_file_environment(const FfSceneFile* scene, const char** out_path, f
     if (out_path) *out_path = scene->env_path.c_str();
     if (out_intensity) *out_intensity = scene->env_intensity;
     if (out_rotation_deg) *out_rotation_deg = scene->env_rotation;
+    return 1;
+}
+
+int ff_scene_file_texture_count(const FfSceneFile* scene) { return scene ? (int)scene->textures.size() : 0; }
+
+int ff_scene_file_texture(const FfSceneFile* scene, int index, const char** out_name, const char** out_path, int* out_flags)
+{
+    ff::clear_error();
+    if (!scene || index < 0 || (size_t)index >= scene->textures.size()) return ff::fail(FF_ERR_INVALID_ARG, "ff_scene_file_texture: no texture statement %d", index);
+    const FfSceneFile::Texture& t = scene->textures[(size_t)index];
+    if (out_name) *out_name = t.name.c_str();
+    if (out_path) *out_path = t.path.c_str();
+    if (out_flags) *out_flags = t.flags;
+    return FF_OK;
+}
+
+int ff_scene_file_albedo_map(const FfSceneFile* scene, int geometry_index, int* out_texture, float* out_scale2, float* out_offset2)
+{
+    ff::clear_error();
+    if (!scene || geometry_index < 0 || (size_t)geometry_index >= scene->albedo_maps.size()) return 0;
+    const FfSceneFile::AlbedoMap& m = scene->albedo_maps[(size_t)geometry_index];
+    if (m.texture < 0) return 0;
+    if (out_texture) *out_texture = m.texture;
+    if (out_scale2) { out_scale2[0] = m.scale[0]; out_scale2[1] = m.scale[1]; }
+    if (out_offset2) { out_offset2[0] = m.offset[0]; out_offset2[1] = m.offset[1]; }
     return 1;
 }
 

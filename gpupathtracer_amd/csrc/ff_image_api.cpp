@@ -322,6 +322,9 @@ int ff_gbuffer(FfState* s, const FfCamera* camera, const FfRenderParams* params,
     r.tris = s->d_tris;
     r.num_geoms = s->num_geoms;
     r.num_tris = (long long)s->num_tris;
+    r.tex_bind = s->tex_bound > 0 ? s->d_tex_bind : nullptr;
+    r.tex_desc = s->d_tex_desc;
+    r.uvs = s->d_uvs;
     r.depth = depth;
     r.position = position;
     r.normal = normal;

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "../../include/firefly/ff_api.h"
+#include "ff_texture.h"
 
 namespace ff {
 
@@ -138,6 +139,7 @@ struct CompiledScene {
     std::vector<GeomRecord> geoms;
     std::vector<TriRecord> tris;   // leaf order
     std::vector<TriNormals> normals; // parallel to tris
+    std::vector<TriUVs> uvs;       // parallel to tris (ff_texture.h)
     std::vector<BvhNode> nodes;    // all meshes, each mesh's nodes contiguous in breadth-first order
     int max_depth = 0;             // deepest root-to-leaf path in inner nodes over all meshes
     uint64_t total_tris = 0;
@@ -159,7 +161,7 @@ BvhBuildParams default_bvh_params();
 // Build the object-space BVH of one mesh.  Appends inner nodes to `nodes` (breadth-first, root first) and the mesh's
 // triangles, in leaf order, to `tris`.  Returns the root inner-node index (into `nodes`) and the tree depth.
 int build_mesh_bvh(const FfTriangle* triangles, int count, const BvhBuildParams& params, std::vector<BvhNode>& nodes,
-                   std::vector<TriRecord>& tris, int* out_depth, std::vector<TriNormals>* normals = nullptr);
+                   std::vector<TriRecord>& tris, int* out_depth, std::vector<TriNormals>* normals = nullptr, std::vector<TriUVs>* uvs = nullptr);
 
 // Flatten host geometries into device records.  Returns an FfStatus.  build_bvh = false fills the geometry records only
 // (tri_first / tri_count assigned, bvh_root = -1, no triangle records, no nodes): the device builder's input.

@@ -174,6 +174,11 @@ struct NeeParams {
     float env_rotation;       // radians, in [0, 2 pi)
     float p_env;              // probability of choosing the environment for a light sample: 0, 1/2 or 1
     float p_area;             // 1 - p_env: the area lights' share
+    // Albedo textures (nee_path_kernel<..., TEX = 1> only; ff_texture.h): the binding of every record, the textures' descriptors and
+    // the triangles' UVs (parallel to KParams::tris).  (at the end: the kernels without TEX read everything above where it always was)
+    const TexBinding* tex_bind;
+    const TexDesc* tex_desc;
+    const TriUVs* uvs;
 };
 // key ^ this: the choice between the environment and the light table when both are there (first output, u24 < p_env: environment)
 constexpr unsigned kEnvKeyChoose = 0x3C6EF372u;
@@ -210,8 +215,8 @@ hipError_t launch_deinterleave(const void* src, void* dst, int width, int height
 hipError_t launch_unpack_strips(const void* src, unsigned char* rgb8, float* radiance, int width, int height, int strip_rows, int num_parts,
                                 hipStream_t stream);
 // One launch of the NEE path kernel (grid_blocks workgroups of kBlockThreads, persistent over np.items); env: the instantiation
-// with the environment light (np.env_*).
-hipError_t launch_nee(const NeeParams& np, int trace_mode, bool env, int grid_blocks, hipStream_t stream, const char** kernel_name);
+// with the environment light (np.env_*); tex: the one that multiplies bound albedo textures in (np.tex_*).
+hipError_t launch_nee(const NeeParams& np, int trace_mode, bool env, bool tex, int grid_blocks, hipStream_t stream, const char** kernel_name);
 hipError_t prepare_kernels(); // one-time function attributes (dynamic LDS limit)
 
 } // namespace ff

@@ -3300,7 +3300,10 @@ __device__ __forceinline__ float4 env_lookup(const NeeParams& np, float dx, floa
 }
 
 // ENV = 1: the environment is one more light of the MIS estimator (ff_api.h).  ENV = 0 compiles to the kernel without it.
-template <int MODE, int BIG = 0, int ENV = 0>
+// TEX = 1: a diffuse hit's albedo is m_albedo times the texel of the texture bound to its geometry (ff_texture.h), looked up at the
+// world hit point; FF_SHADE_DIFFUSE_PATH frames of a textured scene run here with no light table, as they do under an environment.
+// TEX = 0 compiles to the kernel without it.
+template <int MODE, int BIG = 0, int ENV = 0, int TEX = 0>
 __global__ __launch_bounds__(kBlockThreads) void nee_path_kernel(const NeeParams np)
 {
     const KParams& p = np.k;
@@ -3385,7 +3388,7 @@ __global__ __launch_bounds__(kBlockThreads) void nee_path_kernel(const NeeParams
                 const float4 emission = mat_f4(M, 13);
                 float cx = P.bx * emission.x, cy = P.by * emission.y, cz = P.bz * emission.z;
                 // (FF_SHADE_DIFFUSE_PATH under an environment runs here with no light table: weight 1)
-                const float area_pdf = (ENV && np.num_lights == 0) ? 0.f : np.light_pdf[best.geom];
+                const float area_pdf = ((ENV || TEX) && np.num_lights == 0) ? 0.f : np.light_pdf[best.geom];
                 if (prev_pdf > 0.f && area_pdf > 0.f) {
                     float nx, ny, nz;
                     world_normal(M, best, false, nx, ny, nz);
@@ -3404,7 +3407,16 @@ __global__ __launch_bounds__(kBlockThreads) void nee_path_kernel(const NeeParams
                 Lz = Lz + cz;
             } else {
                 const bool glass = bxdf == FF_BXDF_GLASS;
-                const float4 albedo = mat_f4(M, 12);
+                float4 albedo = mat_f4(M, 12);
+                if (TEX && bxdf == FF_BXDF_DIFFUSE) {
+                    float texel[3];
+                    if (tex_albedo(np.tex_bind, np.tex_desc, np.uvs, best.geom, best.rec, M.global->type, reinterpret_cast<const float*>(M.global),
+                                   reinterpret_cast<const float*>(p.tris), best.px, best.py, best.pz, texel)) {
+                        albedo.x = albedo.x * texel[0];
+                        albedo.y = albedo.y * texel[1];
+                        albedo.z = albedo.z * texel[2];
+                    }
+                }
                 if (!glass) {
                     P.bx = P.bx * albedo.x;
                     P.by = P.by * albedo.y;
@@ -3556,10 +3568,14 @@ __global__ __launch_bounds__(kBlockThreads) void nee_path_kernel(const NeeParams
 
 } // namespace
 
-#ifdef FF_PROBE
+#if defined(FF_PROBE) || defined(FF_PROBE_NEE)
 // Register-pressure probes (tools/diag/probe_kernel.sh): compile ONE instantiation to ISA in a few seconds.
 namespace {
+#ifdef FF_PROBE
 template __global__ void FF_PROBE(const KParams);
+#else
+template __global__ void FF_PROBE_NEE(const NeeParams); // (nee_path_kernel takes the frame's parameters plus the light tables)
+#endif
 }
 #else
 // (num_geoms: the records cached in LDS; 0 for scenes of more than 32 geometries, whose records stay in global memory)
@@ -3636,6 +3652,12 @@ hipError_t prepare_kernels()
     FF_SET_LDS((nee_path_kernel<FF_TRACE_BVH, 0, 1>))
     FF_SET_LDS((nee_path_kernel<FF_TRACE_BVH, 1, 1>))
     FF_SET_LDS((nee_path_kernel<FF_TRACE_BVH, 2, 1>))
+    FF_SET_LDS((nee_path_kernel<FF_TRACE_BVH, 0, 0, 1>))
+    FF_SET_LDS((nee_path_kernel<FF_TRACE_BVH, 1, 0, 1>))
+    FF_SET_LDS((nee_path_kernel<FF_TRACE_BVH, 2, 0, 1>))
+    FF_SET_LDS((nee_path_kernel<FF_TRACE_BVH, 0, 1, 1>))
+    FF_SET_LDS((nee_path_kernel<FF_TRACE_BVH, 1, 1, 1>))
+    FF_SET_LDS((nee_path_kernel<FF_TRACE_BVH, 2, 1, 1>))
 #undef FF_SET_LDS
     return hipSuccess;
 }
@@ -3765,7 +3787,7 @@ hipError_t launch_ray_batch(const RayBatchParams& p, int trace_mode, hipStream_t
     return hipGetLastError();
 }
 
-hipError_t launch_nee(const NeeParams& np, int trace_mode, bool env, int grid_blocks, hipStream_t stream, const char** kernel_name)
+hipError_t launch_nee(const NeeParams& np, int trace_mode, bool env, bool tex, int grid_blocks, hipStream_t stream, const char** kernel_name)
 {
     if (np.items == 0u) return hipSuccess;
     const KParams& p = np.k;
@@ -3774,7 +3796,23 @@ hipError_t launch_nee(const NeeParams& np, int trace_mode, bool env, int grid_bl
                                                   : (size_t)kBruteBatchTris * sizeof(TriRecord);
     const dim3 grid(grid_blocks), block(kBlockThreads);
     const char* name;
-    if (env) {
+    if (tex) {
+#define FF_LAUNCH_TEX(MODE, BIG, ENV) \
+    do { hipLaunchKernelGGL((nee_path_kernel<MODE, BIG, ENV, 1>), grid, block, lds, stream, np); name = "nee_path_kernel<" #MODE ", " #BIG ", " #ENV ", 1>"; } while (0)
+        if (env) {
+            if (trace_mode == FF_TRACE_BVH && big == 1) FF_LAUNCH_TEX(1, 1, 1);
+            else if (trace_mode == FF_TRACE_BVH && big == 2) FF_LAUNCH_TEX(1, 2, 1);
+            else if (trace_mode == FF_TRACE_BVH) FF_LAUNCH_TEX(1, 0, 1);
+            else FF_LAUNCH_TEX(0, 0, 1);
+        } else {
+            if (trace_mode == FF_TRACE_BVH && big == 1) FF_LAUNCH_TEX(1, 1, 0);
+            else if (trace_mode == FF_TRACE_BVH && big == 2) FF_LAUNCH_TEX(1, 2, 0);
+            else if (trace_mode == FF_TRACE_BVH) FF_LAUNCH_TEX(1, 0, 0);
+            else FF_LAUNCH_TEX(0, 0, 0);
+        }
+#undef FF_LAUNCH_TEX
+    }
+    else if (env) {
         if (trace_mode == FF_TRACE_BVH && big == 1) { hipLaunchKernelGGL((nee_path_kernel<FF_TRACE_BVH, 1, 1>), grid, block, lds, stream, np); name = "nee_path_kernel<1, 1, 1>"; }
         else if (trace_mode == FF_TRACE_BVH && big == 2) { hipLaunchKernelGGL((nee_path_kernel<FF_TRACE_BVH, 2, 1>), grid, block, lds, stream, np); name = "nee_path_kernel<1, 2, 1>"; }
         else if (trace_mode == FF_TRACE_BVH) { hipLaunchKernelGGL((nee_path_kernel<FF_TRACE_BVH, 0, 1>), grid, block, lds, stream, np); name = "nee_path_kernel<1, 0, 1>"; }

@@ -457,7 +457,7 @@ BvhBuildParams default_bvh_params()
 }
 
 int build_mesh_bvh(const FfTriangle* triangles, int count, const BvhBuildParams& params, std::vector<BvhNode>& nodes,
-                   std::vector<TriRecord>& tris, int* out_depth, std::vector<TriNormals>* normals)
+                   std::vector<TriRecord>& tris, int* out_depth, std::vector<TriNormals>* normals, std::vector<TriUVs>* uvs)
 {
     if (count <= 0) {
         if (out_depth) *out_depth = 0;
@@ -501,6 +501,10 @@ int build_mesh_bvh(const FfTriangle* triangles, int count, const BvhBuildParams&
             std::memcpy(nr.n1, &t.m_n1, 12);
             std::memcpy(nr.n2, &t.m_n2, 12);
             normals->push_back(nr);
+        }
+        if (uvs) {
+            const TriUVs ur = { { t.m_uv0.x, t.m_uv0.y, t.m_uv1.x, t.m_uv1.y, t.m_uv2.x, t.m_uv2.y } };
+            uvs->push_back(ur);
         }
     }
 
@@ -930,7 +934,7 @@ int compile_scene(const FfGeometry* geoms, int n, const BvhBuildParams& params, 
             r.tri_count = cnt;
             if (build_bvh) {
                 int depth = 0;
-                r.bvh_root = build_mesh_bvh(g.m_triangles, cnt, params, out.nodes, out.tris, &depth, &out.normals);
+                r.bvh_root = build_mesh_bvh(g.m_triangles, cnt, params, out.nodes, out.tris, &depth, &out.normals, &out.uvs);
                 out.max_depth = std::max(out.max_depth, depth);
             }
             out.total_tris += (uint64_t)cnt;

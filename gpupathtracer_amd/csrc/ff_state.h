@@ -11,6 +11,7 @@
 #include "ff_image.h"
 #include "ff_internal.h"
 #include "ff_kernels.h"
+#include "ff_texture.h"
 
 struct FfDistContext; // ff_dist.cpp
 
@@ -23,6 +24,7 @@ struct FfState {
     ff::GeomRecord* d_geoms = nullptr;
     ff::TriRecord* d_tris = nullptr;
     ff::TriNormals* d_normals = nullptr; // vertex normals, parallel to d_tris
+    ff::TriUVs* d_uvs = nullptr;         // vertex UVs, parallel to d_tris (read only where an albedo texture is bound)
     ff::BvhNode* d_nodes = nullptr;   // binary trees: what the builders write and refit works on
     ff::WallTable walls = {};          // the axis-aligned planes among the records every query screens (finalize_layout)
     int num_scan = 0;                  // big scenes: leading plane records kept out of the geometry tree (count_scan_planes)
@@ -146,6 +148,21 @@ struct FfState {
     size_t env_alias_bytes = 0;
     float* d_env_z = nullptr;          // ff::NeeParams::env_z
     size_t env_z_bytes = 0;
+    // Albedo textures (ff_texture.cpp).  Textures belong to the state (id = index into `textures`; d_texels null: a free id); bindings
+    // belong to the scene (one per CALLER geometry index; an upload drops them).  The device tables - one TexBinding per record in
+    // processing order, one TexDesc per id - are rewritten whenever either changes.  While tex_bound > 0, FF_SHADE_DIFFUSE_PATH and
+    // FF_SHADE_DIFFUSE_PATH_NEE frames run nee_path_kernel<..., TEX = 1> and ff_gbuffer's resolve reads the tables.
+    struct Texture {
+        float4* d_texels = nullptr;
+        int w = 0, h = 0, flags = 0;
+    };
+    std::vector<Texture> textures;
+    std::vector<ff::TexBinding> tex_bindings; // per caller geometry index (tex < 0: none)
+    int tex_bound = 0;                        // bindings in force
+    ff::TexBinding* d_tex_bind = nullptr;
+    size_t tex_bind_bytes = 0;
+    ff::TexDesc* d_tex_desc = nullptr;
+    size_t tex_desc_bytes = 0;
     // display transform (ff_display, ff_display.hip): the adapted exposure, the last call's results (ff_display_state) and the
     // device buffers - 256 histogram counters and the 255 sRGB thresholds in d_disp_const, the bloom pyramid ({rgb, 0} float4 per
     // texel, levels 1 .. n one after another) and the staging of host buffers in d_disp_work.  Not reset by uploads.
@@ -258,6 +275,10 @@ int nee_rebuild(FfState* s);
 int enqueue_nee(FfState* s, KParams& k, const FfRenderParams* prm, int launches, int blocks_per_launch, size_t local_pixels);
 // Environment light (ff_env.cpp): frees the state's device table (ff_destroy).
 void env_release(FfState* s);
+// Albedo textures (ff_texture.cpp): drop the scene's bindings (ff_upload_scene), rewrite the device tables, free everything (ff_destroy).
+void tex_drop_bindings(FfState* s);
+int tex_sync_tables(FfState* s);
+void tex_release(FfState* s);
 // Display transform (ff_display_api.cpp): frees the state's device buffers (ff_destroy).
 void display_release(FfState* s);
 // The pixel buffer registered with ff_register_gl_pbo, mapped on the state's stream (kernel.cu:338-339) and unmapped again

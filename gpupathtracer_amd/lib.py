@@ -34,6 +34,8 @@ EXPORTS = [
     "ff_set_environment", "ff_environment_table", "ff_load_hdr", "ff_free_hdr", "ff_scene_file_environment",
     "ff_display_params_init", "ff_display", "ff_display_to_pbo", "ff_display_reset", "ff_display_state",
     "ff_srgb_thresholds", "ff_display_curve", "ff_display_exposure", "ff_save_hdr",
+    "ff_texture_create", "ff_texture_destroy", "ff_set_albedo_texture", "ff_texture_sample", "ff_surface_uv",
+    "ff_load_ppm", "ff_free_ppm", "ff_rgb8_to_linear", "ff_scene_file_texture_count", "ff_scene_file_texture", "ff_scene_file_albedo_map",
 ]
 DIST_ID_BYTES = 128
 
@@ -189,6 +191,19 @@ def load():
     lib.ff_display_curve.argtypes = [P(T.FfDisplayParams), vp, i32, vp, vp]
     lib.ff_display_exposure.argtypes = [P(T.FfDisplayParams), vp, f32, P(f32), P(f32)]
     lib.ff_save_hdr.argtypes = [C.c_char_p, vp, i32, i32]
+    # albedo textures
+    lib.ff_texture_create.argtypes = [vp, vp, i32, i32, i32, P(i32)]
+    lib.ff_texture_destroy.argtypes = [vp, i32]
+    lib.ff_set_albedo_texture.argtypes = [vp, i32, i32, f32, f32, f32, f32]
+    lib.ff_texture_sample.argtypes = [vp, i32, i32, i32, vp, i32, vp]
+    lib.ff_surface_uv.argtypes = [P(T.FfGeometry), i32, i32, vp, vp, i32, vp]
+    lib.ff_load_ppm.argtypes = [C.c_char_p, P(P(C.c_ubyte)), P(i32), P(i32)]
+    lib.ff_free_ppm.argtypes = [P(C.c_ubyte)]
+    lib.ff_free_ppm.restype = None
+    lib.ff_rgb8_to_linear.argtypes = [vp, i32, i32, vp]
+    lib.ff_scene_file_texture_count.argtypes = [vp]
+    lib.ff_scene_file_texture.argtypes = [vp, i32, P(C.c_char_p), P(C.c_char_p), P(i32)]
+    lib.ff_scene_file_albedo_map.argtypes = [vp, i32, P(i32), P(f32), P(f32)]
     _lib = real
     return real
 
@@ -241,6 +256,24 @@ class SceneFile:
         if self._lib.ff_scene_file_environment(self._handle, C.byref(path), C.byref(inten), C.byref(rot)) == 0:
             return None
         return os.fsdecode(path.value), float(inten.value), float(rot.value)
+
+    def textures(self):
+        """The file's texture statements, in file order: a list of (name, resolved path, flags) with flags the T.TEX_* bits and
+        T.SCENE_TEX_SRGB for `srgb`."""
+        out = []
+        for i in range(self._lib.ff_scene_file_texture_count(self._handle)):
+            name, path, flags = C.c_char_p(), C.c_char_p(), C.c_int(0)
+            check(self._lib.ff_scene_file_texture(self._handle, i, C.byref(name), C.byref(path), C.byref(flags)))
+            out.append((name.value.decode(), os.fsdecode(path.value), int(flags.value)))
+        return out
+
+    def albedo_map(self, geometry_index):
+        """Geometry `geometry_index`'s albedo_map as (index of its texture statement, (scale u, v), (offset u, v)), or None."""
+        tex = C.c_int(-1)
+        scale, offset = (C.c_float * 2)(), (C.c_float * 2)()
+        if self._lib.ff_scene_file_albedo_map(self._handle, geometry_index, C.byref(tex), scale, offset) == 0:
+            return None
+        return int(tex.value), (float(scale[0]), float(scale[1])), (float(offset[0]), float(offset[1]))
 
     def camera(self, width, height):
         cam = T.FfCamera()
@@ -326,6 +359,63 @@ def save_hdr(path, rgb):
     if a.ndim != 3 or a.shape[2] != 3:
         raise ValueError("an image is [H, W, 3]")
     check(load().ff_save_hdr(os.fsencode(path), a.ctypes.data, a.shape[1], a.shape[0]))
+
+
+def _texture_image(rgb):
+    a = np.ascontiguousarray(rgb, dtype=np.float32)
+    if a.ndim != 3 or a.shape[2] != 3:
+        raise ValueError(f"a texture is an [H, W, 3] array (got shape {a.shape})")
+    return a
+
+
+def texture_sample(rgb, uv, flags=0):
+    """The texel lookup of the kernels on the host (ff_texture_sample): [H, W, 3] texels (row 0 the top), lookup coordinates
+    [..., 2], flags T.TEX_* -> float32 [..., 3]."""
+    a = _texture_image(rgb)
+    c = np.ascontiguousarray(uv, dtype=np.float32)
+    if c.shape[-1:] != (2,):
+        raise ValueError("coordinates are [..., 2]")
+    out = np.zeros(c.shape[:-1] + (3,), dtype=np.float32)
+    check(load().ff_texture_sample(a.ctypes.data, a.shape[1], a.shape[0], int(flags), c.ctypes.data, c.size // 2, out.ctypes.data))
+    return out
+
+
+def surface_uv(scene, geometry_index, world_points, triangle_indices=None):
+    """The surface coordinate (before scale and offset) the kernels compute for world points [..., 3] on one geometry of a host
+    scene (ff_surface_uv) -> float32 [..., 2].  triangle_indices [...]: each point's triangle, for a mesh."""
+    p = np.ascontiguousarray(world_points, dtype=np.float32)
+    if p.shape[-1:] != (3,):
+        raise ValueError("points are [..., 3]")
+    n = p.size // 3
+    tri = None
+    if triangle_indices is not None:
+        tri = np.ascontiguousarray(triangle_indices, dtype=np.int32)
+        if tri.size != n:
+            raise ValueError("one triangle index per point")
+    out = np.zeros(p.shape[:-1] + (2,), dtype=np.float32)
+    check(load().ff_surface_uv(scene.geometries, len(scene), int(geometry_index), tri.ctypes.data if tri is not None else None,
+                               p.ctypes.data, n, out.ctypes.data))
+    return out
+
+
+def load_ppm(path):
+    """An 8-bit P3 or P6 PPM (ff_load_ppm) -> uint8 [H, W, 3], top row first."""
+    lib = load()
+    ptr = C.POINTER(C.c_ubyte)()
+    w, h = C.c_int(0), C.c_int(0)
+    check(lib.ff_load_ppm(os.fsencode(path), C.byref(ptr), C.byref(w), C.byref(h)))
+    try:
+        return np.ctypeslib.as_array(ptr, shape=(h.value * w.value * 3,)).reshape(h.value, w.value, 3).copy()
+    finally:
+        lib.ff_free_ppm(ptr)
+
+
+def rgb8_to_linear(rgb8, srgb=True):
+    """Bytes of any shape -> float32 texels (ff_rgb8_to_linear): the sRGB EOTF of ff_display, or b / 255 with srgb=False."""
+    a = np.ascontiguousarray(rgb8, dtype=np.uint8)
+    out = np.zeros(a.shape, dtype=np.float32)
+    check(load().ff_rgb8_to_linear(a.ctypes.data, a.size, 1 if srgb else 0, out.ctypes.data))
+    return out
 
 
 def check_render_params(params):
@@ -468,6 +558,24 @@ class Tracer:
 
     def clear_environment(self):
         check(self._lib.ff_set_environment(self._state, None, 0, 0, 0.0, 0.0))
+
+    def create_texture(self, rgb, flags=0):
+        """Copy an [H, W, 3] float32 texture (linear RGB, row 0 the top) to the device (ff_texture_create) -> its id.  flags:
+        T.TEX_REPEAT or T.TEX_CLAMP, T.TEX_BILINEAR or T.TEX_NEAREST.  It stays until destroy_texture(), across scene uploads."""
+        a = _texture_image(rgb)
+        tid = C.c_int(-1)
+        check(self._lib.ff_texture_create(self._state, a.ctypes.data, a.shape[1], a.shape[0], int(flags), C.byref(tid)))
+        return tid.value
+
+    def destroy_texture(self, texture_id):
+        """ff_texture_destroy: frees the texture and unbinds it wherever it is bound."""
+        check(self._lib.ff_texture_destroy(self._state, int(texture_id)))
+
+    def set_albedo_texture(self, geometry_index, texture_id, scale=(1.0, 1.0), offset=(0.0, 0.0)):
+        """Bind a texture to a diffuse geometry's albedo (ff_set_albedo_texture): albedo = m_albedo * texel(uv * scale + offset);
+        texture_id -1 (or None) unbinds.  Bindings last until the next upload_scene."""
+        check(self._lib.ff_set_albedo_texture(self._state, int(geometry_index), -1 if texture_id is None else int(texture_id),
+                                              float(scale[0]), float(scale[1]), float(offset[0]), float(offset[1])))
 
     def set_builder(self, builder):
         """T.BUILD_HOST_SAH (default) or T.BUILD_GPU_LBVH for the following upload_scene calls."""

@@ -272,3 +272,22 @@ def open_floor_scene(area_light=False, wahoo=None):
     if area_light:
         s.add_plane((1.0, 0.5, 0.5), (90, 0, 0), (1.5, 1.5, 1.5), make_bxdf(T.BXDF_EMITTER, emissive=(1.0, 0.9, 0.8), intensity=4.0))
     return s.finalize()
+
+
+def checker_texture(width, height, cells=8, a=(0.9, 0.9, 0.9), b=(0.15, 0.15, 0.15)):
+    """A checkerboard albedo texture (float32 [H, W, 3], row 0 the top): `cells` squares across the width, colours a and b."""
+    y, x = np.mgrid[0:height, 0:width]
+    size = max(width // max(cells, 1), 1)
+    odd = (((x // size) + (y // size)) & 1).astype(bool)
+    return np.where(odd[..., None], np.asarray(b, np.float32), np.asarray(a, np.float32)).astype(np.float32)
+
+
+def gradient_texture(width, height, lo=(0.1, 0.2, 0.3), hi=(0.9, 0.8, 0.7)):
+    """A smooth, periodic albedo texture (float32 [H, W, 3]): each channel a raised cosine of the texel centre's (u, v), between
+    `lo` and `hi`, with a different phase per channel - no edges, so that bilinear lookups of nearby points differ little."""
+    u = (np.arange(width, dtype=np.float64) + 0.5) / width
+    v = (np.arange(height, dtype=np.float64) + 0.5) / height
+    uu, vv = np.meshgrid(u, v)
+    lo, hi = np.asarray(lo, np.float64), np.asarray(hi, np.float64)
+    w = np.stack([0.5 + 0.25 * np.cos(2 * np.pi * (uu + k / 3.0)) + 0.25 * np.cos(2 * np.pi * (vv - k / 5.0)) for k in range(3)], -1)
+    return (lo + (hi - lo) * w).astype(np.float32)

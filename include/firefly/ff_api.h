@@ -377,6 +377,64 @@ FF_API int ff_environment_table(const float* rgb, int width, int height, float* 
 FF_API int ff_load_hdr(const char* path, float** out_rgb, int* out_width, int* out_height);
 FF_API void ff_free_hdr(float* rgb);
 
+/* ---- albedo textures (no counterpart in the reference) ----------------------------------------- */
+
+/* A texture is W x H linear RGB texels, row 0 the top of the image, bound to the albedo of a FF_BXDF_DIFFUSE geometry: at a hit x
+ * of that geometry the surface's albedo is m_albedo * texel(c) per channel, in FF_SHADE_DIFFUSE_PATH, FF_SHADE_DIFFUSE_PATH_NEE
+ * and ff_gbuffer's albedo plane.  All arithmetic is float32, evaluated as parenthesised, no fused multiply-add;
+ * dot(a, b) = (a.x b.x + a.y b.y) + a.z b.z.
+ *   Surface coordinate uv of the WORLD hit point x (the G-buffer's position; never a function of the ray, so the integrator and
+ *   ff_gbuffer compute the same bits for the same hit):
+ *     object point  p_k = (I0_k x.x + I1_k x.y) + (I2_k x.z + I3_k), I0 .. I3 the columns of m_inverseModelMatrix
+ *     triangle      e1 = v1 - v0, e2 = v2 - v0, d = p - v0;  d00 = dot(e1, e1), d01 = dot(e1, e2), d11 = dot(e2, e2),
+ *                   d20 = dot(d, e1), d21 = dot(d, e2);  den = d00 d11 - d01 d01;  u = (d11 d20 - d01 d21) / den,
+ *                   v = (d00 d21 - d01 d20) / den;  uv = (uv0 + u (uv1 - uv0)) + v (uv2 - uv0) with the triangle's m_uv0 .. m_uv2
+ *     plane         uv = (p.x + 0.5, p.y + 0.5) of the unit quad
+ *     sphere        u = atan2f(p.x, -p.z) / 2 pi, plus 1 if negative;  v = 1 - acosf(clamp(p.y / |p|, -1, 1)) / pi
+ *                   (the environment map's orientation, +Y at the top row; host and device may differ by an ulp here)
+ *   Lookup coordinate  c = uv * scale + offset per component (ff_set_albedo_texture).
+ *   Sanitising    a coordinate that is NaN or +-Inf reads as 0.  FF_TEX_REPEAT then takes c - floor(c), in [0, 1] (exact for
+ *                 c >= 0: the lookup is periodic bit for bit), FF_TEX_CLAMP takes min(max(c, 0), 1).  Every texel index is therefore
+ *                 in range for any bit pattern of the coordinate.
+ *   Addressing    image row 0 is v = 1 (the OBJ convention).  FF_TEX_BILINEAR: s = c.u W - 0.5, t = (1 - c.v) H - 0.5,
+ *                 x0 = floor(s), fx = s - x0, y0 = floor(t), fy = t - y0; taps x0, x0 + 1 and y0, y0 + 1, under REPEAT moved by
+ *                 W (H) back into the image, under CLAMP clamped into it;  a = T(x0, y0), b = T(x0 + 1, y0), c = T(x0, y0 + 1),
+ *                 d = T(x0 + 1, y0 + 1):  top = a + fx (b - a), bot = c + fx (d - c), texel = top + fy (bot - top), so a texture of
+ *                 one constant value returns that value exactly.  FF_TEX_NEAREST: x = floor(c.u W), y = floor((1 - c.v) H); an index
+ *                 W (H) becomes 0 under REPEAT and W - 1 (H - 1) under CLAMP.
+ * Textures belong to the state: they stay through ff_upload_scene until ff_texture_destroy or ff_destroy.  Bindings belong to the
+ * scene: ff_upload_scene drops them; ff_update_transforms and ff_update_mesh keep them (after ff_update_mesh the new triangles' UVs
+ * are the ones sampled, in both modes and with every builder).  A binding whose geometry ff_update_transforms makes non-diffuse stays
+ * but is not applied.  While a binding exists, FF_SHADE_DIFFUSE_PATH and FF_SHADE_DIFFUSE_PATH_NEE frames run the NEE kernel (the plain
+ * path mode with no light sample: its estimator and random numbers are unchanged); a texture whose texels are all 1 leaves every
+ * frame and the G-buffer bit for bit as they are without it.  FF_SHADE_NORMAL_DEBUG ignores textures.  FF_SHADE_DIFFUSE_PATH_SMOOTH,
+ * ff_render_distributed, ff_multi_render* and a state whose scene came from ff_multi_upload_scene return FF_ERR_UNSUPPORTED while a
+ * binding exists (the environment light's precedent).  Emission, specular and normal maps and mip-mapping are not offered. */
+
+/* Copies a texture to the device: `rgb` is height rows of width RGB floats.  flags: FF_TEX_REPEAT or FF_TEX_CLAMP, FF_TEX_BILINEAR or
+ * FF_TEX_NEAREST.  *out_id receives its id (>= 0; ids of destroyed textures are reused).  FF_ERR_INVALID_ARG for a size below 1x1
+ * or above 2^26 texels, a negative or non-finite texel, an unknown flag (ff_set_environment's rules). */
+FF_API int ff_texture_create(FfState* state, const float* rgb, int width, int height, int flags, int* out_id);
+
+/* Frees texture `id` and unbinds it wherever it is bound. */
+FF_API int ff_texture_destroy(FfState* state, int id);
+
+/* Binds texture `texture_id` to the albedo of geometry `geometry_index` (the caller's index in the uploaded array) with the lookup
+ * coordinate uv * scale + offset; texture_id = -1 unbinds.  FF_ERR_NO_SCENE without a scene; FF_ERR_INVALID_ARG for an unknown
+ * geometry or texture or a non-finite scale or offset; FF_ERR_UNSUPPORTED for a geometry that is not FF_BXDF_DIFFUSE. */
+FF_API int ff_set_albedo_texture(FfState* state, int geometry_index, int texture_id, float scale_u, float scale_v, float offset_u,
+                                 float offset_v);
+
+/* Host-only twins (no GPU, no state), compiled from the same inline functions the kernels use. */
+/* The texel lookup for n coordinates `uv` (n pairs, taken as the lookup coordinate c) into out_rgb (n triples).
+ * FF_ERR_INVALID_ARG as ff_texture_create. */
+FF_API int ff_texture_sample(const float* rgb, int width, int height, int flags, const float* uv, int n, float* out_rgb);
+/* The surface coordinate uv of `count` world points (count triples) on geometry `geometry_index` of a host scene, before scale and
+ * offset; triangle_indices (count entries, the caller's triangle index of each point) is read for meshes only and may be NULL
+ * otherwise.  FF_ERR_INVALID_ARG for an unknown geometry or triangle index. */
+FF_API int ff_surface_uv(const FfGeometry* host_geometries, int n, int geometry_index, const int* triangle_indices,
+                         const float* world_points, int count, float* out_uv);
+
 /* ---- G-buffer and denoiser (no counterpart in the reference) ----------------------------- */
 
 /* What every pixel's primary ray (kernel.cu:197-205) hits: I = intersectRays (kernel.cu:127-176) for that ray, the FfIntersect
@@ -386,7 +444,7 @@ FF_API void ff_free_hdr(float* rgb);
  *   normal    W*H*3 floats  I.m_normal: the signed world normal NORMAL_DEBUG shades, in every shade mode (not the interpolated
  *                           normal of SMOOTH mode); not renormalised after the inverse-transpose      miss: 0
  *   albedo    W*H*3 floats  emitter m_emissiveColor * m_intensity, mirror m_specularColor, glass m_transmittanceColor,
- *                           anything else m_albedo                                   miss: 0
+ *                           anything else m_albedo, times the texel of a bound albedo texture (diffuse only)   miss: 0
  *   ids       W*H*3 int32   {I.geometryIndex (caller's order), I.triangleIndex (-1 for planes and spheres), bxdf type}
  *                                                                                    miss: {-1, -1, -1}
  * Only the camera, the scene, width, height and grid_mode matter (FF_GRID_REFERENCE_FLOOR: untraced pixels read as misses);
@@ -606,6 +664,17 @@ FF_API int ff_save_hdr(const char* path, const float* rgb, int width, int height
 /* saveToPPM (utilities.h:842-856) for the 8-bit framebuffer: P3 text, one "r g b" line per pixel, top row first. */
 FF_API int ff_save_ppm(const char* path, const unsigned char* rgb8, int width, int height);
 
+/* The reader twin of ff_save_ppm: a P3 (text) or P6 (binary) PPM with maxval 255, '#' comments in the header.  *out_rgb8 is malloc'ed
+ * (height rows of width RGB bytes, top row first); release with ff_free_ppm.  What ff_save_ppm wrote loads back to the same bytes.
+ * FF_ERR_IO for a file that cannot be opened or ends early, FF_ERR_INVALID_ARG for a malformed one, another maxval or a size
+ * outside 1 .. 2^26 pixels. */
+FF_API int ff_load_ppm(const char* path, unsigned char** out_rgb8, int* out_width, int* out_height);
+FF_API void ff_free_ppm(unsigned char* rgb8);
+
+/* n bytes to floats for a texture: srgb != 0: out = float(eotf(b / 255)) with ff_display's eotf (s / 12.92 for s <= 0.04045, else
+ * ((s + 0.055) / 1.055)^2.4), a 256-entry table computed in double; srgb == 0: out = float(b / 255.0). */
+FF_API int ff_rgb8_to_linear(const unsigned char* bytes, int n, int srgb, float* out_floats);
+
 /* ---- measurement -------------------------------------------------------------------------------- */
 
 /* Turn per-launch node/triangle visit counters on (1) or off (0, default).  Ray counting is always on. */
@@ -658,6 +727,10 @@ FF_API void ff_free_triangles(FfTriangle* triangles);
  *   sphere radius R [position X Y Z] [rotation X Y Z] [scale X Y Z] bxdf NAME
  *   environment FILE.hdr [intensity I] [rotation DEG]                       (at most one; path relative to the scene file;
  *                                                                             intensity 1 and rotation 0 by default)
+ *   texture NAME FILE.(hdr|ppm) [srgb] [clamp] [nearest]                    (path relative to the scene file; names are unique;
+ *                                                                             srgb: the .ppm's bytes are sRGB-encoded)
+ *   ... and on mesh, plane and sphere statements, before or after `bxdf NAME`:  [albedo_map NAME [scale U V] [offset U V]]
+ *                                                                            (a texture statement earlier in the file)
  *
  * Geometries keep file order (it is the reference's iteration order, kernel.cu:133).  The returned object owns the
  * triangles and BXDFs its FfGeometry array points to. */
@@ -670,6 +743,14 @@ FF_API void ff_scene_file_free(FfSceneFile* scene);
 /* The file's environment statement: 1 with the resolved path (owned by the scene), intensity and rotation in degrees; 0 if the
  * file has none (the outputs are left alone).  Loading the map and ff_set_environment are the caller's. */
 FF_API int ff_scene_file_environment(const FfSceneFile* scene, const char** out_path, float* out_intensity, float* out_rotation_deg);
+/* The file's texture statements: their number, and statement `index`: name and resolved path (owned by the scene) and flags
+ * (FF_TEX_* bits; bit 8, FF_SCENE_TEX_SRGB, for `srgb`).  Loading the image and ff_texture_create are the caller's. */
+#define FF_SCENE_TEX_SRGB 256
+FF_API int ff_scene_file_texture_count(const FfSceneFile* scene);
+FF_API int ff_scene_file_texture(const FfSceneFile* scene, int index, const char** out_name, const char** out_path, int* out_flags);
+/* The albedo_map of geometry `geometry_index`: 1 with the index of its texture statement, scale and offset (2 floats each; 1 1 and
+ * 0 0 by default); 0 if the geometry has none (the outputs are left alone).  ff_set_albedo_texture is the caller's. */
+FF_API int ff_scene_file_albedo_map(const FfSceneFile* scene, int geometry_index, int* out_texture, float* out_scale2, float* out_offset2);
 
 #ifdef __cplusplus
 } /* extern "C" */

@@ -299,6 +299,12 @@ typedef struct FfDisplayParams {
     int32_t bloom_levels;      /* 1..8 */
 } FfDisplayParams;             /* 64 bytes; every float must be finite */
 
+/* ff_texture_create: how a texture is addressed and filtered (the formulas are in ff_api.h).  0 = repeat, bilinear. */
+#define FF_TEX_REPEAT    0   /* coordinates wrap: c - floor(c) */
+#define FF_TEX_CLAMP     1   /* coordinates clamp to [0, 1] */
+#define FF_TEX_BILINEAR  0   /* the four nearest texels, interpolated */
+#define FF_TEX_NEAREST   2   /* the texel the coordinate falls in */
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif

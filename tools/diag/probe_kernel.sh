@@ -1,9 +1,11 @@
 #!/bin/bash
 # Register pressure of ONE trace-kernel instantiation in a few seconds (no GPU needed):
 #   tools/diag/probe_kernel.sh 'trace_pool_kernel<false, 1024, false>' [extra hipcc flags]
+#   tools/diag/probe_kernel.sh 'nee_path_kernel<1, 0, 0, 1>'   (the NEE kernel: MODE, BIG, ENV, TEX)
 # prints VGPRs / spills / scratch from -Rpass-analysis=kernel-resource-usage and leaves the ISA in /tmp/ff_probe.s
 K=${1:-trace_pool_kernel<false, 1024, false>}; shift
 cd "$(dirname "$0")/../../gpupathtracer_amd/csrc" || exit 1
+case "$K" in nee_path_kernel*) DEF=FF_PROBE_NEE ;; *) DEF=FF_PROBE ;; esac
 /opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt -fno-fast-math -fno-slp-vectorize \
-  --cuda-device-only -S -o /tmp/ff_probe.s ff_kernels.hip "-DFF_PROBE=$K" -Rpass-analysis=kernel-resource-usage "$@" 2>&1 |
+  --cuda-device-only -S -o /tmp/ff_probe.s ff_kernels.hip "-D$DEF=$K" -Rpass-analysis=kernel-resource-usage "$@" 2>&1 |
   grep -E "VGPRs:|ScratchSize|SGPRs Spill|VGPRs Spill|TotalSGPRs|error" | sed 's/.*remark: *//; s/ \[-Rpass.*//' | head -5 | tr "\n" ";"; echo
