@@ -459,6 +459,10 @@ int render_enqueue(FfState* s, const FfCamera* camera, const FfRenderParams* prm
     if (tex && prm->shade_mode == FF_SHADE_DIFFUSE_PATH_SMOOTH)
         return fail(FF_ERR_UNSUPPORTED, "FF_SHADE_DIFFUSE_PATH_SMOOTH does not render albedo textures (ff_set_albedo_texture); "
                     "unbind them or use FF_SHADE_DIFFUSE_PATH / FF_SHADE_DIFFUSE_PATH_NEE");
+    const bool glossy = s->glossy_applied > 0 && !debug; // (... and rough-specular bindings)
+    if (glossy && prm->shade_mode == FF_SHADE_DIFFUSE_PATH_SMOOTH)
+        return fail(FF_ERR_UNSUPPORTED, "FF_SHADE_DIFFUSE_PATH_SMOOTH does not render rough-specular mirrors (ff_set_roughness); "
+                    "unbind them or use FF_SHADE_DIFFUSE_PATH / FF_SHADE_DIFFUSE_PATH_NEE");
     const int spp = debug ? 1 : prm->spp;
     const int bounces = debug ? 1 : prm->bounces;
     // Samples are accumulated in blocks (a multiple of 64, at most 16 blocks per pixel up to 1024 spp and beyond): a
@@ -495,9 +499,9 @@ int render_enqueue(FfState* s, const FfCamera* camera, const FfRenderParams* prm
                         "upload with FF_BUILD_HOST_SAH or render with FF_TRACE_BRUTE_FORCE", s->max_depth4, s->max_depth4 + 1, s->num_geoms);
     }
     fill_scene(s, k, prm->shade_mode == FF_SHADE_DIFFUSE_PATH_SMOOTH, prm->trace_mode == FF_TRACE_BVH ? block_threads : 0);
-    if (prm->shade_mode == FF_SHADE_DIFFUSE_PATH_NEE || env || tex) {
+    if (prm->shade_mode == FF_SHADE_DIFFUSE_PATH_NEE || env || tex || glossy) {
         // (its own kernels: the rest of this function prepares the mega-kernels' frame; under an environment or with albedo textures
-        // bound, FF_SHADE_DIFFUSE_PATH runs there too, with no light table)
+        // or rough-specular mirrors bound, FF_SHADE_DIFFUSE_PATH runs there too, with no light table)
         k.rgb8 = rgb8_dev;
         k.radiance = radiance_dev;
         return enqueue_nee(s, k, prm, launches, blocks_per_launch, local_pixels);
@@ -984,6 +988,7 @@ int ff_destroy(FfState* s)
     if (s->d_nee_pdf) (void)hipFree(s->d_nee_pdf);
     env_release(s);
     tex_release(s);
+    glossy_release(s);
     display_release(s);
     free_build_scratch(s->scratch);
     if (s->d_blocksums) (void)hipFree(s->d_blocksums);
@@ -1181,6 +1186,7 @@ int ff_upload_scene(FfState* s, const FfGeometry* host_geometries, int n)
     const BvhBuildParams bp = default_bvh_params();
     s->nee_valid = false; // (the light table belongs to the scene that goes)
     tex_drop_bindings(s); // (and so do the albedo-texture bindings; the textures stay)
+    glossy_drop_bindings(s); // (and the roughness bindings)
     if (s->builder != FF_BUILD_HOST_SAH) {
         int st = upload_with_device_builder(s, host_geometries, n, bp);
         if (st == FF_OK) {
@@ -1306,6 +1312,7 @@ int upload_compiled_scene(FfState* s, const CompiledScene& cs, double build_ms)
     for (ReprojectionHistory& h : s->history) h.invalidate();
     s->nee_valid = false; // (no light table: FF_SHADE_DIFFUSE_PATH_NEE is not offered on a compiled upload)
     tex_drop_bindings(s);
+    glossy_drop_bindings(s);
     s->nee_geoms.clear();
     s->nee_tris.clear();
     s->build_stats = FfBuildStats();
@@ -1359,6 +1366,8 @@ int ff_update_transforms(FfState* s, const FfGeometry* host_geometries, int n)
     if (st != FF_OK) return st;
     s->has_specular = false; // materials may have changed
     for (const GeomRecord& g : cs.geoms) s->has_specular = s->has_specular || g.bxdf_type == FF_BXDF_MIRROR || g.bxdf_type == FF_BXDF_GLASS;
+    st = glossy_sync_table(s); // (a roughness binding is applied while its geometry is a mirror)
+    if (st != FF_OK) return st;
     if (!s->nee_geoms.empty() || s->nee_valid) { // (the light table follows the emitters' new transforms and materials)
         nee_capture(s, host_geometries, n, /*upload=*/false);
         st = nee_rebuild(s);

@@ -322,6 +322,8 @@ struct FfSceneFile {
     std::vector<Texture> textures;
     struct AlbedoMap { int texture; float scale[2], offset[2]; }; // per geometry (texture < 0: none)
     std::vector<AlbedoMap> albedo_maps;
+    std::vector<float> bxdf_roughness;             // parallel to bxdfs: a mirror's `roughness R` (0: none)
+    std::vector<float> roughness;                  // per geometry: its bxdf's
     ~FfSceneFile()
     {
         for (FfTriangle* t : meshes) std::free(t);
@@ -380,6 +382,9 @@ int ff_scene_file_load(const char* path, FfSceneFile** out_scene)
     auto bad = [&](const char* what) {
         status = ff::fail(FF_ERR_IO, "%s:%d: %s", path, lineno, what);
     };
+    auto bad_value = [&](const char* what) { // (well-formed, but a value the library's setter would refuse)
+        status = ff::fail(FF_ERR_INVALID_ARG, "%s:%d: %s", path, lineno, what);
+    };
     while (status == FF_OK && std::fgets(buf, sizeof buf, f)) {
         ++lineno;
         const std::vector<std::string> tok = split_ws(buf);
@@ -408,6 +413,7 @@ int ff_scene_file_load(const char* path, FfSceneFile** out_scene)
             else if (type == "glass") b->m_type = FF_BXDF_GLASS;
             else { delete b; bad("unknown bxdf type"); break; }
             sc->bxdfs.emplace_back(tok[1], b);
+            sc->bxdf_roughness.push_back(0.f);
             i = 3;
             while (status == FF_OK && i < tok.size()) {
                 const std::string key = tok[i++];
@@ -417,6 +423,13 @@ int ff_scene_file_load(const char* path, FfSceneFile** out_scene)
                 else if (key == "specular") { if (!read_floats(tok, i, 3, v)) bad("specular needs 3 numbers"); else b->m_specularColor = FfVec3{ v[0], v[1], v[2] }; }
                 else if (key == "transmittance") { if (!read_floats(tok, i, 3, v)) bad("transmittance needs 3 numbers"); else b->m_transmittanceColor = FfVec3{ v[0], v[1], v[2] }; }
                 else if (key == "ior") { if (!read_floats(tok, i, 1, v)) bad("ior needs a number"); else b->m_refractiveIndex = v[0]; }
+                else if (key == "roughness") {
+                    // (kept beside the layout-locked FfBXDF: ff_scene_file_roughness hands it out, ff_set_roughness applies it)
+                    if (!read_floats(tok, i, 1, v)) bad("roughness needs a number");
+                    else if (b->m_type != FF_BXDF_MIRROR) bad_value("roughness is a mirror's (rough glass and a glossy coat over diffuse are not offered)");
+                    else if (!std::isfinite(v[0]) || v[0] < 0.f || v[0] > 1.f) bad_value("roughness is a number in [0, 1]");
+                    else sc->bxdf_roughness.back() = v[0];
+                }
                 else if (key == "intensity") { if (!read_floats(tok, i, 1, v)) bad("intensity needs a number"); else b->m_intensity = v[0]; }
                 else bad("unknown bxdf key");
             }
@@ -437,6 +450,7 @@ int ff_scene_file_load(const char* path, FfSceneFile** out_scene)
             }
             FfVec3 pos{ 0, 0, 0 }, rot{ 0, 0, 0 }, scl{ 1, 1, 1 };
             FfBXDF* bx = nullptr;
+            float rough = 0.f;
             FfSceneFile::AlbedoMap amap = { -1, { 1.f, 1.f }, { 0.f, 0.f } };
             while (status == FF_OK && i < tok.size()) {
                 const std::string key = tok[i++];
@@ -447,7 +461,8 @@ int ff_scene_file_load(const char* path, FfSceneFile** out_scene)
                 else if (key == "radius" && is_sphere) { if (!read_floats(tok, i, 1, v) || !(v[0] > 0.f)) bad("radius needs a positive number"); else radius = v[0]; }
                 else if (key == "bxdf") {
                     if (i >= tok.size()) { bad("bxdf needs a name"); break; }
-                    for (auto& b : sc->bxdfs) if (b.first == tok[i]) bx = b.second;
+                    for (size_t k = 0; k < sc->bxdfs.size(); ++k)
+                        if (sc->bxdfs[k].first == tok[i]) { bx = sc->bxdfs[k].second; rough = sc->bxdf_roughness[k]; }
                     if (!bx) bad("bxdf name not defined above");
                     ++i;
                 } else if (key == "albedo_map") {
@@ -472,6 +487,7 @@ int ff_scene_file_load(const char* path, FfSceneFile** out_scene)
             g.m_bxdf = bx;
             sc->geometries.push_back(g);
             sc->albedo_maps.push_back(amap);
+            sc->roughness.push_back(rough);
         } else if (tok[0] == "texture") {
             if (tok.size() < 3) { bad("texture needs a name and an image path"); break; }
             bool dup = false;
@@ -562,6 +578,15 @@ int ff_scene_file_texture(const FfSceneFile* scene, int index, const char** out_
     if (out_path) *out_path = t.path.c_str();
     if (out_flags) *out_flags = t.flags;
     return FF_OK;
+}
+
+int ff_scene_file_roughness(const FfSceneFile* scene, int geometry_index, float* out_roughness)
+{
+    ff::clear_error();
+    if (!scene || geometry_index < 0 || (size_t)geometry_index >= scene->roughness.size()) return 0;
+    if (!(scene->roughness[(size_t)geometry_index] > 0.f)) return 0;
+    if (out_roughness) *out_roughness = scene->roughness[(size_t)geometry_index];
+    return 1;
 }
 
 int ff_scene_file_albedo_map(const FfSceneFile* scene, int geometry_index, int* out_texture, float* out_scale2, float* out_offset2)

@@ -179,6 +179,10 @@ struct NeeParams {
     const TexBinding* tex_bind;
     const TexDesc* tex_desc;
     const TriUVs* uvs;
+    // Rough-specular mirrors (nee_path_kernel<..., GLOSSY = 1> only; ff_glossy.h, ff_glossy.cpp): per record (processing order) the
+    // lobe width alpha = roughness^2 of an applied binding, 0 for every other record (unbound, not a mirror, or alpha < 1e-3: the
+    // perfect mirror).  (appended at the end: the kernels without GLOSSY read everything above where it always was)
+    const float* glossy_alpha;
 };
 // key ^ this: the choice between the environment and the light table when both are there (first output, u24 < p_env: environment)
 constexpr unsigned kEnvKeyChoose = 0x3C6EF372u;
@@ -215,8 +219,9 @@ hipError_t launch_deinterleave(const void* src, void* dst, int width, int height
 hipError_t launch_unpack_strips(const void* src, unsigned char* rgb8, float* radiance, int width, int height, int strip_rows, int num_parts,
                                 hipStream_t stream);
 // One launch of the NEE path kernel (grid_blocks workgroups of kBlockThreads, persistent over np.items); env: the instantiation
-// with the environment light (np.env_*); tex: the one that multiplies bound albedo textures in (np.tex_*).
-hipError_t launch_nee(const NeeParams& np, int trace_mode, bool env, bool tex, int grid_blocks, hipStream_t stream, const char** kernel_name);
+// with the environment light (np.env_*); tex: the one that multiplies bound albedo textures in (np.tex_*); glossy: the one that
+// shades mirrors with a positive np.glossy_alpha as GGX conductors.
+hipError_t launch_nee(const NeeParams& np, int trace_mode, bool env, bool tex, bool glossy, int grid_blocks, hipStream_t stream, const char** kernel_name);
 hipError_t prepare_kernels(); // one-time function attributes (dynamic LDS limit)
 
 } // namespace ff

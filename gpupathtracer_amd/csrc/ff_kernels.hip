@@ -112,6 +112,18 @@ __device__ __forceinline__ float ieee_sqrt(float x)
     return sqrtf(x);
 }
 
+} // namespace
+} // namespace ff
+
+// the rough-specular lobe (shared with the host twins), on the kernels' reciprocal and root
+#define FF_GLOSSY_HD __device__ __forceinline__
+#define FF_GLOSSY_RCP(x) ieee_rcp(x)
+#define FF_GLOSSY_SQRT(x) ieee_sqrt(x)
+#include "ff_glossy.h"
+
+namespace ff {
+namespace {
+
 
 // kernel.cu:138 — Ray(invM * vec4(o,1), normalize(invM * vec4(d,0))).  `len` is |invM*d| before normalisation: an
 // object-space parameter t corresponds to the world distance t * |d_world| / len.
@@ -3303,7 +3315,43 @@ __device__ __forceinline__ float4 env_lookup(const NeeParams& np, float dx, floa
 // TEX = 1: a diffuse hit's albedo is m_albedo times the texel of the texture bound to its geometry (ff_texture.h), looked up at the
 // world hit point; FF_SHADE_DIFFUSE_PATH frames of a textured scene run here with no light table, as they do under an environment.
 // TEX = 0 compiles to the kernel without it.
-template <int MODE, int BIG = 0, int ENV = 0, int TEX = 0>
+// GLOSSY = 1: a mirror whose record has a positive np.glossy_alpha is a GGX conductor (ff_glossy.h; the estimator is in ff_api.h):
+// a light sample weighted against the lobe's pdf, then a direction drawn from its visible normals.  The local frame is rebuilt from
+// the normal where it is needed; nothing of the lobe stays live across a query but prev_pdf and, for a sample whose direction fell
+// below the horizon while its shadow ray is still to be answered, `dead`.  GLOSSY = 0 compiles to the kernel without it.
+
+// The sample's radiance joins its block's sum and the lane goes on to the next sample or gives its item back (GLOSSY = 1: a sample
+// that ends behind its shadow ray; the loop's own ending is the same code).
+__device__ __forceinline__ bool nee_end_sample(const KParams& p, Path& P, float& Lx, float& Ly, float& Lz, float& prev_pdf)
+{
+    P.ax = P.ax + Lx;
+    P.ay = P.ay + Ly;
+    P.az = P.az + Lz;
+    Lx = Ly = Lz = 0.f;
+    prev_pdf = 0.f;
+    ++P.s;
+    if (P.s < P.send) {
+        start_sample(p, P);
+        return true;
+    }
+    p.blocksums[(size_t)((unsigned)P.item & kItemPixelMask) * p.num_blocks + ((unsigned)P.item >> kItemBlockShift)] = make_float4(P.ax, P.ay, P.az, 0.f);
+    return false;
+}
+
+// The Duff basis about the unit normal u (to_world_about's t and s) and a world direction's components in it.
+__device__ __forceinline__ void to_local_about(float ux, float uy, float uz, float wx, float wy, float wz, float& lx, float& ly, float& lz)
+{
+    const float sign = copysignf(1.0f, uz);
+    const float aa = -ieee_rcp(sign + uz);
+    const float bb = (ux * uy) * aa;
+    const float t0 = 1.0f + ((sign * ux) * ux) * aa, t1 = sign * bb, t2 = -sign * ux;
+    const float s0 = bb, s1 = sign + (uy * uy) * aa, s2 = -uy;
+    lx = dot3(t0, t1, t2, wx, wy, wz);
+    ly = dot3(s0, s1, s2, wx, wy, wz);
+    lz = dot3(ux, uy, uz, wx, wy, wz);
+}
+
+template <int MODE, int BIG = 0, int ENV = 0, int TEX = 0, int GLOSSY = 0>
 __global__ __launch_bounds__(kBlockThreads) void nee_path_kernel(const NeeParams np)
 {
     const KParams& p = np.k;
@@ -3327,6 +3375,7 @@ __global__ __launch_bounds__(kBlockThreads) void nee_path_kernel(const NeeParams
     Ray sray = { 0.f, 0.f, 0.f, 0.f, 0.f, 1.f };
     int sgeom = -1, sprim = -1;         // the sampled primitive: record index, caller's triangle index (-1: a plane)
     float scx = 0.f, scy = 0.f, scz = 0.f; // what the light sample adds if the shadow ray reaches it
+    bool dead = false;                  // GLOSSY: the sample ends once its pending shadow ray is answered
     for (;;) {
         while (!active && next < np.items) {
             const unsigned item = next;
@@ -3373,6 +3422,10 @@ __global__ __launch_bounds__(kBlockThreads) void nee_path_kernel(const NeeParams
                 Ly = Ly + scy;
                 Lz = Lz + scz;
             }
+            if (GLOSSY && dead) {
+                dead = false;
+                active = nee_end_sample(p, P, Lx, Ly, Lz, prev_pdf);
+            }
             continue;
         }
         const bool hit = best.geom >= 0;
@@ -3381,14 +3434,16 @@ __global__ __launch_bounds__(kBlockThreads) void nee_path_kernel(const NeeParams
         M.geom_base = 0;
         M.g = 0;
         bool goes_on = false;
+        float galpha = 0.f; // GLOSSY: the lobe width of a glossy hit, 0 at every other hit
         if (hit) {
             const int bxdf = mat_bxdf(M);
+            if (GLOSSY && bxdf == FF_BXDF_MIRROR) galpha = np.glossy_alpha[best.geom];
             if (bxdf == FF_BXDF_EMITTER) {
                 // BSDF-sampled emitter hit: weight 1 after the camera or a specular bounce and for emitters the table leaves out
                 const float4 emission = mat_f4(M, 13);
                 float cx = P.bx * emission.x, cy = P.by * emission.y, cz = P.bz * emission.z;
                 // (FF_SHADE_DIFFUSE_PATH under an environment runs here with no light table: weight 1)
-                const float area_pdf = ((ENV || TEX) && np.num_lights == 0) ? 0.f : np.light_pdf[best.geom];
+                const float area_pdf = ((ENV || TEX || GLOSSY) && np.num_lights == 0) ? 0.f : np.light_pdf[best.geom];
                 if (prev_pdf > 0.f && area_pdf > 0.f) {
                     float nx, ny, nz;
                     world_normal(M, best, false, nx, ny, nz);
@@ -3417,7 +3472,7 @@ __global__ __launch_bounds__(kBlockThreads) void nee_path_kernel(const NeeParams
                         albedo.z = albedo.z * texel[2];
                     }
                 }
-                if (!glass) {
+                if (!glass && !(GLOSSY && galpha > 0.f)) { // (a glossy hit's throughput takes F G2 / G1 at the scatter)
                     P.bx = P.bx * albedo.x;
                     P.by = P.by * albedo.y;
                     P.bz = P.bz * albedo.z;
@@ -3443,6 +3498,7 @@ __global__ __launch_bounds__(kBlockThreads) void nee_path_kernel(const NeeParams
         if (goes_on) {
             const int bxdf = mat_bxdf(M);
             const bool diffuse = bxdf != FF_BXDF_MIRROR && bxdf != FF_BXDF_GLASS;
+            const bool glossy = GLOSSY && galpha > 0.f;
             // the flipped unit shading normal scatter() uses
             float ux, uy, uz;
             {
@@ -3452,7 +3508,15 @@ __global__ __launch_bounds__(kBlockThreads) void nee_path_kernel(const NeeParams
                 ux = nx * ninv; uy = ny * ninv; uz = nz * ninv;
                 if (dot3(ux, uy, uz, P.ray.dx, P.ray.dy, P.ray.dz) > 0.0f) { ux = -ux; uy = -uy; uz = -uz; }
             }
-            if (diffuse && (np.num_lights > 0 || (ENV && np.p_env > 0.f))) {
+            // GLOSSY: wo = minus the ray direction in the local frame (z clamped), F0 = the record's tint (m_specularColor)
+            float gox = 0.f, goy = 0.f, goz = 1.f;
+            float4 f0 = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (glossy) {
+                to_local_about(ux, uy, uz, -P.ray.dx, -P.ray.dy, -P.ray.dz, gox, goy, goz);
+                goz = fmaxf(goz, kGlossyMinCos);
+                f0 = mat_f4(M, 12);
+            }
+            if ((diffuse || glossy) && (np.num_lights > 0 || (ENV && np.p_env > 0.f))) {
                 // light sample: primitive by the alias table, point uniform on it (keys in ff_api.h)
                 const unsigned gpix = (P.gxy >> 16) * (unsigned)p.width + (P.gxy & 0xFFFFu);
                 const unsigned ctr = ((unsigned)P.s << 8) | ((unsigned)P.b & 0xFFu);
@@ -3487,12 +3551,22 @@ __global__ __launch_bounds__(kBlockThreads) void nee_path_kernel(const NeeParams
                     const float cos_x = dot3(ux, uy, uz, wx, wy, wz);
                     const float pl = np.p_env * le.w;
                     if (cos_x > 0.f && pl > 0.f) {
-                        const float pb = cos_x * kInvPi;
                         const float pl2 = pl * pl;
-                        const float f = (pb * (pl2 / (pl2 + pb * pb))) / pl; // (cos_x / pi) * w_l / pdf_l
-                        scx = (P.bx * le.x) * f;
-                        scy = (P.by * le.y) * f;
-                        scz = (P.bz * le.z) * f;
+                        if (glossy) {
+                            float lx, ly, lz;
+                            to_local_about(ux, uy, uz, wx, wy, wz, lx, ly, lz);
+                            const GlossyLobe gl = glossy_eval(galpha, f0.x, f0.y, f0.z, gox, goy, goz, lx, ly, cos_x);
+                            const float f = (cos_x * (pl2 / (pl2 + gl.pdf * gl.pdf))) / pl; // cos_x * w_l / pdf_l
+                            scx = ((P.bx * le.x) * gl.fr) * f;
+                            scy = ((P.by * le.y) * gl.fg) * f;
+                            scz = ((P.bz * le.z) * gl.fb) * f;
+                        } else {
+                            const float pb = cos_x * kInvPi;
+                            const float f = (pb * (pl2 / (pl2 + pb * pb))) / pl; // (cos_x / pi) * w_l / pdf_l
+                            scx = (P.bx * le.x) * f;
+                            scy = (P.by * le.y) * f;
+                            scz = (P.bz * le.z) * f;
+                        }
                         sgeom = -1; // visible iff the shadow ray hits nothing
                         sprim = -1;
                         sray.ox = best.px + ux * kRayEps;
@@ -3527,12 +3601,22 @@ __global__ __launch_bounds__(kBlockThreads) void nee_path_kernel(const NeeParams
                         const float4 le = reinterpret_cast<const float4*>(p.geoms + g)[13];
                         float pl = ex.x * d2 / cos_y;
                         if (ENV) pl = pl * np.p_area;
-                        const float pb = cos_x * kInvPi;
                         const float pl2 = pl * pl;
-                        const float f = (pb * (pl2 / (pl2 + pb * pb))) / pl; // (cos_x / pi) * w_l / pdf_l
-                        scx = (P.bx * le.x) * f;
-                        scy = (P.by * le.y) * f;
-                        scz = (P.bz * le.z) * f;
+                        if (glossy) {
+                            float lx, ly, lz;
+                            to_local_about(ux, uy, uz, wx, wy, wz, lx, ly, lz);
+                            const GlossyLobe gl = glossy_eval(galpha, f0.x, f0.y, f0.z, gox, goy, goz, lx, ly, cos_x);
+                            const float f = (cos_x * (pl2 / (pl2 + gl.pdf * gl.pdf))) / pl; // cos_x * w_l / pdf_l
+                            scx = ((P.bx * le.x) * gl.fr) * f;
+                            scy = ((P.by * le.y) * gl.fg) * f;
+                            scz = ((P.bz * le.z) * gl.fb) * f;
+                        } else {
+                            const float pb = cos_x * kInvPi;
+                            const float f = (pb * (pl2 / (pl2 + pb * pb))) / pl; // (cos_x / pi) * w_l / pdf_l
+                            scx = (P.bx * le.x) * f;
+                            scy = (P.by * le.y) * f;
+                            scz = (P.bz * le.z) * f;
+                        }
                         sgeom = g;
                         sprim = prim;
                         sray.ox = best.px + ux * kRayEps;
@@ -3545,9 +3629,39 @@ __global__ __launch_bounds__(kBlockThreads) void nee_path_kernel(const NeeParams
                     }
                 }
             }
-            scatter<true>(p, best, M, P);
-            prev_pdf = diffuse ? dot3(ux, uy, uz, P.ray.dx, P.ray.dy, P.ray.dz) * kInvPi : 0.f;
-            continue;
+            if (glossy) {
+                // the numbers the diffuse scatter would have drawn at this vertex; the direction from the lobe's visible normals
+                const unsigned gpix = (P.gxy >> 16) * (unsigned)p.width + (P.gxy & 0xFFFFu);
+                unsigned r0, r1;
+                philox2x32_10(gpix, ((unsigned)P.s << 8) | ((unsigned)P.b & 0xFFu), p.key, r0, r1);
+                float lx, ly, lz;
+                const GlossyLobe gl = glossy_sample(galpha, f0.x, f0.y, f0.z, gox, goy, goz, r0 >> 8, nee_u24(r1), lx, ly, lz);
+                if (lz > 0.f) {
+                    P.bx = P.bx * gl.wr;
+                    P.by = P.by * gl.wg;
+                    P.bz = P.bz * gl.wb;
+                    float wox, woy, woz;
+                    to_world_about(ux, uy, uz, lx, ly, lz, wox, woy, woz);
+                    P.ray.ox = best.px + ux * kRayEps;
+                    P.ray.oy = best.py + uy * kRayEps;
+                    P.ray.oz = best.pz + uz * kRayEps;
+                    P.ray.dx = wox;
+                    P.ray.dy = woy;
+                    P.ray.dz = woz;
+                    ++P.b;
+                    prev_pdf = gl.pdf;
+                    continue;
+                }
+                // below the horizon: the sample ends at this vertex, behind its shadow ray if one is pending
+                if (shadow) {
+                    dead = true;
+                    continue;
+                }
+            } else {
+                scatter<true>(p, best, M, P);
+                prev_pdf = diffuse ? dot3(ux, uy, uz, P.ray.dx, P.ray.dy, P.ray.dz) * kInvPi : 0.f;
+                continue;
+            }
         }
         // the sample ends here: its radiance joins the block's sum
         P.ax = P.ax + Lx;
@@ -3658,6 +3772,18 @@ hipError_t prepare_kernels()
     FF_SET_LDS((nee_path_kernel<FF_TRACE_BVH, 0, 1, 1>))
     FF_SET_LDS((nee_path_kernel<FF_TRACE_BVH, 1, 1, 1>))
     FF_SET_LDS((nee_path_kernel<FF_TRACE_BVH, 2, 1, 1>))
+    FF_SET_LDS((nee_path_kernel<FF_TRACE_BVH, 0, 0, 0, 1>))
+    FF_SET_LDS((nee_path_kernel<FF_TRACE_BVH, 1, 0, 0, 1>))
+    FF_SET_LDS((nee_path_kernel<FF_TRACE_BVH, 2, 0, 0, 1>))
+    FF_SET_LDS((nee_path_kernel<FF_TRACE_BVH, 0, 0, 1, 1>))
+    FF_SET_LDS((nee_path_kernel<FF_TRACE_BVH, 1, 0, 1, 1>))
+    FF_SET_LDS((nee_path_kernel<FF_TRACE_BVH, 2, 0, 1, 1>))
+    FF_SET_LDS((nee_path_kernel<FF_TRACE_BVH, 0, 1, 0, 1>))
+    FF_SET_LDS((nee_path_kernel<FF_TRACE_BVH, 1, 1, 0, 1>))
+    FF_SET_LDS((nee_path_kernel<FF_TRACE_BVH, 2, 1, 0, 1>))
+    FF_SET_LDS((nee_path_kernel<FF_TRACE_BVH, 0, 1, 1, 1>))
+    FF_SET_LDS((nee_path_kernel<FF_TRACE_BVH, 1, 1, 1, 1>))
+    FF_SET_LDS((nee_path_kernel<FF_TRACE_BVH, 2, 1, 1, 1>))
 #undef FF_SET_LDS
     return hipSuccess;
 }
@@ -3787,7 +3913,7 @@ hipError_t launch_ray_batch(const RayBatchParams& p, int trace_mode, hipStream_t
     return hipGetLastError();
 }
 
-hipError_t launch_nee(const NeeParams& np, int trace_mode, bool env, bool tex, int grid_blocks, hipStream_t stream, const char** kernel_name)
+hipError_t launch_nee(const NeeParams& np, int trace_mode, bool env, bool tex, bool glossy, int grid_blocks, hipStream_t stream, const char** kernel_name)
 {
     if (np.items == 0u) return hipSuccess;
     const KParams& p = np.k;
@@ -3796,7 +3922,24 @@ hipError_t launch_nee(const NeeParams& np, int trace_mode, bool env, bool tex, i
                                                   : (size_t)kBruteBatchTris * sizeof(TriRecord);
     const dim3 grid(grid_blocks), block(kBlockThreads);
     const char* name;
-    if (tex) {
+    if (glossy) {
+#define FF_LAUNCH_GLOSSY(MODE, BIG, ENV, TEX) \
+    do { hipLaunchKernelGGL((nee_path_kernel<MODE, BIG, ENV, TEX, 1>), grid, block, lds, stream, np); name = "nee_path_kernel<" #MODE ", " #BIG ", " #ENV ", " #TEX ", 1>"; } while (0)
+#define FF_LAUNCH_GLOSSY_MODE(ENV, TEX) \
+    do { \
+        if (trace_mode == FF_TRACE_BVH && big == 1) FF_LAUNCH_GLOSSY(1, 1, ENV, TEX); \
+        else if (trace_mode == FF_TRACE_BVH && big == 2) FF_LAUNCH_GLOSSY(1, 2, ENV, TEX); \
+        else if (trace_mode == FF_TRACE_BVH) FF_LAUNCH_GLOSSY(1, 0, ENV, TEX); \
+        else FF_LAUNCH_GLOSSY(0, 0, ENV, TEX); \
+    } while (0)
+        if (env && tex) FF_LAUNCH_GLOSSY_MODE(1, 1);
+        else if (env) FF_LAUNCH_GLOSSY_MODE(1, 0);
+        else if (tex) FF_LAUNCH_GLOSSY_MODE(0, 1);
+        else FF_LAUNCH_GLOSSY_MODE(0, 0);
+#undef FF_LAUNCH_GLOSSY_MODE
+#undef FF_LAUNCH_GLOSSY
+    }
+    else if (tex) {
 #define FF_LAUNCH_TEX(MODE, BIG, ENV) \
     do { hipLaunchKernelGGL((nee_path_kernel<MODE, BIG, ENV, 1>), grid, block, lds, stream, np); name = "nee_path_kernel<" #MODE ", " #BIG ", " #ENV ", 1>"; } while (0)
         if (env) {

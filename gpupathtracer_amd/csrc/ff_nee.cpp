@@ -237,6 +237,8 @@ int enqueue_nee(FfState* s, KParams& k, const FfRenderParams* prm, int launches,
     if (!s->nee_valid) {
         if (s->tex_bound > 0 && prm->shade_mode != FF_SHADE_DIFFUSE_PATH_NEE && !s->env_set)
             return fail(FF_ERR_UNSUPPORTED, "albedo textures need a scene uploaded with ff_upload_scene (this one has no light table)");
+        if (s->glossy_applied > 0 && prm->shade_mode != FF_SHADE_DIFFUSE_PATH_NEE && !s->env_set)
+            return fail(FF_ERR_UNSUPPORTED, "rough-specular mirrors need a scene uploaded with ff_upload_scene (this one has no light table)");
         if (s->env_set)
             return fail(FF_ERR_UNSUPPORTED, "an environment light needs a scene uploaded with ff_upload_scene (this one has no light table)");
         return fail(FF_ERR_UNSUPPORTED, "FF_SHADE_DIFFUSE_PATH_NEE needs a scene uploaded with ff_upload_scene (this one has no light table)");
@@ -276,13 +278,16 @@ int enqueue_nee(FfState* s, KParams& k, const FfRenderParams* prm, int launches,
     np.light_pdf = s->d_nee_pdf;
     const bool env = s->env_set; // (render_enqueue sends FF_SHADE_NORMAL_DEBUG elsewhere)
     const bool tex = s->tex_bound > 0;
-    // FF_SHADE_DIFFUSE_PATH comes here under an environment or with albedo textures bound: it samples no light at all
+    const bool glossy = s->glossy_applied > 0;
+    // FF_SHADE_DIFFUSE_PATH comes here under an environment or with albedo textures or rough-specular mirrors bound: it samples no
+    // light at all
     if (prm->shade_mode != FF_SHADE_DIFFUSE_PATH_NEE) np.num_lights = 0;
     if (tex) {
         np.tex_bind = s->d_tex_bind;
         np.tex_desc = s->d_tex_desc;
         np.uvs = s->d_uvs;
     }
+    if (glossy) np.glossy_alpha = s->d_glossy_alpha;
     if (env) {
         // the environment as one more light (ff_api.h); without light samples p_env = 0
         np.env_texels = s->d_env_texels;
@@ -303,7 +308,7 @@ int enqueue_nee(FfState* s, KParams& k, const FfRenderParams* prm, int launches,
         k.total_items = k.pix_items * k.whole_blocks;
         np.k = k;
         np.items = k.total_items;
-        FF_HIP(launch_nee(np, prm->trace_mode, env, tex, grid, st, &s->last_kernel_name));
+        FF_HIP(launch_nee(np, prm->trace_mode, env, tex, glossy, grid, st, &s->last_kernel_name));
     }
     FF_HIP(launch_combine(k, st));
     FF_HIP(hipEventRecord(s->ev_end, st));

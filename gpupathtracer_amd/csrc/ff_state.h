@@ -163,6 +163,15 @@ struct FfState {
     size_t tex_bind_bytes = 0;
     ff::TexDesc* d_tex_desc = nullptr;
     size_t tex_desc_bytes = 0;
+    // Rough-specular mirrors (ff_glossy.cpp, ff_set_roughness).  Bindings belong to the scene (one roughness per CALLER geometry index,
+    // 0: none; an upload drops them).  A binding is APPLIED while its geometry's record is FF_BXDF_MIRROR; glossy_applied counts them.
+    // The device table - one alpha = roughness^2 per record in processing order, 0 where nothing is applied or alpha < 1e-3 - is
+    // rewritten whenever a binding or the records' materials change.  While glossy_applied > 0, FF_SHADE_DIFFUSE_PATH and
+    // FF_SHADE_DIFFUSE_PATH_NEE frames run nee_path_kernel<..., GLOSSY = 1>.
+    std::vector<float> glossy_roughness;
+    int glossy_applied = 0;
+    float* d_glossy_alpha = nullptr; // ff::NeeParams::glossy_alpha
+    size_t glossy_alpha_bytes = 0;
     // display transform (ff_display, ff_display.hip): the adapted exposure, the last call's results (ff_display_state) and the
     // device buffers - 256 histogram counters and the 255 sRGB thresholds in d_disp_const, the bloom pyramid ({rgb, 0} float4 per
     // texel, levels 1 .. n one after another) and the staging of host buffers in d_disp_work.  Not reset by uploads.
@@ -279,6 +288,11 @@ void env_release(FfState* s);
 void tex_drop_bindings(FfState* s);
 int tex_sync_tables(FfState* s);
 void tex_release(FfState* s);
+// Rough-specular mirrors (ff_glossy.cpp): drop the scene's bindings (ff_upload_scene), rewrite the device table from the bindings and
+// the records' materials (ff_set_roughness, ff_update_transforms), free it (ff_destroy).
+void glossy_drop_bindings(FfState* s);
+int glossy_sync_table(FfState* s);
+void glossy_release(FfState* s);
 // Display transform (ff_display_api.cpp): frees the state's device buffers (ff_destroy).
 void display_release(FfState* s);
 // The pixel buffer registered with ff_register_gl_pbo, mapped on the state's stream (kernel.cu:338-339) and unmapped again

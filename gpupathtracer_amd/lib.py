@@ -36,6 +36,7 @@ EXPORTS = [
     "ff_srgb_thresholds", "ff_display_curve", "ff_display_exposure", "ff_save_hdr",
     "ff_texture_create", "ff_texture_destroy", "ff_set_albedo_texture", "ff_texture_sample", "ff_surface_uv",
     "ff_load_ppm", "ff_free_ppm", "ff_rgb8_to_linear", "ff_scene_file_texture_count", "ff_scene_file_texture", "ff_scene_file_albedo_map",
+    "ff_set_roughness", "ff_glossy_eval", "ff_glossy_sample", "ff_scene_file_roughness",
 ]
 DIST_ID_BYTES = 128
 
@@ -204,6 +205,11 @@ def load():
     lib.ff_scene_file_texture_count.argtypes = [vp]
     lib.ff_scene_file_texture.argtypes = [vp, i32, P(C.c_char_p), P(C.c_char_p), P(i32)]
     lib.ff_scene_file_albedo_map.argtypes = [vp, i32, P(i32), P(f32), P(f32)]
+    # rough-specular mirrors
+    lib.ff_set_roughness.argtypes = [vp, i32, f32]
+    lib.ff_glossy_eval.argtypes = [f32, vp, vp, vp, i32, vp, vp]
+    lib.ff_glossy_sample.argtypes = [f32, vp, vp, vp, i32, vp, vp, vp]
+    lib.ff_scene_file_roughness.argtypes = [vp, i32, P(f32)]
     _lib = real
     return real
 
@@ -274,6 +280,13 @@ class SceneFile:
         if self._lib.ff_scene_file_albedo_map(self._handle, geometry_index, C.byref(tex), scale, offset) == 0:
             return None
         return int(tex.value), (float(scale[0]), float(scale[1])), (float(offset[0]), float(offset[1]))
+
+    def roughness(self, geometry_index):
+        """The `roughness` of geometry `geometry_index`'s mirror bxdf (ff_scene_file_roughness), or None."""
+        r = C.c_float(0.0)
+        if self._lib.ff_scene_file_roughness(self._handle, geometry_index, C.byref(r)) == 0:
+            return None
+        return float(r.value)
 
     def camera(self, width, height):
         cam = T.FfCamera()
@@ -396,6 +409,42 @@ def surface_uv(scene, geometry_index, world_points, triangle_indices=None):
     check(load().ff_surface_uv(scene.geometries, len(scene), int(geometry_index), tri.ctypes.data if tri is not None else None,
                                p.ctypes.data, n, out.ctypes.data))
     return out
+
+
+def _directions(a, name):
+    d = np.ascontiguousarray(a, dtype=np.float32)
+    if d.shape[-1:] != (3,):
+        raise ValueError(f"{name} is [..., 3]")
+    return d
+
+
+def glossy_eval(alpha, f0, wo, wi):
+    """The rough-specular lobe of the kernels on the host (ff_glossy_eval): unit local-frame directions wo, wi [..., 3] (z the normal)
+    -> (f float32 [..., 3], the BRDF not times cosine; pdf float32 [...], the solid-angle pdf of wi under the sampler)."""
+    o, i = _directions(wo, "wo"), _directions(wi, "wi")
+    if o.shape != i.shape:
+        raise ValueError("wo and wi have the same shape")
+    f0 = np.ascontiguousarray(f0, dtype=np.float32).reshape(3)
+    f = np.zeros(o.shape, dtype=np.float32)
+    pdf = np.zeros(o.shape[:-1], dtype=np.float32)
+    check(load().ff_glossy_eval(float(alpha), f0.ctypes.data, o.ctypes.data, i.ctypes.data, o.size // 3, f.ctypes.data, pdf.ctypes.data))
+    return f, pdf
+
+
+def glossy_sample(alpha, f0, wo, u):
+    """The lobe's sampler on the host (ff_glossy_sample): wo [..., 3], u [..., 2] in [0, 1)^2 -> (wi float32 [..., 3], weight float32
+    [..., 3] = F G2 / G1, pdf float32 [...]); weight and pdf are 0 for a wi at or below the horizon."""
+    o = _directions(wo, "wo")
+    uu = np.ascontiguousarray(u, dtype=np.float32)
+    if uu.shape != o.shape[:-1] + (2,):
+        raise ValueError("u is [..., 2], one pair per direction")
+    f0 = np.ascontiguousarray(f0, dtype=np.float32).reshape(3)
+    wi = np.zeros(o.shape, dtype=np.float32)
+    weight = np.zeros(o.shape, dtype=np.float32)
+    pdf = np.zeros(o.shape[:-1], dtype=np.float32)
+    check(load().ff_glossy_sample(float(alpha), f0.ctypes.data, o.ctypes.data, uu.ctypes.data, o.size // 3, wi.ctypes.data, weight.ctypes.data,
+                                  pdf.ctypes.data))
+    return wi, weight, pdf
 
 
 def load_ppm(path):
@@ -576,6 +625,19 @@ class Tracer:
         texture_id -1 (or None) unbinds.  Bindings last until the next upload_scene."""
         check(self._lib.ff_set_albedo_texture(self._state, int(geometry_index), -1 if texture_id is None else int(texture_id),
                                               float(scale[0]), float(scale[1]), float(offset[0]), float(offset[1])))
+
+    def set_roughness(self, geometry_index, roughness):
+        """Make a mirror geometry a rough (GGX) conductor of this roughness in [0, 1], F0 = its m_specularColor (ff_set_roughness);
+        0 (or None) unbinds.  Bindings last until the next upload_scene."""
+        check(self._lib.ff_set_roughness(self._state, int(geometry_index), 0.0 if roughness is None else float(roughness)))
+
+    def apply_scene_file_materials(self, scene_file):
+        """After upload_scene(scene_file): bind every `roughness` of the file's mirror bxdfs (the file's albedo_maps need their images
+        loaded and created first: textures(), albedo_map(), create_texture(), set_albedo_texture())."""
+        for g in range(len(scene_file)):
+            r = scene_file.roughness(g)
+            if r is not None:
+                self.set_roughness(g, r)
 
     def set_builder(self, builder):
         """T.BUILD_HOST_SAH (default) or T.BUILD_GPU_LBVH for the following upload_scene calls."""

@@ -214,6 +214,7 @@ ENV_MAX_TEXELS = 1 << 26  # largest environment map ff_set_environment takes (wi
 TEX_REPEAT, TEX_CLAMP, TEX_BILINEAR, TEX_NEAREST = 0, 1, 0, 2  # ff_texture_create flags (FF_TEX_*)
 TEX_MAX_TEXELS = 1 << 26  # largest texture ff_texture_create takes (width x height)
 SCENE_TEX_SRGB = 256  # ff_scene_file_texture: the statement says `srgb`
+GLOSSY_MIN_ALPHA = 1.0e-3  # ff_set_roughness: a binding whose alpha = roughness^2 is below it shades as the perfect mirror
 
 # status codes (ff_api.h)
 FF_OK, FF_ERR_INVALID_ARG, FF_ERR_NO_DEVICE, FF_ERR_HIP, FF_ERR_NO_SCENE, FF_ERR_UNSUPPORTED, FF_ERR_GL_UNAVAILABLE, FF_ERR_IO, FF_ERR_OOM, FF_ERR_COMM = range(10)

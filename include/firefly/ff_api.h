@@ -435,6 +435,65 @@ FF_API int ff_texture_sample(const float* rgb, int width, int height, int flags,
 FF_API int ff_surface_uv(const FfGeometry* host_geometries, int n, int geometry_index, const int* triangle_indices,
                          const float* world_points, int count, float* out_uv);
 
+/* ---- rough-specular mirrors (no counterpart in the reference) ----------------------------------- */
+
+/* A roughness bound to a FF_BXDF_MIRROR geometry turns the perfect mirror into a microfacet conductor: GGX normal distribution,
+ * height-correlated Smith masking, Schlick Fresnel with F0 = m_specularColor.  alpha = roughness * roughness (float).  A binding with
+ * alpha < 1e-3 shades as the perfect mirror (the delta branch, no light sample, pdf_b = 0).  FF_SHADE_DIFFUSE_PATH and
+ * FF_SHADE_DIFFUSE_PATH_NEE render it.  All arithmetic is float32, evaluated as parenthesised, no fused multiply-add; a quotient is
+ * a * (1 / b) with a correctly rounded reciprocal, roots are correctly rounded; dot(a, b) = (a.x b.x + a.y b.y) + a.z b.z.
+ *   Frame      the Duff basis (t, s, n^) scatter builds about the unit geometric normal n^ flipped against the incoming ray; a world
+ *              direction w has the local components (dot(t, w), dot(s, w), dot(n^, w)).  wo = minus the ray direction, wo.z clamped
+ *              to >= 1e-6; wi = the direction towards the light.  Every w.z in a quotient is clamped to >= 1e-6.
+ *   Lobe       h = unit(wo + wi);  D(h) = alpha^2 / (pi q^2), q = alpha^2 h.z^2 + (h.x^2 + h.y^2)
+ *              Lambda(w) = (sqrt(1 + alpha^2 (w.x^2 + w.y^2) / w.z^2) - 1) / 2;  G1(w) = 1 / (1 + Lambda(w));
+ *              G2(wo, wi) = 1 / (1 + Lambda(wo) + Lambda(wi));  F(c) = F0 + (1 - F0) m^5 per channel, m = 1 - c, c = max(dot(wo, h), 0),
+ *              m^5 = (m2 m2) m with m2 = m m
+ *              f(wo, wi) = F D G2 / (4 wo.z wi.z) (0 for wi.z <= 0);  pdf_b(wi) = G1(wo) D(h) / (4 wo.z)
+ *              weight = f wi.z / pdf_b = F G2 / G1 = F (1 + Lambda(wo)) / ((1 + Lambda(wo)) + Lambda(wi)), computed in that form
+ *   Sampling   visible normals by spherical caps (Dupuy and Benyoub 2023), from the numbers the diffuse scatter would have drawn at
+ *              this vertex: (r0, r1) = Philox(gpix, s << 8 | b, key), k = r0 >> 8, u1 = k / 2^24, u2 = (r1 >> 8) / 2^24
+ *              v = unit(alpha wo.x, alpha wo.y, wo.z);  z = (1 - u2)(1 + v.z) - v.z;  r = sqrt(max(0, 1 - z^2))
+ *              c = (r cos(2 pi u1), r sin(2 pi u1), z) (sine and cosine: the diffuse bounce's fixed-order polynomials on the octant
+ *              taken exactly off k);  h' = c + v;  h = unit(alpha h'.x, alpha h'.y, max(h'.z, 0));  wi = 2 dot(wo, h) h - wo
+ *              The sample's weight and pdf_b are the lobe's expressions at (wo, wi), h recomputed from them.
+ *   At a glossy hit x of segment b (a mirror with an applied binding and alpha >= 1e-3; beta is NOT multiplied at the hit):
+ *     if b < bounces - 1, in FF_SHADE_DIFFUSE_PATH_NEE, with a non-empty light table or a sampled environment: one light sample, with
+ *       the streams, the choice between environment and table, the point, w, pdf_l, the shadow ray and the visibility rule of the
+ *       blocks above.  With wi = w in the local frame and cos_x = wi.z = dot(n^, w): if cos_x > 0 (and cos_y > 0 for the table)
+ *         pb = pdf_b(wi),  w_l = pdf_l^2 / (pdf_l^2 + pb^2),  L += beta Le f(wo, wi) cos_x w_l / pdf_l
+ *     then the scatter: wi by the sampler.  wi.z <= 0: the sample ends at this vertex (after its shadow ray, if one is pending); its
+ *       radiance so far joins the sum, as for a last segment.  Else beta *= F G2 / G1, the new ray starts at x + 1e-4 n^ along wi,
+ *       and pdf_b(wi) is the pdf a BSDF-sampled emitter hit or environment miss of the next segment is weighted with, exactly as
+ *       after a diffuse bounce: w_b = pdf_b^2 / (pdf_b^2 + pdf_l^2).
+ *     In FF_SHADE_DIFFUSE_PATH, and on the last segment, there is no light sample and w_b = 1.
+ * ff_set_roughness binds; roughness = 0 unbinds.  Bindings belong to the scene: ff_upload_scene drops them; ff_update_transforms
+ * and ff_update_mesh keep them.  A binding whose geometry ff_update_transforms makes non-mirror stays but is not applied.  While an
+ * applied binding exists, FF_SHADE_DIFFUSE_PATH and FF_SHADE_DIFFUSE_PATH_NEE frames run the NEE kernel (the plain path mode with no
+ * light sample: its random numbers at non-glossy vertices are unchanged); without one, every frame launches exactly the kernels it
+ * launched before.  Results do not depend on the lane, spp_per_launch, tile, strip or trace mode.  FF_SHADE_NORMAL_DEBUG ignores
+ * bindings.  FF_SHADE_DIFFUSE_PATH_SMOOTH, ff_render_distributed, ff_multi_render* and a state whose scene came from
+ * ff_multi_upload_scene return FF_ERR_UNSUPPORTED while an applied binding exists (the environment's and the textures' precedent).
+ * ff_gbuffer is unchanged (its albedo plane holds m_specularColor for mirrors) and the denoisers go on treating the pixel as not
+ * filterable.  Not offered: rough glass, anisotropy, multiple-scattering energy compensation, roughness textures, a glossy coat over
+ * diffuse, smooth-normal shading of the lobe, glossy frames on the multi-GPU entry points (there is no ff_multi_set_roughness). */
+
+/* Binds `roughness` in [0, 1] to geometry `geometry_index` (the caller's index in the uploaded array); 0 unbinds.  FF_ERR_NO_SCENE
+ * without a scene; FF_ERR_INVALID_ARG for an unknown geometry or a roughness that is not finite or outside [0, 1];
+ * FF_ERR_UNSUPPORTED for a geometry whose bxdf is not FF_BXDF_MIRROR. */
+FF_API int ff_set_roughness(FfState* state, int geometry_index, float roughness);
+
+/* Host-only twins (no GPU, no state), compiled from the same inline functions the kernel uses.  alpha in (0, 1]; directions are
+ * unit vectors in the local frame (z the normal; wo.z is clamped to >= 1e-6 as in the kernel). */
+/* The lobe for n pairs (wo, wi): out_f_rgb (n triples) = f(wo, wi), the BRDF not times cosine; out_pdf (n) = pdf_b(wi) per steradian.
+ * Both 0 for wi.z <= 0. */
+FF_API int ff_glossy_eval(float alpha, const float* f0_rgb, const float* wo, const float* wi, int n, float* out_f_rgb, float* out_pdf);
+/* The sampler for n directions wo and n pairs u = (u1, u2) in [0, 1)^2 (u1 is used as floor(u1 2^24), the kernel's integer):
+ * out_wi (n triples), out_weight_rgb (n triples) = F G2 / G1, out_pdf (n) = pdf_b(wi).  For a wi at or below the horizon the
+ * weight and the pdf are 0. */
+FF_API int ff_glossy_sample(float alpha, const float* f0_rgb, const float* wo, const float* u, int n, float* out_wi, float* out_weight_rgb,
+                            float* out_pdf);
+
 /* ---- G-buffer and denoiser (no counterpart in the reference) ----------------------------- */
 
 /* What every pixel's primary ray (kernel.cu:197-205) hits: I = intersectRays (kernel.cu:127-176) for that ray, the FfIntersect
@@ -722,6 +781,8 @@ FF_API void ff_free_triangles(FfTriangle* triangles);
  *
  *   camera position X Y Z yaw DEG pitch DEG fov DEG near N far F            (every key optional: kernel.cu:312-321 defaults)
  *   bxdf NAME diffuse|emitter|mirror|glass [albedo R G B] [specular R G B] [transmittance R G B] [ior N] [color R G B] [intensity I]
+ *                                            [roughness R]                  (mirror only, R in [0, 1]; anything else is
+ *                                                                             FF_ERR_INVALID_ARG naming the line)
  *   mesh FILE.obj [position X Y Z] [rotation X Y Z] [scale X Y Z] bxdf NAME (path relative to the scene file)
  *   plane [position X Y Z] [rotation X Y Z] [scale X Y Z] bxdf NAME
  *   sphere radius R [position X Y Z] [rotation X Y Z] [scale X Y Z] bxdf NAME
@@ -751,6 +812,9 @@ FF_API int ff_scene_file_texture(const FfSceneFile* scene, int index, const char
 /* The albedo_map of geometry `geometry_index`: 1 with the index of its texture statement, scale and offset (2 floats each; 1 1 and
  * 0 0 by default); 0 if the geometry has none (the outputs are left alone).  ff_set_albedo_texture is the caller's. */
 FF_API int ff_scene_file_albedo_map(const FfSceneFile* scene, int geometry_index, int* out_texture, float* out_scale2, float* out_offset2);
+/* The `roughness` of geometry `geometry_index`'s bxdf: 1 with the value; 0 if it has none (or 0: the output is left alone).
+ * ff_set_roughness is the caller's. */
+FF_API int ff_scene_file_roughness(const FfSceneFile* scene, int geometry_index, float* out_roughness);
 
 #ifdef __cplusplus
 } /* extern "C" */
