@@ -463,6 +463,10 @@ int render_enqueue(FfState* s, const FfCamera* camera, const FfRenderParams* prm
     if (glossy && prm->shade_mode == FF_SHADE_DIFFUSE_PATH_SMOOTH)
         return fail(FF_ERR_UNSUPPORTED, "FF_SHADE_DIFFUSE_PATH_SMOOTH does not render rough-specular mirrors (ff_set_roughness); "
                     "unbind them or use FF_SHADE_DIFFUSE_PATH / FF_SHADE_DIFFUSE_PATH_NEE");
+    const bool cam = s->cam_active() && !debug; // (... and per-sample camera rays)
+    if (cam && prm->shade_mode == FF_SHADE_DIFFUSE_PATH_SMOOTH)
+        return fail(FF_ERR_UNSUPPORTED, "FF_SHADE_DIFFUSE_PATH_SMOOTH does not render per-sample camera rays (ff_set_camera_sampling); "
+                    "clear the setting or use FF_SHADE_DIFFUSE_PATH / FF_SHADE_DIFFUSE_PATH_NEE");
     const int spp = debug ? 1 : prm->spp;
     const int bounces = debug ? 1 : prm->bounces;
     // Samples are accumulated in blocks (a multiple of 64, at most 16 blocks per pixel up to 1024 spp and beyond): a
@@ -499,12 +503,21 @@ int render_enqueue(FfState* s, const FfCamera* camera, const FfRenderParams* prm
                         "upload with FF_BUILD_HOST_SAH or render with FF_TRACE_BRUTE_FORCE", s->max_depth4, s->max_depth4 + 1, s->num_geoms);
     }
     fill_scene(s, k, prm->shade_mode == FF_SHADE_DIFFUSE_PATH_SMOOTH, prm->trace_mode == FF_TRACE_BVH ? block_threads : 0);
-    if (prm->shade_mode == FF_SHADE_DIFFUSE_PATH_NEE || env || tex || glossy) {
-        // (its own kernels: the rest of this function prepares the mega-kernels' frame; under an environment or with albedo textures
-        // or rough-specular mirrors bound, FF_SHADE_DIFFUSE_PATH runs there too, with no light table)
+    if (prm->shade_mode == FF_SHADE_DIFFUSE_PATH_NEE || env || tex || glossy || cam) {
+        // (its own kernels: the rest of this function prepares the mega-kernels' frame; under an environment, with albedo textures
+        // or rough-specular mirrors bound or with per-sample camera rays, FF_SHADE_DIFFUSE_PATH runs there too, with no light table)
         k.rgb8 = rgb8_dev;
         k.radiance = radiance_dev;
-        return enqueue_nee(s, k, prm, launches, blocks_per_launch, local_pixels);
+        if (cam && s->cam_sampling.pixel_filter == FF_PIXEL_BOX) {
+            // the sample's own point of the pixel replaces the state's jitter: the unjittered matrix
+            FfMat4 cm;
+            ff_camera_ray_matrix(camera, &cm);
+            std::memcpy(k.cam_c0, &cm.m[0], 16);
+            std::memcpy(k.cam_c1, &cm.m[4], 16);
+            std::memcpy(k.cam_c2, &cm.m[8], 16);
+            std::memcpy(k.cam_c3, &cm.m[12], 16);
+        }
+        return enqueue_nee(s, k, camera, prm, launches, blocks_per_launch, local_pixels);
     }
     k.emitter_mask = 0u;
     k.cut_last = 0;

@@ -404,6 +404,8 @@ int ff_render_distributed(FfState* s, const FfCamera* camera, const FfRenderPara
         local = fail(FF_ERR_UNSUPPORTED, "ff_render_distributed: frames with albedo textures render on one device only");
     if (local == FF_OK && s->glossy_applied > 0 && params->shade_mode != FF_SHADE_NORMAL_DEBUG)
         local = fail(FF_ERR_UNSUPPORTED, "ff_render_distributed: frames with rough-specular mirrors (ff_set_roughness) render on one device only");
+    if (local == FF_OK && s->cam_active() && params->shade_mode != FF_SHADE_NORMAL_DEBUG)
+        local = fail(FF_ERR_UNSUPPORTED, "ff_render_distributed: frames with per-sample camera rays (ff_set_camera_sampling) render on one device only");
     if (local == FF_OK && d->fail_rank == rank) local = fail(FF_ERR_OOM, "injected failure on rank %d (FF_DEBUG_DIST_FAIL_RANK)", rank);
     if (local == FF_OK) {
         if (strip_rows <= 0) strip_rows = default_strip_rows(world, params->height);
@@ -699,6 +701,9 @@ int ff_multi_render(FfMulti* m, const FfCamera* camera, const FfRenderParams* pa
     if (params->shade_mode != FF_SHADE_NORMAL_DEBUG)
         for (FfState* s : m->states)
             if (s->glossy_applied > 0) return fail(FF_ERR_UNSUPPORTED, "ff_multi_render: frames with rough-specular mirrors render on one device only");
+    if (params->shade_mode != FF_SHADE_NORMAL_DEBUG)
+        for (FfState* s : m->states)
+            if (s->cam_active()) return fail(FF_ERR_UNSUPPORTED, "ff_multi_render: frames with per-sample camera rays (ff_set_camera_sampling) render on one device only");
     FfState* root = m->states[0];
     FF_HIP(hipSetDevice(root->device));
     RootOutputs out;
@@ -733,6 +738,9 @@ int ff_multi_render_to_pbo(FfMulti* m, const FfCamera* camera, const FfRenderPar
     if (params->shade_mode != FF_SHADE_NORMAL_DEBUG)
         for (FfState* s : m->states)
             if (s->glossy_applied > 0) return fail(FF_ERR_UNSUPPORTED, "ff_multi_render_to_pbo: frames with rough-specular mirrors render on one device only");
+    if (params->shade_mode != FF_SHADE_NORMAL_DEBUG)
+        for (FfState* s : m->states)
+            if (s->cam_active()) return fail(FF_ERR_UNSUPPORTED, "ff_multi_render_to_pbo: frames with per-sample camera rays (ff_set_camera_sampling) render on one device only");
     if (params->width != root->pbo_width || params->height != root->pbo_height)
         return fail(FF_ERR_INVALID_ARG, "ff_multi_render_to_pbo: params are %dx%d but the registered buffer is %dx%d", params->width, params->height, root->pbo_width, root->pbo_height);
     FF_HIP(hipSetDevice(root->device));

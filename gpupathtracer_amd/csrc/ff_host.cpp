@@ -324,6 +324,8 @@ struct FfSceneFile {
     std::vector<AlbedoMap> albedo_maps;
     std::vector<float> bxdf_roughness;             // parallel to bxdfs: a mirror's `roughness R` (0: none)
     std::vector<float> roughness;                  // per geometry: its bxdf's
+    bool has_cam_sampling = false;                 // the camera statement gave aperture, focus or filter
+    FfCameraSampling cam_sampling = { FF_PIXEL_CORNER, 0.f, 1.f, 0 };
     ~FfSceneFile()
     {
         for (FfTriangle* t : meshes) std::free(t);
@@ -400,8 +402,28 @@ int ff_scene_file_load(const char* path, FfSceneFile** out_scene)
                 else if (key == "fov") { if (!read_floats(tok, i, 1, v)) bad("fov needs a number"); else sc->camera.m_fov = v[0]; }
                 else if (key == "near") { if (!read_floats(tok, i, 1, v)) bad("near needs a number"); else sc->camera.m_nearClip = v[0]; }
                 else if (key == "far") { if (!read_floats(tok, i, 1, v)) bad("far needs a number"); else sc->camera.m_farClip = v[0]; }
+                else if (key == "aperture") {
+                    // (kept beside the layout-locked FfCamera: ff_scene_file_camera_sampling hands it out, ff_set_camera_sampling applies it)
+                    if (!read_floats(tok, i, 1, v)) bad_value("aperture needs a number");
+                    else if (!std::isfinite(v[0]) || v[0] < 0.f) bad_value("aperture is a finite lens radius >= 0");
+                    else { sc->cam_sampling.lens_radius = v[0]; sc->has_cam_sampling = true; }
+                }
+                else if (key == "focus") {
+                    if (!read_floats(tok, i, 1, v)) bad_value("focus needs a number");
+                    else if (!std::isfinite(v[0])) bad_value("focus is a finite distance");
+                    else { sc->cam_sampling.focus_distance = v[0]; sc->has_cam_sampling = true; }
+                }
+                else if (key == "filter") {
+                    if (i >= tok.size()) bad_value("filter needs corner or box");
+                    else if (tok[i] == "corner") { sc->cam_sampling.pixel_filter = FF_PIXEL_CORNER; sc->has_cam_sampling = true; ++i; }
+                    else if (tok[i] == "box") { sc->cam_sampling.pixel_filter = FF_PIXEL_BOX; sc->has_cam_sampling = true; ++i; }
+                    else bad_value("filter is corner or box");
+                }
                 else bad("unknown camera key");
             }
+            // (as ff_set_camera_sampling: a focus <= 0 is refused only while there is a lens, whichever key came first)
+            if (status == FF_OK && sc->cam_sampling.lens_radius > 0.f && !(sc->cam_sampling.focus_distance > 0.f))
+                bad_value("focus is a distance > 0 while aperture > 0");
         } else if (tok[0] == "bxdf") {
             if (tok.size() < 3) { bad("bxdf needs a name and a type"); break; }
             FfBXDF* b = new FfBXDF();
@@ -578,6 +600,13 @@ int ff_scene_file_texture(const FfSceneFile* scene, int index, const char** out_
     if (out_path) *out_path = t.path.c_str();
     if (out_flags) *out_flags = t.flags;
     return FF_OK;
+}
+
+int ff_scene_file_camera_sampling(const FfSceneFile* scene, FfCameraSampling* out)
+{
+    if (!scene || !scene->has_cam_sampling) return 0;
+    if (out) *out = scene->cam_sampling;
+    return 1;
 }
 
 int ff_scene_file_roughness(const FfSceneFile* scene, int geometry_index, float* out_roughness)

@@ -183,9 +183,19 @@ struct NeeParams {
     // lobe width alpha = roughness^2 of an applied binding, 0 for every other record (unbound, not a mirror, or alpha < 1e-3: the
     // perfect mirror).  (appended at the end: the kernels without GLOSSY read everything above where it always was)
     const float* glossy_alpha;
+    // Per-sample camera rays (ff_set_camera_sampling; ff_camera.h, ff_camera.cpp).  cam_active != 0: every sample's first ray is
+    // camera_sample_ray's - a point of the pixel drawn under cam_box, a point of the lens under cam_lens_radius > 0 (cam_focus and the
+    // caller's m_forward / m_right / m_up) - and k.cam_c0 .. c3 hold the UNJITTERED matrix for a box frame.  0: primary_ray's, as ever.
+    // launch_nee picks nee_path_kernel<..., CAM = 1> by cam_active; only those instantiations read the rest.  (appended at the end)
+    int cam_active, cam_box;
+    float cam_lens_radius, cam_focus;
+    float cam_fwd[3], cam_right[3], cam_up[3];
 };
 // key ^ this: the choice between the environment and the light table when both are there (first output, u24 < p_env: environment)
 constexpr unsigned kEnvKeyChoose = 0x3C6EF372u;
+// key ^ these, counter (pixel, s << 8): the sample's point in its pixel (FF_PIXEL_BOX) and on the lens (lens_radius > 0)
+constexpr unsigned kCameraKeyPixel = 0xA54FF53Au;
+constexpr unsigned kCameraKeyLens = 0x510E527Fu;
 
 // LDS bytes the BVH kernels need for (lds_nodes, stack_depth).
 size_t bvh_lds_bytes(int lds_nodes, int stack_depth, int block_threads, int num_geoms);
@@ -220,7 +230,7 @@ hipError_t launch_unpack_strips(const void* src, unsigned char* rgb8, float* rad
                                 hipStream_t stream);
 // One launch of the NEE path kernel (grid_blocks workgroups of kBlockThreads, persistent over np.items); env: the instantiation
 // with the environment light (np.env_*); tex: the one that multiplies bound albedo textures in (np.tex_*); glossy: the one that
-// shades mirrors with a positive np.glossy_alpha as GGX conductors.
+// shades mirrors with a positive np.glossy_alpha as GGX conductors; np.cam_active != 0: the one that draws a camera ray per sample.
 hipError_t launch_nee(const NeeParams& np, int trace_mode, bool env, bool tex, bool glossy, int grid_blocks, hipStream_t stream, const char** kernel_name);
 hipError_t prepare_kernels(); // one-time function attributes (dynamic LDS limit)
 

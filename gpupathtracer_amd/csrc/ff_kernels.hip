@@ -120,6 +120,11 @@ __device__ __forceinline__ float ieee_sqrt(float x)
 #define FF_GLOSSY_RCP(x) ieee_rcp(x)
 #define FF_GLOSSY_SQRT(x) ieee_sqrt(x)
 #include "ff_glossy.h"
+// the per-sample camera ray (shared with the host twin), likewise
+#define FF_CAMERA_HD __device__ __forceinline__
+#define FF_CAMERA_RCP(x) ieee_rcp(x)
+#define FF_CAMERA_SQRT(x) ieee_sqrt(x)
+#include "ff_camera.h"
 
 namespace ff {
 namespace {
@@ -3319,11 +3324,35 @@ __device__ __forceinline__ float4 env_lookup(const NeeParams& np, float dx, floa
 // a light sample weighted against the lobe's pdf, then a direction drawn from its visible normals.  The local frame is rebuilt from
 // the normal where it is needed; nothing of the lobe stays live across a query but prev_pdf and, for a sample whose direction fell
 // below the horizon while its shadow ray is still to be answered, `dead`.  GLOSSY = 0 compiles to the kernel without it.
+// CAM = 1: every sample starts with its own camera ray (ff_set_camera_sampling: a point of the pixel, a point of the lens; ff_camera.h)
+// in place of the pixel's one primary ray.  A runtime branch in the 32 instantiations without it raised their SGPR spills and, for
+// the big-scene ones, their scratch, hence a parameter: CAM = 0 compiles to the kernel without it.
+
+// The first ray of sample P.s.  CAM = 0: the pixel's one primary ray (start_sample).  CAM = 1 (a camera-sampling setting is active):
+// the ray camera_sample_ray draws for this sample (ff_camera.h); nothing it computes outlives it but the ray, and the pixel's
+// primary direction (P.pdx ..) is neither computed nor kept.
+template <int CAM>
+__device__ __forceinline__ void nee_start_sample(const NeeParams& np, Path& P)
+{
+    const KParams& p = np.k;
+    if (!CAM) start_sample(p, P);
+    else {
+        P.b = 0;
+        P.bx = P.by = P.bz = 1.f;
+        const CameraRays C = { p.cam_c0, p.cam_c1, p.cam_c2, p.cam_c3, p.cam_pos, p.far_clip, p.screen_w, p.screen_h,
+                               np.cam_box, np.cam_lens_radius, np.cam_focus, np.cam_fwd, np.cam_right, np.cam_up };
+        const unsigned gx = P.gxy & 0xFFFFu, gy = P.gxy >> 16;
+        camera_sample_ray(C, (int)gx, (int)gy, gy * (unsigned)p.width + gx, (unsigned)P.s, p.key, P.ray.ox, P.ray.oy, P.ray.oz, P.ray.dx, P.ray.dy,
+                          P.ray.dz);
+    }
+}
 
 // The sample's radiance joins its block's sum and the lane goes on to the next sample or gives its item back (GLOSSY = 1: a sample
 // that ends behind its shadow ray; the loop's own ending is the same code).
-__device__ __forceinline__ bool nee_end_sample(const KParams& p, Path& P, float& Lx, float& Ly, float& Lz, float& prev_pdf)
+template <int CAM>
+__device__ __forceinline__ bool nee_end_sample(const NeeParams& np, Path& P, float& Lx, float& Ly, float& Lz, float& prev_pdf)
 {
+    const KParams& p = np.k;
     P.ax = P.ax + Lx;
     P.ay = P.ay + Ly;
     P.az = P.az + Lz;
@@ -3331,7 +3360,7 @@ __device__ __forceinline__ bool nee_end_sample(const KParams& p, Path& P, float&
     prev_pdf = 0.f;
     ++P.s;
     if (P.s < P.send) {
-        start_sample(p, P);
+        nee_start_sample<CAM>(np, P);
         return true;
     }
     p.blocksums[(size_t)((unsigned)P.item & kItemPixelMask) * p.num_blocks + ((unsigned)P.item >> kItemBlockShift)] = make_float4(P.ax, P.ay, P.az, 0.f);
@@ -3351,7 +3380,7 @@ __device__ __forceinline__ void to_local_about(float ux, float uy, float uz, flo
     lz = dot3(ux, uy, uz, wx, wy, wz);
 }
 
-template <int MODE, int BIG = 0, int ENV = 0, int TEX = 0, int GLOSSY = 0>
+template <int MODE, int BIG = 0, int ENV = 0, int TEX = 0, int GLOSSY = 0, int CAM = 0>
 __global__ __launch_bounds__(kBlockThreads) void nee_path_kernel(const NeeParams np)
 {
     const KParams& p = np.k;
@@ -3395,11 +3424,13 @@ __global__ __launch_bounds__(kBlockThreads) void nee_path_kernel(const NeeParams
                 P.s = block * p.block_spp;
                 P.send = min(p.spp_total, P.s + p.block_spp);
                 P.ax = P.ay = P.az = 0.f;
-                primary_ray(p, P.gxy, P.ray);
-                P.pdx = P.ray.dx;
-                P.pdy = P.ray.dy;
-                P.pdz = P.ray.dz;
-                start_sample(p, P);
+                if (!CAM) {
+                    primary_ray(p, P.gxy, P.ray);
+                    P.pdx = P.ray.dx;
+                    P.pdy = P.ray.dy;
+                    P.pdz = P.ray.dz;
+                }
+                nee_start_sample<CAM>(np, P);
                 Lx = Ly = Lz = 0.f;
                 prev_pdf = 0.f;
                 shadow = false;
@@ -3424,7 +3455,7 @@ __global__ __launch_bounds__(kBlockThreads) void nee_path_kernel(const NeeParams
             }
             if (GLOSSY && dead) {
                 dead = false;
-                active = nee_end_sample(p, P, Lx, Ly, Lz, prev_pdf);
+                active = nee_end_sample<CAM>(np, P, Lx, Ly, Lz, prev_pdf);
             }
             continue;
         }
@@ -3443,7 +3474,7 @@ __global__ __launch_bounds__(kBlockThreads) void nee_path_kernel(const NeeParams
                 const float4 emission = mat_f4(M, 13);
                 float cx = P.bx * emission.x, cy = P.by * emission.y, cz = P.bz * emission.z;
                 // (FF_SHADE_DIFFUSE_PATH under an environment runs here with no light table: weight 1)
-                const float area_pdf = ((ENV || TEX || GLOSSY) && np.num_lights == 0) ? 0.f : np.light_pdf[best.geom];
+                const float area_pdf = ((ENV || TEX || GLOSSY || CAM) && np.num_lights == 0) ? 0.f : np.light_pdf[best.geom];
                 if (prev_pdf > 0.f && area_pdf > 0.f) {
                     float nx, ny, nz;
                     world_normal(M, best, false, nx, ny, nz);
@@ -3671,7 +3702,7 @@ __global__ __launch_bounds__(kBlockThreads) void nee_path_kernel(const NeeParams
         prev_pdf = 0.f;
         ++P.s;
         if (P.s < P.send) {
-            start_sample(p, P);
+            nee_start_sample<CAM>(np, P);
         } else {
             p.blocksums[(size_t)((unsigned)P.item & kItemPixelMask) * p.num_blocks + ((unsigned)P.item >> kItemBlockShift)] = make_float4(P.ax, P.ay, P.az, 0.f);
             active = false;
@@ -3784,6 +3815,19 @@ hipError_t prepare_kernels()
     FF_SET_LDS((nee_path_kernel<FF_TRACE_BVH, 0, 1, 1, 1>))
     FF_SET_LDS((nee_path_kernel<FF_TRACE_BVH, 1, 1, 1, 1>))
     FF_SET_LDS((nee_path_kernel<FF_TRACE_BVH, 2, 1, 1, 1>))
+#define FF_SET_LDS_CAM(ENV, TEX, GLOSSY) \
+    FF_SET_LDS((nee_path_kernel<FF_TRACE_BVH, 0, ENV, TEX, GLOSSY, 1>)) \
+    FF_SET_LDS((nee_path_kernel<FF_TRACE_BVH, 1, ENV, TEX, GLOSSY, 1>)) \
+    FF_SET_LDS((nee_path_kernel<FF_TRACE_BVH, 2, ENV, TEX, GLOSSY, 1>))
+    FF_SET_LDS_CAM(0, 0, 0)
+    FF_SET_LDS_CAM(0, 0, 1)
+    FF_SET_LDS_CAM(0, 1, 0)
+    FF_SET_LDS_CAM(0, 1, 1)
+    FF_SET_LDS_CAM(1, 0, 0)
+    FF_SET_LDS_CAM(1, 0, 1)
+    FF_SET_LDS_CAM(1, 1, 0)
+    FF_SET_LDS_CAM(1, 1, 1)
+#undef FF_SET_LDS_CAM
 #undef FF_SET_LDS
     return hipSuccess;
 }
@@ -3922,7 +3966,31 @@ hipError_t launch_nee(const NeeParams& np, int trace_mode, bool env, bool tex, b
                                                   : (size_t)kBruteBatchTris * sizeof(TriRecord);
     const dim3 grid(grid_blocks), block(kBlockThreads);
     const char* name;
-    if (glossy) {
+    if (np.cam_active != 0) {
+        // per-sample camera rays: the instantiations with CAM = 1, named by all six parameters
+#define FF_LAUNCH_CAM(MODE, BIG, ENV, TEX, GLOSSY) \
+    do { hipLaunchKernelGGL((nee_path_kernel<MODE, BIG, ENV, TEX, GLOSSY, 1>), grid, block, lds, stream, np); name = "nee_path_kernel<" #MODE ", " #BIG ", " #ENV ", " #TEX ", " #GLOSSY ", 1>"; } while (0)
+#define FF_LAUNCH_CAM_MODE(ENV, TEX, GLOSSY) \
+    do { \
+        if (trace_mode == FF_TRACE_BVH && big == 1) FF_LAUNCH_CAM(1, 1, ENV, TEX, GLOSSY); \
+        else if (trace_mode == FF_TRACE_BVH && big == 2) FF_LAUNCH_CAM(1, 2, ENV, TEX, GLOSSY); \
+        else if (trace_mode == FF_TRACE_BVH) FF_LAUNCH_CAM(1, 0, ENV, TEX, GLOSSY); \
+        else FF_LAUNCH_CAM(0, 0, ENV, TEX, GLOSSY); \
+    } while (0)
+        switch ((env ? 4 : 0) | (tex ? 2 : 0) | (glossy ? 1 : 0)) {
+        case 0: FF_LAUNCH_CAM_MODE(0, 0, 0); break;
+        case 1: FF_LAUNCH_CAM_MODE(0, 0, 1); break;
+        case 2: FF_LAUNCH_CAM_MODE(0, 1, 0); break;
+        case 3: FF_LAUNCH_CAM_MODE(0, 1, 1); break;
+        case 4: FF_LAUNCH_CAM_MODE(1, 0, 0); break;
+        case 5: FF_LAUNCH_CAM_MODE(1, 0, 1); break;
+        case 6: FF_LAUNCH_CAM_MODE(1, 1, 0); break;
+        default: FF_LAUNCH_CAM_MODE(1, 1, 1); break;
+        }
+#undef FF_LAUNCH_CAM_MODE
+#undef FF_LAUNCH_CAM
+    }
+    else if (glossy) {
 #define FF_LAUNCH_GLOSSY(MODE, BIG, ENV, TEX) \
     do { hipLaunchKernelGGL((nee_path_kernel<MODE, BIG, ENV, TEX, 1>), grid, block, lds, stream, np); name = "nee_path_kernel<" #MODE ", " #BIG ", " #ENV ", " #TEX ", 1>"; } while (0)
 #define FF_LAUNCH_GLOSSY_MODE(ENV, TEX) \

@@ -232,7 +232,7 @@ int nee_rebuild(FfState* s)
 
 // The frame of FF_SHADE_DIFFUSE_PATH_NEE (render_enqueue has filled k's camera, image, block and scene fields).  The mega-kernels'
 // stored primary hits, keys and cull mask are neither used nor touched: the next FF_SHADE_DIFFUSE_PATH frame finds them as they were.
-int enqueue_nee(FfState* s, KParams& k, const FfRenderParams* prm, int launches, int blocks_per_launch, size_t local_pixels)
+int enqueue_nee(FfState* s, KParams& k, const FfCamera* camera, const FfRenderParams* prm, int launches, int blocks_per_launch, size_t local_pixels)
 {
     if (!s->nee_valid) {
         if (s->tex_bound > 0 && prm->shade_mode != FF_SHADE_DIFFUSE_PATH_NEE && !s->env_set)
@@ -241,6 +241,8 @@ int enqueue_nee(FfState* s, KParams& k, const FfRenderParams* prm, int launches,
             return fail(FF_ERR_UNSUPPORTED, "rough-specular mirrors need a scene uploaded with ff_upload_scene (this one has no light table)");
         if (s->env_set)
             return fail(FF_ERR_UNSUPPORTED, "an environment light needs a scene uploaded with ff_upload_scene (this one has no light table)");
+        if (s->cam_active())
+            return fail(FF_ERR_UNSUPPORTED, "per-sample camera rays (ff_set_camera_sampling) need a scene uploaded with ff_upload_scene (this one has no light table)");
         return fail(FF_ERR_UNSUPPORTED, "FF_SHADE_DIFFUSE_PATH_NEE needs a scene uploaded with ff_upload_scene (this one has no light table)");
     }
     hipStream_t st = s->stream;
@@ -288,6 +290,17 @@ int enqueue_nee(FfState* s, KParams& k, const FfRenderParams* prm, int launches,
         np.uvs = s->d_uvs;
     }
     if (glossy) np.glossy_alpha = s->d_glossy_alpha;
+    if (s->cam_active()) {
+        // (render_enqueue has put the unjittered matrix into k for a box frame)
+        np.cam_active = 1;
+        np.cam_box = s->cam_sampling.pixel_filter == FF_PIXEL_BOX ? 1 : 0;
+        np.cam_lens_radius = s->cam_sampling.lens_radius;
+        np.cam_focus = s->cam_sampling.focus_distance;
+        const FfVec3 f = camera->m_forward, r = camera->m_right, u = camera->m_up;
+        np.cam_fwd[0] = f.x; np.cam_fwd[1] = f.y; np.cam_fwd[2] = f.z;
+        np.cam_right[0] = r.x; np.cam_right[1] = r.y; np.cam_right[2] = r.z;
+        np.cam_up[0] = u.x; np.cam_up[1] = u.y; np.cam_up[2] = u.z;
+    }
     if (env) {
         // the environment as one more light (ff_api.h); without light samples p_env = 0
         np.env_texels = s->d_env_texels;

@@ -125,6 +125,11 @@ struct FfState {
     ff::ReprojectionHistory history[2];
     // sub-pixel jitter of the primary rays (ff_set_pixel_jitter): composed into the ray matrix of ff_render* and ff_gbuffer
     float jitter_x = 0.f, jitter_y = 0.f;
+    // Per-sample camera rays (ff_camera.cpp, ff_set_camera_sampling): belongs to the state, like the jitter, so it outlives uploads and
+    // updates of the scene.  While it is active (cam_active), FF_SHADE_DIFFUSE_PATH and FF_SHADE_DIFFUSE_PATH_NEE frames run
+    // nee_path_kernel with NeeParams::cam_active set, and a box frame's ray matrix is the unjittered one.
+    FfCameraSampling cam_sampling = { FF_PIXEL_CORNER, 0.f, 1.f, 0 };
+    bool cam_active() const { return cam_sampling.pixel_filter == FF_PIXEL_BOX || cam_sampling.lens_radius > 0.f; }
     // Next-event estimation (ff_nee.cpp): what the light table is built from - the uploaded geometries (caller order) with their
     // materials and, for meshes, the object-space triangles kept since the upload or the last ff_update_mesh - and the device table
     std::vector<FfGeometry> nee_geoms;
@@ -281,7 +286,9 @@ void dist_release(FfState* s); // ff_dist.cpp: frees s->dist (called by ff_destr
 void nee_capture(FfState* s, const FfGeometry* g, int n, bool upload);
 void nee_replace_mesh(FfState* s, int geometry_index, const FfTriangle* tris, int count);
 int nee_rebuild(FfState* s);
-int enqueue_nee(FfState* s, KParams& k, const FfRenderParams* prm, int launches, int blocks_per_launch, size_t local_pixels);
+int enqueue_nee(FfState* s, KParams& k, const FfCamera* camera, const FfRenderParams* prm, int launches, int blocks_per_launch, size_t local_pixels);
+// Per-sample camera rays (ff_camera.cpp): what ff_set_camera_sampling and its host twin refuse (who: the prefix of the error's text).
+int check_camera_sampling(const FfCameraSampling* cs, const char* who);
 // Environment light (ff_env.cpp): frees the state's device table (ff_destroy).
 void env_release(FfState* s);
 // Albedo textures (ff_texture.cpp): drop the scene's bindings (ff_upload_scene), rewrite the device tables, free everything (ff_destroy).

@@ -37,6 +37,7 @@ EXPORTS = [
     "ff_texture_create", "ff_texture_destroy", "ff_set_albedo_texture", "ff_texture_sample", "ff_surface_uv",
     "ff_load_ppm", "ff_free_ppm", "ff_rgb8_to_linear", "ff_scene_file_texture_count", "ff_scene_file_texture", "ff_scene_file_albedo_map",
     "ff_set_roughness", "ff_glossy_eval", "ff_glossy_sample", "ff_scene_file_roughness",
+    "ff_camera_sampling_init", "ff_set_camera_sampling", "ff_camera_sample_rays", "ff_scene_file_camera_sampling",
 ]
 DIST_ID_BYTES = 128
 
@@ -210,6 +211,11 @@ def load():
     lib.ff_glossy_eval.argtypes = [f32, vp, vp, vp, i32, vp, vp]
     lib.ff_glossy_sample.argtypes = [f32, vp, vp, vp, i32, vp, vp, vp]
     lib.ff_scene_file_roughness.argtypes = [vp, i32, P(f32)]
+    lib.ff_camera_sampling_init.argtypes = [P(T.FfCameraSampling)]
+    lib.ff_camera_sampling_init.restype = None
+    lib.ff_set_camera_sampling.argtypes = [vp, P(T.FfCameraSampling)]
+    lib.ff_camera_sample_rays.argtypes = [P(T.FfCamera), P(T.FfCameraSampling), f32, f32, i32, C.c_uint64, vp, vp, vp, i32, vp, vp]
+    lib.ff_scene_file_camera_sampling.argtypes = [vp, P(T.FfCameraSampling)]
     _lib = real
     return real
 
@@ -287,6 +293,14 @@ class SceneFile:
         if self._lib.ff_scene_file_roughness(self._handle, geometry_index, C.byref(r)) == 0:
             return None
         return float(r.value)
+
+    def camera_sampling(self):
+        """The camera statement's aperture / focus / filter keys as a T.FfCameraSampling (ff_scene_file_camera_sampling), or None
+        if the file gives none of them.  Tracer.set_camera_sampling applies it."""
+        cs = T.FfCameraSampling()
+        if self._lib.ff_scene_file_camera_sampling(self._handle, C.byref(cs)) == 0:
+            return None
+        return cs
 
     def camera(self, width, height):
         cam = T.FfCamera()
@@ -445,6 +459,29 @@ def glossy_sample(alpha, f0, wo, u):
     check(load().ff_glossy_sample(float(alpha), f0.ctypes.data, o.ctypes.data, uu.ctypes.data, o.size // 3, wi.ctypes.data, weight.ctypes.data,
                                   pdf.ctypes.data))
     return wi, weight, pdf
+
+
+def camera_sampling(pixel_filter=T.PIXEL_CORNER, lens_radius=0.0, focus_distance=1.0):
+    """A T.FfCameraSampling: ff_camera_sampling_init's defaults (today's camera) with the given fields replaced."""
+    cs = T.FfCameraSampling()
+    load().ff_camera_sampling_init(C.byref(cs))
+    cs.pixel_filter, cs.lens_radius, cs.focus_distance = int(pixel_filter), float(lens_radius), float(focus_distance)
+    return cs
+
+
+def camera_sample_rays(camera, sampling, width, seed, xs, ys, samples, jitter=(0.0, 0.0)):
+    """The kernel's per-sample camera rays on the host (ff_camera_sample_rays): sample samples[i] of pixel (xs[i], ys[i]) of an image
+    `width` pixels wide under `seed` -> (origins float32 [n, 3], directions float32 [n, 3]).  sampling None: the defaults."""
+    x = np.ascontiguousarray(xs, dtype=np.int32).reshape(-1)
+    y = np.ascontiguousarray(ys, dtype=np.int32).reshape(-1)
+    s = np.ascontiguousarray(samples, dtype=np.int32).reshape(-1)
+    if not (x.shape == y.shape == s.shape):
+        raise ValueError("xs, ys and samples have the same length")
+    o = np.zeros((x.size, 3), dtype=np.float32)
+    d = np.zeros((x.size, 3), dtype=np.float32)
+    check(load().ff_camera_sample_rays(C.byref(camera), None if sampling is None else C.byref(sampling), float(jitter[0]), float(jitter[1]), int(width),
+                                       int(seed), x.ctypes.data, y.ctypes.data, s.ctypes.data, x.size, o.ctypes.data, d.ctypes.data))
+    return o, d
 
 
 def load_ppm(path):
@@ -630,6 +667,12 @@ class Tracer:
         """Make a mirror geometry a rough (GGX) conductor of this roughness in [0, 1], F0 = its m_specularColor (ff_set_roughness);
         0 (or None) unbinds.  Bindings last until the next upload_scene."""
         check(self._lib.ff_set_roughness(self._state, int(geometry_index), 0.0 if roughness is None else float(roughness)))
+
+    def set_camera_sampling(self, sampling=None):
+        """ff_set_camera_sampling: a T.FfCameraSampling (lib.camera_sampling(...)) for the following render* calls - T.PIXEL_BOX draws
+        a point of the pixel per sample, lens_radius > 0 a point of a thin lens focused at focus_distance; None: the defaults (today's
+        camera).  The setting stays through upload_scene and the update calls."""
+        check(self._lib.ff_set_camera_sampling(self._state, None if sampling is None else C.byref(sampling)))
 
     def apply_scene_file_materials(self, scene_file):
         """After upload_scene(scene_file): bind every `roughness` of the file's mirror bxdfs (the file's albedo_maps need their images

@@ -196,6 +196,12 @@ class FfLightEntry(C.Structure):
     ]
 
 
+class FfCameraSampling(C.Structure):
+    """ff_set_camera_sampling: the pixel filter and the thin lens of the per-sample camera rays (ff_types.h)."""
+    _fields_ = [("pixel_filter", C.c_int32), ("lens_radius", C.c_float), ("focus_distance", C.c_float), ("reserved", C.c_int32)]
+
+
+assert C.sizeof(FfCameraSampling) == 16
 assert C.sizeof(FfLightEntry) == 72
 assert C.sizeof(FfBXDF) == 60
 assert C.sizeof(FfTriangle) == 96
@@ -214,6 +220,7 @@ ENV_MAX_TEXELS = 1 << 26  # largest environment map ff_set_environment takes (wi
 TEX_REPEAT, TEX_CLAMP, TEX_BILINEAR, TEX_NEAREST = 0, 1, 0, 2  # ff_texture_create flags (FF_TEX_*)
 TEX_MAX_TEXELS = 1 << 26  # largest texture ff_texture_create takes (width x height)
 SCENE_TEX_SRGB = 256  # ff_scene_file_texture: the statement says `srgb`
+PIXEL_CORNER, PIXEL_BOX = 0, 1  # FfCameraSampling.pixel_filter (FF_PIXEL_*)
 GLOSSY_MIN_ALPHA = 1.0e-3  # ff_set_roughness: a binding whose alpha = roughness^2 is below it shades as the perfect mirror
 
 # status codes (ff_api.h)

@@ -494,6 +494,57 @@ FF_API int ff_glossy_eval(float alpha, const float* f0_rgb, const float* wo, con
 FF_API int ff_glossy_sample(float alpha, const float* f0_rgb, const float* wo, const float* u, int n, float* out_wi, float* out_weight_rgb,
                             float* out_pdf);
 
+/* ---- per-sample camera rays: box pixel filter and thin lens (no counterpart in the reference) ---- */
+
+/* Without a setting every sample of a pixel starts with the same ray: primary_ray's, through the pixel's corner moved by the state's
+ * jitter (ff_set_pixel_jitter).  An ACTIVE setting - pixel_filter == FF_PIXEL_BOX or lens_radius > 0 - draws a camera ray per sample:
+ * a uniform point of the pixel (the frame converges to the box-filtered image within one call) and / or a uniform point of a thin
+ * lens of radius lens_radius about m_position in the plane of m_right and m_up, focused on the plane at focus_distance along
+ * m_forward (depth of field).  FF_SHADE_DIFFUSE_PATH and FF_SHADE_DIFFUSE_PATH_NEE render it.  All arithmetic is float32, evaluated
+ * as parenthesised, no fused multiply-add; a quotient by a computed value is a * rcp(b) with a correctly rounded reciprocal, roots
+ * are correctly rounded; dot(a, b) = (a.x b.x + a.y b.y) + a.z b.z.
+ * For sample s of global pixel (x, y): gpix = y * width + x, key = seed ^ (seed >> 32) (the frame key), u24(r) = (r >> 8) / 2^24.
+ *   Pixel point  FF_PIXEL_CORNER: fx = fy = 0 and M = the state's jittered ray matrix (ff_camera_ray_matrix_jittered), as ever.
+ *                FF_PIXEL_BOX: (a0, a1) = Philox2x32-10(gpix, s << 8, key ^ 0xA54FF53A), fx = u24(a0), fy = u24(a1), and M = the
+ *                UNJITTERED ff_camera_ray_matrix: the state's jitter is not applied to such frames (ff_gbuffer goes on using it).
+ *                Px = (((float)x + fx) / screen_w) * 2 - 1,  Py = 1 - (((float)y + fy) / screen_h) * 2
+ *   Pinhole      v = (Px far, Py far, far, far);  w_k = (M0_k v.x + M1_k v.y) + (M2_k v.z + M3_k v.w), M0 .. M3 the columns of M;
+ *                dd = w - o, o = m_position;  d = dd * rcp(sqrt(dot(dd, dd))): kernel.cu:197-205 operation for operation, and with
+ *                fx = fy = 0 the ray every frame without a setting traces, bit for bit.
+ *   Lens         (lens_radius > 0)  f^, r^, u^ = m_forward, m_right, m_up as the caller's floats, not renormalised.
+ *                c = dot(d, f^).  If !(c > 1e-6) the pinhole ray is kept.  Else t = focus_distance * rcp(c), F = o + d t per
+ *                component;  (l0, l1) = Philox(gpix, s << 8, key ^ 0x510E527F);  (sn, cs) = the sine and cosine of 2 pi (l0 >> 8) / 2^24
+ *                by the glossy sampler's fixed-order polynomials on the exactly reduced octant;  rho = lens_radius * sqrt(u24(l1)),
+ *                a = rho cs, b = rho sn;  o' = o + (a r^ + b u^) per component;  dd' = F - o',
+ *                d' = dd' * rcp(sqrt(dot(dd', dd'))).  The sample's ray is (o', d').
+ *   Weight       1 (an ideal thin lens, no vignetting): the throughput starts at 1 as ever.  The path, its random numbers at every
+ *                vertex, the light samples, the accumulation (blocks of 64 samples in order) and every other stream are unchanged.
+ * The setting belongs to the state, like the jitter and the environment: it stays through ff_upload_scene and the update calls
+ * until it is replaced or the state is destroyed.  While it is active, FF_SHADE_DIFFUSE_PATH and FF_SHADE_DIFFUSE_PATH_NEE frames run
+ * the NEE kernel (the plain path mode with no light sample); without it, every frame launches exactly the kernels it launched before
+ * and produces the same bits.  Results do not depend on the lane, spp_per_launch, tile, strip or trace mode.  ff_render,
+ * ff_render_tile, ff_render_strips, ff_render_progressive and the pixel-buffer twins render it.  FF_SHADE_NORMAL_DEBUG ignores the
+ * setting.  FF_SHADE_DIFFUSE_PATH_SMOOTH, ff_render_distributed, ff_multi_render* and a state whose scene came from
+ * ff_multi_upload_scene return FF_ERR_UNSUPPORTED while it is active (the environment's, the textures' and the mirrors' precedent).
+ * ff_gbuffer, ff_intersect_rays and the image filters are unchanged: the G-buffer stays the PINHOLE's first hit (with the state's
+ * jitter), which is the usual guide for denoising a defocused frame.  Not offered: other pixel filters, polygonal apertures,
+ * vignetting, motion blur, a defocus-aware G-buffer, the setting on the multi-GPU entry points. */
+
+/* FF_PIXEL_CORNER, lens_radius 0, focus_distance 1, reserved 0: today's camera. */
+FF_API void ff_camera_sampling_init(FfCameraSampling* cs);
+
+/* Replaces the state's setting; NULL = the defaults.  FF_ERR_INVALID_ARG, naming the field, for an unknown pixel_filter, a negative
+ * or non-finite lens_radius, a non-finite focus_distance or one <= 0 while lens_radius > 0, a non-zero reserved. */
+FF_API int ff_set_camera_sampling(FfState* state, const FfCameraSampling* cs);
+
+/* Host-only twin (no GPU, no state), compiled from the same inline functions the kernel uses: the rays of n samples - sample
+ * samples[i] of pixel (xs[i], ys[i]) of an image `width` pixels wide under `seed` - into out_origins3 and out_directions3 (n triples
+ * each).  cs = NULL: the defaults.  jitter_x / jitter_y: the state's pixel jitter, applied under FF_PIXEL_CORNER only, as in a frame.
+ * FF_ERR_INVALID_ARG for a NULL pointer, n < 0, width < 1, a negative coordinate or sample, a jitter outside [0, 1), and the
+ * setting's own checks. */
+FF_API int ff_camera_sample_rays(const FfCamera* camera, const FfCameraSampling* cs, float jitter_x, float jitter_y, int width, uint64_t seed,
+                                 const int* xs, const int* ys, const int* samples, int n, float* out_origins3, float* out_directions3);
+
 /* ---- G-buffer and denoiser (no counterpart in the reference) ----------------------------- */
 
 /* What every pixel's primary ray (kernel.cu:197-205) hits: I = intersectRays (kernel.cu:127-176) for that ray, the FfIntersect
@@ -780,6 +831,10 @@ FF_API void ff_free_triangles(FfTriangle* triangles);
  * one statement per line, '#' starts a comment:
  *
  *   camera position X Y Z yaw DEG pitch DEG fov DEG near N far F            (every key optional: kernel.cu:312-321 defaults)
+ *          [aperture R] [focus F] [filter corner|box]                       (ff_set_camera_sampling's lens_radius, focus_distance
+ *                                                                             and pixel_filter; what it would refuse - a
+ *                                                                             focus <= 0 only beside an aperture > 0 - is
+ *                                                                             FF_ERR_INVALID_ARG naming the line)
  *   bxdf NAME diffuse|emitter|mirror|glass [albedo R G B] [specular R G B] [transmittance R G B] [ior N] [color R G B] [intensity I]
  *                                            [roughness R]                  (mirror only, R in [0, 1]; anything else is
  *                                                                             FF_ERR_INVALID_ARG naming the line)
@@ -815,6 +870,9 @@ FF_API int ff_scene_file_albedo_map(const FfSceneFile* scene, int geometry_index
 /* The `roughness` of geometry `geometry_index`'s bxdf: 1 with the value; 0 if it has none (or 0: the output is left alone).
  * ff_set_roughness is the caller's. */
 FF_API int ff_scene_file_roughness(const FfSceneFile* scene, int geometry_index, float* out_roughness);
+/* The camera statement's `aperture`, `focus` and `filter` keys: 1 with the setting they describe (keys not given keep
+ * ff_camera_sampling_init's values); 0 if none of them was given (the output is left alone).  ff_set_camera_sampling is the caller's. */
+FF_API int ff_scene_file_camera_sampling(const FfSceneFile* scene, FfCameraSampling* out);
 
 #ifdef __cplusplus
 } /* extern "C" */

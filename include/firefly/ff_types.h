@@ -305,6 +305,18 @@ typedef struct FfDisplayParams {
 #define FF_TEX_BILINEAR  0   /* the four nearest texels, interpolated */
 #define FF_TEX_NEAREST   2   /* the texel the coordinate falls in */
 
+/* ff_set_camera_sampling: where in its pixel, and from where on the lens, every sample's camera ray starts (ff_api.h). */
+typedef enum FfPixelFilter {
+    FF_PIXEL_CORNER = 0, /* every sample through the pixel's corner (plus the state's jitter): the reference's ray */
+    FF_PIXEL_BOX = 1     /* a uniform point of the pixel per sample: the frame converges to the box-filtered image */
+} FfPixelFilter;
+typedef struct FfCameraSampling {
+    int32_t pixel_filter;   /* FfPixelFilter */
+    float   lens_radius;    /* world units, >= 0; 0 = pinhole */
+    float   focus_distance; /* distance of the plane of focus along m_forward, > 0 when lens_radius > 0 */
+    int32_t reserved;       /* 0 */
+} FfCameraSampling;
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif
@@ -317,6 +329,7 @@ static_assert(sizeof(FfRay) == 24, "Ray layout must match utilities.h:257-267");
 static_assert(sizeof(FfIntersect) == 40, "Intersect layout must match utilities.h:57-66");
 static_assert(sizeof(FfCamera) == 108, "Camera layout must match utilities.h:269-291");
 static_assert(sizeof(FfDisplayParams) == 64, "FfDisplayParams is 64 bytes");
+static_assert(sizeof(FfCameraSampling) == 16, "FfCameraSampling is 16 bytes");
 #else
 _Static_assert(sizeof(FfBXDF) == 60, "BXDF layout");
 _Static_assert(sizeof(FfTriangle) == 96, "Triangle layout");
@@ -325,6 +338,7 @@ _Static_assert(sizeof(FfRay) == 24, "Ray layout");
 _Static_assert(sizeof(FfIntersect) == 40, "Intersect layout");
 _Static_assert(sizeof(FfCamera) == 108, "Camera layout");
 _Static_assert(sizeof(FfDisplayParams) == 64, "FfDisplayParams layout");
+_Static_assert(sizeof(FfCameraSampling) == 16, "FfCameraSampling layout");
 #endif
 
 #endif /* FIREFLY_FF_TYPES_H */

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Register pressure of ONE trace-kernel instantiation in a few seconds (no GPU needed):
 #   tools/diag/probe_kernel.sh 'trace_pool_kernel<false, 1024, false>' [extra hipcc flags]
-#   tools/diag/probe_kernel.sh 'nee_path_kernel<1, 0, 0, 1, 1>'   (the NEE kernel: MODE, BIG, ENV, TEX, GLOSSY)
+#   tools/diag/probe_kernel.sh 'nee_path_kernel<1, 0, 0, 1, 1>'   (the NEE kernel: MODE, BIG, ENV, TEX, GLOSSY[, CAM])
 # prints VGPRs / spills / scratch from -Rpass-analysis=kernel-resource-usage and leaves the ISA in /tmp/ff_probe.s
 K=${1:-trace_pool_kernel<false, 1024, false>}; shift
 cd "$(dirname "$0")/../../gpupathtracer_amd/csrc" || exit 1
