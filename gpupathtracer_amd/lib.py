@@ -38,6 +38,7 @@ EXPORTS = [
     "ff_load_ppm", "ff_free_ppm", "ff_rgb8_to_linear", "ff_scene_file_texture_count", "ff_scene_file_texture", "ff_scene_file_albedo_map",
     "ff_set_roughness", "ff_glossy_eval", "ff_glossy_sample", "ff_scene_file_roughness",
     "ff_camera_sampling_init", "ff_set_camera_sampling", "ff_camera_sample_rays", "ff_scene_file_camera_sampling",
+    "ff_upscale_params_init", "ff_upscale", "ff_upscale_host",
 ]
 DIST_ID_BYTES = 128
 
@@ -216,6 +217,11 @@ def load():
     lib.ff_set_camera_sampling.argtypes = [vp, P(T.FfCameraSampling)]
     lib.ff_camera_sample_rays.argtypes = [P(T.FfCamera), P(T.FfCameraSampling), f32, f32, i32, C.c_uint64, vp, vp, vp, i32, vp, vp]
     lib.ff_scene_file_camera_sampling.argtypes = [vp, P(T.FfCameraSampling)]
+    # guided upsampling
+    lib.ff_upscale_params_init.argtypes = [P(T.FfUpscaleParams)]
+    lib.ff_upscale_params_init.restype = None
+    lib.ff_upscale.argtypes = [vp, P(T.FfUpscaleParams), i32, i32, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, i32, vp, i32, vp, i32]
+    lib.ff_upscale_host.argtypes = [P(T.FfUpscaleParams), i32, i32, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp]
     _lib = real
     return real
 
@@ -545,6 +551,43 @@ def taa_params(**overrides):
             raise TypeError(f"FfTaaParams has no field {name!r}")
         setattr(p, name, value)
     return p
+
+
+def upscale_params(**overrides):
+    """ff_upscale_params_init's defaults with the given fields replaced (any FfUpscaleParams field; a jitter as a pair)."""
+    p = T.FfUpscaleParams()
+    load().ff_upscale_params_init(C.byref(p))
+    for name, value in overrides.items():
+        if name not in dict(T.FfUpscaleParams._fields_):
+            raise TypeError(f"FfUpscaleParams has no field {name!r}")
+        setattr(p, name, (C.c_float * 2)(*value) if name in ("lo_jitter", "hi_jitter") else value)
+    return p
+
+
+def _upscale_images(radiance_lo, gbuffer_lo, gbuffer_hi, who):
+    """The nine input images of ff_upscale as contiguous arrays, and (h, w), (H, W)."""
+    rad = np.ascontiguousarray(radiance_lo, dtype=np.float32)
+    names = ("position", "normal", "albedo", "ids")
+    lo = {k: np.ascontiguousarray(gbuffer_lo[k], dtype=np.int32 if k == "ids" else np.float32) for k in names}
+    hi = {k: np.ascontiguousarray(gbuffer_hi[k], dtype=np.int32 if k == "ids" else np.float32) for k in names}
+    h, w = rad.shape[:2]
+    H, W = hi["ids"].shape[:2]
+    if rad.shape != (h, w, 3) or any(lo[k].shape != (h, w, 3) for k in names) or any(hi[k].shape != (H, W, 3) for k in names):
+        raise ValueError(f"{who}: radiance_lo and gbuffer_lo must be [h,w,3] and gbuffer_hi [H,W,3]")
+    return rad, lo, hi, (h, w), (H, W)
+
+
+def upscale_host(radiance_lo, gbuffer_lo, gbuffer_hi, p=None):
+    """ff_upscale_host (no GPU): host radiance [h,w,3] with its gbuffer dict and the [H,W] gbuffer dict of the same view
+    -> (rgb8 [H,W,3] uint8, radiance [H,W,3] float32)."""
+    rad, lo, hi, (h, w), (H, W) = _upscale_images(radiance_lo, gbuffer_lo, gbuffer_hi, "upscale_host")
+    p = p if p is not None else upscale_params()
+    rgb8 = np.zeros((H, W, 3), dtype=np.uint8)
+    out = np.zeros((H, W, 3), dtype=np.float32)
+    check(load().ff_upscale_host(C.byref(p), w, h, rad.ctypes.data, lo["position"].ctypes.data, lo["normal"].ctypes.data, lo["albedo"].ctypes.data,
+                                 lo["ids"].ctypes.data, W, H, hi["position"].ctypes.data, hi["normal"].ctypes.data, hi["albedo"].ctypes.data,
+                                 hi["ids"].ctypes.data, rgb8.ctypes.data, out.ctypes.data))
+    return rgb8, out
 
 
 def display_params(**overrides):
@@ -898,6 +941,27 @@ class Tracer:
         length = np.zeros((h, w), dtype=np.float32)
         check(self._lib.ff_taa_history(self._state, motion.ctypes.data if h * w else None, length.ctypes.data if h * w else None, 0))
         return motion, length
+
+    def upscale(self, radiance_lo, gbuffer_lo, gbuffer_hi, p=None):
+        """ff_upscale of host radiance [h,w,3] with its gbuffer() dict, guided by the [H,W] gbuffer() dict of the same view (p: the
+        jitters both were made with) -> (rgb8 [H,W,3] uint8, radiance [H,W,3] float32)."""
+        rad, lo, hi, (h, w), (H, W) = _upscale_images(radiance_lo, gbuffer_lo, gbuffer_hi, "upscale")
+        p = p if p is not None else upscale_params()
+        rgb8 = np.zeros((H, W, 3), dtype=np.uint8)
+        out = np.zeros((H, W, 3), dtype=np.float32)
+        check(self._lib.ff_upscale(self._state, C.byref(p), w, h, rad.ctypes.data, lo["position"].ctypes.data, lo["normal"].ctypes.data,
+                                   lo["albedo"].ctypes.data, lo["ids"].ctypes.data, W, H, hi["position"].ctypes.data, hi["normal"].ctypes.data,
+                                   hi["albedo"].ctypes.data, hi["ids"].ctypes.data, 0, rgb8.ctypes.data, 0, out.ctypes.data, 0))
+        return rgb8, out
+
+    def upscale_device(self, lo_width, lo_height, radiance_lo_ptr, position_lo_ptr, normal_lo_ptr, albedo_lo_ptr, ids_lo_ptr, width, height, position_ptr,
+                       normal_ptr, albedo_ptr, ids_ptr, p=None, rgb8_ptr=None, radiance_out_ptr=None):
+        """ff_upscale on DEVICE buffers (raw pointers); the outputs must not overlap an input."""
+        p = p if p is not None else upscale_params()
+        vp = lambda q: C.c_void_p(q) if q else None  # noqa: E731
+        check(self._lib.ff_upscale(self._state, C.byref(p), lo_width, lo_height, vp(radiance_lo_ptr), vp(position_lo_ptr), vp(normal_lo_ptr),
+                                   vp(albedo_lo_ptr), vp(ids_lo_ptr), width, height, vp(position_ptr), vp(normal_ptr), vp(albedo_ptr), vp(ids_ptr), 1,
+                                   vp(rgb8_ptr), 1, vp(radiance_out_ptr), 1))
 
     def display(self, radiance, p=None, want_rgb8=True, want_out=True):
         """ff_display of host radiance [H,W,3] -> (rgb8 [H,W,3] uint8, display_out [H,W,3] float32: the curve's output in [0, 1]);

@@ -147,6 +147,14 @@ TAA_PARAMS_BYTES = 16
 TAA_BILINEAR, TAA_NO_CLAMP = 1, 2
 
 
+class FfUpscaleParams(C.Structure):
+    _fields_ = [("sigma_normal", C.c_float), ("sigma_plane", C.c_float), ("flags", C.c_uint32), ("lo_jitter", C.c_float * 2),
+                ("hi_jitter", C.c_float * 2), ("reserved", C.c_uint32)]
+
+
+UPSCALE_PARAMS_BYTES = 32
+
+
 class FfDisplayParams(C.Structure):
     _fields_ = [
         ("curve", C.c_int32), ("encoding", C.c_int32), ("flags", C.c_int32), ("exposure", C.c_float), ("white", C.c_float), ("key", C.c_float),

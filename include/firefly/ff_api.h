@@ -695,6 +695,64 @@ FF_API int ff_taa_reset(FfState* state);
  * length (W*H floats).  Either may be NULL.  FF_ERR_INVALID_ARG when no call was made since the last reset. */
 FF_API int ff_taa_history(FfState* state, float* motion, float* length, int on_device);
 
+/* ---- guided upsampling (joint bilateral upsampling: Kopf et al., SIGGRAPH 2007) ---------------- */
+
+/* Defaults: sigma_normal 0.1, sigma_plane 0.1 (ff_denoise's), both FF_DENOISE_* flags, no jitter. */
+FF_API void ff_upscale_params_init(FfUpscaleParams* p);
+
+/* Turns a w x h float3 radiance image (lo_width x lo_height: raw, ff_denoise's or ff_denoise_temporal's output) plus its w x h
+ * G-buffer plus a W x H G-buffer of the same view (width x height) into a W x H image: trace fewer pixels than are shown, and take
+ * geometry edges and albedo textures from the cheap full-resolution G-buffer.  A pure image operation like ff_denoise: no scene is
+ * read and none is needed.  Both G-buffers are ff_gbuffer's for the same camera pose with m_screenWidth x m_screenHeight = w x h and
+ * W x H, under the pixel jitters lo_jitter = (jx, jy) and hi_jitter = (Jx, Jy) (ff_set_pixel_jitter).  The caller is responsible
+ * for w/h = W/H and for the pose; only the sizes are checked.  Primary rays go through Px = (x + jx) / screen_w * 2 - 1, so high
+ * pixel X looks along low image coordinate ((X + Jx) w) / W - jx; for an integer factor s and no jitter, low pixel i is high
+ * pixel s i.  All arithmetic is float32, evaluated as written with the parentheses shown, no fused multiply-add; a dot product is
+ * (x + y) + z.  Filterable is ff_denoise's: a hit whose bxdf is not emitter, mirror or glass.  Per high pixel P = (X, Y) with
+ * guides x_P, n_P, a_P, ids_P, over low taps q with x_q, n_q, a_q, ids_q and radiance r_q (n: the G-buffer normal times
+ * 1 / sqrt(n.n), 0 for a zero normal):
+ *   1 taps    u = (((float)X + Jx) * (float)w) / (float)W - jx,  i0 = floor(u),  fu = u - i0;  v, j0, fv likewise from Y, Jy, h, H, jy.
+ *             The 2x2 taps are (i0 + {0, 1}, j0 + {0, 1}) and the 4x4 taps (i0 - 1 .. i0 + 2, j0 - 1 .. j0 + 2), row by row, each
+ *             coordinate clamped into the low image (a clamped tap keeps its weight, and counts as often as it is named).
+ *             b_q = (1 - fu | fu) * (1 - fv | fv), the bilinear weight of a 2x2 tap
+ *   mean      over the taps that count, c_0 the first of them: c = c_0 + (sum w_q (c_q - c_0)) / sum w_q, and c = c_0 for a single
+ *             tap.  This is sum w c_q / sum w, and returns one tap, or a colour all taps share, bit for bit
+ *   2 P filterable.  A tap counts when it is filterable, (FF_DENOISE_SAME_GEOMETRY) its geometry index is P's, r_q is finite
+ *             in all three channels, (FF_DENOISE_DEMODULATE_ALBEDO) every channel with a_P > 0 has a_q > 0, b_q > 0, and
+ *             e_q = a_n + a_x <= 30 (ff_denoise's cut-off),  a_n = (1 - n_P . n_q) / sigma_normal,
+ *             a_x = (d * d) / ((sigma_plane * sigma_plane) * |x_q - x_P|^2 + 1e-30),  d = n_P . (x_q - x_P).
+ *             w_q = b_q * exp(-e_q)  (= b_q w_n w_x of ff_denoise).  c_q = r_q / a_q in the channels with a_P > 0
+ *             (DEMODULATE_ALBEDO), r_q elsewhere.  If a 2x2 tap counts: the mean over them.  Otherwise the mean over the 4x4 taps
+ *             under the same rule without b_q (w_q = exp(-e_q)).  Otherwise step 4.  Output = c * a_P in the divided channels
+ *   3 P not filterable (a miss, an emitter, a mirror, glass: there is no high-resolution radiance to copy through).  A tap counts
+ *             when its geometry index and bxdf type equal P's (a miss matches a miss), r_q is finite and b_q > 0;  w_q = b_q,
+ *             c_q = r_q.  If none counts: the 4x4 taps with w_q = 1.  Otherwise step 4
+ *   4 fallback  r of the low pixel (floor(u + 0.5), floor(v + 0.5)), clamped into the image, as it is.
+ * rgb8 = trunc(clamp(v * 255)) as ff_render's.  Equal sizes, no jitter and no DEMODULATE_ALBEDO return a finite input image bit
+ * for bit.  Non-finite input: a NaN or +-Inf in radiance_lo never counts as a tap, so it reaches high pixels through step 4 only;
+ * every other output stays finite.  rgb8 (W*H*3 bytes) and radiance_out (W*H*3 floats) may each be NULL and must not overlap an
+ * input.  inputs_on_device covers all nine input images.  Host buffers are staged through the state's image staging buffer; the
+ * call keeps nothing else in the state and leaves FfStats, the stored primary hits and their key, every filter's history and the
+ * progressive sum as they were.  Synchronous, on the state's stream.  FF_ERR_INVALID_ARG, naming the field, before any device
+ * work for: a NULL state, params, radiance_lo, position, normal or ids of either grid; a NULL albedo of either grid with
+ * DEMODULATE_ALBEDO (without it albedo is not read); sizes outside 1 <= lo <= hi <= 8 lo per axis or hi > 65535; a sigma that is
+ * not positive and finite; a jitter outside [0, 1); unknown flags; a nonzero `reserved`.
+ * Not offered: a temporal upsampler (ff_taa writing a larger image than it reads), upscaling ff_denoise_temporal's history,
+ * non-uniform or foveated sampling, a multi-GPU twin. */
+FF_API int ff_upscale(FfState* state, const FfUpscaleParams* p,
+                      int lo_width, int lo_height, const float* radiance_lo, const float* position_lo, const float* normal_lo,
+                      const float* albedo_lo, const int32_t* ids_lo,
+                      int width, int height, const float* position, const float* normal, const float* albedo, const int32_t* ids,
+                      int inputs_on_device, void* rgb8, int rgb8_on_device, float* radiance_out, int radiance_out_on_device);
+
+/* Host-only twin (no GPU, no state, host pointers), compiled from the same inline per-pixel function the kernel uses: the same
+ * image arguments, the same checks.  It differs from ff_upscale in the last bits of exp alone. */
+FF_API int ff_upscale_host(const FfUpscaleParams* p,
+                           int lo_width, int lo_height, const float* radiance_lo, const float* position_lo, const float* normal_lo,
+                           const float* albedo_lo, const int32_t* ids_lo,
+                           int width, int height, const float* position, const float* normal, const float* albedo, const int32_t* ids,
+                           unsigned char* rgb8, float* radiance_out);
+
 /* ---- display transform (exposure, bloom, tone curve, sRGB) ------------------------------------- */
 
 /* Defaults: ACES, SRGB, flags 0, exposure 1, white 4, key 0.18, percentiles 0.5 / 0.95, min_exposure 2^-10, max_exposure 2^10,

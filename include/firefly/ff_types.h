@@ -276,6 +276,17 @@ typedef struct FfTaaParams {
     int32_t reserved;   /* 0 */
 } FfTaaParams;          /* 16 bytes */
 
+/* ff_upscale: G-buffer-guided upsampling of a low-resolution frame (joint bilateral upsampling, Kopf et al. 2007, with ff_denoise's
+ * edge-stopping functions).  ff_upscale_params_init gives the defaults; the operator is in ff_api.h. */
+typedef struct FfUpscaleParams {
+    float    sigma_normal;  /* normal edge-stop, as FfDenoiseParams (> 0) */
+    float    sigma_plane;   /* plane-distance edge-stop, as FfDenoiseParams (> 0) */
+    uint32_t flags;         /* FF_DENOISE_SAME_GEOMETRY | FF_DENOISE_DEMODULATE_ALBEDO */
+    float    lo_jitter[2];  /* the pixel jitter (ff_set_pixel_jitter) the low G-buffer and frame were made with, each in [0, 1) */
+    float    hi_jitter[2];  /* ... and the high G-buffer's */
+    uint32_t reserved;      /* 0 */
+} FfUpscaleParams;          /* 32 bytes */
+
 /* ff_display: the display transform, W x H float3 radiance -> 8-bit RGB (exposure, bloom, tone curve, encoding).
  * ff_display_params_init gives the defaults; the formulas are in ff_api.h. */
 #define FF_CURVE_CLAMP     0   /* y = x */
