@@ -1,5 +1,6 @@
 // ff_image_api.cpp — host side of the image-space entry points of the C ABI (include/firefly/ff_api.h): ff_gbuffer's resolve,
-// ff_denoise, ff_denoise_temporal and ff_taa with their histories (kernels in ff_denoise.hip, ff_temporal.hip, ff_taa.hip), and
+// ff_denoise, ff_denoise_temporal, ff_taa and ff_taa_upscale with their histories (kernels in ff_denoise.hip, ff_temporal.hip,
+// ff_taa.hip, ff_taa_upscale.hip), and
 // what they share with ff_display_api.cpp (ff_image.h).  No trace kernel is launched from here: ff_gbuffer's primary hits come
 // from frame_primary_hits (ff_api.cpp).
 #include <algorithm>
@@ -11,6 +12,7 @@
 #include "ff_denoise.h"
 #include "ff_state.h"
 #include "ff_taa.h"
+#include "ff_taa_upscale.h"
 #include "ff_temporal.h"
 
 using namespace ff;
@@ -639,6 +641,132 @@ int ff_taa_reset(FfState* s) { return history_reset(s, FfState::kHistoryTaa, "ff
 int ff_taa_history(FfState* s, float* motion, float* length, int on_device)
 {
     return history_readback(s, FfState::kHistoryTaa, "ff_taa_history", "ff_taa", motion, length, on_device,
+                            [s](const ReprojectionHistory& h, float* d_motion, float* d_length) {
+                                return launch_taa_history(taa_buffers(h.d_work, h.width, h.height, h.cur), d_motion, d_length, s->stream);
+                            });
+}
+
+// ---- temporal upsampling (kernel in ff_taa_upscale.hip) ---------------------------------------------------------------------
+
+void ff_taa_upscale_params_init(FfTaaUpscaleParams* p)
+{
+    if (!p) return;
+    // (ff_taa's: DESIGN.md section 8 rows 7 and 15)
+    p->alpha_min = 0.1f;
+    p->gamma = 1.0f;
+    p->lo_jitter[0] = p->lo_jitter[1] = 0.f;
+    p->flags = 0;
+    p->reserved = 0;
+}
+
+int ff_taa_upscale(FfState* s, const FfCamera* camera, const FfTaaUpscaleParams* p, int lo_width, int lo_height, const float* radiance_lo,
+                   const int32_t* ids_lo, int width, int height, const float* position, const int32_t* ids, int inputs_on_device, void* rgb8,
+                   int rgb8_on_device, float* radiance_out, int radiance_out_on_device)
+{
+    const char* who = "ff_taa_upscale";
+    clear_error();
+    // every check comes before the device and the history are touched: a refused call leaves both as they were
+    if (!s) return fail(FF_ERR_INVALID_ARG, "%s: state is null", who);
+    if (!camera) return fail(FF_ERR_INVALID_ARG, "%s: camera is null", who);
+    if (!p) return fail(FF_ERR_INVALID_ARG, "%s: params are null", who);
+    if (lo_width < 1 || lo_height < 1) return fail(FF_ERR_INVALID_ARG, "%s: lo_width x lo_height %dx%d is invalid", who, lo_width, lo_height);
+    if (width > 65535 || height > 65535) return fail(FF_ERR_INVALID_ARG, "%s: width x height %dx%d is invalid (at most 65535)", who, width, height);
+    if (width < lo_width || (long long)width > 8ll * lo_width)
+        return fail(FF_ERR_INVALID_ARG, "%s: width %d must be in lo_width .. 8 lo_width (lo_width %d)", who, width, lo_width);
+    if (height < lo_height || (long long)height > 8ll * lo_height)
+        return fail(FF_ERR_INVALID_ARG, "%s: height %d must be in lo_height .. 8 lo_height (lo_height %d)", who, height, lo_height);
+    if (!(p->alpha_min > 0.f && p->alpha_min <= 1.f)) return fail(FF_ERR_INVALID_ARG, "%s: alpha_min must be in (0, 1] (got %g)", who, (double)p->alpha_min);
+    if (!(p->gamma > 0.f) || !std::isfinite(p->gamma)) return fail(FF_ERR_INVALID_ARG, "%s: gamma must be positive and finite (got %g)", who, (double)p->gamma);
+    if (!(p->lo_jitter[0] >= 0.f && p->lo_jitter[0] < 1.f && p->lo_jitter[1] >= 0.f && p->lo_jitter[1] < 1.f))
+        return fail(FF_ERR_INVALID_ARG, "%s: lo_jitter must be in [0, 1) (got %g %g)", who, (double)p->lo_jitter[0], (double)p->lo_jitter[1]);
+    if (p->flags & ~(FF_TAA_BILINEAR | FF_TAA_NO_CLAMP)) return fail(FF_ERR_INVALID_ARG, "%s: unknown flags 0x%x", who, p->flags);
+    if (p->reserved != 0) return fail(FF_ERR_INVALID_ARG, "%s: reserved must be 0", who);
+    if (!radiance_lo) return fail(FF_ERR_INVALID_ARG, "%s: radiance_lo is null", who);
+    if (!ids_lo) return fail(FF_ERR_INVALID_ARG, "%s: ids_lo is null", who);
+    if (!position) return fail(FF_ERR_INVALID_ARG, "%s: position is null", who);
+    if (!ids) return fail(FF_ERR_INVALID_ARG, "%s: ids is null", who);
+    TaaUpscaleArgs a;
+    std::memset(&a, 0, sizeof a);
+    FfMat4 cm;
+    bool invertible = inverse_ray_matrix(camera, a.taa.inv_cur, &cm);
+    for (int k = 0; k < 16; ++k) invertible = invertible && std::isfinite(a.taa.inv_cur[k]); // (a degenerate camera gives NaN, not 0)
+    if (!invertible) return fail(FF_ERR_INVALID_ARG, "%s: the camera's ray matrix is singular", who);
+    if (!s->has_scene) return fail(FF_ERR_NO_SCENE, "%s: no scene uploaded (the history follows its geometries)", who);
+    ReprojectionHistory& hist = s->history[FfState::kHistoryTaaUpscale];
+    float inv_prev[16] = {};
+    if (hist.valid) {
+        FfMat4 pm;
+        if (!inverse_ray_matrix(&hist.camera, inv_prev, &pm)) return fail(FF_ERR_INVALID_ARG, "%s: the previous camera's ray matrix is singular", who);
+    }
+    FF_HIP(hipSetDevice(s->device));
+    const size_t lo_px = (size_t)lo_width * (size_t)lo_height, px = (size_t)width * (size_t)height;
+    hipStream_t stream = s->stream;
+    // host buffers are staged, as in ff_upscale: the inputs the call reads, the outputs it writes
+    const float* d_rad = radiance_lo;
+    const int* d_ids_lo = ids_lo;
+    const float* d_pos = position;
+    const int* d_ids = ids;
+    unsigned char* d_rgb8 = (unsigned char*)rgb8;
+    float* d_out = radiance_out;
+    Staging stage(&s->d_img_stage, &s->img_stage_bytes);
+    if (!inputs_on_device) {
+        stage.in(&d_rad, radiance_lo, lo_px * 12);
+        stage.in(&d_ids_lo, ids_lo, lo_px * 12);
+        stage.in(&d_pos, position, px * 12);
+        stage.in(&d_ids, ids, px * 12);
+    }
+    if (rgb8 && !rgb8_on_device) stage.out(&d_rgb8, rgb8, px * 3);
+    if (radiance_out && !radiance_out_on_device) stage.out(&d_out, radiance_out, px * 12);
+    int st = stage.commit(stream, "ff_taa_upscale: staging the inputs failed");
+    if (st != FF_OK) return st;
+    // history: ff_taa's, on the high grid; kept only while both sizes stay what they were
+    if (lo_width != s->taa_upscale_lo_width || lo_height != s->taa_upscale_lo_height) hist.invalidate();
+    ReprojectionHistory::Frame f;
+    st = hist.begin(s->h_geoms, width, height, 2 * px * sizeof(float4) + px * sizeof(float2), stream, &f);
+    if (st != FF_OK) return st;
+    const TaaArgs buffers = taa_buffers(hist.d_work, width, height, f.cur);
+    a.taa.width = width;
+    a.taa.height = height;
+    a.taa.cur = f.cur;
+    a.taa.hist[0] = buffers.hist[0];
+    a.taa.hist[1] = buffers.hist[1];
+    a.taa.motion = buffers.motion;
+    a.taa.has_history = f.has_history ? 1 : 0;
+    a.taa.bilinear = (p->flags & FF_TAA_BILINEAR) ? 1 : 0;
+    a.taa.clamp = (p->flags & FF_TAA_NO_CLAMP) ? 0 : 1;
+    a.taa.alpha_min = p->alpha_min;
+    a.taa.gamma = p->gamma;
+    std::memcpy(a.taa.ray, cm.m, sizeof a.taa.ray);
+    a.taa.far_clip = camera->m_farClip;
+    a.taa.screen_w = camera->m_screenWidth;
+    a.taa.screen_h = camera->m_screenHeight;
+    a.taa.num_geoms = f.num;
+    a.taa.geoms = f.geoms;
+    if (f.has_history) {
+        a.taa.cam_rest = std::memcmp(camera, &hist.camera, sizeof(FfCamera)) == 0 ? 1 : 0;
+        std::memcpy(a.taa.inv_prev, inv_prev, sizeof inv_prev);
+        a.taa.prev_screen_w = hist.camera.m_screenWidth;
+        a.taa.prev_screen_h = hist.camera.m_screenHeight;
+    }
+    a.lo_width = lo_width;
+    a.lo_height = lo_height;
+    a.lo_jx = p->lo_jitter[0];
+    a.lo_jy = p->lo_jitter[1];
+    a.sx = (float)width / (float)lo_width;
+    a.sy = (float)height / (float)lo_height;
+    FF_HIP(launch_taa_upscale(a, d_rad, d_ids_lo, d_pos, d_ids, d_rgb8, d_out, stream));
+    FF_HIP(hipStreamSynchronize(stream));
+    hist.commit(s->h_geoms, camera, width, height, f);
+    s->taa_upscale_lo_width = lo_width;
+    s->taa_upscale_lo_height = lo_height;
+    return stage.finish();
+}
+
+int ff_taa_upscale_reset(FfState* s) { return history_reset(s, FfState::kHistoryTaaUpscale, "ff_taa_upscale_reset"); }
+
+int ff_taa_upscale_history(FfState* s, float* motion, float* length, int on_device)
+{
+    return history_readback(s, FfState::kHistoryTaaUpscale, "ff_taa_upscale_history", "ff_taa_upscale", motion, length, on_device,
                             [s](const ReprojectionHistory& h, float* d_motion, float* d_length) {
                                 return launch_taa_history(taa_buffers(h.d_work, h.width, h.height, h.cur), d_motion, d_length, s->stream);
                             });

@@ -120,9 +120,11 @@ struct FfState {
     size_t dn_work_bytes = 0;
     // The reprojection histories (ff_image.h).  ff_denoise_temporal (ff_temporal.hip): two sets of 4 float4 per pixel (guide position
     // and class, unit normal, colour history, moments {l, l^2, len}), then the two working colour buffers and the motion (float2 per
-    // pixel).  ff_taa (ff_taa.hip): two buffers of one float4 per pixel {rgb, len}, then the motion.
-    enum { kHistoryTemporal = 0, kHistoryTaa = 1 };
-    ff::ReprojectionHistory history[2];
+    // pixel).  ff_taa (ff_taa.hip): two buffers of one float4 per pixel {rgb, len}, then the motion.  ff_taa_upscale
+    // (ff_taa_upscale.hip): ff_taa's layout on the high grid; its history also belongs to the low size of the call that wrote it.
+    enum { kHistoryTemporal = 0, kHistoryTaa = 1, kHistoryTaaUpscale = 2 };
+    ff::ReprojectionHistory history[3];
+    int taa_upscale_lo_width = 0, taa_upscale_lo_height = 0;
     // sub-pixel jitter of the primary rays (ff_set_pixel_jitter): composed into the ray matrix of ff_render* and ff_gbuffer
     float jitter_x = 0.f, jitter_y = 0.f;
     // Per-sample camera rays (ff_camera.cpp, ff_set_camera_sampling): belongs to the state, like the jitter, so it outlives uploads and

@@ -7,8 +7,8 @@
 // with -ffp-contract=off), true divisions and square roots (correctly rounded on the device under the library's flags, so the two
 // sides differ only in expf).  A dot product is (x + y) + z, as everywhere in the library.
 //
-// Not offered: a temporal upsampler (ff_taa writing a larger image than it reads), upscaling ff_denoise_temporal's history,
-// non-uniform or foveated sampling, a multi-GPU twin.
+// Not offered: upscaling ff_denoise_temporal's history, non-uniform or foveated sampling, a multi-GPU twin.  (The temporal
+// upsampler is ff_taa_upscale: ff_taa_upscale.h.)
 #pragma once
 
 #include <math.h>

@@ -39,6 +39,7 @@ EXPORTS = [
     "ff_set_roughness", "ff_glossy_eval", "ff_glossy_sample", "ff_scene_file_roughness",
     "ff_camera_sampling_init", "ff_set_camera_sampling", "ff_camera_sample_rays", "ff_scene_file_camera_sampling",
     "ff_upscale_params_init", "ff_upscale", "ff_upscale_host",
+    "ff_taa_upscale_params_init", "ff_taa_upscale", "ff_taa_upscale_reset", "ff_taa_upscale_history",
 ]
 DIST_ID_BYTES = 128
 
@@ -222,6 +223,11 @@ def load():
     lib.ff_upscale_params_init.restype = None
     lib.ff_upscale.argtypes = [vp, P(T.FfUpscaleParams), i32, i32, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, i32, vp, i32, vp, i32]
     lib.ff_upscale_host.argtypes = [P(T.FfUpscaleParams), i32, i32, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp]
+    lib.ff_taa_upscale_params_init.argtypes = [P(T.FfTaaUpscaleParams)]
+    lib.ff_taa_upscale_params_init.restype = None
+    lib.ff_taa_upscale.argtypes = [vp, P(T.FfCamera), P(T.FfTaaUpscaleParams), i32, i32, vp, vp, i32, i32, vp, vp, i32, vp, i32, vp, i32]
+    lib.ff_taa_upscale_reset.argtypes = [vp]
+    lib.ff_taa_upscale_history.argtypes = [vp, vp, vp, i32]
     _lib = real
     return real
 
@@ -561,6 +567,17 @@ def upscale_params(**overrides):
         if name not in dict(T.FfUpscaleParams._fields_):
             raise TypeError(f"FfUpscaleParams has no field {name!r}")
         setattr(p, name, (C.c_float * 2)(*value) if name in ("lo_jitter", "hi_jitter") else value)
+    return p
+
+
+def taa_upscale_params(**overrides):
+    """ff_taa_upscale_params_init's defaults with the given fields replaced (any FfTaaUpscaleParams field; lo_jitter as a pair)."""
+    p = T.FfTaaUpscaleParams()
+    load().ff_taa_upscale_params_init(C.byref(p))
+    for name, value in overrides.items():
+        if name not in dict(T.FfTaaUpscaleParams._fields_):
+            raise TypeError(f"FfTaaUpscaleParams has no field {name!r}")
+        setattr(p, name, (C.c_float * 2)(*value) if name == "lo_jitter" else value)
     return p
 
 
@@ -962,6 +979,47 @@ class Tracer:
         check(self._lib.ff_upscale(self._state, C.byref(p), lo_width, lo_height, vp(radiance_lo_ptr), vp(position_lo_ptr), vp(normal_lo_ptr),
                                    vp(albedo_lo_ptr), vp(ids_lo_ptr), width, height, vp(position_ptr), vp(normal_ptr), vp(albedo_ptr), vp(ids_ptr), 1,
                                    vp(rgb8_ptr), 1, vp(radiance_out_ptr), 1))
+
+    def taa_upscale(self, radiance_lo, gbuffer_lo, gbuffer_hi, camera, p=None):
+        """ff_taa_upscale of this frame's host radiance [h,w,3], rendered under p.lo_jitter, with the ids of its gbuffer() (same
+        jitter) and the position and ids of the unjittered [H,W] gbuffer() of `camera` (the W x H pose); the history stays in the
+        state -> (rgb8 [H,W,3] uint8, radiance [H,W,3] float32)."""
+        rad = np.ascontiguousarray(radiance_lo, dtype=np.float32)
+        ids_lo = np.ascontiguousarray(gbuffer_lo["ids"], dtype=np.int32)
+        pos = np.ascontiguousarray(gbuffer_hi["position"], dtype=np.float32)
+        ids = np.ascontiguousarray(gbuffer_hi["ids"], dtype=np.int32)
+        h, w = rad.shape[:2]
+        H, W = ids.shape[:2]
+        if rad.shape != (h, w, 3) or ids_lo.shape != (h, w, 3) or pos.shape != (H, W, 3) or ids.shape != (H, W, 3):
+            raise ValueError("taa_upscale: radiance_lo and gbuffer_lo must be [h,w,3] and gbuffer_hi [H,W,3]")
+        p = p if p is not None else taa_upscale_params()
+        rgb8 = np.zeros((H, W, 3), dtype=np.uint8)
+        out = np.zeros((H, W, 3), dtype=np.float32)
+        check(self._lib.ff_taa_upscale(self._state, C.byref(camera), C.byref(p), w, h, rad.ctypes.data, ids_lo.ctypes.data, W, H, pos.ctypes.data,
+                                       ids.ctypes.data, 0, rgb8.ctypes.data, 0, out.ctypes.data, 0))
+        self._taa_upscale_size = (H, W)
+        return rgb8, out
+
+    def taa_upscale_device(self, camera, lo_width, lo_height, radiance_lo_ptr, ids_lo_ptr, width, height, position_ptr, ids_ptr, p=None, rgb8_ptr=None,
+                           radiance_out_ptr=None):
+        """ff_taa_upscale on DEVICE buffers (raw pointers); the outputs must not overlap an input."""
+        p = p if p is not None else taa_upscale_params()
+        vp = lambda q: C.c_void_p(q) if q else None  # noqa: E731
+        check(self._lib.ff_taa_upscale(self._state, C.byref(camera), C.byref(p), lo_width, lo_height, vp(radiance_lo_ptr), vp(ids_lo_ptr), width, height,
+                                       vp(position_ptr), vp(ids_ptr), 1, vp(rgb8_ptr), 1, vp(radiance_out_ptr), 1))
+        self._taa_upscale_size = (height, width)
+
+    def taa_upscale_reset(self):
+        """Drop the temporal upsampler's history (ff_taa_upscale_reset)."""
+        check(self._lib.ff_taa_upscale_reset(self._state))
+
+    def taa_upscale_history(self):
+        """The last taa_upscale call's (motion [H,W,2] float32, history length [H,W] float32)."""
+        h, w = getattr(self, "_taa_upscale_size", (0, 0))
+        motion = np.zeros((h, w, 2), dtype=np.float32)
+        length = np.zeros((h, w), dtype=np.float32)
+        check(self._lib.ff_taa_upscale_history(self._state, motion.ctypes.data if h * w else None, length.ctypes.data if h * w else None, 0))
+        return motion, length
 
     def display(self, radiance, p=None, want_rgb8=True, want_out=True):
         """ff_display of host radiance [H,W,3] -> (rgb8 [H,W,3] uint8, display_out [H,W,3] float32: the curve's output in [0, 1]);

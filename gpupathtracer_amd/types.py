@@ -155,6 +155,13 @@ class FfUpscaleParams(C.Structure):
 UPSCALE_PARAMS_BYTES = 32
 
 
+class FfTaaUpscaleParams(C.Structure):
+    _fields_ = [("alpha_min", C.c_float), ("gamma", C.c_float), ("lo_jitter", C.c_float * 2), ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+TAA_UPSCALE_PARAMS_BYTES = 24
+
+
 class FfDisplayParams(C.Structure):
     _fields_ = [
         ("curve", C.c_int32), ("encoding", C.c_int32), ("flags", C.c_int32), ("exposure", C.c_float), ("white", C.c_float), ("key", C.c_float),

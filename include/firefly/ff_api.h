@@ -737,8 +737,8 @@ FF_API void ff_upscale_params_init(FfUpscaleParams* p);
  * work for: a NULL state, params, radiance_lo, position, normal or ids of either grid; a NULL albedo of either grid with
  * DEMODULATE_ALBEDO (without it albedo is not read); sizes outside 1 <= lo <= hi <= 8 lo per axis or hi > 65535; a sigma that is
  * not positive and finite; a jitter outside [0, 1); unknown flags; a nonzero `reserved`.
- * Not offered: a temporal upsampler (ff_taa writing a larger image than it reads), upscaling ff_denoise_temporal's history,
- * non-uniform or foveated sampling, a multi-GPU twin. */
+ * Not offered: upscaling ff_denoise_temporal's history, non-uniform or foveated sampling, a multi-GPU twin.  (The temporal
+ * upsampler is ff_taa_upscale.) */
 FF_API int ff_upscale(FfState* state, const FfUpscaleParams* p,
                       int lo_width, int lo_height, const float* radiance_lo, const float* position_lo, const float* normal_lo,
                       const float* albedo_lo, const int32_t* ids_lo,
@@ -752,6 +752,82 @@ FF_API int ff_upscale_host(const FfUpscaleParams* p,
                            const float* albedo_lo, const int32_t* ids_lo,
                            int width, int height, const float* position, const float* normal, const float* albedo, const int32_t* ids,
                            unsigned char* rgb8, float* radiance_out);
+
+/* ---- temporal upsampling (ff_taa writing a larger image than it reads) --------------------------- */
+
+/* Defaults: alpha_min 0.1, gamma 1 (ff_taa's), lo_jitter 0 0, Catmull-Rom history with the clamp (flags 0). */
+FF_API void ff_taa_upscale_params_init(FfTaaUpscaleParams* p);
+
+/* Accumulates jittered w x h frames (lo_width x lo_height) into a W x H image (width x height): a viewer at rest that cycles
+ * ff_jitter_sequence over low-resolution frames ends up with the full-resolution picture - shadow edges, reflections and every
+ * texture included - where ff_upscale alone can only sharpen one low frame along the G-buffer's edges.  `camera` is the pose
+ * with m_screenWidth x m_screenHeight = W x H.  position and ids are ff_gbuffer's at W x H under jitter 0 0.  radiance_lo
+ * (w x h float3) is a frame of the same pose with the screen set to w x h, rendered under ff_set_pixel_jitter(lo_jitter); it
+ * must be an FF_PIXEL_CORNER frame, because FF_PIXEL_BOX frames ignore the state's jitter.  ids_lo is ff_gbuffer's at w x h under
+ * that jitter.  The caller is responsible for the pose; only the sizes are checked.  The state keeps a history of its own (colour
+ * and length per high pixel, the previous camera and the per-geometry model matrices), separate from ff_taa's and
+ * ff_denoise_temporal's.  All arithmetic is float32, evaluated as parenthesised, no fused multiply-add.  P(M, X), M_cur, M_prev
+ * as in ff_taa.  Per high pixel P = (X, Y) with (g_P, k_P) = its geometry index and bxdf type, (jx, jy) = lo_jitter:
+ *   1 motion  hit of geometry g: x^ = Mprev_g inverse(Mcur_g) x_p (ff_denoise_temporal's rows, composed in double on the host),
+ *             m = P(M_prev, x^) - P(M_cur, x_p).  Miss: X = the kernel.cu:203 far point of the pixel's unjittered ray under M_cur,
+ *             m = P(M_prev, X) - (x, y).  Camera bitwise the previous call's and g not moved (a miss: the camera alone): m = 0
+ *             exactly, nothing is projected
+ *     history looked up at h = (X, Y) + m in the W x H history.  Valid when there is history, q.w > 0 (of P(M_prev, .)),
+ *             0 <= h.x <= W-1, 0 <= h.y <= H-1 and g's mesh was not replaced by ff_update_mesh since the previous call.  Colour: the
+ *             4x4 Catmull-Rom sum around floor(h), taps clamped into the image, t = h - floor(h) per axis, weights
+ *             ((-t^3 + 2t^2 - t)/2, (3t^3 - 5t^2 + 2)/2, (-3t^3 + 4t^2 + t)/2, (t^3 - t^2)/2) for floor(h) - 1 .. floor(h) + 2,
+ *             not renormalised (FF_TAA_BILINEAR: the 2x2 taps floor(h) + {0, 1} with weights (1 - t, t)).  A resampled colour
+ *             that is not finite (a zero weight times a stored NaN included) is no history: invalid.  len_h: the history
+ *             length at the nearest tap floor(h + 0.5).  m = 0 gives t = 0: exactly the pixel's own history
+ *   2 look    u = ((float)X * (float)w) / (float)W - jx, v likewise from Y, h, H, jy: where P's ray crosses the low frame.  The
+ *             nearest low sample q* = (i*, j*), i* = clamp(floor(u + 0.5), 0, w-1), j* likewise; dx = u - (float)i*, dy likewise
+ *   3 confidence  k = max(0, 1 - |dx| * sx) * max(0, 1 - |dy| * sy), sx = (float)W / (float)w, sy = (float)H / (float)h, each
+ *             formed once: a tent one high pixel wide about the point the low ray went through.  k = 0 when (geometry, bxdf) of
+ *             ids_lo[q*] differ from (g_P, k_P) (a miss matches a miss), and when radiance_lo[q*] is not finite in all three
+ *             channels.  The current sample is c = radiance_lo[q*]
+ *   4 spatial estimate c_up (used only in step 6's last case): ff_upscale's step 3 applied to every P, then its step 4.  The mean
+ *             (ff_upscale's "mean") over the 2x2 taps about (floor u, floor v) whose bilinear weight is > 0, whose (geometry,
+ *             bxdf) equal P's and whose radiance is finite, weights b_q; else over the 4x4 taps under the same rule with weight 1;
+ *             else radiance_lo[q*] as it is
+ *   5 clamp   (not with FF_TAA_NO_CLAMP, not without valid history, not when k = 0) ff_taa's YCoCg box (mean +- gamma sigma, cut by
+ *             min / max, over the finite samples only) over the 3x3 low pixels about q*, coordinates clamped into the low image.
+ *             With no finite sample nothing is clamped
+ *   6 blend   with valid history, wsum = min(len_h + k, 4096).
+ *             wsum > 0 and k > 0: alpha = max(alpha_min * k, k / wsum), o = h' + alpha (c - h') with h' the clamped history,
+ *                                 len = wsum
+ *             wsum > 0 and k = 0: o = h exactly (the unclamped history, no arithmetic on c), len = len_h
+ *             no valid history and k > 0: o = c, len = k
+ *             every other case:   o = c_up, len = 0
+ *   stored    {o, len} is the next call's history, m the motion; rgb8 = trunc(clamp(o * 255)).
+ * Consequences.  Equal sizes and lo_jitter 0 0 give k = 1 on finite input, and the call is ff_taa's, bit for bit.  With a
+ * factor 2 and jitters in {0, 1/2}^2, u, dx and k are exact and k is 0 or 1: at rest, a cycle of the four jitters hands every high
+ * pixel, exactly once, the low sample whose ray is its own; under FF_TAA_NO_CLAMP the accumulated image is then the
+ * full-resolution image's samples, bit for bit, with every length 1, and a second cycle of the same frames leaves the bits alone
+ * and makes every length 2.  (From the second frame on, a pixel's first sample c meets the c_up the frame before stored with
+ * length 0, at alpha = 1: o = h + (c - h), which is c whenever c - h is exact, as it is for h / 2 <= c <= 2 h.)  A non-finite low
+ * pixel never enters a history as c: it can reach an output only through c_up's last fallback.
+ * History is dropped by ff_taa_upscale_reset, the first call, a change of either size and ff_upload_scene; ff_update_mesh(g)
+ * drops geometry g's only; ff_update_transforms moves it with its geometry.  The call leaves FfStats, the stored primary hits
+ * and their key, the other histories and the progressive sum as they were.  rgb8 (W*H*3 bytes) and radiance_out (W*H*3 floats)
+ * may each be NULL and must not overlap an input.  inputs_on_device covers all four input images.  Synchronous, on the state's
+ * stream.  FF_ERR_NO_SCENE without a scene.  FF_ERR_INVALID_ARG, naming the field, before any device work and with the history
+ * untouched, for: a NULL state, params, camera or input; sizes outside 1 <= lo <= hi <= 8 lo per axis or hi > 65535; alpha_min
+ * outside (0, 1]; gamma <= 0 or not finite; a jitter outside [0, 1) or not finite; unknown flags; a nonzero `reserved`; a singular
+ * ray matrix.
+ * Not offered: guides other than ids (normals, albedo demodulation), ff_denoise_temporal's moments at high resolution, a jittered
+ * high G-buffer, a multi-GPU twin. */
+FF_API int ff_taa_upscale(FfState* state, const FfCamera* camera, const FfTaaUpscaleParams* p,
+                          int lo_width, int lo_height, const float* radiance_lo, const int32_t* ids_lo,
+                          int width, int height, const float* position, const int32_t* ids, int inputs_on_device,
+                          void* rgb8, int rgb8_on_device, float* radiance_out, int radiance_out_on_device);
+
+/* Drops the temporal upsampler's history: the next ff_taa_upscale call starts afresh. */
+FF_API int ff_taa_upscale_reset(FfState* state);
+
+/* The last ff_taa_upscale call's per-pixel motion m (W*H*2 floats; 0 on the first call after a reset and where q.w <= 0) and
+ * history length (W*H floats: the confidence accumulated so far).  Either may be NULL.  FF_ERR_INVALID_ARG when no call was made
+ * since the last reset. */
+FF_API int ff_taa_upscale_history(FfState* state, float* motion, float* length, int on_device);
 
 /* ---- display transform (exposure, bloom, tone curve, sRGB) ------------------------------------- */
 

@@ -287,6 +287,16 @@ typedef struct FfUpscaleParams {
     uint32_t reserved;      /* 0 */
 } FfUpscaleParams;          /* 32 bytes */
 
+/* ff_taa_upscale: temporal upsampling, ff_taa writing a W x H image from jittered w x h frames.  ff_taa_upscale_params_init gives
+ * the defaults; the operator is in ff_api.h. */
+typedef struct FfTaaUpscaleParams {
+    float   alpha_min;     /* least weight of a full-confidence sample, in (0, 1] (ff_taa's) */
+    float   gamma;         /* half-width of the clamp box in standard deviations, > 0 (ff_taa's) */
+    float   lo_jitter[2];  /* the pixel jitter (ff_set_pixel_jitter) the LOW frame and ids_lo were made under, each in [0, 1) */
+    int32_t flags;         /* FF_TAA_BILINEAR | FF_TAA_NO_CLAMP, as in ff_taa */
+    int32_t reserved;      /* 0 */
+} FfTaaUpscaleParams;      /* 24 bytes */
+
 /* ff_display: the display transform, W x H float3 radiance -> 8-bit RGB (exposure, bloom, tone curve, encoding).
  * ff_display_params_init gives the defaults; the formulas are in ff_api.h. */
 #define FF_CURVE_CLAMP     0   /* y = x */
