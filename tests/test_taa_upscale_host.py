@@ -86,3 +86,33 @@ def test_the_reference_rebuilds_the_target_from_a_cycle_of_jittered_low_frames()
     print(f"factor 3: largest relative error {err.max():.3g}, lengths {r['length'].min():.7f} .. {r['length'].max():.7f}")
     assert np.allclose(r["out"], target, rtol=1e-5, atol=0)
     assert np.allclose(r["length"], 1.0, rtol=1e-5, atol=0)
+
+
+def test_the_reference_rebuilds_the_target_from_sixteen_quarter_resolution_frames():
+    """Factor 4, 68 x 36 from 17 x 9 (tiles cut on both edges): low frame (a, b) is target[b::4, a::4] under jitter (a/4, b/4).
+    u = (X * 17) / 68 - a/4 is exactly X/4 - a/4 in float32, so k is 1 on the pixel's own sample and 0 on every other (|dx| >= 1/4:
+    the tent, one high pixel wide, is 0 there), and the argument of the factor-2 cycle holds phase by phase: after the sixteen
+    frames the image is the target bit for bit with every length 1, and a second cycle brings every length to 2."""
+    W, H, F = 68, 36, 4
+    target, gb = _target(W, H, 13)
+    cam = scenes.posed_camera(W, H, position=(0.0, 0.0, 2.4), yaw=-90.0, pitch=0.0)
+    ref = TaaUpscaleRef()
+    done = np.zeros((H, W), bool)
+    for cycle in range(2):
+        for b in range(F):
+            for a in range(F):
+                p = lib.taa_upscale_params(lo_jitter=(a / F, b / F), flags=T.TAA_NO_CLAMP)
+                r = ref.step(target[b::F, a::F], gb["ids"][b::F, a::F], gb, cam, [IDENTITY] * 3, p)
+                own = np.zeros((H, W), bool)
+                own[b::F, a::F] = True
+                assert np.array_equal(r["k"], own.astype(np.float32))
+                if cycle == 0 and (a, b) == (0, 0):
+                    assert (r["case"][own] == FIRST).all() and (r["case"][~own] == SPATIAL).all()
+                else:
+                    assert (r["case"][own] == BLEND).all()
+                    assert (r["case"][~own & done] == HOLD).all() and (r["case"][~own & ~done] == SPATIAL).all()
+                done |= own
+                assert np.array_equal(r["out"][done], target.astype(np.float64)[done])
+                assert not r["tainted"].any() and not r["motion"].any()
+        assert done.all() and np.array_equal(r["out"], target.astype(np.float64))
+        assert (r["length"] == cycle + 1).all()

@@ -10,6 +10,7 @@ from gpupathtracer_amd import lib
 from gpupathtracer_amd import types as T
 from gbuffer_ref import filterable, rgb8_of
 from upscale_ref import STEP_2X2, STEP_FALLBACK, bilinear_ref, upscale_ref
+from upscale_views import EDGE_FLAGS, EDGE_JITTERS, EDGE_PAIRS, EDGE_SIGMAS, SCALING_EXPONENT, noisy_radiance, pair_id, view, zero_normal_patch
 
 BOTH = T.DENOISE_SAME_GEOMETRY | T.DENOISE_DEMODULATE_ALBEDO
 PALETTE = np.array([[0.3, 0.2, 0.1], [1.5, 0.7, 0.2], [0.05, 0.4, 0.9], [2.0, 2.0, 2.0], [0.6, 0.6, 0.3]], dtype=np.float32)
@@ -19,62 +20,16 @@ def bits(a):
     return np.ascontiguousarray(a).view(np.uint32)
 
 
-def view(w, h, jitter=(0.0, 0.0)):
-    """The G-buffer of one fixed synthetic view at w x h under a pixel jitter: pixel (x, y) looks at s = (x + jx) / w,
-    t = (y + jy) / h.  Two planes meeting at the edge s = 0.55 (the left one with a checker albedo of 48 x 27 squares, the right one
-    tilted, its normal not unit length and its green albedo 0 in a band), a disc with a sphere's normals, a band of misses on top,
-    an emitter and a mirror."""
-    yy, xx = np.mgrid[0:h, 0:w].astype(np.float64)
-    s, t = (xx + jitter[0]) / w, (yy + jitter[1]) / h
-    ids = np.zeros((h, w, 3), np.int32)
-    ids[..., 1] = -1
-    ids[..., 2] = T.BXDF_DIFFUSE
-    pos = np.stack([s, t, np.zeros_like(s)], -1)
-    nrm = np.zeros((h, w, 3)) + np.array([0.0, 0.0, 1.0])
-    checker = ((np.floor(s * 48) + np.floor(t * 27)) % 2 == 0)[..., None]
-    alb = np.where(checker, np.array([0.8, 0.6, 0.4]), np.array([0.2, 0.3, 0.5]))
-    right = s >= 0.55
-    ids[right, 0] = 1
-    pos[right, 2] = (s[right] - 0.55) * 0.8
-    nrm[right] = np.array([-0.8, 0.0, 1.0]) * 1.7
-    alb[right] = np.array([0.7, 0.5, 0.6])
-    alb[right & (t > 0.7), 1] = 0.0
-    dx, dy = s - 0.3, t - 0.55
-    disc = dx * dx + dy * dy < 0.15 ** 2
-    ids[disc, 0] = 2
-    nz = np.sqrt(np.maximum(0.15 ** 2 - dx * dx - dy * dy, 0.0))
-    sphere_n = np.stack([dx, dy, nz], -1) / 0.15
-    nrm[disc] = sphere_n[disc]
-    pos[disc] = (np.array([0.3, 0.55, 0.0]) + 0.15 * sphere_n)[disc]
-    alb[disc] = np.array([0.9, 0.9, 0.2])
-    for geom, kind, box, colour in ((3, T.BXDF_EMITTER, (0.62, 0.8, 0.3, 0.5), (5.0, 5.0, 5.0)), (4, T.BXDF_MIRROR, (0.1, 0.3, 0.15, 0.3), (0.9, 0.9, 0.9))):
-        m = (s >= box[0]) & (s < box[1]) & (t >= box[2]) & (t < box[3])
-        ids[m, 0] = geom
-        ids[m, 2] = kind
-        alb[m] = colour
-    miss = t < 0.12
-    ids[miss] = -1
-    pos[miss] = 0.0
-    nrm[miss] = 0.0
-    alb[miss] = 0.0
-    return {"ids": ids, "position": pos.astype(np.float32), "normal": nrm.astype(np.float32), "albedo": alb.astype(np.float32)}
-
-
-def noisy_radiance(gb, seed=7):
-    """Smooth light times the albedo times seeded noise on the filterable pixels; sky, emitter and mirror colours elsewhere."""
-    rng = np.random.default_rng(seed)
-    h, w = gb["ids"].shape[:2]
-    yy, xx = np.mgrid[0:h, 0:w]
-    light = np.stack([0.6 + 0.3 * np.sin(xx * 9.0 / w), 0.5 + 0.2 * np.cos(yy * 7.0 / h), 0.4 + 0.3 * xx / w], -1)
-    rad = light * np.where(gb["albedo"] > 0, gb["albedo"], 0.3) * rng.uniform(0.5, 1.5, size=(h, w, 3))
-    rad = np.where(filterable(gb["ids"])[..., None], rad, gb["albedo"] * rng.uniform(0.9, 1.1, size=(h, w, 3)) + 0.05 * yy[..., None] / h)
-    return rad.astype(np.float32)
-
-
 def assert_matches(out, ref):
     big = np.abs(ref) > 1e-3
     err = np.abs(out.astype(np.float64) - ref)[big] / np.abs(ref)[big]
     assert err.max() <= 1e-4, err.max()
+
+
+def largest_error(out, ref):
+    """assert_matches' figure (0 where no reference value is above 1e-3)."""
+    big = np.abs(ref) > 1e-3
+    return float((np.abs(out.astype(np.float64) - ref)[big] / np.abs(ref)[big]).max(initial=0.0))
 
 
 def test_new_entry_points_are_exported(ff):
@@ -251,3 +206,77 @@ def test_non_finite_input_reaches_fallback_pixels_only():
     assert allowed.sum() <= 16 * len(bad)
     assert np.isfinite(out[~allowed]).all()
     assert_matches(out[~allowed], ref[~allowed])
+
+
+# ---- edge sizes, ratios and parameters (tests/upscale_views.py; test_gpu_upscale_edges.py holds the kernel to the same cases) -------
+
+@pytest.mark.parametrize("flags", EDGE_FLAGS)
+@pytest.mark.parametrize("pair", EDGE_PAIRS, ids=pair_id)
+def test_host_twin_matches_the_reference_at_edge_sizes(pair, flags):
+    """Every jitter pair and every sigma pair at every size pair and flag set: low images of one pixel, one row and one column,
+    factors 1 and 8, ratios that differ along the axes.  The reference itself stays five times inside the tolerance here (largest
+    error of the whole product: 1.86e-5), so no pixel is excused."""
+    (w, h), (W, H) = pair
+    worst = 0.0
+    for lo_j, hi_j in EDGE_JITTERS:
+        lo, hi = view(w, h, lo_j), view(W, H, hi_j)
+        rad = noisy_radiance(lo)
+        for sn, sp in EDGE_SIGMAS:
+            p = lib.upscale_params(flags=flags, sigma_normal=sn, sigma_plane=sp, lo_jitter=lo_j, hi_jitter=hi_j)
+            out8, out = lib.upscale_host(rad, lo, hi, p)
+            ref, _ = upscale_ref(rad, lo, hi, sn, sp, flags, lo_j, hi_j)
+            err = largest_error(out, ref)
+            worst = max(worst, err)
+            assert np.isfinite(out).all()
+            assert err <= 1e-4, (lo_j, hi_j, sn, sp, err)
+            assert np.array_equal(out8, rgb8_of(out))
+    print(f"{pair_id(pair)} flags {flags}: largest relative error {worst:.3g}")
+
+
+@pytest.mark.parametrize("flags", EDGE_FLAGS)
+@pytest.mark.parametrize("pair", [((21, 12), (161, 91)), ((9, 7), (65, 35))], ids=pair_id)
+def test_host_twin_matches_the_reference_on_zero_length_normals(pair, flags):
+    """A patch of filterable pixels whose guide normal is (0, 0, 0), in both views: the unit normal is 0, so a_n = 1 / sigma_normal on
+    and about the patch (10 at the default: a weight of e^-10; 80 at sigma_normal 0.0125: past the cut-off, so the pixel falls through
+    to the 4x4 round and then to the nearest low pixel)."""
+    (w, h), (W, H) = pair
+    for lo_j, hi_j in EDGE_JITTERS:
+        lo, hi = view(w, h, lo_j, zero_normal=True), view(W, H, hi_j, zero_normal=True)
+        assert zero_normal_patch(lo).sum() >= 2 and zero_normal_patch(hi).sum() >= 20
+        rad = noisy_radiance(lo)
+        for sn, sp in EDGE_SIGMAS[:3]:
+            p = lib.upscale_params(flags=flags, sigma_normal=sn, sigma_plane=sp, lo_jitter=lo_j, hi_jitter=hi_j)
+            _, out = lib.upscale_host(rad, lo, hi, p)
+            ref, steps = upscale_ref(rad, lo, hi, sn, sp, flags, lo_j, hi_j)
+            assert np.isfinite(out).all()
+            assert_matches(out, ref)
+            if sn == 0.0125:
+                assert (steps[zero_normal_patch(hi)] == STEP_FALLBACK).all()
+            else:
+                assert (steps[zero_normal_patch(hi)] == STEP_2X2).all()
+
+
+def test_the_default_view_is_unchanged_by_the_zero_normal_argument():
+    for size, jitter in (((21, 12), (0.0, 0.0)), ((161, 91), (0.25, 0.75))):
+        a, b, c = view(*size, jitter), view(*size, jitter, zero_normal=False), view(*size, jitter, zero_normal=True)
+        for k in a:
+            assert np.array_equal(bits(a[k]), bits(b[k])), k
+            assert np.array_equal(bits(a[k]), bits(c[k])) == (k != "normal"), k
+        assert not zero_normal_patch(a).any() and zero_normal_patch(c).any()
+
+
+@pytest.mark.parametrize("flags", EDGE_FLAGS)
+@pytest.mark.parametrize("pair", [((21, 12), (161, 91)), ((9, 7), (65, 35))], ids=pair_id)
+def test_power_of_two_scaling_is_exact_through_the_host_twin(pair, flags):
+    """out(rad * s) == out(rad) * s bit for bit for s = 2^-20 and 2^20, under every jitter pair: the weights do not depend on the
+    radiance, and c0 + sum w (c - c0) / sum w scales exactly as long as no product w (c - c0) goes subnormal.  With noisy_radiance
+    (every channel that is not 0 is above 0.01) none does at 2^-20, so the exponent stays 20; the kernel is held to the same exponent."""
+    (w, h), (W, H) = pair
+    for lo_j, hi_j in EDGE_JITTERS:
+        lo, hi = view(w, h, lo_j), view(W, H, hi_j)
+        rad = noisy_radiance(lo)
+        p = lib.upscale_params(flags=flags, lo_jitter=lo_j, hi_jitter=hi_j)
+        _, base = lib.upscale_host(rad, lo, hi, p)
+        for s in (np.float32(2.0 ** -SCALING_EXPONENT), np.float32(2.0 ** SCALING_EXPONENT)):
+            _, scaled = lib.upscale_host(rad * s, lo, hi, p)
+            assert np.array_equal(bits(scaled), bits(base * s)), (lo_j, hi_j, float(s))

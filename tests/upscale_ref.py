@@ -34,16 +34,20 @@ def _unit(n):
 
 
 def upscale_ref(radiance_lo, gbuffer_lo, gbuffer_hi, sigma_normal=0.1, sigma_plane=0.1,
-                flags=T.DENOISE_SAME_GEOMETRY | T.DENOISE_DEMODULATE_ALBEDO, lo_jitter=(0.0, 0.0), hi_jitter=(0.0, 0.0)):
-    """ff_upscale in float64 -> (radiance [H,W,3] float64, steps [H,W] int: STEP_2X2, STEP_4X4 or STEP_FALLBACK)."""
+                flags=T.DENOISE_SAME_GEOMETRY | T.DENOISE_DEMODULATE_ALBEDO, lo_jitter=(0.0, 0.0), hi_jitter=(0.0, 0.0), rows=None):
+    """ff_upscale in float64 -> (radiance [H,W,3] float64, steps [H,W] int: STEP_2X2, STEP_4X4 or STEP_FALLBACK).  rows = (Y0, Y1):
+    the high rows Y0 .. Y1-1 only ([Y1-Y0,W,...]: a large image is compared a band at a time)."""
     with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
-        return _upscale_ref(radiance_lo, gbuffer_lo, gbuffer_hi, sigma_normal, sigma_plane, flags, lo_jitter, hi_jitter)
+        return _upscale_ref(radiance_lo, gbuffer_lo, gbuffer_hi, sigma_normal, sigma_plane, flags, lo_jitter, hi_jitter, rows)
 
 
-def _upscale_ref(radiance_lo, gl, gh, sigma_normal, sigma_plane, flags, lo_jitter, hi_jitter):
+def _upscale_ref(radiance_lo, gl, gh, sigma_normal, sigma_plane, flags, lo_jitter, hi_jitter, rows=None):
     r = np.asarray(radiance_lo, dtype=np.float64)
     h, w = r.shape[:2]
-    ids_P = np.asarray(gh["ids"])
+    full_H = np.shape(gh["ids"])[0]
+    Y0, Y1 = rows if rows is not None else (0, full_H)
+    gh = {k: np.asarray(gh[k])[Y0:Y1] for k in ("ids", "position", "normal", "albedo") if k in gh}
+    ids_P = gh["ids"]
     H, W = ids_P.shape[:2]
     ids_lo = np.asarray(gl["ids"])
     same = bool(flags & T.DENOISE_SAME_GEOMETRY)
@@ -51,7 +55,7 @@ def _upscale_ref(radiance_lo, gl, gh, sigma_normal, sigma_plane, flags, lo_jitte
     sn = float(np.float32(sigma_normal))
     sp2 = float(np.float32(sigma_plane) * np.float32(sigma_plane))  # (the library squares it in float32)
     i0, fu, u = low_coordinates(W, w, hi_jitter[0], lo_jitter[0])
-    j0, fv, v = low_coordinates(H, h, hi_jitter[1], lo_jitter[1])
+    j0, fv, v = (c[Y0:Y1] for c in low_coordinates(full_H, h, hi_jitter[1], lo_jitter[1]))
     I0, J0 = np.broadcast_to(i0[None, :], (H, W)), np.broadcast_to(j0[:, None], (H, W))
     bu = {0: 1.0 - fu.astype(np.float64), 1: fu.astype(np.float64)}
     bv = {0: 1.0 - fv.astype(np.float64), 1: fv.astype(np.float64)}
