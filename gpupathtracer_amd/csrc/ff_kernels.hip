@@ -2395,9 +2395,6 @@ __global__ __launch_bounds__(BLOCK) void trace_bvh_kernel(const KParams p)
 //
 // Scenes of up to 32 geometries (the reference has five); larger ones run trace_bvh_kernel.
 
-#ifndef FF_POOL_DEBUG
-#define FF_POOL_DEBUG 0
-#endif
 constexpr int kPoolRing = 2048;          // queue entries (16-bit slot numbers): twice the most jobs that can be outstanding, so an
                                          // entry claimed by a consumer is never the one a producer writes
 constexpr unsigned kRingEmpty = 0xFFFFu;
@@ -2763,14 +2760,10 @@ __global__ __launch_bounds__(BLOCK) void trace_pool_kernel(const KParams p)
     unsigned long long tw_setup = 0ull, tw_role = 0ull, tw_rest = 0ull, tw_mark = __builtin_amdgcn_s_memtime();
     unsigned n_setup = 0u, n_role = 0u;
     for (unsigned turns = 0;; ++turns) {
-        if (stuck || idle_polls > kPoolSpinLimit || (FF_POOL_DEBUG && turns > (1u << 16))) {
+        (void)turns; // (counted, never read: what is left of a debug watchdog.  The loop compiles to other, equivalent code without the
+                     // counter, and this kernel's machine code is kept as it was measured.)
+        if (stuck || idle_polls > kPoolSpinLimit) {
             cnt.guard_hits |= 1ull;
-            if (FF_POOL_DEBUG) {
-                const unsigned long long bw = __ballot(waiting), bi = __ballot(inflight), ba = __ballot(active), be = __ballot(exhausted);
-                if (lane == 0)
-                    printf("pool watchdog: block %d wave %d stuck %d idle %d turns %u waiting %llx inflight %llx active %llx exhausted %llx head %u tail %u\n", (int)blockIdx.x,
-                           tid / kWave, (int)stuck, idle_polls, turns, bw, bi, ba, be, pool_u32()[Q.ctrl], pool_u32()[Q.ctrl + 1]);
-            }
             break;
         }
         // ---- what can this wave do? ----
@@ -2801,9 +2794,6 @@ __global__ __launch_bounds__(BLOCK) void trace_pool_kernel(const KParams p)
         }
         starved = 0;
         idle_polls = 0;
-#ifdef FF_EXP_NO_SETUP
-        if (do_setup) { active = false; exhausted = true; waiting = false; continue; }
-#endif
         {
             const unsigned long long now = __builtin_amdgcn_s_memtime();
             tw_rest += now - tw_mark;
@@ -3737,171 +3727,135 @@ int max_lds_nodes(int stack_depth, int block_threads, int num_geoms, size_t rese
     return avail > 0 ? (int)(avail / (long)sizeof(Bvh4Node)) : 0;
 }
 
+// The scene-size class BIG of the BVH kernels: 0 = up to kChunkGeometries geometries (records scanned in LDS), 1 = up to
+// kMaxLdsRecords (tree over the geometries, records in LDS), 2 = more (records read from global memory).
+static int scene_size_class(int num_geoms) { return num_geoms <= kChunkGeometries ? 0 : (num_geoms <= kMaxLdsRecords ? 1 : 2); }
+
+// Dynamic LDS of a launch on a scene of class `big`: the BVH layout, or the brute-force kernels' triangle batch.
+static size_t trace_lds_bytes(bool bvh, int lds_nodes, int stack_depth, int block_threads, int num_geoms, int big)
+{
+    return bvh ? bvh_lds_bytes(lds_nodes, stack_depth, block_threads, big == 2 ? 0 : num_geoms) : (size_t)kBruteBatchTris * sizeof(TriRecord);
+}
+
+// Does a scene of up to kChunkGeometries geometries need the full kernel (EXTRAS): non-quad planes or spheres, MIRROR / GLASS, smooth normals?
+static bool needs_extras(const KParams& p) { return p.num_planes > p.num_quads || p.has_specular != 0 || p.trinormals != nullptr; }
+
+// Only the BVH kernels go past the 64 KiB default (node cache + stacks + geometry records); the brute-force kernels
+// use a 48 KiB batch buffer plus a little static LDS, and asking for 160 KiB on top of static LDS is rejected.
+template <class K>
+static hipError_t allow_full_lds(K* kernel)
+{
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBudgetBytes);
+}
+
+// ---- launch tables ---------------------------------------------------------------------------------------------------
+// Every kernel family has ONE list of its instantiations (an X-macro).  prepare_kernels walks the lists to raise each BVH
+// instantiation's dynamic-LDS limit, and the family's launcher walks the same list to find the instantiation that matches the
+// run-time key: what can be launched has its attribute, and a key outside the list is hipErrorInvalidValue.
+
+// The instantiations of trace_bvh_kernel, X(STATS, BLOCK, EXTRAS, BIG, PREPASS, START), for each workgroup size: the frame's kernel
+// for scenes of up to kChunkGeometries geometries without and with extras and for the two classes of larger scenes (always with
+// extras), with and without statistics; the pre-pass, one per scene class (the general kernel, no statistics); the kernel that runs
+// on start records (diffuse small scenes).
+// The reported name is "trace_bvh_kernel<STATS, BLOCK, EXTRAS, BIG, PREPASS>" - the five parameters there were before START, as
+// tools and tests parse it - and START = true appends ", true"; the pre-pass reports one literal for all its instantiations.
+#define FF_TRACE_BVH_KERNELS_OF(X, B)                                                                                                                \
+    X(false, B, false, 0, false, false) X(true, B, false, 0, false, false) X(false, B, true, 0, false, false) X(true, B, true, 0, false, false)      \
+    X(false, B, true, 1, false, false) X(true, B, true, 1, false, false) X(false, B, true, 2, false, false) X(true, B, true, 2, false, false)        \
+    X(false, B, true, 0, true, false) X(false, B, true, 1, true, false) X(false, B, true, 2, true, false)                                           \
+    X(false, B, false, 0, false, true) X(true, B, false, 0, false, true)
+#define FF_TRACE_BVH_KERNELS(X) FF_TRACE_BVH_KERNELS_OF(X, 512) FF_TRACE_BVH_KERNELS_OF(X, 768) FF_TRACE_BVH_KERNELS_OF(X, 1024)
+#define FF_NAME_START_false ""
+#define FF_NAME_START_true ", true"
+// ... and of ray_batch_kernel, X(MODE, BIG).
+#define FF_RAY_BATCH_KERNELS(X) X(FF_TRACE_BVH, 0) X(FF_TRACE_BVH, 1) X(FF_TRACE_BVH, 2) X(FF_TRACE_BRUTE_FORCE, 0)
+
+// The instantiations of trace_pool_kernel, X(STATS, BLOCK, EXTRAS), reported as "trace_pool_kernel<STATS, BLOCK, EXTRAS>"
+// (an experiment: only the workgroup size the production kernel runs is instantiated).
+#define FF_TRACE_POOL_KERNELS(X) X(false, 1024, false) X(false, 1024, true) X(true, 1024, false) X(true, 1024, true)
+
+// The instantiations of nee_path_kernel, X(MODE, BIG, ENV, TEX, GLOSSY, CAM, name tail): the sixteen feature combinations for each of
+// BVH mode's three scene-size classes and for brute force (MODE 1 = FF_TRACE_BVH, 0 = FF_TRACE_BRUTE_FORCE).
+// The reported name is "nee_path_kernel<MODE, BIG" plus as many of ENV, TEX, GLOSSY, CAM as reach the last one that is 1 - each
+// parameter was added with a default of 0 and the older names stayed as tools and tests parse them - hence the tail column.
+#define FF_NEE_KERNELS_OF(X, MODE, BIG)                                                                               \
+    X(MODE, BIG, 0, 0, 0, 0, "")           X(MODE, BIG, 1, 0, 0, 0, ", 1")                                            \
+    X(MODE, BIG, 0, 1, 0, 0, ", 0, 1")     X(MODE, BIG, 1, 1, 0, 0, ", 1, 1")                                         \
+    X(MODE, BIG, 0, 0, 1, 0, ", 0, 0, 1")  X(MODE, BIG, 1, 0, 1, 0, ", 1, 0, 1")                                      \
+    X(MODE, BIG, 0, 1, 1, 0, ", 0, 1, 1")  X(MODE, BIG, 1, 1, 1, 0, ", 1, 1, 1")                                      \
+    X(MODE, BIG, 0, 0, 0, 1, ", 0, 0, 0, 1") X(MODE, BIG, 1, 0, 0, 1, ", 1, 0, 0, 1")                                 \
+    X(MODE, BIG, 0, 1, 0, 1, ", 0, 1, 0, 1") X(MODE, BIG, 1, 1, 0, 1, ", 1, 1, 0, 1")                                 \
+    X(MODE, BIG, 0, 0, 1, 1, ", 0, 0, 1, 1") X(MODE, BIG, 1, 0, 1, 1, ", 1, 0, 1, 1")                                 \
+    X(MODE, BIG, 0, 1, 1, 1, ", 0, 1, 1, 1") X(MODE, BIG, 1, 1, 1, 1, ", 1, 1, 1, 1")
+#define FF_NEE_KERNELS(X) FF_NEE_KERNELS_OF(X, 1, 0) FF_NEE_KERNELS_OF(X, 1, 1) FF_NEE_KERNELS_OF(X, 1, 2) FF_NEE_KERNELS_OF(X, 0, 0)
+static_assert(FF_TRACE_BVH == 1 && FF_TRACE_BRUTE_FORCE == 0, "the MODE column and the reported names spell the trace modes as numerals");
+
 hipError_t prepare_kernels()
 {
     hipError_t e;
-#define FF_SET_LDS(K)                                                                                                     \
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&K), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBudgetBytes); \
-    if (e != hipSuccess) return e;
-    // Only the BVH kernels go past the 64 KiB default (node cache + stacks + geometry records); the brute-force kernels
-    // use a 48 KiB batch buffer plus a little static LDS, and asking for 160 KiB on top of static LDS is rejected.
-    FF_SET_LDS((trace_bvh_kernel<false, 512, false>))
-    FF_SET_LDS((trace_bvh_kernel<false, 512, true>))
-    FF_SET_LDS((trace_bvh_kernel<true, 512, false>))
-    FF_SET_LDS((trace_bvh_kernel<true, 512, true>))
-    FF_SET_LDS((trace_bvh_kernel<false, 768, false>))
-    FF_SET_LDS((trace_bvh_kernel<false, 768, true>))
-    FF_SET_LDS((trace_bvh_kernel<true, 768, false>))
-    FF_SET_LDS((trace_bvh_kernel<true, 768, true>))
-    FF_SET_LDS((trace_bvh_kernel<false, 1024, false>))
-    FF_SET_LDS((trace_bvh_kernel<false, 1024, true>))
-    FF_SET_LDS((trace_bvh_kernel<true, 1024, false>))
-    FF_SET_LDS((trace_bvh_kernel<true, 1024, true>))
-    FF_SET_LDS((trace_bvh_kernel<false, 512, true, 1>))
-    FF_SET_LDS((trace_bvh_kernel<true, 512, true, 1>))
-    FF_SET_LDS((trace_bvh_kernel<false, 768, true, 1>))
-    FF_SET_LDS((trace_bvh_kernel<true, 768, true, 1>))
-    FF_SET_LDS((trace_bvh_kernel<false, 1024, true, 1>))
-    FF_SET_LDS((trace_bvh_kernel<true, 1024, true, 1>))
-    FF_SET_LDS((trace_bvh_kernel<false, 512, true, 2>))
-    FF_SET_LDS((trace_bvh_kernel<true, 512, true, 2>))
-    FF_SET_LDS((trace_bvh_kernel<false, 768, true, 2>))
-    FF_SET_LDS((trace_bvh_kernel<true, 768, true, 2>))
-    FF_SET_LDS((trace_bvh_kernel<false, 1024, true, 2>))
-    FF_SET_LDS((trace_bvh_kernel<true, 1024, true, 2>))
-    FF_SET_LDS((trace_bvh_kernel<false, 512, true, 0, true>))
-    FF_SET_LDS((trace_bvh_kernel<false, 768, true, 0, true>))
-    FF_SET_LDS((trace_bvh_kernel<false, 1024, true, 0, true>))
-    FF_SET_LDS((trace_bvh_kernel<false, 512, true, 1, true>))
-    FF_SET_LDS((trace_bvh_kernel<false, 768, true, 1, true>))
-    FF_SET_LDS((trace_bvh_kernel<false, 1024, true, 1, true>))
-    FF_SET_LDS((trace_bvh_kernel<false, 512, true, 2, true>))
-    FF_SET_LDS((trace_bvh_kernel<false, 768, true, 2, true>))
-    FF_SET_LDS((trace_bvh_kernel<false, 1024, true, 2, true>))
-    FF_SET_LDS((trace_bvh_kernel<false, 512, false, 0, false, true>))
-    FF_SET_LDS((trace_bvh_kernel<true, 512, false, 0, false, true>))
-    FF_SET_LDS((trace_bvh_kernel<false, 768, false, 0, false, true>))
-    FF_SET_LDS((trace_bvh_kernel<true, 768, false, 0, false, true>))
-    FF_SET_LDS((trace_bvh_kernel<false, 1024, false, 0, false, true>))
-    FF_SET_LDS((trace_bvh_kernel<true, 1024, false, 0, false, true>))
-    FF_SET_LDS((trace_pool_kernel<false, 1024, false>))
-    FF_SET_LDS((trace_pool_kernel<false, 1024, true>))
-    FF_SET_LDS((trace_pool_kernel<true, 1024, false>))
-    FF_SET_LDS((trace_pool_kernel<true, 1024, true>))
-    FF_SET_LDS((ray_batch_kernel<FF_TRACE_BVH>))
-    FF_SET_LDS((ray_batch_kernel<FF_TRACE_BVH, 1>))
-    FF_SET_LDS((ray_batch_kernel<FF_TRACE_BVH, 2>))
-    FF_SET_LDS((nee_path_kernel<FF_TRACE_BVH>))
-    FF_SET_LDS((nee_path_kernel<FF_TRACE_BVH, 1>))
-    FF_SET_LDS((nee_path_kernel<FF_TRACE_BVH, 2>))
-    FF_SET_LDS((nee_path_kernel<FF_TRACE_BVH, 0, 1>))
-    FF_SET_LDS((nee_path_kernel<FF_TRACE_BVH, 1, 1>))
-    FF_SET_LDS((nee_path_kernel<FF_TRACE_BVH, 2, 1>))
-    FF_SET_LDS((nee_path_kernel<FF_TRACE_BVH, 0, 0, 1>))
-    FF_SET_LDS((nee_path_kernel<FF_TRACE_BVH, 1, 0, 1>))
-    FF_SET_LDS((nee_path_kernel<FF_TRACE_BVH, 2, 0, 1>))
-    FF_SET_LDS((nee_path_kernel<FF_TRACE_BVH, 0, 1, 1>))
-    FF_SET_LDS((nee_path_kernel<FF_TRACE_BVH, 1, 1, 1>))
-    FF_SET_LDS((nee_path_kernel<FF_TRACE_BVH, 2, 1, 1>))
-    FF_SET_LDS((nee_path_kernel<FF_TRACE_BVH, 0, 0, 0, 1>))
-    FF_SET_LDS((nee_path_kernel<FF_TRACE_BVH, 1, 0, 0, 1>))
-    FF_SET_LDS((nee_path_kernel<FF_TRACE_BVH, 2, 0, 0, 1>))
-    FF_SET_LDS((nee_path_kernel<FF_TRACE_BVH, 0, 0, 1, 1>))
-    FF_SET_LDS((nee_path_kernel<FF_TRACE_BVH, 1, 0, 1, 1>))
-    FF_SET_LDS((nee_path_kernel<FF_TRACE_BVH, 2, 0, 1, 1>))
-    FF_SET_LDS((nee_path_kernel<FF_TRACE_BVH, 0, 1, 0, 1>))
-    FF_SET_LDS((nee_path_kernel<FF_TRACE_BVH, 1, 1, 0, 1>))
-    FF_SET_LDS((nee_path_kernel<FF_TRACE_BVH, 2, 1, 0, 1>))
-    FF_SET_LDS((nee_path_kernel<FF_TRACE_BVH, 0, 1, 1, 1>))
-    FF_SET_LDS((nee_path_kernel<FF_TRACE_BVH, 1, 1, 1, 1>))
-    FF_SET_LDS((nee_path_kernel<FF_TRACE_BVH, 2, 1, 1, 1>))
-#define FF_SET_LDS_CAM(ENV, TEX, GLOSSY) \
-    FF_SET_LDS((nee_path_kernel<FF_TRACE_BVH, 0, ENV, TEX, GLOSSY, 1>)) \
-    FF_SET_LDS((nee_path_kernel<FF_TRACE_BVH, 1, ENV, TEX, GLOSSY, 1>)) \
-    FF_SET_LDS((nee_path_kernel<FF_TRACE_BVH, 2, ENV, TEX, GLOSSY, 1>))
-    FF_SET_LDS_CAM(0, 0, 0)
-    FF_SET_LDS_CAM(0, 0, 1)
-    FF_SET_LDS_CAM(0, 1, 0)
-    FF_SET_LDS_CAM(0, 1, 1)
-    FF_SET_LDS_CAM(1, 0, 0)
-    FF_SET_LDS_CAM(1, 0, 1)
-    FF_SET_LDS_CAM(1, 1, 0)
-    FF_SET_LDS_CAM(1, 1, 1)
-#undef FF_SET_LDS_CAM
-#undef FF_SET_LDS
+#define FF_X(STATS, B, EXTRAS, BIG, PREPASS, START) \
+    if ((e = allow_full_lds(&trace_bvh_kernel<STATS, B, EXTRAS, BIG, PREPASS, START>)) != hipSuccess) return e;
+    FF_TRACE_BVH_KERNELS(FF_X)
+#undef FF_X
+#define FF_X(STATS, B, EXTRAS) \
+    if ((e = allow_full_lds(&trace_pool_kernel<STATS, B, EXTRAS>)) != hipSuccess) return e;
+    FF_TRACE_POOL_KERNELS(FF_X)
+#undef FF_X
+#define FF_X(MODE, BIG) \
+    if (MODE == FF_TRACE_BVH && (e = allow_full_lds(&ray_batch_kernel<MODE, BIG>)) != hipSuccess) return e;
+    FF_RAY_BATCH_KERNELS(FF_X)
+#undef FF_X
+#define FF_X(MODE, BIG, ENV, TEX, GLOSSY, CAM, TAIL) \
+    if (MODE == FF_TRACE_BVH && (e = allow_full_lds(&nee_path_kernel<MODE, BIG, ENV, TEX, GLOSSY, CAM>)) != hipSuccess) return e;
+    FF_NEE_KERNELS(FF_X)
+#undef FF_X
     return hipSuccess;
 }
 
 size_t pool_lds_bytes(int block_threads) { return (size_t)block_threads * 48 + (size_t)kPoolRing * 2 + 128; } // jobs, ring, [head, tail, -, -], the role's inputs, the workgroup's tallies
+
+// (launch_trace sends scenes of up to kChunkGeometries geometries here, and workgroups of 1024 threads)
+static hipError_t launch_pool(const KParams& p, bool collect_stats, int grid_blocks, int block_threads, hipStream_t stream, const char** kernel_name)
+{
+    const dim3 grid(grid_blocks), block(block_threads);
+    const size_t lds = bvh_lds_bytes(p.lds_nodes, p.stack_depth, block_threads, p.num_geoms) + pool_lds_bytes(block_threads);
+    const bool extras = needs_extras(p);
+    const char* name = "";
+#define FF_X(STATS, B, EXTRAS)                                                                                  \
+    if (collect_stats == STATS && block_threads == B && extras == EXTRAS) {                                     \
+        hipLaunchKernelGGL((trace_pool_kernel<STATS, B, EXTRAS>), grid, block, lds, stream, p);                 \
+        name = "trace_pool_kernel<" #STATS ", " #B ", " #EXTRAS ">";                                            \
+    } else
+    FF_TRACE_POOL_KERNELS(FF_X) return hipErrorInvalidValue;
+#undef FF_X
+    if (kernel_name) *kernel_name = name;
+    return hipGetLastError();
+}
 
 hipError_t launch_trace(const KParams& p, int trace_mode, bool collect_stats, int grid_blocks, int block_threads, hipStream_t stream,
                         const char** kernel_name, bool pool, bool prepass, bool start)
 {
     const dim3 grid(grid_blocks);
     const char* name = "";
-    if (prepass) {
-        // the pre-pass of a frame (KParams::primary_hits): one instantiation per workgroup size and scene size, the general one
+    // (the pre-pass of a frame (KParams::primary_hits) runs the BVH kernels whatever the frame's trace mode)
+    if (!prepass && trace_mode == FF_TRACE_BVH && pool && p.num_geoms <= kChunkGeometries && block_threads == 1024)
+        return launch_pool(p, collect_stats, grid_blocks, block_threads, stream, kernel_name);
+    if (prepass || trace_mode == FF_TRACE_BVH) {
         const dim3 block(block_threads);
-        const int big = p.num_geoms <= kChunkGeometries ? 0 : (p.num_geoms <= kMaxLdsRecords ? 1 : 2);
-        const size_t lds = bvh_lds_bytes(p.lds_nodes, p.stack_depth, block_threads, big == 2 ? 0 : p.num_geoms);
-#define FF_LAUNCH_PRE(B)                                                                                                  \
-    do {                                                                                                                  \
-        if (big == 0) hipLaunchKernelGGL((trace_bvh_kernel<false, B, true, 0, true>), grid, block, lds, stream, p);      \
-        else if (big == 1) hipLaunchKernelGGL((trace_bvh_kernel<false, B, true, 1, true>), grid, block, lds, stream, p); \
-        else hipLaunchKernelGGL((trace_bvh_kernel<false, B, true, 2, true>), grid, block, lds, stream, p);               \
-    } while (0)
-        if (block_threads == 1024) FF_LAUNCH_PRE(1024);
-        else if (block_threads == 768) FF_LAUNCH_PRE(768);
-        else FF_LAUNCH_PRE(512);
-#undef FF_LAUNCH_PRE
-        if (kernel_name) *kernel_name = "trace_bvh_kernel<false, B, true, big, true>"; // (the frame's own launches name their kernel exactly; nobody asks for this one)
-        return hipGetLastError();
-    }
-    if (trace_mode == FF_TRACE_BVH && pool && p.num_geoms <= kChunkGeometries && block_threads == 1024) {
-        const dim3 block(block_threads);
-        const size_t lds = bvh_lds_bytes(p.lds_nodes, p.stack_depth, block_threads, p.num_geoms) + pool_lds_bytes(block_threads);
-        const bool extras = p.num_planes > p.num_quads || p.has_specular != 0 || p.trinormals != nullptr;
-#define FF_LAUNCH_POOL(B)                                                                                                 \
-    do {                                                                                                                  \
-        if (collect_stats) {                                                                                              \
-            if (extras) { hipLaunchKernelGGL((trace_pool_kernel<true, B, true>), grid, block, lds, stream, p); name = "trace_pool_kernel<true, " #B ", true>"; } \
-            else { hipLaunchKernelGGL((trace_pool_kernel<true, B, false>), grid, block, lds, stream, p); name = "trace_pool_kernel<true, " #B ", false>"; } \
-        } else {                                                                                                          \
-            if (extras) { hipLaunchKernelGGL((trace_pool_kernel<false, B, true>), grid, block, lds, stream, p); name = "trace_pool_kernel<false, " #B ", true>"; } \
-            else { hipLaunchKernelGGL((trace_pool_kernel<false, B, false>), grid, block, lds, stream, p); name = "trace_pool_kernel<false, " #B ", false>"; } \
-        }                                                                                                                 \
-    } while (0)
-        FF_LAUNCH_POOL(1024); // (an experiment: only the workgroup size the production kernel runs is instantiated)
-#undef FF_LAUNCH_POOL
-    } else if (trace_mode == FF_TRACE_BVH) {
-        const dim3 block(block_threads);
-        const int big = p.num_geoms <= kChunkGeometries ? 0 : (p.num_geoms <= kMaxLdsRecords ? 1 : 2);
-        const size_t lds = bvh_lds_bytes(p.lds_nodes, p.stack_depth, block_threads, big == 2 ? 0 : p.num_geoms);
-        const bool spheres = p.num_planes > p.num_quads || p.has_specular != 0 || p.trinormals != nullptr; // any extra: the full kernel
-        if (start && (big != 0 || spheres || p.start_records == nullptr)) return hipErrorInvalidValue; // (the host asks for it on diffuse small scenes only)
-#define FF_LAUNCH_BVH(B)                                                                                                  \
-    do {                                                                                                                  \
-        if (start) {                                                                                                      \
-            if (collect_stats) { hipLaunchKernelGGL((trace_bvh_kernel<true, B, false, 0, false, true>), grid, block, lds, stream, p); name = "trace_bvh_kernel<true, " #B ", false, 0, false, true>"; } \
-            else { hipLaunchKernelGGL((trace_bvh_kernel<false, B, false, 0, false, true>), grid, block, lds, stream, p); name = "trace_bvh_kernel<false, " #B ", false, 0, false, true>"; } \
-        } else if (big == 1) {                                                                                                   \
-            if (collect_stats) { hipLaunchKernelGGL((trace_bvh_kernel<true, B, true, 1>), grid, block, lds, stream, p); name = "trace_bvh_kernel<true, " #B ", true, 1, false>"; } \
-            else { hipLaunchKernelGGL((trace_bvh_kernel<false, B, true, 1>), grid, block, lds, stream, p); name = "trace_bvh_kernel<false, " #B ", true, 1, false>"; } \
-        } else if (big == 2) {                                                                                            \
-            if (collect_stats) { hipLaunchKernelGGL((trace_bvh_kernel<true, B, true, 2>), grid, block, lds, stream, p); name = "trace_bvh_kernel<true, " #B ", true, 2, false>"; } \
-            else { hipLaunchKernelGGL((trace_bvh_kernel<false, B, true, 2>), grid, block, lds, stream, p); name = "trace_bvh_kernel<false, " #B ", true, 2, false>"; } \
-        } else if (collect_stats) {                                                                                       \
-            if (spheres) { hipLaunchKernelGGL((trace_bvh_kernel<true, B, true>), grid, block, lds, stream, p); name = "trace_bvh_kernel<true, " #B ", true, 0, false>"; } \
-            else { hipLaunchKernelGGL((trace_bvh_kernel<true, B, false>), grid, block, lds, stream, p); name = "trace_bvh_kernel<true, " #B ", false, 0, false>"; } \
-        } else {                                                                                                          \
-            if (spheres) { hipLaunchKernelGGL((trace_bvh_kernel<false, B, true>), grid, block, lds, stream, p); name = "trace_bvh_kernel<false, " #B ", true, 0, false>"; } \
-            else { hipLaunchKernelGGL((trace_bvh_kernel<false, B, false>), grid, block, lds, stream, p); name = "trace_bvh_kernel<false, " #B ", false, 0, false>"; } \
-        }                                                                                                                 \
-    } while (0)
-        if (block_threads == 1024) FF_LAUNCH_BVH(1024);
-        else if (block_threads == 768) FF_LAUNCH_BVH(768);
-        else FF_LAUNCH_BVH(512);
-#undef FF_LAUNCH_BVH
+        const int big = scene_size_class(p.num_geoms);
+        const size_t lds = trace_lds_bytes(true, p.lds_nodes, p.stack_depth, block_threads, p.num_geoms, big);
+        if (!prepass && start && (big != 0 || needs_extras(p) || p.start_records == nullptr)) return hipErrorInvalidValue; // (the host asks for it on diffuse small scenes only)
+        // the key of the instantiation: the pre-pass has one per workgroup size and scene size, the general one; larger scenes always run the full kernel
+        const int threads = block_threads == 1024 ? 1024 : (block_threads == 768 ? 768 : 512);
+        const bool stats = !prepass && collect_stats, extras = prepass || big != 0 || needs_extras(p), from_start = !prepass && start;
+#define FF_X(STATS, B, EXTRAS, BIG, PREPASS, START)                                                                                                  \
+    if (stats == STATS && threads == B && extras == EXTRAS && big == BIG && prepass == PREPASS && from_start == START) {                             \
+        hipLaunchKernelGGL((trace_bvh_kernel<STATS, B, EXTRAS, BIG, PREPASS, START>), grid, block, lds, stream, p);                                  \
+        name = "trace_bvh_kernel<" #STATS ", " #B ", " #EXTRAS ", " #BIG ", " #PREPASS FF_NAME_START_##START ">";                                    \
+    } else
+        FF_TRACE_BVH_KERNELS(FF_X) return hipErrorInvalidValue;
+#undef FF_X
+        if (prepass) name = "trace_bvh_kernel<false, B, true, big, true>"; // (the frame's own launches name their kernel exactly; nobody asks for this one)
     } else {
         const size_t lds = (size_t)kBruteBatchTris * sizeof(TriRecord);
         const dim3 block(kBlockThreads);
@@ -3946,14 +3900,14 @@ hipError_t launch_accumulate(float* sum, const float* frame, float* mean, unsign
 hipError_t launch_ray_batch(const RayBatchParams& p, int trace_mode, hipStream_t stream)
 {
     if (p.n <= 0) return hipSuccess;
-    const int big = p.num_geoms <= kChunkGeometries ? 0 : (p.num_geoms <= kMaxLdsRecords ? 1 : 2);
-    const size_t lds = trace_mode == FF_TRACE_BVH ? bvh_lds_bytes(p.lds_nodes, p.stack_depth, kBlockThreads, big == 2 ? 0 : p.num_geoms)
-                                                  : (size_t)kBruteBatchTris * sizeof(TriRecord);
+    const bool bvh = trace_mode == FF_TRACE_BVH;
+    const int mode = bvh ? FF_TRACE_BVH : FF_TRACE_BRUTE_FORCE, big = scene_size_class(p.num_geoms), big_key = bvh ? big : 0;
+    const size_t lds = trace_lds_bytes(bvh, p.lds_nodes, p.stack_depth, kBlockThreads, p.num_geoms, big);
     const dim3 grid((p.n + kBlockThreads - 1) / kBlockThreads), block(kBlockThreads);
-    if (trace_mode == FF_TRACE_BVH && big == 1) hipLaunchKernelGGL((ray_batch_kernel<FF_TRACE_BVH, 1>), grid, block, lds, stream, p);
-    else if (trace_mode == FF_TRACE_BVH && big == 2) hipLaunchKernelGGL((ray_batch_kernel<FF_TRACE_BVH, 2>), grid, block, lds, stream, p);
-    else if (trace_mode == FF_TRACE_BVH) hipLaunchKernelGGL((ray_batch_kernel<FF_TRACE_BVH>), grid, block, lds, stream, p);
-    else hipLaunchKernelGGL((ray_batch_kernel<FF_TRACE_BRUTE_FORCE>), grid, block, lds, stream, p);
+#define FF_X(MODE, BIG) \
+    if (mode == MODE && big_key == BIG) hipLaunchKernelGGL((ray_batch_kernel<MODE, BIG>), grid, block, lds, stream, p); else
+    FF_RAY_BATCH_KERNELS(FF_X) return hipErrorInvalidValue;
+#undef FF_X
     return hipGetLastError();
 }
 
@@ -3961,78 +3915,18 @@ hipError_t launch_nee(const NeeParams& np, int trace_mode, bool env, bool tex, b
 {
     if (np.items == 0u) return hipSuccess;
     const KParams& p = np.k;
-    const int big = p.num_geoms <= kChunkGeometries ? 0 : (p.num_geoms <= kMaxLdsRecords ? 1 : 2);
-    const size_t lds = trace_mode == FF_TRACE_BVH ? bvh_lds_bytes(p.lds_nodes, p.stack_depth, kBlockThreads, big == 2 ? 0 : p.num_geoms)
-                                                  : (size_t)kBruteBatchTris * sizeof(TriRecord);
+    const bool bvh = trace_mode == FF_TRACE_BVH, cam = np.cam_active != 0; // (cam: per-sample camera rays)
+    const int mode = bvh ? 1 : 0, big = scene_size_class(p.num_geoms), big_key = bvh ? big : 0;
+    const size_t lds = trace_lds_bytes(bvh, p.lds_nodes, p.stack_depth, kBlockThreads, p.num_geoms, big);
     const dim3 grid(grid_blocks), block(kBlockThreads);
-    const char* name;
-    if (np.cam_active != 0) {
-        // per-sample camera rays: the instantiations with CAM = 1, named by all six parameters
-#define FF_LAUNCH_CAM(MODE, BIG, ENV, TEX, GLOSSY) \
-    do { hipLaunchKernelGGL((nee_path_kernel<MODE, BIG, ENV, TEX, GLOSSY, 1>), grid, block, lds, stream, np); name = "nee_path_kernel<" #MODE ", " #BIG ", " #ENV ", " #TEX ", " #GLOSSY ", 1>"; } while (0)
-#define FF_LAUNCH_CAM_MODE(ENV, TEX, GLOSSY) \
-    do { \
-        if (trace_mode == FF_TRACE_BVH && big == 1) FF_LAUNCH_CAM(1, 1, ENV, TEX, GLOSSY); \
-        else if (trace_mode == FF_TRACE_BVH && big == 2) FF_LAUNCH_CAM(1, 2, ENV, TEX, GLOSSY); \
-        else if (trace_mode == FF_TRACE_BVH) FF_LAUNCH_CAM(1, 0, ENV, TEX, GLOSSY); \
-        else FF_LAUNCH_CAM(0, 0, ENV, TEX, GLOSSY); \
-    } while (0)
-        switch ((env ? 4 : 0) | (tex ? 2 : 0) | (glossy ? 1 : 0)) {
-        case 0: FF_LAUNCH_CAM_MODE(0, 0, 0); break;
-        case 1: FF_LAUNCH_CAM_MODE(0, 0, 1); break;
-        case 2: FF_LAUNCH_CAM_MODE(0, 1, 0); break;
-        case 3: FF_LAUNCH_CAM_MODE(0, 1, 1); break;
-        case 4: FF_LAUNCH_CAM_MODE(1, 0, 0); break;
-        case 5: FF_LAUNCH_CAM_MODE(1, 0, 1); break;
-        case 6: FF_LAUNCH_CAM_MODE(1, 1, 0); break;
-        default: FF_LAUNCH_CAM_MODE(1, 1, 1); break;
-        }
-#undef FF_LAUNCH_CAM_MODE
-#undef FF_LAUNCH_CAM
-    }
-    else if (glossy) {
-#define FF_LAUNCH_GLOSSY(MODE, BIG, ENV, TEX) \
-    do { hipLaunchKernelGGL((nee_path_kernel<MODE, BIG, ENV, TEX, 1>), grid, block, lds, stream, np); name = "nee_path_kernel<" #MODE ", " #BIG ", " #ENV ", " #TEX ", 1>"; } while (0)
-#define FF_LAUNCH_GLOSSY_MODE(ENV, TEX) \
-    do { \
-        if (trace_mode == FF_TRACE_BVH && big == 1) FF_LAUNCH_GLOSSY(1, 1, ENV, TEX); \
-        else if (trace_mode == FF_TRACE_BVH && big == 2) FF_LAUNCH_GLOSSY(1, 2, ENV, TEX); \
-        else if (trace_mode == FF_TRACE_BVH) FF_LAUNCH_GLOSSY(1, 0, ENV, TEX); \
-        else FF_LAUNCH_GLOSSY(0, 0, ENV, TEX); \
-    } while (0)
-        if (env && tex) FF_LAUNCH_GLOSSY_MODE(1, 1);
-        else if (env) FF_LAUNCH_GLOSSY_MODE(1, 0);
-        else if (tex) FF_LAUNCH_GLOSSY_MODE(0, 1);
-        else FF_LAUNCH_GLOSSY_MODE(0, 0);
-#undef FF_LAUNCH_GLOSSY_MODE
-#undef FF_LAUNCH_GLOSSY
-    }
-    else if (tex) {
-#define FF_LAUNCH_TEX(MODE, BIG, ENV) \
-    do { hipLaunchKernelGGL((nee_path_kernel<MODE, BIG, ENV, 1>), grid, block, lds, stream, np); name = "nee_path_kernel<" #MODE ", " #BIG ", " #ENV ", 1>"; } while (0)
-        if (env) {
-            if (trace_mode == FF_TRACE_BVH && big == 1) FF_LAUNCH_TEX(1, 1, 1);
-            else if (trace_mode == FF_TRACE_BVH && big == 2) FF_LAUNCH_TEX(1, 2, 1);
-            else if (trace_mode == FF_TRACE_BVH) FF_LAUNCH_TEX(1, 0, 1);
-            else FF_LAUNCH_TEX(0, 0, 1);
-        } else {
-            if (trace_mode == FF_TRACE_BVH && big == 1) FF_LAUNCH_TEX(1, 1, 0);
-            else if (trace_mode == FF_TRACE_BVH && big == 2) FF_LAUNCH_TEX(1, 2, 0);
-            else if (trace_mode == FF_TRACE_BVH) FF_LAUNCH_TEX(1, 0, 0);
-            else FF_LAUNCH_TEX(0, 0, 0);
-        }
-#undef FF_LAUNCH_TEX
-    }
-    else if (env) {
-        if (trace_mode == FF_TRACE_BVH && big == 1) { hipLaunchKernelGGL((nee_path_kernel<FF_TRACE_BVH, 1, 1>), grid, block, lds, stream, np); name = "nee_path_kernel<1, 1, 1>"; }
-        else if (trace_mode == FF_TRACE_BVH && big == 2) { hipLaunchKernelGGL((nee_path_kernel<FF_TRACE_BVH, 2, 1>), grid, block, lds, stream, np); name = "nee_path_kernel<1, 2, 1>"; }
-        else if (trace_mode == FF_TRACE_BVH) { hipLaunchKernelGGL((nee_path_kernel<FF_TRACE_BVH, 0, 1>), grid, block, lds, stream, np); name = "nee_path_kernel<1, 0, 1>"; }
-        else { hipLaunchKernelGGL((nee_path_kernel<FF_TRACE_BRUTE_FORCE, 0, 1>), grid, block, lds, stream, np); name = "nee_path_kernel<0, 0, 1>"; }
-    }
-    else if (trace_mode == FF_TRACE_BVH && big == 1) { hipLaunchKernelGGL((nee_path_kernel<FF_TRACE_BVH, 1>), grid, block, lds, stream, np); name = "nee_path_kernel<1, 1>"; }
-    else if (trace_mode == FF_TRACE_BVH && big == 2) { hipLaunchKernelGGL((nee_path_kernel<FF_TRACE_BVH, 2>), grid, block, lds, stream, np); name = "nee_path_kernel<1, 2>"; }
-    else if (trace_mode == FF_TRACE_BVH) { hipLaunchKernelGGL((nee_path_kernel<FF_TRACE_BVH>), grid, block, lds, stream, np); name = "nee_path_kernel<1, 0>"; }
-    else { hipLaunchKernelGGL((nee_path_kernel<FF_TRACE_BRUTE_FORCE>), grid, block, lds, stream, np); name = "nee_path_kernel<0, 0>"; }
+    const char* name = "";
+#define FF_X(MODE, BIG, ENV, TEX, GLOSSY, CAM, TAIL)                                                                  \
+    if (mode == MODE && big_key == BIG && env == (ENV != 0) && tex == (TEX != 0) && glossy == (GLOSSY != 0) && cam == (CAM != 0)) { \
+        hipLaunchKernelGGL((nee_path_kernel<MODE, BIG, ENV, TEX, GLOSSY, CAM>), grid, block, lds, stream, np);        \
+        name = "nee_path_kernel<" #MODE ", " #BIG TAIL ">";                                                           \
+    } else
+    FF_NEE_KERNELS(FF_X) return hipErrorInvalidValue;
+#undef FF_X
     if (kernel_name) *kernel_name = name;
     return hipGetLastError();
 }
