@@ -635,7 +635,7 @@ int render_enqueue(FfState* s, const FfCamera* camera, const FfRenderParams* prm
     }
 
     {
-        // Work queue (csrc/ff_kernels.hip acquire_pixel): 16 counters in different memory channels, and a wave takes at least
+        // Work queue (csrc/ff_k_shade.h acquire_pixel): 16 counters in different memory channels, and a wave takes at least
         // queue_chunk consecutive items per atomic.  One counter asked for every item serves about 10^8 requests a second, which
         // held every frame of short items far below the saturated rate (1080p C2, before -> after: the reference's own 1-ray frame
         // 0.40 -> 0.19 ms, path-traced 1 spp 2.98 -> 1.33 ms, 4 spp 7.3 -> 4.8, 16 spp 20.8 -> 18.0; the 1 024-spp frame from the

@@ -1,11 +1,11 @@
 // ff_camera.h — the per-sample camera ray (ff_set_camera_sampling): a box pixel filter and a thin lens, as inline functions compiled
-// for the host and the device alike.  nee_path_kernel (ff_kernels.hip) draws every sample's first ray with camera_sample_ray while a
+// for the host and the device alike.  nee_path_kernel (ff_k_nee.h) draws every sample's first ray with camera_sample_ray while a
 // setting is active, and the host twin ff_camera_sample_rays (ff_camera.cpp) calls the same function, so the integrator and the host
 // agree on every operation.  The estimator is spelled out in ff_api.h.
 //
 // Arithmetic: float32 throughout, every expression evaluated exactly as parenthesised below, no fused multiply-add (the library is
 // built with -ffp-contract=off).  Quotients by a computed length are a * rcp(b) and roots sqrt(x), both correctly rounded:
-// FF_CAMERA_RCP / FF_CAMERA_SQRT are the kernels' ieee_rcp / ieee_sqrt on the device (ff_kernels.hip defines them before it includes
+// FF_CAMERA_RCP / FF_CAMERA_SQRT are the kernels' ieee_rcp / ieee_sqrt on the device (ff_k_core.h defines them before it includes
 // this file) and 1.0f / x, sqrtf on the host - the same bits.  The lens point's sine and cosine are ff_glossy.h's fixed-order
 // polynomials on an exactly reduced octant.  The random numbers are Philox2x32-10 outputs: integers, the same everywhere.
 //
@@ -23,7 +23,7 @@
 #include "ff_kernels.h"
 
 #if defined(FF_CAMERA_HD)
-// (ff_kernels.hip: device only, with the kernels' own reciprocal and root)
+// (ff_k_core.h: device only, with the kernels' own reciprocal and root)
 #elif defined(__HIPCC__)
 #define FF_CAMERA_HD __host__ __device__ __forceinline__
 #else
@@ -50,7 +50,7 @@ struct CameraRays {
     const float *fwd, *right, *up;  // m_forward, m_right, m_up as the caller's floats (read only when lens_radius > 0)
 };
 
-// Philox2x32-10 (ff_kernels.hip philox2x32_10, the same integers)
+// Philox2x32-10 (ff_k_shade.h philox2x32_10, the same integers)
 FF_CAMERA_HD void camera_philox(unsigned c0, unsigned c1, unsigned key, unsigned& o0, unsigned& o1)
 {
     for (int r = 0; r < 10; ++r) {
@@ -71,7 +71,7 @@ FF_CAMERA_HD float camera_dot3(float ax, float ay, float az, float bx, float by,
     return (px + py) + pz;
 }
 
-// primary_ray (ff_kernels.hip) through the point (x + fx, y + fy) of the pixel grid: the unit direction from the camera position.
+// primary_ray (ff_k_shade.h) through the point (x + fx, y + fy) of the pixel grid: the unit direction from the camera position.
 FF_CAMERA_HD void camera_pinhole(const CameraRays& C, int x, int y, float fx, float fy, float& dx, float& dy, float& dz)
 {
     const float Px = (((float)x + fx) / C.screen_w) * 2.f - 1.f;

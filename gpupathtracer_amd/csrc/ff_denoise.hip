@@ -3,7 +3,7 @@
 // with, the trace kernels: their schedule moves with any edit around them.
 //
 // Numerics of the resolve: compiled with the library's flags (-ffp-contract=off, IEEE-correct sqrt and divide), it restates the
-// few lines of ff_kernels.hip it needs - the world-normal transform of Intersect::m_normal and the tile-major item order - with
+// few lines of the trace kernels it needs - the world-normal transform of Intersect::m_normal and the tile-major item order - with
 // the same operation order, so every channel is bit for bit what ff_intersect_rays returns for the pixel's primary ray.
 #include "ff_denoise.h"
 
@@ -189,7 +189,7 @@ __global__ __launch_bounds__(256) void denoise_pass_kernel(const DenoiseBuffers 
 
 __device__ __forceinline__ unsigned char to_u8(float v)
 {
-    // the project's 8-bit rule (kernel.cu:214 truncation, out-of-range values clamped): ff_kernels.hip to_u8
+    // the project's 8-bit rule (kernel.cu:214 truncation, out-of-range values clamped): ff_k_shade.h to_u8
     const float s = v * 255.0f;
     if (!(s > 0.0f)) return 0;
     if (s >= 255.0f) return 255;

@@ -27,7 +27,7 @@ __host__ __device__ __forceinline__ float display_curve(float ep, float w2)
     return y < 0.f ? 0.f : (y > 1.f ? 1.f : y);
 }
 
-// FF_ENCODE_LINEAR: the project's 8-bit rule (ff_kernels.hip to_u8)
+// FF_ENCODE_LINEAR: the project's 8-bit rule (ff_k_shade.h to_u8)
 __host__ __device__ __forceinline__ unsigned display_linear_u8(float y)
 {
     const float s = y * 255.0f;

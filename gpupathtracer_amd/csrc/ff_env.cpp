@@ -3,7 +3,7 @@
 // A map is W x H linear RGB texels, row 0 at the top (+Y), looked up at the nearest texel, so its radiance is constant per texel
 // and a texel's pdf in solid angle is exact.  Texels are chosen with probability luminance x solid angle / sum (a Vose alias table,
 // built in double like the light table of ff_nee.cpp); a map of zero total luminance has an empty table and is never sampled.
-// The estimator is in ff_api.h; the kernel is nee_path_kernel<..., ENV = 1> (ff_kernels.hip).
+// The estimator is in ff_api.h; the kernel is nee_path_kernel<..., ENV = 1> (ff_k_nee.h).
 #include <algorithm>
 #include <cerrno>
 #include <cmath>

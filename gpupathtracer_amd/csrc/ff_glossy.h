@@ -1,10 +1,10 @@
 // ff_glossy.h — the rough-specular (GGX) conductor lobe: its value, its pdf and its sampler, as inline functions compiled for the
-// host and the device alike.  nee_path_kernel<..., GLOSSY = 1> (ff_kernels.hip) and the host twins ff_glossy_eval / ff_glossy_sample
+// host and the device alike.  nee_path_kernel<..., GLOSSY = 1> (ff_k_nee.h) and the host twins ff_glossy_eval / ff_glossy_sample
 // (ff_glossy.cpp) call these, so the integrator and the host agree on every operation.  The estimator they serve is in ff_api.h.
 //
 // Arithmetic: float32 throughout, every expression evaluated exactly as parenthesised below, no fused multiply-add (the library is
 // built with -ffp-contract=off).  Quotients are a * rcp(b) and roots sqrt(x), both correctly rounded: FF_GLOSSY_RCP / FF_GLOSSY_SQRT
-// are the kernels' ieee_rcp / ieee_sqrt on the device (ff_kernels.hip defines them before it includes this file) and 1.0f / x, sqrtf
+// are the kernels' ieee_rcp / ieee_sqrt on the device (ff_k_core.h defines them before it includes this file) and 1.0f / x, sqrtf
 // on the host - the same bits.  The sampler's sine and cosine are fixed-order polynomials on an exactly reduced octant (the scheme
 // of the diffuse bounce's cosine_sample), so the sampled direction, too, is the same on the host and on the device bit for bit.
 //
@@ -28,7 +28,7 @@
 #include <math.h>
 
 #if defined(FF_GLOSSY_HD)
-// (ff_kernels.hip: device only, with the kernels' own reciprocal and root)
+// (ff_k_core.h: device only, with the kernels' own reciprocal and root)
 #elif defined(__HIPCC__)
 #include <hip/hip_runtime.h>
 #define FF_GLOSSY_HD __host__ __device__ __forceinline__

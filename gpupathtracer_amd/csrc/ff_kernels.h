@@ -1,4 +1,4 @@
-// ff_kernels.h — host-visible launch interface of the gfx950 trace kernels (ff_kernels.hip).
+// ff_kernels.h — host-visible launch interface of the gfx950 trace kernels (ff_kernels.hip, ff_frame_kernels.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -4,7 +4,7 @@
 // (an ellipsoid under a general model matrix has no closed-form area sampling) and emitters of zero luminance are left out; BSDF
 // sampling still finds them, with MIS weight 1.  Entries are chosen with probability area x luminance / sum (a Vose alias table),
 // so the pdf of a light sample per unit area is luminance / sum on every entry of a geometry: one number per geometry.
-// The estimator itself is in ff_api.h; the kernel is nee_path_kernel (ff_kernels.hip).
+// The estimator itself is in ff_api.h; the kernel is nee_path_kernel (ff_k_nee.h).
 #include <algorithm>
 #include <cmath>
 #include <cstring>

@@ -13,7 +13,7 @@ constexpr float kTaaMaxLength = 4096.f;
 
 __device__ __forceinline__ unsigned char taa_u8(float v)
 {
-    // the project's 8-bit rule (kernel.cu:214 truncation, out-of-range values clamped): ff_kernels.hip to_u8
+    // the project's 8-bit rule (kernel.cu:214 truncation, out-of-range values clamped): ff_k_shade.h to_u8
     const float s = v * 255.0f;
     if (!(s > 0.0f)) return 0;
     if (s >= 255.0f) return 255;

@@ -1,5 +1,5 @@
 // ff_texture.h — albedo textures: the surface coordinate of a hit and the texel lookup, as inline functions compiled for the host and
-// the device alike.  nee_path_kernel (ff_kernels.hip), gbuffer_resolve_kernel (ff_denoise.hip) and the host twins ff_surface_uv /
+// the device alike.  nee_path_kernel (ff_k_nee.h), gbuffer_resolve_kernel (ff_denoise.hip) and the host twins ff_surface_uv /
 // ff_texture_sample (ff_texture.cpp) all call these, so the integrator, the G-buffer and the host agree on every operation.
 //
 // Arithmetic: float32 throughout, every expression evaluated exactly as parenthesised below, no fused multiply-add (the library is

@@ -7,7 +7,7 @@ import hashlib
 import os
 
 _CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
-KERNEL_SOURCES = ("ff_kernels.hip", "ff_kernels.h", "ff_internal.h", "ff_state.h", "ff_build.hip", "ff_build.h", "ff_scene.cpp", "ff_api.cpp", "Makefile")
+KERNEL_SOURCES = ("ff_kernels.hip", "ff_frame_kernels.hip", "ff_k_core.h", "ff_k_lds.h", "ff_k_traverse.h", "ff_k_shade.h", "ff_k_nee.h", "ff_kernels.h", "ff_internal.h", "ff_state.h", "ff_build.hip", "ff_build.h", "ff_scene.cpp", "ff_api.cpp", "Makefile")
 
 
 def kernel_source_hash():

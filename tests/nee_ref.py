@@ -20,7 +20,7 @@ RAY_EPS = 1e-4
 
 
 def philox(c0, c1, key):
-    """Philox2x32-10 (ff_kernels.hip philox2x32_10), vectorised over uint32 arrays."""
+    """Philox2x32-10 (ff_k_shade.h philox2x32_10), vectorised over uint32 arrays."""
     c0 = np.asarray(c0, dtype=np.uint64) & 0xFFFFFFFF
     c1 = np.asarray(c1, dtype=np.uint64) & 0xFFFFFFFF
     k = np.uint64(key & 0xFFFFFFFF)

@@ -67,7 +67,7 @@ def test_twin_equals_the_reference_bit_for_bit(cam_name, setting, seed):
 # ---- 2. the defaults are primary_ray --------------------------------------------------------------------------------------------------
 
 def primary_ray_formula(cam, jitter, xs, ys):
-    """kernel.cu:197-205 as ff_kernels.hip's primary_ray evaluates it, on the jittered matrix."""
+    """kernel.cu:197-205 as ff_k_shade.h's primary_ray evaluates it, on the jittered matrix."""
     m = camera_ref.ray_matrix(cam, jitter)
     f = np.float32
     px = (xs.astype(np.float32) / f(cam.m_screenWidth)) * f(2) - f(1)

@@ -233,7 +233,7 @@ def _wall_rooms(rng):
 
 @pytest.mark.parametrize("seed", [1, 2, 3, 4])
 def test_wall_table_edges_corners_and_grazing_rays(tracer, seed):
-    """Axis-aligned walls are screened in world space by a wave-uniform loop (csrc/ff_kernels.hip screen_walls); everything inside
+    """Axis-aligned walls are screened in world space by a wave-uniform loop (csrc/ff_k_traverse.h screen_walls); everything inside
     its margins goes to the exact reference test.  Rays aimed at the walls' edges and corners (offsets from 0 to 1e-3 of the
     room), rays almost parallel to a wall, origins on and next to wall planes and far outside: ff_intersect_rays through the BVH
     kernel equals the brute-force kernel and the oracle in every field."""

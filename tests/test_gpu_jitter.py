@@ -80,7 +80,7 @@ def test_jittered_g_buffer_and_normal_frame_match_the_oracle(tracer, pose, jitte
             for k in want:
                 bad = np.argwhere(bits(got[k]) != bits(want[k]))
                 assert bad.size == 0, f"{pose} {jitter} mode {mode} {k}: {len(bad)} differ, first {bad[:3].tolist()}"
-            # NORMAL_DEBUG (kernel.cu shade(), ff_kernels.hip K:178-184): |normal| per channel, misses 0
+            # NORMAL_DEBUG (kernel.cu shade(), ff_k_shade.h settle_hit): |normal| per channel, misses 0
             _, rad = tracer.render(cam, lib.render_params(W, H, 1, 1, 3, trace_mode=mode, shade_mode=T.SHADE_NORMAL_DEBUG))
             hit = want["ids"][..., 0] >= 0
             expect = np.where(hit[..., None], np.abs(want["normal"]), np.float32(0))

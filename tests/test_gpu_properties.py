@@ -324,7 +324,7 @@ def test_fine_grained_tail_is_bit_identical(monkeypatch):
 
 
 def test_work_queue_knobs_do_not_change_a_bit(tracer, monkeypatch):
-    """The work queue (csrc/ff_kernels.hip acquire_pixel: several counters that each own every n-th stripe of 64 items, waves that
+    """The work queue (csrc/ff_k_shade.h acquire_pixel: several counters that each own every n-th stripe of 64 items, waves that
     take a chunk per atomic and deal it to their lanes) only decides WHO traces an item: any number of counters and any chunk size
     give the same frame - every item exactly once - on frames of one and of several launches, with the fine-grained tail, on the
     strips of a multi-GPU rank and in brute-force mode."""
@@ -466,7 +466,7 @@ def test_failed_scene_allocation_leaves_no_half_uploaded_scene(monkeypatch, buil
 
 def test_primary_rays_that_miss_the_scene_box_are_dropped_at_the_queue(tracer, monkeypatch):
     """A camera outside the padded box around all geometries (the reference's default one, kernel.cu:312-321): pixels whose primary
-    ray misses that box are written as zero sums when their work item is fetched (csrc/ff_kernels.hip acquire_pixel) instead of
+    ray misses that box are written as zero sums when their work item is fetched (csrc/ff_k_shade.h acquire_pixel) instead of
     being traced sample by sample.  The frame, and the number of rays counted, equal the brute-force kernel's (which takes no such
     shortcut) and the same kernel's with the shortcut off; in path mode, in the reference's own shade mode, on tiles and strips,
     and with enough samples for several blocks per pixel."""
@@ -525,7 +525,7 @@ def test_culled_pixels_have_a_stored_primary_hit_for_their_tail_items():
 def test_primary_rays_are_answered_from_the_pixel_s_stored_hit(tracer, monkeypatch):
     """Every sample of a pixel starts with the same ray (kernel.cu:200-205 has no jitter): a pre-pass of the frame traces every
     pixel's primary ray once and stores its closest hit per pixel; every sample of the frame starts from there (csrc/ff_kernels.hip
-    trace_bvh_kernel, settle_hit; csrc/ff_api.cpp render_enqueue).  Same bits and the same number of path segments as with the
+    trace_bvh_kernel, csrc/ff_k_shade.h settle_hit; csrc/ff_api.cpp render_enqueue).  Same bits and the same number of path segments as with the
     reuse off (FF_NO_PRIMARY_REUSE=1) and as the brute-force kernel, which traces every one of them; FfStats::rays_answered counts
     exactly the primary segments: one per sample (camera inside the box: no pixel is culled); with diffuse, mirror and glass
     surfaces, one bounce (every path is its primary segment), partial last blocks, several launches per frame and interpolated
@@ -577,7 +577,7 @@ def test_primary_rays_are_answered_from_the_pixel_s_stored_hit(tracer, monkeypat
 
 def test_last_bounce_queries_end_after_the_planes_when_no_emitter_is_held(tracer, monkeypatch):
     """The last segment of a path (bounce index bounces - 1) adds radiance only when it ends on an emitter
-    (csrc/ff_kernels.hip shade_and_advance; oracle/ff_oracle.c restates the loop).  When every emitter of the scene is a plane
+    (csrc/ff_k_shade.h shade_and_advance; oracle/ff_oracle.c restates the loop).  When every emitter of the scene is a plane
     or a sphere - records every query screens before any mesh - a last-bounce query that holds no emitter after that screening
     ends there (scan_records; FfStats::rays_cut_short).  Same bits and the same number of path segments as with the shortcut off
     (FF_NO_LAST_BOUNCE_CUT=1) and as the brute-force kernel; an emitter MESH switches it off; so does the normal-debug shade."""
@@ -616,7 +616,7 @@ def test_last_bounce_queries_end_after_the_planes_when_no_emitter_is_held(tracer
 
 def test_wall_pairs_and_wall_table_do_not_change_a_bit(monkeypatch):
     """Floor and ceiling, left and right wall of the box share one entry of the wall table (csrc/ff_scene.cpp build_wall_table,
-    csrc/ff_kernels.hip wall_test_pair): with pairs, without them (FF_NO_WALL_PAIRS=1) and without the table (FF_NO_WALL_TABLE=1;
+    csrc/ff_k_traverse.h wall_test_pair): with pairs, without them (FF_NO_WALL_PAIRS=1) and without the table (FF_NO_WALL_TABLE=1;
     both read at ff_create) the frame is the same, from inside the box, from outside it (origins beyond the pair: the other wall
     goes to the exact per-lane screen) and from a camera ON the floor plane."""
     scene = scenes.cornell_wahoo_scene()
