@@ -26,6 +26,7 @@ void free_scene(FfState* s)
     if (s->d_geoms) (void)hipFree(s->d_geoms);
     if (s->d_tris) (void)hipFree(s->d_tris);
     if (s->d_normals) (void)hipFree(s->d_normals);
+    if (s->d_world_normals) (void)hipFree(s->d_world_normals);
     if (s->d_uvs) (void)hipFree(s->d_uvs);
     if (s->d_nodes) (void)hipFree(s->d_nodes);
     if (s->d_nodes4) (void)hipFree(s->d_nodes4);
@@ -39,6 +40,7 @@ void free_scene(FfState* s)
     s->d_geoms = nullptr;
     s->d_tris = nullptr;
     s->d_normals = nullptr;
+    s->d_world_normals = nullptr;
     s->d_uvs = nullptr;
     s->d_nodes = nullptr;
     s->d_parent = nullptr;
@@ -59,6 +61,14 @@ hipError_t scene_alloc(FfState* s, void** ptr, size_t bytes)
         return hipErrorOutOfMemory;
     }
     return hipMalloc(ptr, bytes);
+}
+
+// The normal tables of a scene of `geoms` records and `tris` triangle records (FfState::d_world_normals): the scenes whose frames can
+// run the kernels that read them.
+hipError_t alloc_world_normals(FfState* s, size_t geoms, size_t tris)
+{
+    if (geoms > (size_t)kChunkGeometries) return hipSuccess;
+    return scene_alloc(s, (void**)&s->d_world_normals, (tris + geoms) * sizeof(float4));
 }
 
 } // namespace
@@ -273,6 +283,14 @@ int finalize_layout(FfState* s)
         next += r.lds_nodes;
     }
     FF_HIP(hipMemcpyAsync(s->d_geoms, s->h_geoms.data(), s->h_geoms.size() * sizeof(GeomRecord), hipMemcpyHostToDevice, s->stream));
+    // The normal tables follow the records and the triangle records just written (behind the builders and the refit on the stream): a
+    // transform moves every normal of its geometry, a mesh update the mesh's own.  All of them, each time: one short launch (16 bytes
+    // written per triangle), and no bookkeeping of what moved.
+    if (s->d_world_normals) {
+        int max_tris = 0;
+        for (const GeomRecord& g : s->h_geoms) max_tris = std::max(max_tris, g.type == FF_GEOM_TRIANGLEMESH ? g.tri_count : 0);
+        FF_HIP(launch_world_normals(s->d_geoms, s->d_tris, s->num_geoms, max_tris, s->d_world_normals, s->d_world_normals + s->num_tris, s->stream));
+    }
     FF_HIP(hipStreamSynchronize(s->stream));
     return FF_OK;
 }
@@ -355,6 +373,8 @@ void fill_scene(const FfState* s, KParams& k, bool smooth, int lds_block_threads
     k.tris = s->d_tris;
     k.trinormals = smooth ? reinterpret_cast<const float4*>(s->d_normals) : nullptr;
     k.nodes4 = s->d_nodes4;
+    k.tri_world_normals = s->d_world_normals;
+    k.geom_world_normals = s->d_world_normals ? s->d_world_normals + s->num_tris : nullptr;
     if (s->sw.lds_fill && lds_block_threads > 0) {
         const size_t bytes = bvh_lds_bytes(s->lds_cap, s->stack_lds_levels, lds_block_threads, lds_records(s)); // (the pool behind it is initialised by the kernel)
         k.debug_lds_words = (unsigned)std::min<size_t>(s->sw.lds_fill_words, bytes / 4);
@@ -775,7 +795,8 @@ int render_enqueue(FfState* s, const FfCamera* camera, const FfRenderParams* prm
             k.total_items = k.tail_first_item + k.pix_items * groups;
         }
         if (l > 0) FF_HIP(hipMemsetAsync(s->d_queue, 0, (size_t)k.queue_counters * kQueueStride * sizeof(unsigned), st));
-        FF_HIP(launch_trace(k, prm->trace_mode, s->collect_stats, grid, block_threads, st, &s->last_kernel_name, pool, /*prepass=*/false, /*start=*/use_start));
+        FF_HIP(launch_trace(k, prm->trace_mode, s->collect_stats, grid, block_threads, st, &s->last_kernel_name, pool, /*prepass=*/false, /*start=*/use_start,
+                            /*world_normals=*/!s->sw.no_world_normals));
     }
     FF_HIP(launch_combine(k, st));
     FF_HIP(hipEventRecord(s->ev_end, st));
@@ -891,6 +912,7 @@ void read_switches(FfState* s)
     w.no_primary_reuse = std::getenv("FF_NO_PRIMARY_REUSE") != nullptr;
     w.no_primary_cache = std::getenv("FF_NO_PRIMARY_CACHE") != nullptr;
     w.no_start_records = std::getenv("FF_NO_START_RECORDS") != nullptr;
+    w.no_world_normals = std::getenv("FF_NO_WORLD_NORMALS") != nullptr;
     if (const char* e = std::getenv("FF_TAIL_BLOCKS")) w.tail_blocks = std::max(1, std::min(3, std::atoi(e)));
     if (const char* e = std::getenv("FF_REUSE_MIN_SPP")) w.reuse_min_spp = std::max(1, std::atoi(e));
     if (const char* e = std::getenv("FF_REUSE_QUORUM")) w.reuse_quorum = std::max(1, std::min(65, std::atoi(e)));
@@ -1112,6 +1134,7 @@ int upload_with_device_builder(FfState* s, const FfGeometry* host_geometries, in
     FF_HIP(scene_alloc(s, (void**)&s->d_geoms, cs.geoms.size() * sizeof(GeomRecord)));
     FF_HIP(scene_alloc(s, (void**)&s->d_tris, (cs.total_tris ? (size_t)cs.total_tris : 1) * sizeof(TriRecord)));
     FF_HIP(scene_alloc(s, (void**)&s->d_normals, (cs.total_tris ? (size_t)cs.total_tris : 1) * sizeof(TriNormals)));
+    FF_HIP(alloc_world_normals(s, cs.geoms.size(), (size_t)cs.total_tris));
     FF_HIP(hipMalloc((void**)&s->d_uvs, (cs.total_tris ? (size_t)cs.total_tris : 1) * sizeof(TriUVs)));
     FF_HIP(scene_alloc(s, (void**)&s->d_nodes, (node_cap ? node_cap : 1) * sizeof(BvhNode)));
     // (the kernels address a node by a 32-bit byte offset from the array's base)
@@ -1252,6 +1275,7 @@ int upload_compiled(FfState* s, const CompiledScene& cs)
     const size_t node_bytes = (cs.nodes.size() ? cs.nodes.size() : 1) * sizeof(BvhNode);
     FF_HIP(scene_alloc(s, (void**)&s->d_tris, tri_bytes));
     FF_HIP(scene_alloc(s, (void**)&s->d_normals, tri_bytes));
+    FF_HIP(alloc_world_normals(s, cs.geoms.size(), cs.tris.size()));
     static_assert(sizeof(TriNormals) == sizeof(TriRecord), "parallel arrays of equal stride");
     if (!cs.normals.empty()) FF_HIP(hipMemcpy(s->d_normals, cs.normals.data(), cs.normals.size() * sizeof(TriNormals), hipMemcpyHostToDevice));
     FF_HIP(hipMalloc((void**)&s->d_uvs, (cs.uvs.size() ? cs.uvs.size() : 1) * sizeof(TriUVs)));

@@ -180,7 +180,43 @@ __global__ void unpack_strips_kernel(const unsigned char* __restrict__ src, unsi
         for (size_t i = first; i < (size_t)width * 3; i += stride) d[i] = s[i];
     }
 }
+
+// The normal tables of the scene (KParams::tri_world_normals / geom_world_normals): what the shading pass computes per hit -
+// fill_object_normal and unit_world_normal, the functions it calls, on the records it reads - once per triangle record and per
+// geometry record.  One row of workgroups per geometry (blockIdx.y); an analytic record's one entry is written by its first thread.
+__global__ void world_normals_kernel(const GeomRecord* __restrict__ geoms, const TriRecord* __restrict__ tris, float4* __restrict__ tri_out,
+                                     float4* __restrict__ geom_out)
+{
+    const int g = (int)blockIdx.y;
+    const GeomRecord& G = geoms[g];
+    const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool mesh = G.type == FF_GEOM_TRIANGLEMESH;
+    if (mesh ? i >= (unsigned)G.tri_count : i != 0u) return;
+    Best best;
+    best.dist = 0.f;
+    best.geom = g;
+    best.rec = mesh ? G.tri_first + (int)i : -1;
+    best.px = best.py = best.pz = 0.f;
+    fill_object_normal(geoms, tris, best);
+    MaterialRef M;
+    M.global = &G;
+    M.geom_base = 0;
+    M.g = g;
+    float ux, uy, uz;
+    unit_world_normal(M, best, ux, uy, uz);
+    if (mesh) tri_out[best.rec] = make_float4(ux, uy, uz, 0.f);
+    else geom_out[g] = make_float4(ux, uy, uz, 0.f);
+}
 } // namespace
+
+hipError_t launch_world_normals(const GeomRecord* geoms, const TriRecord* tris, int num_geoms, int max_tri_count, float4* tri_out, float4* geom_out,
+                                hipStream_t stream)
+{
+    if (num_geoms <= 0) return hipSuccess;
+    const dim3 block(256), grid((unsigned)(((max_tri_count > 1 ? max_tri_count : 1) + 255) / 256), (unsigned)num_geoms);
+    hipLaunchKernelGGL(world_normals_kernel, grid, block, 0, stream, geoms, tris, tri_out, geom_out);
+    return hipGetLastError();
+}
 
 hipError_t launch_combine(const KParams& p, hipStream_t stream)
 {

@@ -13,6 +13,7 @@ namespace {
 extern __shared__ uint4 ff_smem[];
 
 constexpr int kGeomVec4 = (int)(sizeof(GeomRecord) / 16); // 18 float4 per geometry record
+constexpr int kGeomWorldNormalVec4 = 8;                   // kernels on the normal tables: this quarter of a PLANE's LDS record (nrm_c0, which they never read) holds its unit world normal
 constexpr int kNodeVec4 = (int)(sizeof(Bvh4Node) / 16);   // 7 quarters per 4-wide node: six box planes + links
 constexpr int kDone = 0x7fffffff;                         // traversal cursor of a lane with nothing left to visit
 constexpr int kMeshDone = 0x7ffffffe;                     // big scenes: the current mesh is exhausted, the walk through the geometry tree resumes

@@ -29,8 +29,12 @@ __device__ __forceinline__ int mat_bxdf(const MaterialRef& M)
 
 // `unit_object_normal`: normalise a triangle's face normal in object space first (kernel.cu:101, what Intersect::m_normal
 // and the NORMAL_DEBUG shade carry); the path integrator transforms the raw cross product and normalises once in world space.
+// WN: the instantiation of the caller (trace_bvh_kernel<..., WN>).  The kernels on the normal tables keep a plane's unit world normal in
+// quarter 8 of its LDS record - the first of the columns read here - so nothing in them may come this way: it does not compile.
+template <bool WN = false>
 __device__ __forceinline__ void world_normal(const MaterialRef& M, const Best& best, bool unit_object_normal, float& nx, float& ny, float& nz)
 {
+    static_assert(!WN, "the kernels on the normal tables overwrite the inverse-transpose in LDS: take the normal from Best::cx, cy, cz");
     float ox = best.cx, oy = best.cy, oz = best.cz;
     if (best.rec >= 0 && unit_object_normal) {
         const float inv = ieee_rcp(ieee_sqrt(dot3(ox, oy, oz, ox, oy, oz)));
@@ -42,6 +46,21 @@ __device__ __forceinline__ void world_normal(const MaterialRef& M, const Best& b
     nx = (n0.x * ox + n1.x * oy) + (n2.x * oz + n0.w);
     ny = (n0.y * ox + n1.y * oy) + (n2.y * oz + n1.w);
     nz = (n0.z * ox + n1.z * oy) + (n2.z * oz + n2.w);
+}
+
+// The unit world normal of a hit before the flip against the ray: the object-space normal as found (Best::cx, cy, cz - a triangle's
+// raw cross product, a plane's m_normal) through the record's inverse-transpose, normalised once in world space.  A function of the
+// scene alone: the shading passes evaluate it per hit, world_normals_kernel (ff_frame_kernels.hip) once per triangle and plane -
+// the same operations in the same order, so the stored bits are the bits computed here (a zero-area triangle's NaN included).
+template <bool WN = false>
+__device__ __forceinline__ void unit_world_normal(const MaterialRef& M, const Best& best, float& ux, float& uy, float& uz)
+{
+    float nx, ny, nz;
+    world_normal<WN>(M, best, false, nx, ny, nz);
+    const float ninv = ieee_rcp(ieee_sqrt(dot3(nx, ny, nz, nx, ny, nz)));
+    ux = nx * ninv;
+    uy = ny * ninv;
+    uz = nz * ninv;
 }
 
 // ---- build-defined integrator pieces (DESIGN.md "Integrator"; mirrored by the oracle) ------------------------------
@@ -360,7 +379,7 @@ __device__ __forceinline__ bool acquire_pixel(const KParams& p, int lane, Path& 
 // settle_hit returns kPixelDone (the lane gives the pixel up), kNewSample (the next sample's primary ray is in P.ray) or kGoesOn
 // (scatter must follow with the same hit).  SPECULAR = false: the caller guarantees a scene without MIRROR / GLASS surfaces.
 enum { kPixelDone = 0, kNewSample = 1, kGoesOn = 2 };
-template <bool SPECULAR = true, bool PREPASS = false>
+template <bool SPECULAR = true, bool PREPASS = false, bool WN = false>
 __device__ __forceinline__ int settle_hit(const KParams& p, const Best& best, bool hit, const MaterialRef& M, Path& P)
 {
     if constexpr (PREPASS) {
@@ -386,10 +405,8 @@ __device__ __forceinline__ int settle_hit(const KParams& p, const Best& best, bo
                     cls = kStartGeneral;
                 } else if (p.start_bounces > 1) {
                     cls = kStartGoesOn;
-                    float nx, ny, nz;
-                    world_normal(M, best, false, nx, ny, nz);
-                    const float ninv = ieee_rcp(ieee_sqrt(dot3(nx, ny, nz, nx, ny, nz)));
-                    float ux = nx * ninv, uy = ny * ninv, uz = nz * ninv;
+                    float ux, uy, uz;
+                    unit_world_normal(M, best, ux, uy, uz);
                     if (dot3(ux, uy, uz, P.ray.dx, P.ray.dy, P.ray.dz) > 0.0f) { ux = -ux; uy = -uy; uz = -uz; }
                     q0.x = best.px + ux * kRayEps;
                     q0.y = best.py + uy * kRayEps;
@@ -417,16 +434,19 @@ __device__ __forceinline__ int settle_hit(const KParams& p, const Best& best, bo
         }
         return kPixelDone;
     }
-    const bool debug_shade = p.shade_mode == FF_SHADE_NORMAL_DEBUG;
+    // (WN: the kernels that carry the unit world normal in `best` run path frames only; the reference's own shade wants the object-space one)
+    const bool debug_shade = !WN && p.shade_mode == FF_SHADE_NORMAL_DEBUG;
     // Radiance of the path: it is zero until the path ends on an emitter (the only light transport here), so it is not
     // carried across segments; "0 + beta*Le" of the integrator is beta*Le bit for bit.
     float Lx = 0.f, Ly = 0.f, Lz = 0.f;
     if (hit) {
         if (debug_shade) {
             // shade(), kernel.cu:178-184
-            float nx, ny, nz;
-            world_normal(M, best, true, nx, ny, nz);
-            Lx = fabsf(nx); Ly = fabsf(ny); Lz = fabsf(nz);
+            if constexpr (!WN) {
+                float nx, ny, nz;
+                world_normal<WN>(M, best, true, nx, ny, nz);
+                Lx = fabsf(nx); Ly = fabsf(ny); Lz = fabsf(nz);
+            }
         } else if (mat_bxdf(M) == FF_BXDF_EMITTER) {
             // utilities.h:96-103: two-sided emitter, m_emissiveColor * m_intensity
             const float4 emission = mat_f4(M, 13);
@@ -492,16 +512,15 @@ __device__ __forceinline__ void to_world_about(float ux, float uy, float uz, flo
 // The next ray of a path that goes on from `best` (settle_hit returned kGoesOn; the throughput already carries the surface's
 // albedo, glass excepted).  MIRROR: perfect reflection.  GLASS: smooth dielectric, Fresnel-weighted choice between reflection and
 // refraction (oracle/ff_oracle.c is the definition).  Everything else: cosine-weighted direction about the world normal.
-template <bool SPECULAR = true>
+// WN (diffuse small-scene kernels on the scene's normal tables): best.cx, cy, cz hold the unit world normal already (finish_segment).
+template <bool SPECULAR = true, bool WN = false>
 __device__ __forceinline__ void scatter(const KParams& p, const Best& best, const MaterialRef& M, Path& P)
 {
-    float nx, ny, nz;
-    world_normal(M, best, false, nx, ny, nz);
+    float ux = best.cx, uy = best.cy, uz = best.cz;
+    if constexpr (!WN) unit_world_normal<WN>(M, best, ux, uy, uz);
     const int bxdf = mat_bxdf(M);
     const bool mirror = SPECULAR && bxdf == FF_BXDF_MIRROR, glass = SPECULAR && bxdf == FF_BXDF_GLASS;
     const float4 albedo = mat_f4(M, 12);
-    const float ninv = ieee_rcp(ieee_sqrt(dot3(nx, ny, nz, nx, ny, nz)));
-    float ux = nx * ninv, uy = ny * ninv, uz = nz * ninv;
     bool flipped = false;
     if (dot3(ux, uy, uz, P.ray.dx, P.ray.dy, P.ray.dz) > 0.0f) { ux = -ux; uy = -uy; uz = -uz; flipped = true; }
     float wox, woy, woz;
@@ -568,14 +587,13 @@ __device__ __forceinline__ void scatter(const KParams& p, const Best& best, cons
 // the pre-pass answered and shaded.  For those the throughput, the normal, the flip and the origin come from the record; the random
 // numbers, the cosine sample, the basis and the direction are common code.  The record's quarters are first touched behind the
 // Philox rounds: the caller issued their loads just before, and the rounds cover the latency.
+template <bool WN = false>
 __device__ __forceinline__ void scatter_start(const KParams& p, const Best& best, MaterialRef& M, Path& P, bool from_rec, const float4& q0, const float4& q1)
 {
     float ux = 0.f, uy = 0.f, uz = 1.f, ox = 0.f, oy = 0.f, oz = 0.f;
     if (!from_rec) {
-        float nx, ny, nz;
-        world_normal(M, best, false, nx, ny, nz);
-        const float ninv = ieee_rcp(ieee_sqrt(dot3(nx, ny, nz, nx, ny, nz)));
-        ux = nx * ninv; uy = ny * ninv; uz = nz * ninv;
+        if constexpr (WN) { ux = best.cx; uy = best.cy; uz = best.cz; }
+        else unit_world_normal<WN>(M, best, ux, uy, uz);
         if (dot3(ux, uy, uz, P.ray.dx, P.ray.dy, P.ray.dz) > 0.0f) { ux = -ux; uy = -uy; uz = -uz; }
         ox = best.px + ux * kRayEps;
         oy = best.py + uy * kRayEps;

@@ -63,9 +63,11 @@ struct HitPoint {
     float cx, cy, cz; // object-space normal as found (see Best)
 };
 
-template <class LDS>
+// WN (the kernels on the scene's normal tables, KParams::tri_world_normals): H.cx, cy, cz is the candidate's unit WORLD normal instead - a
+// triangle's from the table, fetched with its record; a plane's from quarter 8 of its LDS record, where those kernels keep it.
+template <bool WN = false, class LDS>
 __device__ __forceinline__ bool exact_hit(const LDS& L, const TriRecord* __restrict__ tris, const Ray& wr, int g, int rec, float& dist, HitPoint& H,
-                                          int& orig_tri)
+                                          int& orig_tri, const float4* __restrict__ wn_tris = nullptr)
 {
     Ray osr;
     float len;
@@ -76,13 +78,21 @@ __device__ __forceinline__ bool exact_hit(const LDS& L, const TriRecord* __restr
         const float4* tp = reinterpret_cast<const float4*>(tris) + (size_t)rec * 3;
         const float4 a = tp[0], b = tp[1], c = tp[2];
         orig_tri = __float_as_int(a.w);
-        t = triangle_t(a, b, c, osr);
-        const float e1x = b.x, e1y = b.y, e1z = b.z;
-        const float e2x = c.x, e2y = c.y, e2z = c.z;
-        H.cx = e1y * e2z - e2y * e1z; // kernel.cu:101 cross(edge1, edge2), shading normalises it where the reference does
-        H.cy = e1z * e2x - e2z * e1x;
-        H.cz = e1x * e2y - e2x * e1y;
-        if (L.smooth_normals) smooth_normal(a, b, c, L.smooth_normals + (size_t)rec * 3, osr, H.cx, H.cy, H.cz);
+        if constexpr (WN) {
+            const float4 n = wn_tris[rec];
+            t = triangle_t(a, b, c, osr);
+            H.cx = n.x;
+            H.cy = n.y;
+            H.cz = n.z;
+        } else {
+            t = triangle_t(a, b, c, osr);
+            const float e1x = b.x, e1y = b.y, e1z = b.z;
+            const float e2x = c.x, e2y = c.y, e2z = c.z;
+            H.cx = e1y * e2z - e2y * e1z; // kernel.cu:101 cross(edge1, edge2), shading normalises it where the reference does
+            H.cy = e1z * e2x - e2z * e1x;
+            H.cz = e1x * e2y - e2x * e1y;
+            if (L.smooth_normals) smooth_normal(a, b, c, L.smooth_normals + (size_t)rec * 3, osr, H.cx, H.cy, H.cz);
+        }
     } else {
         const float4 pn = lds_geom4(L, g, 11);
         if (g >= L.num_quads) {
@@ -90,9 +100,16 @@ __device__ __forceinline__ bool exact_hit(const LDS& L, const TriRecord* __restr
             sphere_normal(pn.w, osr, t, H.cx, H.cy, H.cz);
         } else {
             t = plane_t(pn.x, pn.y, pn.z, osr);
-            H.cx = pn.x; // kernel.cu:26
-            H.cy = pn.y;
-            H.cz = pn.z;
+            if constexpr (WN) {
+                const float4 n = lds_geom4(L, g, kGeomWorldNormalVec4);
+                H.cx = n.x;
+                H.cy = n.y;
+                H.cz = n.z;
+            } else {
+                H.cx = pn.x; // kernel.cu:26
+                H.cy = pn.y;
+                H.cz = pn.z;
+            }
         }
     }
     if (!(t > 0.0f)) return false;
@@ -108,16 +125,16 @@ __device__ __forceinline__ bool exact_hit(const LDS& L, const TriRecord* __restr
 
 // Resolve the pending candidate exactly and merge it into `best` (kernel.cu:115-121).  Returns true if it became the
 // best; then H is its hit point and normal.
-template <class LDS>
+template <bool WN = false, class LDS>
 __device__ __forceinline__ bool resolve_pending(const LDS& L, const TriRecord* __restrict__ tris, const Ray& wr, Pending& pend, BestId& best,
-                                                HitPoint& H)
+                                                HitPoint& H, const float4* __restrict__ wn_tris = nullptr)
 {
     const int g = pend.geom, rec = pend.rec;
     pend.geom = -1;
     pend.dist = kInf;
     float dist;
     int orig_tri;
-    if (!exact_hit(L, tris, wr, g, rec, dist, H, orig_tri)) return false;
+    if (!exact_hit<WN>(L, tris, wr, g, rec, dist, H, orig_tri, wn_tris)) return false;
     bool take = dist < best.dist; // kernel.cu:115
     if (!take && dist == best.dist && best.geom >= 0) {
         // the reference keeps the first hit in (geometry, triangle) iteration order among equal distances
@@ -787,18 +804,19 @@ __device__ __forceinline__ void leaf_step(const LDS& L, const TriRecord* __restr
 }
 
 // Settle what is still pending (the common case: the one exact evaluation of the ray, all hitting lanes together) and
-// produce the hit point of the winner.
-template <class LDS>
-__device__ __forceinline__ void finish_segment(const LDS& L, const TriRecord* __restrict__ tris, const Ray& wr, Segment& S, Best& best)
+// produce the hit point of the winner.  WN: best.cx, cy, cz receive its unit world normal (exact_hit).
+template <bool WN = false, class LDS>
+__device__ __forceinline__ void finish_segment(const LDS& L, const TriRecord* __restrict__ tris, const Ray& wr, Segment& S, Best& best,
+                                               const float4* __restrict__ wn_tris = nullptr)
 {
     bool have_point = false;
     HitPoint H = { 0.f, 0.f, 0.f, 0.f, 0.f, 1.f };
-    if (S.pend.geom >= 0) have_point = resolve_pending(L, tris, wr, S.pend, S.best, H);
+    if (S.pend.geom >= 0) have_point = resolve_pending<WN>(L, tris, wr, S.pend, S.best, H, wn_tris);
     if (!have_point && S.best.geom >= 0) {
         // the winner was resolved earlier (two candidates had been too close to rank approximately): recompute its point
         float dist;
         int orig_tri;
-        exact_hit(L, tris, wr, S.best.geom, S.best.rec, dist, H, orig_tri);
+        exact_hit<WN>(L, tris, wr, S.best.geom, S.best.rec, dist, H, orig_tri, wn_tris);
     }
     best.dist = S.best.dist;
     best.geom = S.best.geom;

@@ -116,6 +116,12 @@ struct KParams {
     // (at the end: the kernels without START read everything above at the offsets they always had)
     float4* start_records;
     int start_bounces;
+    // Normal tables (trace_bvh_kernel<..., WN = true>; world_normals_kernel writes them whenever the scene changes): the unit world normal,
+    // before the flip against the ray, of every triangle record (parallel to tris) and of every geometry record (planes; a mesh's entry
+    // is unused).  finish_segment fetches the winner's instead of its object-space normal, and shading starts from there.
+    // (appended at the end, like the start records)
+    const float4* tri_world_normals;
+    const float4* geom_world_normals;
 };
 // The ray count of a launch is added up in kRaySlots 64-bit slots of the counter block, kRaySlotStride words apart, from slot
 // kRaySlotFirst on (the first 256 bytes hold the named counters): counters[kRaySlotStride * (kRaySlotFirst + j)].
@@ -209,8 +215,14 @@ size_t pool_lds_bytes(int block_threads);
 // without START are named by their first five parameters, as before START existed (a profiler appends ", false").
 // pool: the job-pool kernel (scenes of up to kChunkGeometries geometries; the LDS layout must have left pool_lds_bytes free).
 // start: the instantiation that runs on KParams::start_records (diffuse scenes of up to kChunkGeometries geometries, not the pool).
+// world_normals: where the frame runs the kernel without the extras on a small scene (with or without start), the instantiation that
+// reads KParams::tri_world_normals / geom_world_normals (path frames only); the reported name does not tell the two apart.
 hipError_t launch_trace(const KParams& p, int trace_mode, bool collect_stats, int grid_blocks, int block_threads, hipStream_t stream,
-                        const char** kernel_name = nullptr, bool pool = false, bool prepass = false, bool start = false);
+                        const char** kernel_name = nullptr, bool pool = false, bool prepass = false, bool start = false, bool world_normals = false);
+// Fills the normal tables of a scene of num_geoms records (at most kChunkGeometries: one grid row each) whose largest mesh has
+// max_tri_count triangles: tri_out parallel to tris, geom_out parallel to geoms (device pointers; the records as the trace kernels read them).
+hipError_t launch_world_normals(const GeomRecord* geoms, const TriRecord* tris, int num_geoms, int max_tri_count, float4* tri_out, float4* geom_out,
+                                hipStream_t stream);
 // Sums every pixel's sample blocks in order, scales by 1/spp and writes radiance / rgb8 (row-major, coalesced).
 hipError_t launch_combine(const KParams& p, hipStream_t stream);
 // Fills mask[pix_items / 64] (see KParams::cull_mask) and zeroes the block sums of the culled pixels.

@@ -61,10 +61,17 @@ namespace {
 // START = true (diffuse scenes of up to 32 geometries: EXTRAS = false, BIG = 0) is the instantiation that runs on the pre-pass's start
 // records instead of its raw hits: a sample starts inside the shading pass that ended the one before it, and the settle loop below
 // is not part of it; a template parameter and not a branch for the reason PREPASS is one.
-template <bool STATS, int BLOCK, bool EXTRAS, int BIG = 0, bool PREPASS = false, bool START = false>
+// WN = true (the same scenes, with START and without) is the instantiation that runs on the scene's normal tables (KParams::tri_world_normals,
+// geom_world_normals): the unit world normal of a hit depends on the scene alone, so finish_segment fetches the winner's - a triangle's
+// with its record, a plane's from its LDS record - into Best::cx, cy, cz, which otherwise carry the object-space normal, and the shading
+// pass starts at the flip against the ray: no inverse-transpose product and no normalisation per hit (the cross product is still formed
+// inside the winner's exact triangle test, which needs it; what goes is its second copy's way through the matrix).  WN = false computes them
+// there (FF_NO_WORLD_NORMALS; the reference's own shade, which wants the object-space normal).
+template <bool STATS, int BLOCK, bool EXTRAS, int BIG = 0, bool PREPASS = false, bool START = false, bool WN = false>
 __global__ __launch_bounds__(BLOCK) void trace_bvh_kernel(const KParams p)
 {
     static_assert(!START || (!EXTRAS && BIG == 0 && !PREPASS), "start records: the diffuse small-scene kernel only");
+    static_assert(!WN || (!EXTRAS && BIG == 0 && !PREPASS), "normal tables: the diffuse small-scene kernels only");
     const int tid = threadIdx.x;
     const int lane = tid & (kWave - 1);
     const LdsT<BIG> L = make_lds<BIG>(p.lds_nodes, p.stack_depth, BLOCK, tid, EXTRAS ? p.num_quads : 0x7fffffff, EXTRAS ? p.trinormals : nullptr,
@@ -75,6 +82,11 @@ __global__ __launch_bounds__(BLOCK) void trace_bvh_kernel(const KParams p)
         __syncthreads();
     }
     stage_scene(L, nodes4, p.geoms, p.num_geoms, p.num_planes, tid, BLOCK);
+    if constexpr (WN) {
+        // a plane's unit world normal takes the place of the first inverse-transpose column in its LDS record (nothing else read those)
+        for (int g = tid; g < p.num_planes; g += BLOCK) reinterpret_cast<float4*>(ff_smem)[L.geom_base + g * kGeomVec4 + kGeomWorldNormalVec4] = p.geom_world_normals[g];
+        __syncthreads();
+    }
 
     Counters cnt = {};
     Path P;
@@ -139,7 +151,7 @@ __global__ __launch_bounds__(BLOCK) void trace_bvh_kernel(const KParams p)
         bool hit = false;
         bool shade_now = setup && inflight; // lanes with a finished query
         if (shade_now) {
-            finish_segment(L, p.tris, P.ray, S, best);
+            finish_segment<WN>(L, p.tris, P.ray, S, best, p.tri_world_normals);
             hit = best.geom >= 0;
         }
         if (STATS) t1 = __builtin_amdgcn_s_memtime();
@@ -157,7 +169,7 @@ __global__ __launch_bounds__(BLOCK) void trace_bvh_kernel(const KParams p)
             M.g = 0;
             if (shade_now) {
                 M.g = best.geom;
-                const int r = settle_hit<false, false>(p, best, hit, M, P);
+                const int r = settle_hit<false, false, WN>(p, best, hit, M, P);
                 inflight = false;
                 active = r != kPixelDone;
                 goes_on = r == kGoesOn;
@@ -176,7 +188,7 @@ __global__ __launch_bounds__(BLOCK) void trace_bvh_kernel(const KParams p)
                 cnt.reused += reused_now;
                 if (STATS && p.timeline) tl_count += reused_now; // (the launch timeline counts every path segment where it completes)
             }
-            if (goes_on) scatter_start(p, best, M, P, from_rec, q0, q1);
+            if (goes_on) scatter_start<WN>(p, best, M, P, from_rec, q0, q1);
         } else {
             // A lane that waits with a new sample (it starts from the pixel's stored primary hit, see below) joins this iteration's shading.
             bool from_cache = setup && !inflight && active && P.b == 0 && reuse;
@@ -195,6 +207,15 @@ __global__ __launch_bounds__(BLOCK) void trace_bvh_kernel(const KParams p)
                     best.geom = __float_as_int(c1.w);
                     best.rec = __float_as_int(c2.x);
                     hit = best.geom >= 0;
+                    if constexpr (WN) {
+                        // (the pre-pass stores the object-space normal, for every reader of the hits: this kernel wants the table's)
+                        float4 n = make_float4(0.f, 0.f, 1.f, 0.f);
+                        if (hit) {
+                            if (best.rec >= 0) n = p.tri_world_normals[best.rec];
+                            else n = lds_geom4(L, best.geom, kGeomWorldNormalVec4);
+                        }
+                        best.cx = n.x; best.cy = n.y; best.cz = n.z;
+                    }
                     cnt.rays += 1; // a path segment like any other, answered without a traversal (counted apart below)
                     settle_now = true;
                 }
@@ -210,7 +231,7 @@ __global__ __launch_bounds__(BLOCK) void trace_bvh_kernel(const KParams p)
                     M.global = BIG == 2 ? p.geoms + (hit ? best.geom : 0) : nullptr;
                     M.geom_base = L.geom_base;
                     M.g = best.geom;
-                    const int r = settle_hit<EXTRAS, PREPASS>(p, best, hit, M, P);
+                    const int r = settle_hit<EXTRAS, PREPASS, WN>(p, best, hit, M, P);
                     inflight = false;
                     active = r != kPixelDone;
                     goes_on = r == kGoesOn;
@@ -224,7 +245,7 @@ __global__ __launch_bounds__(BLOCK) void trace_bvh_kernel(const KParams p)
                 M.global = BIG == 2 ? p.geoms + best.geom : nullptr;
                 M.geom_base = L.geom_base;
                 M.g = best.geom;
-                scatter<EXTRAS>(p, best, M, P);
+                scatter<EXTRAS, WN>(p, best, M, P);
             }
         }
         if (STATS) t2 = __builtin_amdgcn_s_memtime();
@@ -1067,17 +1088,21 @@ static hipError_t allow_full_lds(K* kernel)
 // instantiation's dynamic-LDS limit, and the family's launcher walks the same list to find the instantiation that matches the
 // run-time key: what can be launched has its attribute, and a key outside the list is hipErrorInvalidValue.
 
-// The instantiations of trace_bvh_kernel, X(STATS, BLOCK, EXTRAS, BIG, PREPASS, START), for each workgroup size: the frame's kernel
+// The instantiations of trace_bvh_kernel, X(STATS, BLOCK, EXTRAS, BIG, PREPASS, START, WN), for each workgroup size: the frame's kernel
 // for scenes of up to kChunkGeometries geometries without and with extras and for the two classes of larger scenes (always with
 // extras), with and without statistics; the pre-pass, one per scene class (the general kernel, no statistics); the kernel that runs
-// on start records (diffuse small scenes).
+// on start records (diffuse small scenes); the two diffuse small-scene kernels once more on the scene's normal tables (WN).
 // The reported name is "trace_bvh_kernel<STATS, BLOCK, EXTRAS, BIG, PREPASS>" - the five parameters there were before START, as
-// tools and tests parse it - and START = true appends ", true"; the pre-pass reports one literal for all its instantiations.
+// tools and tests parse it - and START = true appends ", true"; the pre-pass reports one literal for all its instantiations.  WN does
+// not show in the name: it is the same kernel of the frame, computing the same bits, with one chain of arithmetic taken out.
 #define FF_TRACE_BVH_KERNELS_OF(X, B)                                                                                                                \
-    X(false, B, false, 0, false, false) X(true, B, false, 0, false, false) X(false, B, true, 0, false, false) X(true, B, true, 0, false, false)      \
-    X(false, B, true, 1, false, false) X(true, B, true, 1, false, false) X(false, B, true, 2, false, false) X(true, B, true, 2, false, false)        \
-    X(false, B, true, 0, true, false) X(false, B, true, 1, true, false) X(false, B, true, 2, true, false)                                           \
-    X(false, B, false, 0, false, true) X(true, B, false, 0, false, true)
+    X(false, B, false, 0, false, false, false) X(true, B, false, 0, false, false, false) X(false, B, true, 0, false, false, false)                   \
+    X(true, B, true, 0, false, false, false) X(false, B, true, 1, false, false, false) X(true, B, true, 1, false, false, false)                      \
+    X(false, B, true, 2, false, false, false) X(true, B, true, 2, false, false, false)                                                               \
+    X(false, B, true, 0, true, false, false) X(false, B, true, 1, true, false, false) X(false, B, true, 2, true, false, false)                       \
+    X(false, B, false, 0, false, true, false) X(true, B, false, 0, false, true, false)                                                               \
+    X(false, B, false, 0, false, false, true) X(true, B, false, 0, false, false, true)                                                               \
+    X(false, B, false, 0, false, true, true) X(true, B, false, 0, false, true, true)
 #define FF_TRACE_BVH_KERNELS(X) FF_TRACE_BVH_KERNELS_OF(X, 512) FF_TRACE_BVH_KERNELS_OF(X, 768) FF_TRACE_BVH_KERNELS_OF(X, 1024)
 #define FF_NAME_START_false ""
 #define FF_NAME_START_true ", true"
@@ -1107,8 +1132,8 @@ static_assert(FF_TRACE_BVH == 1 && FF_TRACE_BRUTE_FORCE == 0, "the MODE column a
 hipError_t prepare_kernels()
 {
     hipError_t e;
-#define FF_X(STATS, B, EXTRAS, BIG, PREPASS, START) \
-    if ((e = allow_full_lds(&trace_bvh_kernel<STATS, B, EXTRAS, BIG, PREPASS, START>)) != hipSuccess) return e;
+#define FF_X(STATS, B, EXTRAS, BIG, PREPASS, START, WN) \
+    if ((e = allow_full_lds(&trace_bvh_kernel<STATS, B, EXTRAS, BIG, PREPASS, START, WN>)) != hipSuccess) return e;
     FF_TRACE_BVH_KERNELS(FF_X)
 #undef FF_X
 #define FF_X(STATS, B, EXTRAS) \
@@ -1147,7 +1172,7 @@ static hipError_t launch_pool(const KParams& p, bool collect_stats, int grid_blo
 }
 
 hipError_t launch_trace(const KParams& p, int trace_mode, bool collect_stats, int grid_blocks, int block_threads, hipStream_t stream,
-                        const char** kernel_name, bool pool, bool prepass, bool start)
+                        const char** kernel_name, bool pool, bool prepass, bool start, bool world_normals)
 {
     const dim3 grid(grid_blocks);
     const char* name = "";
@@ -1162,9 +1187,11 @@ hipError_t launch_trace(const KParams& p, int trace_mode, bool collect_stats, in
         // the key of the instantiation: the pre-pass has one per workgroup size and scene size, the general one; larger scenes always run the full kernel
         const int threads = block_threads == 1024 ? 1024 : (block_threads == 768 ? 768 : 512);
         const bool stats = !prepass && collect_stats, extras = prepass || big != 0 || needs_extras(p), from_start = !prepass && start;
-#define FF_X(STATS, B, EXTRAS, BIG, PREPASS, START)                                                                                                  \
-    if (stats == STATS && threads == B && extras == EXTRAS && big == BIG && prepass == PREPASS && from_start == START) {                             \
-        hipLaunchKernelGGL((trace_bvh_kernel<STATS, B, EXTRAS, BIG, PREPASS, START>), grid, block, lds, stream, p);                                  \
+        // (the normal tables serve the kernels without the extras, on path frames: the reference's own shade wants the object-space normal)
+        const bool wn = world_normals && !extras && p.shade_mode == FF_SHADE_DIFFUSE_PATH && p.tri_world_normals != nullptr && p.geom_world_normals != nullptr;
+#define FF_X(STATS, B, EXTRAS, BIG, PREPASS, START, WN)                                                                                              \
+    if (stats == STATS && threads == B && extras == EXTRAS && big == BIG && prepass == PREPASS && from_start == START && wn == WN) {                 \
+        hipLaunchKernelGGL((trace_bvh_kernel<STATS, B, EXTRAS, BIG, PREPASS, START, WN>), grid, block, lds, stream, p);                              \
         name = "trace_bvh_kernel<" #STATS ", " #B ", " #EXTRAS ", " #BIG ", " #PREPASS FF_NAME_START_##START ">";                                    \
     } else
         FF_TRACE_BVH_KERNELS(FF_X) return hipErrorInvalidValue;

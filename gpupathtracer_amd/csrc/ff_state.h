@@ -25,6 +25,10 @@ struct FfState {
     ff::TriRecord* d_tris = nullptr;
     ff::TriNormals* d_normals = nullptr; // vertex normals, parallel to d_tris
     ff::TriUVs* d_uvs = nullptr;         // vertex UVs, parallel to d_tris (read only where an albedo texture is bound)
+    // Normal tables (KParams::tri_world_normals / geom_world_normals; scenes of up to kChunkGeometries geometries, null otherwise): one
+    // allocation of the upload, num_tris entries parallel to d_tris, then num_geoms parallel to d_geoms.  Rewritten by finalize_layout,
+    // which every change of the scene ends with (upload, ff_update_transforms, ff_update_mesh).
+    float4* d_world_normals = nullptr;
     ff::BvhNode* d_nodes = nullptr;   // binary trees: what the builders write and refit works on
     ff::WallTable walls = {};          // the axis-aligned planes among the records every query screens (finalize_layout)
     int num_scan = 0;                  // big scenes: leading plane records kept out of the geometry tree (count_scan_planes)
@@ -201,6 +205,7 @@ struct FfState {
     struct Switches {
         bool no_last_bounce_cut = false, no_primary_cull = false, no_primary_reuse = false; // per frame (render_enqueue)
         bool no_start_records = false; // FF_NO_START_RECORDS: every sample starts from the pixel's raw stored hit (the kernel without START)
+        bool no_world_normals = false; // FF_NO_WORLD_NORMALS: the shading pass computes every hit's world normal (the kernels without WN)
         bool no_primary_cache = false; // FF_NO_PRIMARY_CACHE: every frame runs its own pre-pass (the stored hits are not kept from frame to frame)
         int tail_blocks = 0;           // FF_TAIL_BLOCKS: how many of the frame's last sample blocks go out as short items (0: the library's choice)
         int reuse_min_spp = 2;         // FF_REUSE_MIN_SPP: frames of fewer samples per pixel trace their primary rays themselves unless the hits are there
