@@ -194,6 +194,10 @@ struct FfState {
     float disp_prev_exposure = 0.f;           // E of the last automatic call (the next one adapts from it)
     float disp_exposure = 0.f, disp_target = 0.f;
     uint32_t disp_histogram[256] = {};
+    // motion blur (ff_motion_blur, ff_motion_blur.hip): the packed {v, l, z} plane (one float4 per pixel), the tile and neighbour
+    // maxima (one float4 per tile each), then the staging of host buffers.  Not reset by uploads.
+    void* d_mblur_work = nullptr;
+    size_t mblur_work_bytes = 0;
     unsigned* d_queue = nullptr;               // work-queue counter: lives right behind the counters (one memset clears both)
     unsigned long long* d_counters = nullptr;  // 28 counters + 4 queue words
     unsigned long long* h_counters = nullptr;  // pinned mirror for the per-frame read-back
@@ -309,6 +313,8 @@ int glossy_sync_table(FfState* s);
 void glossy_release(FfState* s);
 // Display transform (ff_display_api.cpp): frees the state's device buffers (ff_destroy).
 void display_release(FfState* s);
+// Motion blur (ff_motion_blur_api.cpp): frees the state's work buffer (ff_destroy).
+void motion_blur_release(FfState* s);
 // The pixel buffer registered with ff_register_gl_pbo, mapped on the state's stream (kernel.cu:338-339) and unmapped again
 // (kernel.cu:344): what ff_render_to_pbo and ff_display_to_pbo write.  need_bytes: the least size the mapping must have.
 int map_pbo(FfState* s, size_t need_bytes, void** out_ptr);

@@ -40,6 +40,7 @@ EXPORTS = [
     "ff_camera_sampling_init", "ff_set_camera_sampling", "ff_camera_sample_rays", "ff_scene_file_camera_sampling",
     "ff_upscale_params_init", "ff_upscale", "ff_upscale_host",
     "ff_taa_upscale_params_init", "ff_taa_upscale", "ff_taa_upscale_reset", "ff_taa_upscale_history",
+    "ff_motion_blur_params_init", "ff_motion_blur", "ff_motion_blur_host",
 ]
 DIST_ID_BYTES = 128
 
@@ -223,6 +224,10 @@ def load():
     lib.ff_upscale_params_init.restype = None
     lib.ff_upscale.argtypes = [vp, P(T.FfUpscaleParams), i32, i32, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, i32, vp, i32, vp, i32]
     lib.ff_upscale_host.argtypes = [P(T.FfUpscaleParams), i32, i32, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp]
+    lib.ff_motion_blur_params_init.argtypes = [P(T.FfMotionBlurParams)]
+    lib.ff_motion_blur_params_init.restype = None
+    lib.ff_motion_blur.argtypes = [vp, i32, i32, P(T.FfMotionBlurParams), vp, vp, vp, i32, vp, i32, vp, i32]
+    lib.ff_motion_blur_host.argtypes = [i32, i32, P(T.FfMotionBlurParams), vp, vp, vp, vp, vp]
     lib.ff_taa_upscale_params_init.argtypes = [P(T.FfTaaUpscaleParams)]
     lib.ff_taa_upscale_params_init.restype = None
     lib.ff_taa_upscale.argtypes = [vp, P(T.FfCamera), P(T.FfTaaUpscaleParams), i32, i32, vp, vp, i32, i32, vp, vp, i32, vp, i32, vp, i32]
@@ -604,6 +609,40 @@ def upscale_host(radiance_lo, gbuffer_lo, gbuffer_hi, p=None):
     check(load().ff_upscale_host(C.byref(p), w, h, rad.ctypes.data, lo["position"].ctypes.data, lo["normal"].ctypes.data, lo["albedo"].ctypes.data,
                                  lo["ids"].ctypes.data, W, H, hi["position"].ctypes.data, hi["normal"].ctypes.data, hi["albedo"].ctypes.data,
                                  hi["ids"].ctypes.data, rgb8.ctypes.data, out.ctypes.data))
+    return rgb8, out
+
+
+def motion_blur_params(**overrides):
+    """ff_motion_blur_params_init's defaults with the given fields replaced (any FfMotionBlurParams field)."""
+    p = T.FfMotionBlurParams()
+    load().ff_motion_blur_params_init(C.byref(p))
+    for name, value in overrides.items():
+        if name not in dict(T.FfMotionBlurParams._fields_):
+            raise TypeError(f"FfMotionBlurParams has no field {name!r}")
+        setattr(p, name, value)
+    return p
+
+
+def _motion_blur_images(radiance, motion, depth, who):
+    """The three input images of ff_motion_blur as contiguous float32 arrays, and (h, w)."""
+    rad = np.ascontiguousarray(radiance, dtype=np.float32)
+    mot = np.ascontiguousarray(motion, dtype=np.float32)
+    dep = np.ascontiguousarray(depth, dtype=np.float32)
+    h, w = rad.shape[:2]
+    if rad.shape != (h, w, 3) or mot.shape != (h, w, 2) or dep.shape != (h, w):
+        raise ValueError(f"{who}: radiance must be [H,W,3], motion [H,W,2] and depth [H,W]")
+    return rad, mot, dep, (h, w)
+
+
+def motion_blur_host(radiance, motion, depth, p=None, want_rgb8=True, want_out=True):
+    """ff_motion_blur_host (no GPU): host radiance [H,W,3], motion [H,W,2] (a *_history call's) and depth [H,W] (gbuffer()'s)
+    -> (rgb8 [H,W,3] uint8, radiance [H,W,3] float32)."""
+    rad, mot, dep, (h, w) = _motion_blur_images(radiance, motion, depth, "motion_blur_host")
+    p = p if p is not None else motion_blur_params()
+    rgb8 = np.zeros((h, w, 3), dtype=np.uint8) if want_rgb8 else None
+    out = np.zeros((h, w, 3), dtype=np.float32) if want_out else None
+    check(load().ff_motion_blur_host(w, h, C.byref(p), rad.ctypes.data, mot.ctypes.data, dep.ctypes.data, rgb8.ctypes.data if want_rgb8 else None,
+                                     out.ctypes.data if want_out else None))
     return rgb8, out
 
 
@@ -1020,6 +1059,24 @@ class Tracer:
         length = np.zeros((h, w), dtype=np.float32)
         check(self._lib.ff_taa_upscale_history(self._state, motion.ctypes.data if h * w else None, length.ctypes.data if h * w else None, 0))
         return motion, length
+
+    def motion_blur(self, radiance, motion, depth, p=None, want_rgb8=True, want_out=True):
+        """ff_motion_blur of host radiance [H,W,3] with the motion [H,W,2] of a *_history call and gbuffer()'s depth [H,W]
+        -> (rgb8 [H,W,3] uint8, radiance [H,W,3] float32)."""
+        rad, mot, dep, (h, w) = _motion_blur_images(radiance, motion, depth, "motion_blur")
+        p = p if p is not None else motion_blur_params()
+        rgb8 = np.zeros((h, w, 3), dtype=np.uint8) if want_rgb8 else None
+        out = np.zeros((h, w, 3), dtype=np.float32) if want_out else None
+        check(self._lib.ff_motion_blur(self._state, w, h, C.byref(p), rad.ctypes.data, mot.ctypes.data, dep.ctypes.data, 0,
+                                       rgb8.ctypes.data if want_rgb8 else None, 0, out.ctypes.data if want_out else None, 0))
+        return rgb8, out
+
+    def motion_blur_device(self, width, height, radiance_ptr, motion_ptr, depth_ptr, p=None, rgb8_ptr=None, radiance_out_ptr=None):
+        """ff_motion_blur on DEVICE buffers (raw pointers); the outputs must not overlap an input."""
+        p = p if p is not None else motion_blur_params()
+        vp = lambda q: C.c_void_p(q) if q else None  # noqa: E731
+        check(self._lib.ff_motion_blur(self._state, width, height, C.byref(p), vp(radiance_ptr), vp(motion_ptr), vp(depth_ptr), 1, vp(rgb8_ptr), 1,
+                                       vp(radiance_out_ptr), 1))
 
     def display(self, radiance, p=None, want_rgb8=True, want_out=True):
         """ff_display of host radiance [H,W,3] -> (rgb8 [H,W,3] uint8, display_out [H,W,3] float32: the curve's output in [0, 1]);

@@ -177,6 +177,14 @@ ENCODE_LINEAR, ENCODE_SRGB = 0, 1
 DISPLAY_AUTO_EXPOSURE, DISPLAY_BLOOM = 1, 2
 DISPLAY_BINS = 256  # ff_display's luminance histogram: 8 bins per stop from 2^-16 up
 
+
+class FfMotionBlurParams(C.Structure):
+    _fields_ = [("shutter", C.c_float), ("max_radius", C.c_int32), ("samples", C.c_int32), ("depth_extent", C.c_float), ("flags", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+MOTION_BLUR_PARAMS_BYTES = 24
+
 BUILD_HOST_SAH, BUILD_GPU_LBVH, BUILD_GPU_PLOC = 0, 1, 2
 UPDATE_REFIT, UPDATE_REBUILD = 0, 1
 

@@ -829,6 +829,66 @@ FF_API int ff_taa_upscale_reset(FfState* state);
  * since the last reset. */
 FF_API int ff_taa_upscale_history(FfState* state, float* motion, float* length, int on_device);
 
+/* ---- motion blur (a reconstruction filter on stored motion: McGuire et al., I3D 2012) ----------- */
+
+/* Defaults: shutter 0.5, max_radius 16, samples 15, depth_extent 0.1, flags 0. */
+FF_API void ff_motion_blur_params_init(FfMotionBlurParams* p);
+
+/* Blurs a W x H float3 radiance image along the per-pixel screen motion: a 1-spp frame is an instant, this spreads it over the time
+ * the shutter is open.  It sits after ff_taa / ff_taa_upscale and before ff_display.  A pure image operation like ff_denoise and
+ * ff_display: no scene is read, none is needed, and no history is kept.  motion is W*H*2 floats exactly as ff_taa_history,
+ * ff_temporal_history and ff_taa_upscale_history write it (previous position minus current position, in pixels); depth is W*H
+ * floats, ff_gbuffer's depth plane (m_t; a miss is 0).  All arithmetic is float32, evaluated as written with the parentheses shown,
+ * no fused multiply-add, IEEE sqrt and division; exp and pow appear nowhere, so ff_motion_blur, ff_motion_blur_host and a float32
+ * restatement agree bit for bit.  clamp(v) = 0 for v < 0, 1 for v > 1, else v.  With k = max_radius, S = samples:
+ *   1 half-spread  per pixel, hs = 0.5f * shutter (formed once), v = (m.x * hs, m.y * hs).  If either component of v is not finite,
+ *                v = (0, 0).  l = sqrt(v.x * v.x + v.y * v.y).  If l > (float)k: s = (float)k / l, v = (v.x * s, v.y * s) and
+ *                l = sqrt(v.x * v.x + v.y * v.y) again, from the scaled components.  z = depth if it is finite and > 0, else
+ *                FLT_MAX (a miss is behind everything).  The pixel keeps {v.x, v.y, l, z}
+ *   2 tile max   tiles are k x k pixels from the top-left corner, partial at the right and bottom edges.  T(tile) = the kept {v, l}
+ *                of the tile's pixel with the largest v.x * v.x + v.y * v.y (of the kept v); among equals the first in row-major order
+ *   3 neighbour max  N(tile) = the T with the largest v.x * v.x + v.y * v.y over the 3x3 tiles around it that exist; among equals the
+ *                first in row-major order of the tiles
+ *   4 gather     pixel X = (x, y) with (vn, ln) = N(tile (x / k, y / k)) and its own kept lX, zX and colour cX.  If ln <= 0.5, or cX
+ *                is not finite in all three channels, the output is cX bit for bit.  Otherwise, in uint32 arithmetic,
+ *                h = (x * 0x9E3779B1) ^ (y * 0x85EBCA77);  h ^= h >> 15;  h *= 0x2C1B3C6D;  h ^= h >> 12;
+ *                j = (float)(h >> 8) * 2^-24 - 0.5.  For i = 0 .. S-1 in order:
+ *                  t = ((((float)i + j) + 1) / (float)(S + 1)) * 2 - 1,
+ *                  dx = (int)floor(vn.x * t + 0.5), dy = (int)floor(vn.y * t + 0.5), Y = X + (dx, dy).
+ *                The tap is skipped when dx = dy = 0, when Y is outside the image and when cY is not finite in all three channels.
+ *                Otherwise, with Y's kept lY, zY:  d = sqrt((float)(dx * dx + dy * dy)),
+ *                  soft(a, b) = clamp(1 - (a - b) / depth_extent);  f = soft(zY, zX) (1 when Y is nearer),  b = soft(zX, zY),
+ *                  cone(d, l) = clamp(1 - d / l) for l > 0, else 0,
+ *                  cyl(d, l)  = 1 - ((u * u) * (3 - (2 * u))),  u = clamp((d - 0.95f * l) / (1.05f * l - 0.95f * l)), for l > 0, else 0,
+ *                  a = (f * cone(d, lY) + b * cone(d, lX)) + (cyl(d, lY) * cyl(d, lX)) * 2,
+ *                  s_c = s_c + a * (cY_c - cX_c) per channel c,  A = A + a   (s_c and A start at 0).
+ *                After the taps  w0 = 1 / max(lX, 0.5)  and per channel  out_c = cX_c + s_c / (w0 + A)  where s_c != 0, and
+ *                out_c = cX_c itself where s_c = 0 (so a -0 stays -0): ff_upscale's "mean" form of (w0 cX + sum a cY) / (w0 + sum a).
+ *                When every tap has the centre's colour, or none counts, cX comes back bit for bit
+ *   5 rgb8 = trunc(clamp(out * 255)), the rule of every rgb8 output here.
+ * Consequences.  Motion 0 everywhere, or shutter 0, returns the input bit for bit, NaN and Inf pixels included; so does every pixel
+ * whose 3x3 tile neighbourhood holds no motion with l > 0.5.  Non-finite radiance follows the project's rule: such a pixel may spoil
+ * only itself - it is copied through and never counts as a tap; non-finite motion is no motion and non-finite depth is a miss.
+ * rgb8 (W*H*3 bytes) and radiance_out (W*H*3 floats) may each be NULL.  Neither may overlap an input (the gather reads neighbours;
+ * radiance_out == radiance_in is refused), and the two outputs may not overlap each other.  inputs_on_device covers all three
+ * input images.  Width and height are 1 .. 65535.
+ * Synchronous, on the state's stream; host buffers are staged.  The call leaves FfStats, the stored primary hits and their key, every
+ * filter's history, the display exposure and the progressive sum as they were; its own state is a work buffer (allocated on first
+ * use, regrown for a larger size, freed by ff_destroy).  FF_ERR_INVALID_ARG, naming the field, before any device work for: a NULL
+ * state, params, radiance_in, motion or depth; a bad size; shutter outside 0 .. 4, max_radius or samples outside 1 .. 64,
+ * depth_extent not positive (every float must be finite); nonzero flags or reserved; an output that overlaps an input or
+ * the other output.
+ * Not offered: time-sampled blur inside the path kernels, motion of deforming meshes (the stored motion is rigid), McGuire's
+ * diagonal-tile rule, per-tile sample counts, a multi-GPU twin, blurring ff_denoise_temporal's moments. */
+FF_API int ff_motion_blur(FfState* state, int width, int height, const FfMotionBlurParams* p,
+                          const float* radiance_in, const float* motion, const float* depth, int inputs_on_device,
+                          void* rgb8, int rgb8_on_device, float* radiance_out, int radiance_out_on_device);
+
+/* Host-only twin (no GPU, no state, host pointers), compiled from the same inline per-pixel functions the kernels use: the same
+ * image arguments, the same checks, the same bits. */
+FF_API int ff_motion_blur_host(int width, int height, const FfMotionBlurParams* p, const float* radiance_in, const float* motion,
+                               const float* depth, unsigned char* rgb8, float* radiance_out);
+
 /* ---- display transform (exposure, bloom, tone curve, sRGB) ------------------------------------- */
 
 /* Defaults: ACES, SRGB, flags 0, exposure 1, white 4, key 0.18, percentiles 0.5 / 0.95, min_exposure 2^-10, max_exposure 2^10,

@@ -320,6 +320,17 @@ typedef struct FfDisplayParams {
     int32_t bloom_levels;      /* 1..8 */
 } FfDisplayParams;             /* 64 bytes; every float must be finite */
 
+/* ff_motion_blur: a motion-blur reconstruction filter on stored screen motion (McGuire et al., I3D 2012).
+ * ff_motion_blur_params_init gives the defaults; the operator is in ff_api.h. */
+typedef struct FfMotionBlurParams {
+    float   shutter;       /* fraction of the frame interval the shutter is open, 0 .. 4 */
+    int32_t max_radius;    /* k: longest half-spread in pixels = tile edge, 1 .. 64 */
+    int32_t samples;       /* S: taps along the dominant velocity, 1 .. 64 */
+    float   depth_extent;  /* world distance over which "in front" fades, > 0 */
+    int32_t flags;         /* none defined yet: 0 */
+    int32_t reserved;      /* 0 */
+} FfMotionBlurParams;      /* 24 bytes; every float must be finite */
+
 /* ff_texture_create: how a texture is addressed and filtered (the formulas are in ff_api.h).  0 = repeat, bilinear. */
 #define FF_TEX_REPEAT    0   /* coordinates wrap: c - floor(c) */
 #define FF_TEX_CLAMP     1   /* coordinates clamp to [0, 1] */
@@ -351,6 +362,7 @@ static_assert(sizeof(FfIntersect) == 40, "Intersect layout must match utilities.
 static_assert(sizeof(FfCamera) == 108, "Camera layout must match utilities.h:269-291");
 static_assert(sizeof(FfDisplayParams) == 64, "FfDisplayParams is 64 bytes");
 static_assert(sizeof(FfCameraSampling) == 16, "FfCameraSampling is 16 bytes");
+static_assert(sizeof(FfMotionBlurParams) == 24, "FfMotionBlurParams is 24 bytes");
 #else
 _Static_assert(sizeof(FfBXDF) == 60, "BXDF layout");
 _Static_assert(sizeof(FfTriangle) == 96, "Triangle layout");
@@ -360,6 +372,7 @@ _Static_assert(sizeof(FfIntersect) == 40, "Intersect layout");
 _Static_assert(sizeof(FfCamera) == 108, "Camera layout");
 _Static_assert(sizeof(FfDisplayParams) == 64, "FfDisplayParams layout");
 _Static_assert(sizeof(FfCameraSampling) == 16, "FfCameraSampling layout");
+_Static_assert(sizeof(FfMotionBlurParams) == 24, "FfMotionBlurParams layout");
 #endif
 
 #endif /* FIREFLY_FF_TYPES_H */
