@@ -1026,6 +1026,7 @@ int ff_destroy(FfState* s)
     glossy_release(s);
     display_release(s);
     motion_blur_release(s);
+    dof_release(s);
     free_build_scratch(s->scratch);
     if (s->d_blocksums) (void)hipFree(s->d_blocksums);
     if (s->d_rgb8) (void)hipFree(s->d_rgb8);

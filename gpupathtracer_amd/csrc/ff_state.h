@@ -198,6 +198,10 @@ struct FfState {
     // maxima (one float4 per tile each), then the staging of host buffers.  Not reset by uploads.
     void* d_mblur_work = nullptr;
     size_t mblur_work_bytes = 0;
+    // depth of field (ff_depth_of_field, ff_dof.hip): the packed {l, z} plane (one float2 per pixel), the tile and neighbour maxima
+    // (one float per tile each), then the staging of host buffers.  Not reset by uploads.
+    void* d_dof_work = nullptr;
+    size_t dof_work_bytes = 0;
     unsigned* d_queue = nullptr;               // work-queue counter: lives right behind the counters (one memset clears both)
     unsigned long long* d_counters = nullptr;  // 28 counters + 4 queue words
     unsigned long long* h_counters = nullptr;  // pinned mirror for the per-frame read-back
@@ -315,6 +319,8 @@ void glossy_release(FfState* s);
 void display_release(FfState* s);
 // Motion blur (ff_motion_blur_api.cpp): frees the state's work buffer (ff_destroy).
 void motion_blur_release(FfState* s);
+// Depth of field (ff_dof_api.cpp): frees the state's work buffer (ff_destroy).
+void dof_release(FfState* s);
 // The pixel buffer registered with ff_register_gl_pbo, mapped on the state's stream (kernel.cu:338-339) and unmapped again
 // (kernel.cu:344): what ff_render_to_pbo and ff_display_to_pbo write.  need_bytes: the least size the mapping must have.
 int map_pbo(FfState* s, size_t need_bytes, void** out_ptr);

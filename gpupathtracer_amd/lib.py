@@ -41,6 +41,7 @@ EXPORTS = [
     "ff_upscale_params_init", "ff_upscale", "ff_upscale_host",
     "ff_taa_upscale_params_init", "ff_taa_upscale", "ff_taa_upscale_reset", "ff_taa_upscale_history",
     "ff_motion_blur_params_init", "ff_motion_blur", "ff_motion_blur_host",
+    "ff_dof_params_init", "ff_dof_params_from_camera", "ff_depth_of_field", "ff_depth_of_field_host",
 ]
 DIST_ID_BYTES = 128
 
@@ -228,6 +229,11 @@ def load():
     lib.ff_motion_blur_params_init.restype = None
     lib.ff_motion_blur.argtypes = [vp, i32, i32, P(T.FfMotionBlurParams), vp, vp, vp, i32, vp, i32, vp, i32]
     lib.ff_motion_blur_host.argtypes = [i32, i32, P(T.FfMotionBlurParams), vp, vp, vp, vp, vp]
+    lib.ff_dof_params_init.argtypes = [P(T.FfDofParams)]
+    lib.ff_dof_params_init.restype = None
+    lib.ff_dof_params_from_camera.argtypes = [P(T.FfCamera), P(T.FfCameraSampling), P(T.FfDofParams)]
+    lib.ff_depth_of_field.argtypes = [vp, P(T.FfCamera), i32, i32, P(T.FfDofParams), vp, vp, vp, i32, vp, i32, vp, i32]
+    lib.ff_depth_of_field_host.argtypes = [P(T.FfCamera), i32, i32, P(T.FfDofParams), vp, vp, vp, vp, vp]
     lib.ff_taa_upscale_params_init.argtypes = [P(T.FfTaaUpscaleParams)]
     lib.ff_taa_upscale_params_init.restype = None
     lib.ff_taa_upscale.argtypes = [vp, P(T.FfCamera), P(T.FfTaaUpscaleParams), i32, i32, vp, vp, i32, i32, vp, vp, i32, vp, i32, vp, i32]
@@ -643,6 +649,50 @@ def motion_blur_host(radiance, motion, depth, p=None, want_rgb8=True, want_out=T
     out = np.zeros((h, w, 3), dtype=np.float32) if want_out else None
     check(load().ff_motion_blur_host(w, h, C.byref(p), rad.ctypes.data, mot.ctypes.data, dep.ctypes.data, rgb8.ctypes.data if want_rgb8 else None,
                                      out.ctypes.data if want_out else None))
+    return rgb8, out
+
+
+def dof_params(**overrides):
+    """ff_dof_params_init's defaults with the given fields replaced (any FfDofParams field; reserved: a pair)."""
+    p = T.FfDofParams()
+    load().ff_dof_params_init(C.byref(p))
+    for name, value in overrides.items():
+        if name not in dict(T.FfDofParams._fields_):
+            raise TypeError(f"FfDofParams has no field {name!r}")
+        setattr(p, name, (C.c_int32 * 2)(*value) if name == "reserved" else value)
+    return p
+
+
+def dof_params_from_camera(camera, cs, **overrides):
+    """dof_params(**overrides) with the focus_distance and coc_scale of the thin lens `cs` (lib.camera_sampling(...)) under
+    `camera` (ff_dof_params_from_camera)."""
+    p = dof_params(**overrides)
+    check(load().ff_dof_params_from_camera(C.byref(camera), C.byref(cs), C.byref(p)))
+    return p
+
+
+def _dof_images(radiance, gbuffer_or_planes, who):
+    """The three input images of ff_depth_of_field as contiguous float32 arrays, and (h, w).  gbuffer_or_planes: a gbuffer() dict
+    or the pair (position [H,W,3], depth [H,W])."""
+    position, depth = (gbuffer_or_planes["position"], gbuffer_or_planes["depth"]) if isinstance(gbuffer_or_planes, dict) else gbuffer_or_planes
+    rad = np.ascontiguousarray(radiance, dtype=np.float32)
+    pos = np.ascontiguousarray(position, dtype=np.float32)
+    dep = np.ascontiguousarray(depth, dtype=np.float32)
+    h, w = rad.shape[:2]
+    if rad.shape != (h, w, 3) or pos.shape != (h, w, 3) or dep.shape != (h, w):
+        raise ValueError(f"{who}: radiance and position must be [H,W,3] and depth [H,W]")
+    return rad, pos, dep, (h, w)
+
+
+def depth_of_field_host(radiance, gbuffer_or_planes, camera, p=None, want_rgb8=True, want_out=True):
+    """ff_depth_of_field_host (no GPU): host radiance [H,W,3] and a gbuffer() dict of `camera` (or its (position, depth) planes)
+    -> (rgb8 [H,W,3] uint8, radiance [H,W,3] float32)."""
+    rad, pos, dep, (h, w) = _dof_images(radiance, gbuffer_or_planes, "depth_of_field_host")
+    p = p if p is not None else dof_params()
+    rgb8 = np.zeros((h, w, 3), dtype=np.uint8) if want_rgb8 else None
+    out = np.zeros((h, w, 3), dtype=np.float32) if want_out else None
+    check(load().ff_depth_of_field_host(C.byref(camera), w, h, C.byref(p), rad.ctypes.data, pos.ctypes.data, dep.ctypes.data,
+                                        rgb8.ctypes.data if want_rgb8 else None, out.ctypes.data if want_out else None))
     return rgb8, out
 
 
@@ -1077,6 +1127,24 @@ class Tracer:
         vp = lambda q: C.c_void_p(q) if q else None  # noqa: E731
         check(self._lib.ff_motion_blur(self._state, width, height, C.byref(p), vp(radiance_ptr), vp(motion_ptr), vp(depth_ptr), 1, vp(rgb8_ptr), 1,
                                        vp(radiance_out_ptr), 1))
+
+    def depth_of_field(self, radiance, gbuffer_or_planes, camera, p=None, want_rgb8=True, want_out=True):
+        """ff_depth_of_field of host radiance [H,W,3] with a gbuffer() dict of `camera` (or its (position [H,W,3], depth [H,W])
+        planes) -> (rgb8 [H,W,3] uint8, radiance [H,W,3] float32)."""
+        rad, pos, dep, (h, w) = _dof_images(radiance, gbuffer_or_planes, "depth_of_field")
+        p = p if p is not None else dof_params()
+        rgb8 = np.zeros((h, w, 3), dtype=np.uint8) if want_rgb8 else None
+        out = np.zeros((h, w, 3), dtype=np.float32) if want_out else None
+        check(self._lib.ff_depth_of_field(self._state, C.byref(camera), w, h, C.byref(p), rad.ctypes.data, pos.ctypes.data, dep.ctypes.data, 0,
+                                          rgb8.ctypes.data if want_rgb8 else None, 0, out.ctypes.data if want_out else None, 0))
+        return rgb8, out
+
+    def depth_of_field_device(self, camera, width, height, radiance_ptr, position_ptr, depth_ptr, p=None, rgb8_ptr=None, radiance_out_ptr=None):
+        """ff_depth_of_field on DEVICE buffers (raw pointers); the outputs must not overlap an input."""
+        p = p if p is not None else dof_params()
+        vp = lambda q: C.c_void_p(q) if q else None  # noqa: E731
+        check(self._lib.ff_depth_of_field(self._state, C.byref(camera), width, height, C.byref(p), vp(radiance_ptr), vp(position_ptr), vp(depth_ptr), 1,
+                                          vp(rgb8_ptr), 1, vp(radiance_out_ptr), 1))
 
     def display(self, radiance, p=None, want_rgb8=True, want_out=True):
         """ff_display of host radiance [H,W,3] -> (rgb8 [H,W,3] uint8, display_out [H,W,3] float32: the curve's output in [0, 1]);

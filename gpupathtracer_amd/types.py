@@ -185,6 +185,14 @@ class FfMotionBlurParams(C.Structure):
 
 MOTION_BLUR_PARAMS_BYTES = 24
 
+
+class FfDofParams(C.Structure):
+    _fields_ = [("focus_distance", C.c_float), ("coc_scale", C.c_float), ("max_radius", C.c_int32), ("grid", C.c_int32), ("depth_extent", C.c_float),
+                ("flags", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+DOF_PARAMS_BYTES = 32
+
 BUILD_HOST_SAH, BUILD_GPU_LBVH, BUILD_GPU_PLOC = 0, 1, 2
 UPDATE_REFIT, UPDATE_REBUILD = 0, 1
 

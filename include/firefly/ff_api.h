@@ -889,6 +889,81 @@ FF_API int ff_motion_blur(FfState* state, int width, int height, const FfMotionB
 FF_API int ff_motion_blur_host(int width, int height, const FfMotionBlurParams* p, const float* radiance_in, const float* motion,
                                const float* depth, unsigned char* rgb8, float* radiance_out);
 
+/* ---- depth of field (a gather filter on the G-buffer: the thin lens as a post filter) ------------- */
+
+/* Defaults: focus_distance 1, coc_scale 0 (no blur), max_radius 16, grid 4, depth_extent 0.1, flags 0. */
+FF_API void ff_dof_params_init(FfDofParams* p);
+
+/* Makes the filter agree with the in-path thin lens of ff_set_camera_sampling: sets p->focus_distance = cs->focus_distance and
+ * p->coc_scale = (float)(lens_radius * 0.5 * m_screenHeight / tan(radians(m_fov) / 2)), evaluated in double and rounded once, and
+ * leaves the other fields alone.  m_fov is the vertical field of view and pixels are square, so a lens of radius R focused at z_f
+ * spreads a point at axial depth z over a circle of R (H / 2) / tan(fov / 2) |1 / z_f - 1 / z| pixels' radius.  A setting with
+ * lens_radius 0 gives coc_scale 0: the filter copies.  FF_ERR_INVALID_ARG for a NULL pointer, for each of ff_set_camera_sampling's
+ * own checks, and for an m_fov outside (0, 180) or an m_screenHeight that is not positive (every float must be finite). */
+FF_API int ff_dof_params_from_camera(const FfCamera* camera, const FfCameraSampling* cs, FfDofParams* p);
+
+/* Spreads every pixel of a W x H float3 radiance image over its circle of confusion: defocus as a post filter on a PINHOLE frame, so
+ * that a 1-spp frame can be denoised, resolved and upsampled against the pinhole G-buffer first.  It sits where ff_motion_blur sits:
+ * after ff_taa / ff_taa_upscale, before or after ff_motion_blur, before ff_display.  A pure image operation like ff_denoise and
+ * ff_display: no scene is read, none is needed, and no history is kept.  position is W*H*3 floats and depth W*H floats, ff_gbuffer's
+ * planes of the same pose (a miss: depth 0).  Of camera only m_position and m_forward are read, as the caller's floats, not
+ * renormalised (the thin lens's precedent).  All arithmetic is float32, evaluated as written with the parentheses shown, no fused
+ * multiply-add, IEEE sqrt and division; exp, pow and trigonometry appear nowhere, so ff_depth_of_field, ff_depth_of_field_host and a
+ * float32 restatement agree bit for bit.  clamp(v) = 0 for v < 0, 1 for v > 1, else v.  With k = max_radius, g = grid, f^ = m_forward:
+ *   1 radius     per pixel, e = position - m_position per component, z = (e.x * f^.x + e.y * f^.y) + e.z * f^.z.  The pixel is a HIT
+ *                when depth is finite and > 0 and z is finite and > 1e-6f.  iz = 1 / z for a hit, else 0 (a miss lies at infinity).
+ *                fi = 1 / focus_distance (formed once).  l = coc_scale * fabs(fi - iz), and l > (float)k becomes (float)k.  The
+ *                pixel keeps {l, zk}, zk = z for a hit and FLT_MAX otherwise.  (l is finite and >= 0.)
+ *   2 tile max   tiles are k x k pixels from the top-left corner, partial at the right and bottom edges.  T(tile) = the largest kept l
+ *                in the tile
+ *   3 neighbour max  N(tile) = the largest T over the 3x3 tiles around it that exist (a maximum of finite numbers >= 0: no order,
+ *                no tie rule)
+ *   4 gather     pixel X = (x, y) with n = N(tile (x / k, y / k)) and its own kept lX, zX and colour cX.  If n <= 0.5, or cX is not
+ *                finite in all three channels, the output is cX bit for bit.  Otherwise, in uint32 arithmetic (ff_motion_blur's hash),
+ *                h = (x * 0x9E3779B1) ^ (y * 0x85EBCA77);  h ^= h >> 15;  h *= 0x2C1B3C6D;  h ^= h >> 12;
+ *                jx = (float)(h >> 8) * 2^-24 - 0.5,  jy = (float)((h * 0x9E3779B1) >> 8) * 2^-24 - 0.5.
+ *                For b = -g .. g (outer) and a = -g .. g (inner), in that order, over the points with a * a + b * b <= g * g (integers):
+ *                  dx = (int)floor(n * (((float)a + jx) / (float)g) + 0.5),  dy = (int)floor(n * (((float)b + jy) / (float)g) + 0.5),
+ *                  Y = X + (dx, dy).
+ *                The tap is skipped when dx = dy = 0, when Y is outside the image and when cY is not finite in all three channels.
+ *                Otherwise, with Y's kept lY, zY:  d = sqrt((float)(dx * dx + dy * dy)),
+ *                  f = clamp(1 - (zY - zX) / depth_extent)      (1 when Y is nearer or level, 0 when it is farther by depth_extent),
+ *                  cov(d, l) = clamp((l - d) + 0.5),  m = lY < lX ? lY : lX,
+ *                  inten(l) = 1 / (q * q),  q = l > 0.5 ? l : 0.5,
+ *                  w = (f * cov(d, lY) + (1 - f) * cov(d, m)) * inten(lY),
+ *                  s_c = s_c + w * (cY_c - cX_c) per channel c,  A = A + w   (s_c and A start at 0).
+ *                A tap in front spreads as far as its own circle; a tap behind reaches X only as far as X itself is blurred, so a
+ *                sharp foreground keeps its edge against a blurred background; every tap carries energy inversely to its circle's
+ *                area.  After the taps  w0 = inten(lX)  and per channel  out_c = cX_c + s_c / (w0 + A)  where s_c != 0, and
+ *                out_c = cX_c itself where s_c = 0 (so a -0 stays -0): ff_motion_blur's mean form.  When every tap has the centre's
+ *                colour, or none counts, cX comes back bit for bit
+ *   5 rgb8 = trunc(clamp(out * 255)), the rule of every rgb8 output here.
+ * Consequences.  coc_scale 0 returns the input bit for bit, NaN and Inf pixels included; so does every pixel whose 3x3 tile
+ * neighbourhood holds no l > 0.5 (everything in focus: the whole image).  Non-finite radiance follows the project's rule: such a
+ * pixel may spoil only itself - it is copied through and never counts as a tap; non-finite position or depth is a miss.
+ * focus_distance must be so large that 1 / focus_distance is finite (above about 2.94e-39): otherwise step 1 would form 0 * Inf
+ * under coc_scale 0.
+ * rgb8 (W*H*3 bytes) and radiance_out (W*H*3 floats) may each be NULL.  Neither may overlap an input (the gather reads neighbours;
+ * radiance_out == radiance_in is refused), and the two outputs may not overlap each other.  inputs_on_device covers all three
+ * input images.  Width and height are 1 .. 65535.
+ * Synchronous, on the state's stream; host buffers are staged.  The call leaves FfStats, the stored primary hits and their key, every
+ * filter's history, the display exposure and the progressive sum as they were; its own state is a work buffer (allocated on first
+ * use, regrown for a larger size, freed by ff_destroy).  FF_ERR_INVALID_ARG, naming the field, before any device work for: a NULL
+ * state, camera, params, radiance_in, position or depth; a bad size; focus_distance not > 0, coc_scale < 0, max_radius outside
+ * 1 .. 64, grid outside 1 .. 8, depth_extent not > 0 (every float must be finite); nonzero flags or reserved; a non-finite
+ * m_position or m_forward; an output that overlaps an input or the other output.
+ * Not offered: a separate near-field layer with background reconstruction behind a blurred foreground, polygonal or anamorphic
+ * apertures, bokeh highlights, an autofocus call, a multi-GPU twin, filtering ff_denoise_temporal's moments. */
+FF_API int ff_depth_of_field(FfState* state, const FfCamera* camera, int width, int height, const FfDofParams* p,
+                             const float* radiance_in, const float* position, const float* depth, int inputs_on_device,
+                             void* rgb8, int rgb8_on_device, float* radiance_out, int radiance_out_on_device);
+
+/* Host-only twin (no GPU, no state, host pointers), compiled from the same inline per-pixel functions the kernels use: the same
+ * image arguments, the same checks, the same bits. */
+FF_API int ff_depth_of_field_host(const FfCamera* camera, int width, int height, const FfDofParams* p,
+                                  const float* radiance_in, const float* position, const float* depth,
+                                  unsigned char* rgb8, float* radiance_out);
+
 /* ---- display transform (exposure, bloom, tone curve, sRGB) ------------------------------------- */
 
 /* Defaults: ACES, SRGB, flags 0, exposure 1, white 4, key 0.18, percentiles 0.5 / 0.95, min_exposure 2^-10, max_exposure 2^10,

@@ -331,6 +331,18 @@ typedef struct FfMotionBlurParams {
     int32_t reserved;      /* 0 */
 } FfMotionBlurParams;      /* 24 bytes; every float must be finite */
 
+/* ff_depth_of_field: a gather depth-of-field filter on the G-buffer's position and depth planes.  ff_dof_params_init gives the
+ * defaults, ff_dof_params_from_camera the focus and scale of a thin lens (ff_set_camera_sampling); the operator is in ff_api.h. */
+typedef struct FfDofParams {
+    float   focus_distance; /* distance of the plane of focus along m_forward, > 0 (and 1 / focus_distance finite) */
+    float   coc_scale;      /* radius of the circle of confusion in pixels per unit of |1/focus_distance - 1/z|, >= 0 */
+    int32_t max_radius;     /* k: largest radius in pixels = tile edge, 1 .. 64 */
+    int32_t grid;           /* g: the taps are the points of a (2g+1)^2 grid inside the disk, 1 .. 8 */
+    float   depth_extent;   /* world distance over which "in front" fades, > 0 */
+    int32_t flags;          /* none defined yet: 0 */
+    int32_t reserved[2];    /* 0 */
+} FfDofParams;              /* 32 bytes; every float must be finite */
+
 /* ff_texture_create: how a texture is addressed and filtered (the formulas are in ff_api.h).  0 = repeat, bilinear. */
 #define FF_TEX_REPEAT    0   /* coordinates wrap: c - floor(c) */
 #define FF_TEX_CLAMP     1   /* coordinates clamp to [0, 1] */
@@ -363,6 +375,7 @@ static_assert(sizeof(FfCamera) == 108, "Camera layout must match utilities.h:269
 static_assert(sizeof(FfDisplayParams) == 64, "FfDisplayParams is 64 bytes");
 static_assert(sizeof(FfCameraSampling) == 16, "FfCameraSampling is 16 bytes");
 static_assert(sizeof(FfMotionBlurParams) == 24, "FfMotionBlurParams is 24 bytes");
+static_assert(sizeof(FfDofParams) == 32, "FfDofParams is 32 bytes");
 #else
 _Static_assert(sizeof(FfBXDF) == 60, "BXDF layout");
 _Static_assert(sizeof(FfTriangle) == 96, "Triangle layout");
@@ -373,6 +386,7 @@ _Static_assert(sizeof(FfCamera) == 108, "Camera layout");
 _Static_assert(sizeof(FfDisplayParams) == 64, "FfDisplayParams layout");
 _Static_assert(sizeof(FfCameraSampling) == 16, "FfCameraSampling layout");
 _Static_assert(sizeof(FfMotionBlurParams) == 24, "FfMotionBlurParams layout");
+_Static_assert(sizeof(FfDofParams) == 32, "FfDofParams layout");
 #endif
 
 #endif /* FIREFLY_FF_TYPES_H */
