@@ -1,6 +1,7 @@
 // ff_image.h — what the image-space entry points (ff_image_api.cpp: ff_gbuffer, ff_denoise, ff_denoise_temporal, ff_taa;
-// ff_display_api.cpp) keep in the tracer state and share: the staging of host buffers and the reprojection history.  Nothing
-// here reaches a trace kernel.
+// ff_display_api.cpp; the gather filters ff_motion_blur_api.cpp and ff_dof_api.cpp) keep in the tracer state and share: the
+// staging of host buffers, the gather filters' size and overlap checks, and the reprojection history.  Nothing here reaches a
+// trace kernel.
 #pragma once
 
 #include <vector>
@@ -44,6 +45,37 @@ private:
     size_t used;
     std::vector<Piece> pieces;
 };
+
+// What the gather filters (ff_motion_blur, ff_depth_of_field) refuse before they look at a buffer: an image size out of range ...
+inline int check_image_size(int width, int height, const char* who)
+{
+    if (width < 1 || height < 1 || width > 65535 || height > 65535) return fail(FF_ERR_INVALID_ARG, "%s: image size %dx%d is invalid", who, width, height);
+    return FF_OK;
+}
+
+// ... and, as a gather reads neighbours, an output (rgb8, radiance_out; either may be null) that lies on an input or on the other
+// output, which different lanes write.
+struct Span {
+    const void* ptr;
+    size_t bytes;
+    const char* name;
+};
+
+inline bool overlaps(const Span& a, const Span& b)
+{
+    const char* p = (const char*)a.ptr;
+    const char* q = (const char*)b.ptr;
+    return p < q + b.bytes && q < p + a.bytes;
+}
+
+inline int check_disjoint(const Span (&outs)[2], const Span (&ins)[3], const char* who)
+{
+    for (const Span& o : outs)
+        for (const Span& i : ins)
+            if (o.ptr && overlaps(o, i)) return fail(FF_ERR_INVALID_ARG, "%s: %s overlaps %s", who, o.name, i.name);
+    if (outs[0].ptr && outs[1].ptr && overlaps(outs[0], outs[1])) return fail(FF_ERR_INVALID_ARG, "%s: %s overlaps %s", who, outs[0].name, outs[1].name);
+    return FF_OK;
+}
 
 // What a filter that reprojects its last result (ff_denoise_temporal, ff_taa) remembers between calls: two history sets in
 // d_work that swap by index (`cur`: the one the last call wrote; the layout is the filter's own), and the camera, image size and

@@ -194,12 +194,13 @@ struct FfState {
     float disp_prev_exposure = 0.f;           // E of the last automatic call (the next one adapts from it)
     float disp_exposure = 0.f, disp_target = 0.f;
     uint32_t disp_histogram[256] = {};
-    // motion blur (ff_motion_blur, ff_motion_blur.hip): the packed {v, l, z} plane (one float4 per pixel), the tile and neighbour
-    // maxima (one float4 per tile each), then the staging of host buffers.  Not reset by uploads.
+    // motion blur (ff_motion_blur): ff_tile_filter.h's work buffer under MotionBlurFilter - the packed {v, l, z} plane (one float4 per
+    // pixel), the tile and neighbour maxima (one float4 per tile each), then, from a multiple of 16 bytes on, the staging of host
+    // buffers.  Not reset by uploads.
     void* d_mblur_work = nullptr;
     size_t mblur_work_bytes = 0;
-    // depth of field (ff_depth_of_field, ff_dof.hip): the packed {l, z} plane (one float2 per pixel), the tile and neighbour maxima
-    // (one float per tile each), then the staging of host buffers.  Not reset by uploads.
+    // depth of field (ff_depth_of_field): the same under DofFilter - the packed {l, z} plane (one float2 per pixel), the tile and
+    // neighbour maxima (one float per tile each), then the staging.  A buffer of its own.  Not reset by uploads.
     void* d_dof_work = nullptr;
     size_t dof_work_bytes = 0;
     unsigned* d_queue = nullptr;               // work-queue counter: lives right behind the counters (one memset clears both)

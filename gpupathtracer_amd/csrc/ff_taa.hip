@@ -66,9 +66,9 @@ __global__ __launch_bounds__(256) void taa_kernel(const TaaArgs a, const float* 
         radiance_out[3 * i + 2] = ob;
     }
     if (rgb8) {
-        rgb8[3 * i] = taa_u8(orr);
-        rgb8[3 * i + 1] = taa_u8(og);
-        rgb8[3 * i + 2] = taa_u8(ob);
+        rgb8[3 * i] = pixel_u8(orr);
+        rgb8[3 * i + 1] = pixel_u8(og);
+        rgb8[3 * i + 2] = pixel_u8(ob);
     }
 }
 

@@ -5,20 +5,12 @@
 // include/firefly/ff_api.h.  Device code only: include it from a .hip file.
 #pragma once
 
+#include "ff_pixel.h"
 #include "ff_taa.h"
 
 namespace ff {
 
 constexpr float kTaaMaxLength = 4096.f;
-
-__device__ __forceinline__ unsigned char taa_u8(float v)
-{
-    // the project's 8-bit rule (kernel.cu:214 truncation, out-of-range values clamped): ff_k_shade.h to_u8
-    const float s = v * 255.0f;
-    if (!(s > 0.0f)) return 0;
-    if (s >= 255.0f) return 255;
-    return (unsigned char)s;
-}
 
 // P(M, X) of ff_api.h: q = inverse(M) (X, 1); false when q.w <= 0 (or NaN)
 __device__ __forceinline__ bool taa_project(const float* P, float x, float y, float z, float sw, float sh, float& fx, float& fy)

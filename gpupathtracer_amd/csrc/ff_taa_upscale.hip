@@ -88,7 +88,7 @@ __global__ __launch_bounds__(256) void taa_upscale_kernel(const TaaUpscaleArgs a
     int gq, kq;
     low(is, js, c, gq, kq);
     if (gq != gP || kq != kP) k = 0.f;
-    if (!(upscale_finite(c[0]) && upscale_finite(c[1]) && upscale_finite(c[2]))) k = 0.f;
+    if (!(pixel_finite(c[0]) && pixel_finite(c[1]) && pixel_finite(c[2]))) k = 0.f;
     // 6. blend (5, the clamp, inside its first case)
     float o[3], len;
     const float wsum = valid ? fminf(len_h + k, kTaaMaxLength) : 0.f;
@@ -135,7 +135,7 @@ __global__ __launch_bounds__(256) void taa_upscale_kernel(const TaaUpscaleArgs a
             int gn, kn;
             low((int)ic, (int)jc, n, gn, kn);
             if (gn != gP || kn != kP) return false;
-            if (!(upscale_finite(n[0]) && upscale_finite(n[1]) && upscale_finite(n[2]))) return false;
+            if (!(pixel_finite(n[0]) && pixel_finite(n[1]) && pixel_finite(n[2]))) return false;
             m.add(b, n[0], n[1], n[2]);
             return true;
         });
@@ -156,9 +156,9 @@ __global__ __launch_bounds__(256) void taa_upscale_kernel(const TaaUpscaleArgs a
         radiance_out[3 * i + 2] = o[2];
     }
     if (rgb8) {
-        rgb8[3 * i] = taa_u8(o[0]);
-        rgb8[3 * i + 1] = taa_u8(o[1]);
-        rgb8[3 * i + 2] = taa_u8(o[2]);
+        rgb8[3 * i] = pixel_u8(o[0]);
+        rgb8[3 * i + 1] = pixel_u8(o[1]);
+        rgb8[3 * i + 2] = pixel_u8(o[2]);
     }
 }
 

@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/firefly/ff_types.h"
+#include "ff_pixel.h"
 
 #if defined(__HIPCC__)
 #define FF_UPSCALE_HD __host__ __device__ __forceinline__
@@ -47,23 +48,12 @@ FF_UPSCALE_HD float upscale_dot3(float ax, float ay, float az, float bx, float b
     return (px + py) + pz;
 }
 
-FF_UPSCALE_HD bool upscale_finite(float v) { return fabsf(v) <= 3.402823466e+38f; } // (false for NaN)
-
 FF_UPSCALE_HD bool upscale_filterable(int geom, int bxdf)
 {
     return geom >= 0 && bxdf != FF_BXDF_EMITTER && bxdf != FF_BXDF_MIRROR && bxdf != FF_BXDF_GLASS;
 }
 
 FF_UPSCALE_HD int upscale_clamp(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
-
-FF_UPSCALE_HD unsigned char upscale_u8(float v)
-{
-    // the project's 8-bit rule (kernel.cu:214 truncation, out-of-range values clamped): ff_k_shade.h to_u8
-    const float s = v * 255.0f;
-    if (!(s > 0.0f)) return 0;
-    if (s >= 255.0f) return 255;
-    return (unsigned char)s;
-}
 
 // The weighted mean of the taps that count, as c_0 + sum w (c_q - c_0) / sum w with c_0 the first of them: equal to
 // sum w c_q / sum w, and a single tap, or a colour every tap shares, comes back bit for bit.
@@ -149,7 +139,7 @@ FF_UPSCALE_HD void upscale_pixel(const UpscaleArgs& a, int X, int Y, float* out)
             const int gq = a.ids_lo[3 * q];
             if (!upscale_filterable(gq, a.ids_lo[3 * q + 2]) || (a.same_geometry && gq != gP)) return false;
             float c[3] = { a.radiance_lo[3 * q], a.radiance_lo[3 * q + 1], a.radiance_lo[3 * q + 2] };
-            if (!(upscale_finite(c[0]) && upscale_finite(c[1]) && upscale_finite(c[2]))) return false;
+            if (!(pixel_finite(c[0]) && pixel_finite(c[1]) && pixel_finite(c[2]))) return false;
             if (a.demodulate) {
                 const float aq[3] = { a.albedo_lo[3 * q], a.albedo_lo[3 * q + 1], a.albedo_lo[3 * q + 2] };
                 if ((aP[0] > 0.f && !(aq[0] > 0.f)) || (aP[1] > 0.f && !(aq[1] > 0.f)) || (aP[2] > 0.f && !(aq[2] > 0.f))) return false;
@@ -182,7 +172,7 @@ FF_UPSCALE_HD void upscale_pixel(const UpscaleArgs& a, int X, int Y, float* out)
         const bool any = upscale_taps(a, i0, j0, fu, fv, [&](size_t q, float b) {
             if (a.ids_lo[3 * q] != gP || a.ids_lo[3 * q + 2] != kP) return false;
             const float cx = a.radiance_lo[3 * q], cy = a.radiance_lo[3 * q + 1], cz = a.radiance_lo[3 * q + 2];
-            if (!(upscale_finite(cx) && upscale_finite(cy) && upscale_finite(cz))) return false;
+            if (!(pixel_finite(cx) && pixel_finite(cy) && pixel_finite(cz))) return false;
             m.add(b, cx, cy, cz);
             return true;
         });

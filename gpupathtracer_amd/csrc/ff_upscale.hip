@@ -19,7 +19,7 @@ __global__ __launch_bounds__(256) void upscale_kernel(const UpscaleArgs a, unsig
     float v[3];
     upscale_pixel(a, x, y, v);
     if (radiance_out) { radiance_out[3 * i] = v[0]; radiance_out[3 * i + 1] = v[1]; radiance_out[3 * i + 2] = v[2]; }
-    if (rgb8) { rgb8[3 * i] = upscale_u8(v[0]); rgb8[3 * i + 1] = upscale_u8(v[1]); rgb8[3 * i + 2] = upscale_u8(v[2]); }
+    if (rgb8) { rgb8[3 * i] = pixel_u8(v[0]); rgb8[3 * i + 1] = pixel_u8(v[1]); rgb8[3 * i + 2] = pixel_u8(v[2]); }
 }
 
 } // namespace

@@ -137,8 +137,7 @@ int ff_upscale_host(const FfUpscaleParams* p, int lo_width, int lo_height, const
             const size_t i = (size_t)y * (size_t)width + (size_t)x;
             float v[3];
             upscale_pixel(a, x, y, v);
-            if (radiance_out) { radiance_out[3 * i] = v[0]; radiance_out[3 * i + 1] = v[1]; radiance_out[3 * i + 2] = v[2]; }
-            if (rgb8) { rgb8[3 * i] = upscale_u8(v[0]); rgb8[3 * i + 1] = upscale_u8(v[1]); rgb8[3 * i + 2] = upscale_u8(v[2]); }
+            store_rgb(i, v, rgb8, radiance_out);
         }
     return FF_OK;
 }
