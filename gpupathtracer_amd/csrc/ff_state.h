@@ -203,6 +203,10 @@ struct FfState {
     // neighbour maxima (one float per tile each), then the staging.  A buffer of its own.  Not reset by uploads.
     void* d_dof_work = nullptr;
     size_t dof_work_bytes = 0;
+    // firefly clamp (ff_despeckle): the partial counts of clamped pixels (ff_despeckle.h kDespeckleSlots), then the staging of host buffers.
+    // Not reset by uploads.
+    void* d_despeckle_work = nullptr;
+    size_t despeckle_work_bytes = 0;
     unsigned* d_queue = nullptr;               // work-queue counter: lives right behind the counters (one memset clears both)
     unsigned long long* d_counters = nullptr;  // 28 counters + 4 queue words
     unsigned long long* h_counters = nullptr;  // pinned mirror for the per-frame read-back
@@ -322,6 +326,8 @@ void display_release(FfState* s);
 void motion_blur_release(FfState* s);
 // Depth of field (ff_dof_api.cpp): frees the state's work buffer (ff_destroy).
 void dof_release(FfState* s);
+// Firefly clamp (ff_despeckle_api.cpp): frees the state's work buffer (ff_destroy).
+void despeckle_release(FfState* s);
 // The pixel buffer registered with ff_register_gl_pbo, mapped on the state's stream (kernel.cu:338-339) and unmapped again
 // (kernel.cu:344): what ff_render_to_pbo and ff_display_to_pbo write.  need_bytes: the least size the mapping must have.
 int map_pbo(FfState* s, size_t need_bytes, void** out_ptr);

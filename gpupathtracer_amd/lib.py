@@ -42,6 +42,7 @@ EXPORTS = [
     "ff_taa_upscale_params_init", "ff_taa_upscale", "ff_taa_upscale_reset", "ff_taa_upscale_history",
     "ff_motion_blur_params_init", "ff_motion_blur", "ff_motion_blur_host",
     "ff_dof_params_init", "ff_dof_params_from_camera", "ff_depth_of_field", "ff_depth_of_field_host",
+    "ff_despeckle_params_init", "ff_despeckle", "ff_despeckle_host",
 ]
 DIST_ID_BYTES = 128
 
@@ -234,6 +235,10 @@ def load():
     lib.ff_dof_params_from_camera.argtypes = [P(T.FfCamera), P(T.FfCameraSampling), P(T.FfDofParams)]
     lib.ff_depth_of_field.argtypes = [vp, P(T.FfCamera), i32, i32, P(T.FfDofParams), vp, vp, vp, i32, vp, i32, vp, i32]
     lib.ff_depth_of_field_host.argtypes = [P(T.FfCamera), i32, i32, P(T.FfDofParams), vp, vp, vp, vp, vp]
+    lib.ff_despeckle_params_init.argtypes = [P(T.FfDespeckleParams)]
+    lib.ff_despeckle_params_init.restype = None
+    lib.ff_despeckle.argtypes = [vp, i32, i32, P(T.FfDespeckleParams), vp, vp, vp, i32, vp, i32, vp, i32, P(C.c_uint32)]
+    lib.ff_despeckle_host.argtypes = [i32, i32, P(T.FfDespeckleParams), vp, vp, vp, vp, vp, P(C.c_uint32)]
     lib.ff_taa_upscale_params_init.argtypes = [P(T.FfTaaUpscaleParams)]
     lib.ff_taa_upscale_params_init.restype = None
     lib.ff_taa_upscale.argtypes = [vp, P(T.FfCamera), P(T.FfTaaUpscaleParams), i32, i32, vp, vp, i32, i32, vp, vp, i32, vp, i32, vp, i32]
@@ -696,6 +701,49 @@ def depth_of_field_host(radiance, gbuffer_or_planes, camera, p=None, want_rgb8=T
     return rgb8, out
 
 
+def despeckle_params(**overrides):
+    """ff_despeckle_params_init's defaults with the given fields replaced (any FfDespeckleParams field)."""
+    p = T.FfDespeckleParams()
+    load().ff_despeckle_params_init(C.byref(p))
+    for name, value in overrides.items():
+        if name not in dict(T.FfDespeckleParams._fields_):
+            raise TypeError(f"FfDespeckleParams has no field {name!r}")
+        setattr(p, name, value)
+    return p
+
+
+def _despeckle_planes(gbuffer_or_planes):
+    """(albedo, ids) of a gbuffer() dict or of the pair itself; albedo may be None (a frame judged without demodulation)."""
+    if isinstance(gbuffer_or_planes, dict):
+        return gbuffer_or_planes.get("albedo"), gbuffer_or_planes["ids"]
+    return gbuffer_or_planes
+
+
+def _despeckle_images(radiance, gbuffer_or_planes, who):
+    """The three input images of ff_despeckle as contiguous arrays (albedo: None where none was given), and (h, w)."""
+    albedo, ids = _despeckle_planes(gbuffer_or_planes)
+    rad = np.ascontiguousarray(radiance, dtype=np.float32)
+    alb = None if albedo is None else np.ascontiguousarray(albedo, dtype=np.float32)
+    idp = np.ascontiguousarray(ids, dtype=np.int32)
+    h, w = rad.shape[:2]
+    if rad.shape != (h, w, 3) or idp.shape != (h, w, 3) or (alb is not None and alb.shape != (h, w, 3)):
+        raise ValueError(f"{who}: radiance, albedo and ids must be [H,W,3]")
+    return rad, alb, idp, (h, w)
+
+
+def despeckle_host(radiance, gbuffer_or_planes, p=None, want_rgb8=True, want_out=True):
+    """ff_despeckle_host (no GPU): host radiance [H,W,3] and a gbuffer() dict (or its (albedo, ids) planes; albedo None without
+    FF_DESPECKLE_DEMODULATE_ALBEDO) -> (rgb8 [H,W,3] uint8, radiance [H,W,3] float32, the number of clamped pixels)."""
+    rad, alb, ids, (h, w) = _despeckle_images(radiance, gbuffer_or_planes, "despeckle_host")
+    p = p if p is not None else despeckle_params()
+    rgb8 = np.zeros((h, w, 3), dtype=np.uint8) if want_rgb8 else None
+    out = np.zeros((h, w, 3), dtype=np.float32) if want_out else None
+    clamped = C.c_uint32(0)
+    check(load().ff_despeckle_host(w, h, C.byref(p), rad.ctypes.data, alb.ctypes.data if alb is not None else None, ids.ctypes.data,
+                                   rgb8.ctypes.data if want_rgb8 else None, out.ctypes.data if want_out else None, C.byref(clamped)))
+    return rgb8, out, int(clamped.value)
+
+
 def display_params(**overrides):
     """ff_display_params_init's defaults with the given fields replaced (any FfDisplayParams field)."""
     p = T.FfDisplayParams()
@@ -1145,6 +1193,42 @@ class Tracer:
         vp = lambda q: C.c_void_p(q) if q else None  # noqa: E731
         check(self._lib.ff_depth_of_field(self._state, C.byref(camera), width, height, C.byref(p), vp(radiance_ptr), vp(position_ptr), vp(depth_ptr), 1,
                                           vp(rgb8_ptr), 1, vp(radiance_out_ptr), 1))
+
+    def despeckle(self, radiance, gbuffer_or_planes, p=None, want_rgb8=True, want_out=True):
+        """ff_despeckle of radiance [H,W,3] with a gbuffer() dict (or its (albedo, ids) planes; albedo None without
+        FF_DESPECKLE_DEMODULATE_ALBEDO) -> (rgb8 [H,W,3] uint8, radiance [H,W,3] float32, the number of clamped pixels).  Host
+        arrays give host arrays; contiguous device tensors (torch, float32 / int32) give device tensors."""
+        p = p if p is not None else despeckle_params()
+        if hasattr(radiance, "data_ptr"):
+            import torch
+            albedo, ids = _despeckle_planes(gbuffer_or_planes)
+            h, w = radiance.shape[:2]
+            for name, t, dtype in (("radiance", radiance, torch.float32), ("albedo", albedo, torch.float32), ("ids", ids, torch.int32)):
+                if t is not None and (not t.is_cuda or t.dtype != dtype or tuple(t.shape) != (h, w, 3) or not t.is_contiguous()):
+                    raise ValueError(f"despeckle: {name} must be a contiguous [H,W,3] {dtype} tensor on the device")
+            rgb8 = torch.zeros((h, w, 3), dtype=torch.uint8, device=radiance.device) if want_rgb8 else None
+            out = torch.zeros((h, w, 3), dtype=torch.float32, device=radiance.device) if want_out else None
+            torch.cuda.synchronize(radiance.device)
+            clamped = self.despeckle_device(w, h, radiance.data_ptr(), albedo.data_ptr() if albedo is not None else None, ids.data_ptr(), p,
+                                            rgb8.data_ptr() if want_rgb8 else None, out.data_ptr() if want_out else None)
+            return rgb8, out, clamped
+        rad, alb, idp, (h, w) = _despeckle_images(radiance, gbuffer_or_planes, "despeckle")
+        rgb8 = np.zeros((h, w, 3), dtype=np.uint8) if want_rgb8 else None
+        out = np.zeros((h, w, 3), dtype=np.float32) if want_out else None
+        clamped = C.c_uint32(0)
+        check(self._lib.ff_despeckle(self._state, w, h, C.byref(p), rad.ctypes.data, alb.ctypes.data if alb is not None else None, idp.ctypes.data, 0,
+                                     rgb8.ctypes.data if want_rgb8 else None, 0, out.ctypes.data if want_out else None, 0, C.byref(clamped)))
+        return rgb8, out, int(clamped.value)
+
+    def despeckle_device(self, width, height, radiance_ptr, albedo_ptr, ids_ptr, p=None, rgb8_ptr=None, radiance_out_ptr=None, want_count=True):
+        """ff_despeckle on DEVICE buffers (raw pointers); the outputs must not overlap an input -> the number of clamped pixels
+        (None with want_count=False: out_clamped is passed as NULL)."""
+        p = p if p is not None else despeckle_params()
+        vp = lambda q: C.c_void_p(q) if q else None  # noqa: E731
+        clamped = C.c_uint32(0)
+        check(self._lib.ff_despeckle(self._state, width, height, C.byref(p), vp(radiance_ptr), vp(albedo_ptr), vp(ids_ptr), 1, vp(rgb8_ptr), 1,
+                                     vp(radiance_out_ptr), 1, C.byref(clamped) if want_count else None))
+        return int(clamped.value) if want_count else None
 
     def display(self, radiance, p=None, want_rgb8=True, want_out=True):
         """ff_display of host radiance [H,W,3] -> (rgb8 [H,W,3] uint8, display_out [H,W,3] float32: the curve's output in [0, 1]);

@@ -193,6 +193,15 @@ class FfDofParams(C.Structure):
 
 DOF_PARAMS_BYTES = 32
 
+
+class FfDespeckleParams(C.Structure):
+    _fields_ = [("radius", C.c_int32), ("rank", C.c_int32), ("min_neighbours", C.c_int32), ("threshold", C.c_float), ("floor", C.c_float),
+                ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+DESPECKLE_PARAMS_BYTES = 28
+DESPECKLE_DEMODULATE_ALBEDO = 1
+
 BUILD_HOST_SAH, BUILD_GPU_LBVH, BUILD_GPU_PLOC = 0, 1, 2
 UPDATE_REFIT, UPDATE_REBUILD = 0, 1
 

@@ -964,6 +964,69 @@ FF_API int ff_depth_of_field_host(const FfCamera* camera, int width, int height,
                                   const float* radiance_in, const float* position, const float* depth,
                                   unsigned char* rgb8, float* radiance_out);
 
+/* ---- firefly clamp (a G-buffer-guided outlier clamp on the raw frame) ----------------------------- */
+
+/* Defaults: radius 1, rank 2, min_neighbours 3, threshold 2, floor 0, FF_DESPECKLE_DEMODULATE_ALBEDO. */
+FF_API void ff_despeckle_params_init(FfDespeckleParams* p);
+
+/* Pulls the fireflies of a W x H float3 radiance image down: every pixel whose illumination is far above that of its neighbours on
+ * the same surface is scaled to a multiple of their rank-th largest.  A 1-spp frame with next-event estimation carries isolated
+ * pixels orders of magnitude brighter than their surroundings (an emitter hit through a glossy lobe, a sun texel on a low-pdf
+ * path), and every filter downstream is linear in radiance or weighs its taps by colour distance: this call sits after ff_render /
+ * ff_gbuffer and BEFORE ff_denoise, ff_denoise_temporal, ff_taa or ff_taa_upscale.  A pure image operation like ff_denoise and
+ * ff_display: no scene is read, none is needed, and no history is kept.  albedo is W*H*3 floats and ids W*H*3 int32, ff_gbuffer's
+ * planes of the frame's pose ({geometry, triangle, bxdf} per pixel; a miss has geometry -1).  All arithmetic is float32, evaluated
+ * as written with the parentheses shown, no fused multiply-add, IEEE division; exp, pow and sqrt appear nowhere, and the filter is a
+ * selection, not a sum, so ff_despeckle, ff_despeckle_host and a float32 restatement agree bit for bit whatever the order.  With
+ * r = radius:
+ *   1 measure    per pixel, g = ids[3p] and b = ids[3p+2].  With FF_DESPECKLE_DEMODULATE_ALBEDO, per channel k, c_k = radiance_k /
+ *                albedo_k where albedo_k > 0 and c_k = radiance_k otherwise (ff_denoise's division); without the flag c = radiance
+ *                and albedo is not read (it may be NULL).  l = (0.2126f * c.r + 0.7152f * c.g) + 0.0722f * c.b.  The pixel COUNTS
+ *                when g >= 0, b != FF_BXDF_EMITTER, its three radiance channels are finite, l is finite and, under the flag, none
+ *                of its three albedo channels is NaN
+ *   2 yardstick  for a counting pixel X the neighbours are the pixels Y != X of the (2r+1)^2 window around X that lie in the image,
+ *                count, and have g_Y == g_X.  n = their number, m = the rank-th largest of their l (a value: ties need no rule)
+ *   3 clamp      limit = threshold * m, and a limit that is not above floor becomes floor (a limit below floor, and a zero of
+ *                either sign under floor 0).  X is clamped when it counts, n >= min_neighbours, l_X > 0 and l_X > limit.  For a
+ *                clamped X: s = limit / l_X and out_k = radiance_k * s per channel - the same factor scales the raw and the
+ *                demodulated colour, so nothing is multiplied back.  The quotient, the products and a measure of them are each
+ *                rounded and may each round up, so the result is measured: l' = step 1's l of out under X's albedo, and while
+ *                l' > limit and s > 0, s becomes the float32 next below it (its bit pattern minus 1) and out and l' are formed
+ *                again; a 65th such step sets s = 0 instead.  (One or two steps in practice.  More than 64 need radiance of
+ *                mixed sign whose channels cancel in l.)  Every other pixel's output is its input bit for bit: misses, emitters,
+ *                non-finite pixels, pixels with too few neighbours, pixels at or below their limit
+ *   4 rgb8 = trunc(clamp(out * 255)), the rule of every rgb8 output here; *out_clamped = the number of clamped pixels.
+ * Consequences.  A constant image (and, under the flag, a constant albedo) returns the input bit for bit (threshold >= 1).  A threshold so large that limit overflows returns
+ * the input bit for bit (nothing is above +Inf).  With floor 0, scaling all radiance by a power of two scales the output by it
+ * exactly and leaves the count as it is (short of overflow and subnormals).  A clamped pixel, measured again as step 1 measures, is
+ * at or below its limit, in float32 and without allowance; no pixel's l grows (s < 1) and no channel changes its sign; a -0 channel of an unclamped pixel stays -0.  Non-finite input follows the project's rule for every image filter: such a
+ * pixel may spoil only itself - it is copied through and is nobody's neighbour, as if its ids marked a miss.
+ * Bias.  The filter REMOVES energy and puts it nowhere else: the mean of the output is below the mean of the input, and the
+ * expectation of a despeckled frame is not the converged image.  It is meant for frames with next-event estimation, whose
+ * fireflies are rare events on top of a well-sampled direct term.  The plain path mode at 1 spp carries nearly all of its energy in
+ * isolated pixels (the paths that happened to reach an emitter): there the clamp removes the image.  floor is the caller's guard:
+ * no pixel is pulled below it.  tools/despeckle_bench.py reports the share of energy removed beside the error (DESIGN.md section 8
+ * row 18).
+ * rgb8 (W*H*3 bytes) and radiance_out (W*H*3 floats) may each be NULL.  Neither may overlap an input (the window reads neighbours;
+ * radiance_out == radiance_in is refused), and the two outputs may not overlap each other.  inputs_on_device covers all three input
+ * images.  out_clamped is a host pointer and may be NULL.  Width and height are 1 .. 65535.
+ * Synchronous, on the state's stream; host buffers are staged.  The call leaves FfStats, the stored primary hits and their key, every
+ * filter's history, the display exposure and the progressive sum as they were; its own state is a work buffer (allocated on first
+ * use, regrown for a larger size, freed by ff_destroy).  FF_ERR_INVALID_ARG, naming the field, before any device work for: a NULL
+ * state, params, radiance_in or ids; a NULL albedo under the flag; a bad size; radius outside 1 .. 3, rank outside 1 .. 4,
+ * min_neighbours outside rank .. (2r+1)^2 - 1 (so min_neighbours < rank is refused), threshold < 1, floor < 0 (every float must be
+ * finite); unknown flags or a nonzero reserved; an output that overlaps an input or the other output.
+ * Not offered: a temporal test against ff_denoise_temporal's moments, redistribution of the removed energy, a multi-GPU twin. */
+FF_API int ff_despeckle(FfState* state, int width, int height, const FfDespeckleParams* p,
+                        const float* radiance_in, const float* albedo, const int32_t* ids, int inputs_on_device,
+                        void* rgb8, int rgb8_on_device, float* radiance_out, int radiance_out_on_device,
+                        uint32_t* out_clamped);
+
+/* Host-only twin (no GPU, no state, host pointers), compiled from the same inline per-pixel functions the kernel uses: the same
+ * image arguments, the same checks, the same bits and the same count. */
+FF_API int ff_despeckle_host(int width, int height, const FfDespeckleParams* p, const float* radiance_in, const float* albedo,
+                             const int32_t* ids, unsigned char* rgb8, float* radiance_out, uint32_t* out_clamped);
+
 /* ---- display transform (exposure, bloom, tone curve, sRGB) ------------------------------------- */
 
 /* Defaults: ACES, SRGB, flags 0, exposure 1, white 4, key 0.18, percentiles 0.5 / 0.95, min_exposure 2^-10, max_exposure 2^10,

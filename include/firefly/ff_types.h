@@ -343,6 +343,19 @@ typedef struct FfDofParams {
     int32_t reserved[2];    /* 0 */
 } FfDofParams;              /* 32 bytes; every float must be finite */
 
+/* ff_despeckle: a G-buffer-guided firefly clamp on the raw frame, ahead of the denoisers.  ff_despeckle_params_init gives the
+ * defaults; the operator is in ff_api.h. */
+#define FF_DESPECKLE_DEMODULATE_ALBEDO 1   /* judge radiance / albedo (ff_denoise's division), not radiance */
+typedef struct FfDespeckleParams {
+    int32_t  radius;          /* r: the window is (2r+1)^2 pixels; 1 .. 3 */
+    int32_t  rank;            /* the rank-th largest neighbour is the yardstick; 1 .. 4 */
+    int32_t  min_neighbours;  /* fewer counting neighbours: the pixel is not judged; rank .. (2r+1)^2 - 1 */
+    float    threshold;       /* limit = threshold * yardstick; finite, >= 1 */
+    float    floor;           /* a limit below this becomes this; finite, >= 0 */
+    uint32_t flags;           /* FF_DESPECKLE_DEMODULATE_ALBEDO */
+    uint32_t reserved;        /* 0 */
+} FfDespeckleParams;          /* 28 bytes; every float must be finite */
+
 /* ff_texture_create: how a texture is addressed and filtered (the formulas are in ff_api.h).  0 = repeat, bilinear. */
 #define FF_TEX_REPEAT    0   /* coordinates wrap: c - floor(c) */
 #define FF_TEX_CLAMP     1   /* coordinates clamp to [0, 1] */
@@ -376,6 +389,7 @@ static_assert(sizeof(FfDisplayParams) == 64, "FfDisplayParams is 64 bytes");
 static_assert(sizeof(FfCameraSampling) == 16, "FfCameraSampling is 16 bytes");
 static_assert(sizeof(FfMotionBlurParams) == 24, "FfMotionBlurParams is 24 bytes");
 static_assert(sizeof(FfDofParams) == 32, "FfDofParams is 32 bytes");
+static_assert(sizeof(FfDespeckleParams) == 28, "FfDespeckleParams is 28 bytes");
 #else
 _Static_assert(sizeof(FfBXDF) == 60, "BXDF layout");
 _Static_assert(sizeof(FfTriangle) == 96, "Triangle layout");
@@ -387,6 +401,7 @@ _Static_assert(sizeof(FfDisplayParams) == 64, "FfDisplayParams layout");
 _Static_assert(sizeof(FfCameraSampling) == 16, "FfCameraSampling layout");
 _Static_assert(sizeof(FfMotionBlurParams) == 24, "FfMotionBlurParams layout");
 _Static_assert(sizeof(FfDofParams) == 32, "FfDofParams layout");
+_Static_assert(sizeof(FfDespeckleParams) == 28, "FfDespeckleParams layout");
 #endif
 
 #endif /* FIREFLY_FF_TYPES_H */
