@@ -1,6 +1,6 @@
-// ff_api.cpp — the C ABI (include/firefly/ff_api.h): tracer state, scene upload, frame rendering, HIP-GL pixel-buffer
-// interop and measurement.  Host side of the seam the reference has at kernel.cu:268-298 (upload) and
-// kernel.cu:335-344 (per-frame map -> clear -> kernel -> unmap).
+// ff_api.cpp — the C ABI (include/firefly/ff_api.h): tracer state, scene upload, the render entry points, HIP-GL pixel-buffer
+// interop and measurement.  Host side of the seam the reference has at kernel.cu:268-298 (upload); the frame itself
+// (kernel.cu:335-344) is ff_frame.cpp.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -152,8 +152,6 @@ int check_render_call(const FfState* s, const FfCamera* camera, const FfRenderPa
 
 namespace {
 
-// Geometry records the BVH kernels keep in LDS: all of them up to kMaxLdsRecords, none beyond (read from global memory).
-int lds_records(const FfState* s) { return s->num_geoms > kMaxLdsRecords ? 0 : s->num_geoms; }
 
 // Workgroup size of the BVH kernel for the uploaded scene: the preferred size if the lane-strided traversal stacks
 // (4 bytes x workgroup size per tree level) and the geometry records fit the 160 KiB of LDS, else the largest smaller
@@ -318,577 +316,6 @@ int collapse_slot(FfState* s, size_t gi, bool with_info)
     }
     return FF_OK;
 }
-
-// The camera and the pixel mapping of a frame part into `k`: strips of strip_rows rows dealt to num_parts parts, of which this is
-// `part` with local_rows rows, and the window [x0, x0 + win_w) x (y0 + ...) of the W x H image.  num_blocks: the sample blocks a
-// pixel item is queued for (the work queue counts items in 31 bits); who: the prefix of that error's text.
-int fill_frame_mapping(const FfState* s, KParams& k, const FfCamera* camera, int W, int H, int grid_mode, int strip_rows, int part, int num_parts,
-                       int local_rows, int x0, int y0, int win_w, int num_blocks, const char* who)
-{
-    FfMat4 cm;
-    ff_camera_ray_matrix_jittered(camera, s->jitter_x, s->jitter_y, &cm); // (the state's pixel jitter; 0 0: ff_camera_ray_matrix)
-    std::memcpy(k.cam_c0, &cm.m[0], 16);
-    std::memcpy(k.cam_c1, &cm.m[4], 16);
-    std::memcpy(k.cam_c2, &cm.m[8], 16);
-    std::memcpy(k.cam_c3, &cm.m[12], 16);
-    k.cam_pos[0] = camera->m_position.x;
-    k.cam_pos[1] = camera->m_position.y;
-    k.cam_pos[2] = camera->m_position.z;
-    k.far_clip = camera->m_farClip;
-    k.screen_w = camera->m_screenWidth;
-    k.screen_h = camera->m_screenHeight;
-    k.width = W;
-    k.height = H;
-    k.xlim = W;
-    k.ylim = H;
-    if (grid_mode == FF_GRID_REFERENCE_FLOOR) { // kernel.cu:306-309
-        k.xlim = (W / 16) * 16;
-        k.ylim = (H / 16) * 16;
-    }
-    k.strip_rows = strip_rows;
-    k.part = part;
-    k.num_parts = num_parts;
-    k.local_rows = local_rows;
-    k.x0 = x0;
-    k.y0 = y0;
-    k.local_width = win_w;
-    k.tiles_per_row = (win_w + 7) / 8;
-    const uint64_t tiles = (uint64_t)k.tiles_per_row * (uint64_t)((local_rows + 7) / 8);
-    if (tiles * 64 * (uint64_t)(num_blocks + 64) >= (1ull << 31)) return fail(FF_ERR_INVALID_ARG, "%simage too large for the work queue", who);
-    k.pix_items = (unsigned)(tiles * 64);
-    return FF_OK;
-}
-
-// The uploaded scene and its LDS layout (finalize_layout) into `k`.  smooth: the frame shades with vertex normals; lds_block_threads:
-// the BVH kernel's workgroup size, for FF_DEBUG_LDS_FILL (0: a brute-force frame, which has no such layout).
-void fill_scene(const FfState* s, KParams& k, bool smooth, int lds_block_threads)
-{
-    k.setup_threshold = s->setup_threshold;
-    k.leaf_threshold = s->leaf_threshold;
-    k.num_geoms = s->num_geoms;
-    k.num_planes = s->num_planes;
-    k.num_quads = s->num_quads;
-    k.has_specular = s->has_specular ? 1 : 0;
-    k.geoms = s->d_geoms;
-    k.tris = s->d_tris;
-    k.trinormals = smooth ? reinterpret_cast<const float4*>(s->d_normals) : nullptr;
-    k.nodes4 = s->d_nodes4;
-    k.tri_world_normals = s->d_world_normals;
-    k.geom_world_normals = s->d_world_normals ? s->d_world_normals + s->num_tris : nullptr;
-    if (s->sw.lds_fill && lds_block_threads > 0) {
-        const size_t bytes = bvh_lds_bytes(s->lds_cap, s->stack_lds_levels, lds_block_threads, lds_records(s)); // (the pool behind it is initialised by the kernel)
-        k.debug_lds_words = (unsigned)std::min<size_t>(s->sw.lds_fill_words, bytes / 4);
-        k.debug_lds_pattern = (unsigned)s->sw.lds_fill_pattern;
-    }
-    k.stack_depth = s->stack_lds_levels;
-    k.stack_spill = nullptr;
-    k.lds_nodes = s->lds_cap;
-    k.top_first = (int)s->node_capacity;
-    k.top_lds_first = 0;
-    k.top_lds_count = s->top_lds_count;
-    k.num_scan = s->num_scan;
-    k.walls = s->walls;
-}
-
-// The stack levels that did not get LDS (finalize_layout): one int per level and thread of the launch.
-int attach_stack_spill(FfState* s, KParams& k, int grid, int block_threads)
-{
-    if (s->stack_lds_levels >= s->stack_entries) return FF_OK;
-    const int st = ensure_bytes((void**)&s->d_stack_spill, &s->stack_spill_bytes,
-                                (size_t)(s->stack_entries - s->stack_lds_levels) * (size_t)grid * (size_t)block_threads * sizeof(int));
-    if (st == FF_OK) k.stack_spill = s->d_stack_spill;
-    return st;
-}
-
-// The work queue's counters for a launch of `grid` workgroups, and its as-asked tail zone: tail_per_wave items (FF_QUEUE_TAIL
-// overrides) for every wave that draws from a counter.
-void size_work_queue(const FfState* s, KParams& k, int grid, int block_threads, int tail_per_wave)
-{
-    k.queue_counters = std::min(kQueueCountersDefault, grid);
-    if (s->sw.queue_counters > 0) k.queue_counters = std::min(std::min(kQueueCounters, grid), s->sw.queue_counters);
-    const int waves_per_counter = (grid * (block_threads / 64) + k.queue_counters - 1) / k.queue_counters;
-    k.queue_tail_items = (unsigned)(waves_per_counter * (s->sw.queue_tail >= 0 ? s->sw.queue_tail : tail_per_wave));
-}
-
-// What stored primary hits were computed for: the camera and the pixel mapping in `k` (fill_frame_mapping), and whether the stored
-// normal is the interpolated one (the frame shades with vertex normals).  Compared bytewise.
-FfState::PrimaryKey primary_key(const KParams& k, bool smooth)
-{
-    FfState::PrimaryKey key;
-    std::memset(&key, 0, sizeof key);
-    std::memcpy(key.cam, k.cam_c0, 16 * sizeof(float));
-    std::memcpy(key.cam + 16, k.cam_pos, 3 * sizeof(float));
-    key.cam[19] = k.far_clip; key.cam[20] = k.screen_w; key.cam[21] = k.screen_h;
-    const int dims[12] = { k.width, k.height, k.xlim, k.ylim, k.strip_rows, k.part, k.num_parts, k.local_rows, k.x0, k.y0, k.local_width, smooth ? 1 : 0 };
-    std::memcpy(key.dims, dims, sizeof dims);
-    key.pix_items = k.pix_items;
-    return key;
-}
-
-// The pre-pass of a frame whose launch parameters are `k`: the same persistent kernel, one item per pixel, one primary ray each, the
-// hit stored per pixel in `hits` (settle_hit) and the pixels that hit nothing marked in mask_out (may be null).  Its rays are not path
-// segments of the frame: the kernel does not count them, and the work queue starts from zero again behind it.  (Always the lane-owned
-// kernel, never instrumented: the frame's own launches are what the statistics describe.)
-int enqueue_prepass(FfState* s, const KParams& k, float4* hits, unsigned long long* mask_out, int frame_blocks, int grid, int block_threads)
-{
-    KParams kp = k;
-    kp.shade_mode = kShadePrimaryPass;
-    kp.primary_hits = hits;
-    kp.bounces = 1;
-    kp.spp_total = 1;
-    kp.block_spp = 1;
-    kp.num_blocks = 1;
-    kp.block_begin = 0;
-    kp.block_end = 1;
-    kp.whole_blocks = 1u;
-    kp.total_items = kp.pix_items;
-    kp.tail_block = -1;
-    kp.cull_mask = nullptr; // (every pixel gets its stored hit: a culled pixel's tail items - its last block, traced sample by sample - read it too)
-    kp.cull_mask_out = mask_out;
-    kp.frame_blocks = frame_blocks;
-    kp.cut_last = 0;
-    kp.timeline = nullptr;
-    kp.queue_chunk = 32u;
-    if (s->sw.queue_chunk > 0) kp.queue_chunk = (unsigned)s->sw.queue_chunk;
-    FF_HIP(launch_trace(kp, FF_TRACE_BVH, false, grid, block_threads, s->stream, nullptr, false, /*prepass=*/true));
-    FF_HIP(hipMemsetAsync(s->d_queue, 0, (size_t)k.queue_counters * kQueueStride * sizeof(unsigned), s->stream));
-    return FF_OK;
-}
-
-} // namespace
-
-namespace ff {
-
-// Core of every render entry point (declared in ff_state.h).
-int render_enqueue(FfState* s, const FfCamera* camera, const FfRenderParams* prm, int strip_rows, int part, int num_parts, int local_rows,
-                   unsigned char* rgb8_dev, float* radiance_dev, int x0, int y0, int win_w)
-{
-    const int W = prm->width, H = prm->height;
-    if (win_w < 0) win_w = W;
-    const size_t local_pixels = (size_t)local_rows * (size_t)win_w;
-    s->stats = FfStats();
-    s->pending = false;
-    if (local_pixels == 0) return FF_OK;
-
-    const bool debug = prm->shade_mode == FF_SHADE_NORMAL_DEBUG;
-    const bool env = s->env_set && !debug; // (FF_SHADE_NORMAL_DEBUG ignores the environment)
-    if (env && prm->shade_mode == FF_SHADE_DIFFUSE_PATH_SMOOTH)
-        return fail(FF_ERR_UNSUPPORTED, "FF_SHADE_DIFFUSE_PATH_SMOOTH does not render under an environment light (ff_set_environment); "
-                    "clear it or use FF_SHADE_DIFFUSE_PATH / FF_SHADE_DIFFUSE_PATH_NEE");
-    const bool tex = s->tex_bound > 0 && !debug; // (... and albedo textures)
-    if (tex && prm->shade_mode == FF_SHADE_DIFFUSE_PATH_SMOOTH)
-        return fail(FF_ERR_UNSUPPORTED, "FF_SHADE_DIFFUSE_PATH_SMOOTH does not render albedo textures (ff_set_albedo_texture); "
-                    "unbind them or use FF_SHADE_DIFFUSE_PATH / FF_SHADE_DIFFUSE_PATH_NEE");
-    const bool glossy = s->glossy_applied > 0 && !debug; // (... and rough-specular bindings)
-    if (glossy && prm->shade_mode == FF_SHADE_DIFFUSE_PATH_SMOOTH)
-        return fail(FF_ERR_UNSUPPORTED, "FF_SHADE_DIFFUSE_PATH_SMOOTH does not render rough-specular mirrors (ff_set_roughness); "
-                    "unbind them or use FF_SHADE_DIFFUSE_PATH / FF_SHADE_DIFFUSE_PATH_NEE");
-    const bool cam = s->cam_active() && !debug; // (... and per-sample camera rays)
-    if (cam && prm->shade_mode == FF_SHADE_DIFFUSE_PATH_SMOOTH)
-        return fail(FF_ERR_UNSUPPORTED, "FF_SHADE_DIFFUSE_PATH_SMOOTH does not render per-sample camera rays (ff_set_camera_sampling); "
-                    "clear the setting or use FF_SHADE_DIFFUSE_PATH / FF_SHADE_DIFFUSE_PATH_NEE");
-    const int spp = debug ? 1 : prm->spp;
-    const int bounces = debug ? 1 : prm->bounces;
-    // Samples are accumulated in blocks (a multiple of 64, at most 16 blocks per pixel up to 1024 spp and beyond): a
-    // block sums its samples sequentially, the combine kernel adds a pixel's blocks in order.  (pixel, block) is the unit
-    // of work, which keeps the persistent lanes balanced at the end of a frame and when a frame is split over GPUs.
-    const int block_spp = 64 * ((spp + 1023) / 1024);
-    const int num_blocks = (spp + block_spp - 1) / block_spp;
-    int blocks_per_launch = num_blocks;
-    if (prm->spp_per_launch > 0 && !debug) blocks_per_launch = std::max(1, (prm->spp_per_launch + block_spp - 1) / block_spp);
-    const int launches = (num_blocks + blocks_per_launch - 1) / blocks_per_launch;
-
-    KParams k;
-    std::memset(&k, 0, sizeof k);
-    {
-        const int mst = fill_frame_mapping(s, k, camera, W, H, prm->grid_mode, strip_rows, part, num_parts, local_rows, x0, y0, win_w, num_blocks, "");
-        if (mst != FF_OK) return mst;
-    }
-    k.bounces = bounces;
-    k.spp_total = spp;
-    k.block_spp = block_spp;
-    k.num_blocks = num_blocks;
-    {
-        int bst = ensure_bytes((void**)&s->d_blocksums, &s->blocksums_bytes, (size_t)k.pix_items * (size_t)num_blocks * 4 * sizeof(float));
-        if (bst != FF_OK) return bst;
-    }
-    k.blocksums = reinterpret_cast<float4*>(s->d_blocksums);
-    k.key = (unsigned)prm->seed ^ (unsigned)(prm->seed >> 32);
-    k.shade_mode = prm->shade_mode;
-    int block_threads = kBlockThreads;
-    if (prm->trace_mode == FF_TRACE_BVH) {
-        block_threads = s->scene_block_threads;
-        if (block_threads == 0)
-            return fail(FF_ERR_UNSUPPORTED, "4-wide BVH of depth %d does not fit the LDS traversal stack (512 threads x %d levels + %d geometry records > 160 KiB); "
-                        "upload with FF_BUILD_HOST_SAH or render with FF_TRACE_BRUTE_FORCE", s->max_depth4, s->max_depth4 + 1, s->num_geoms);
-    }
-    fill_scene(s, k, prm->shade_mode == FF_SHADE_DIFFUSE_PATH_SMOOTH, prm->trace_mode == FF_TRACE_BVH ? block_threads : 0);
-    if (prm->shade_mode == FF_SHADE_DIFFUSE_PATH_NEE || env || tex || glossy || cam) {
-        // (its own kernels: the rest of this function prepares the mega-kernels' frame; under an environment, with albedo textures
-        // or rough-specular mirrors bound or with per-sample camera rays, FF_SHADE_DIFFUSE_PATH runs there too, with no light table)
-        k.rgb8 = rgb8_dev;
-        k.radiance = radiance_dev;
-        if (cam && s->cam_sampling.pixel_filter == FF_PIXEL_BOX) {
-            // the sample's own point of the pixel replaces the state's jitter: the unjittered matrix
-            FfMat4 cm;
-            ff_camera_ray_matrix(camera, &cm);
-            std::memcpy(k.cam_c0, &cm.m[0], 16);
-            std::memcpy(k.cam_c1, &cm.m[4], 16);
-            std::memcpy(k.cam_c2, &cm.m[8], 16);
-            std::memcpy(k.cam_c3, &cm.m[12], 16);
-        }
-        return enqueue_nee(s, k, camera, prm, launches, blocks_per_launch, local_pixels);
-    }
-    k.emitter_mask = 0u;
-    k.cut_last = 0;
-    if (prm->trace_mode == FF_TRACE_BVH && !debug && !s->sw.no_last_bounce_cut) {
-        // The last segment of a path adds radiance only when it ends on an emitter.  If every emitter is one of the analytic records
-        // all queries screen before anything else (all planes and spheres of a small scene, the scan planes of a big one), a
-        // last-bounce query that holds no emitter after that screening is over (scan_records).
-        const int screened = s->num_geoms > kChunkGeometries ? s->num_scan : s->num_planes;
-        bool all_screened = true;
-        for (int i = 0; i < s->num_geoms; ++i) {
-            if (s->h_geoms[i].bxdf_type != FF_BXDF_EMITTER) continue;
-            if (i < screened && i < 32) k.emitter_mask |= 1u << i;
-            else all_screened = false;
-        }
-        k.cut_last = all_screened ? 1 : 0;
-    }
-    k.cull_mask = nullptr;
-    s->pending_culled_rays_per_pixel = 0;
-    bool cull = false;
-    {
-        // the padded world box around everything (the records' own boxes are padded); a camera outside it lets the work queue
-        // drop the pixels whose primary ray misses it (acquire_pixel)
-        float mn[3] = { 3.0e38f, 3.0e38f, 3.0e38f }, mx[3] = { -3.0e38f, -3.0e38f, -3.0e38f };
-        for (const GeomRecord& r : s->h_geoms) {
-            if (!(r.wmin[0] <= r.wmax[0])) continue;
-            for (int a = 0; a < 3; ++a) { mn[a] = std::min(mn[a], r.wmin[a]); mx[a] = std::max(mx[a], r.wmax[a]); }
-        }
-        const float cp[3] = { camera->m_position.x, camera->m_position.y, camera->m_position.z };
-        bool outside = false, valid = true;
-        for (int a = 0; a < 3; ++a) {
-            k.scene_min[a] = mn[a];
-            k.scene_max[a] = mx[a];
-            valid = valid && mn[a] <= mx[a] && std::fabs(mn[a]) < 1e30f && std::fabs(mx[a]) < 1e30f;
-            outside = outside || !(cp[a] >= mn[a] && cp[a] <= mx[a]);
-        }
-        cull = prm->trace_mode == FF_TRACE_BVH && valid && outside && !s->sw.no_primary_cull;
-    }
-    k.rgb8 = rgb8_dev;
-    k.radiance = radiance_dev;
-    k.queue = s->d_queue;
-    k.counters = s->d_counters;
-    k.timeline = nullptr;
-    k.timeline_ticks = 1;
-    if (s->collect_stats && s->timeline_bucket_us > 0) {
-        const size_t rows = (size_t)s->num_cus * 2 * (kBlockThreads / 64); // one row per wave of the largest grid
-        if (!s->d_timeline) FF_HIP(hipMalloc((void**)&s->d_timeline, rows * kTimelineBuckets * sizeof(unsigned)));
-        FF_HIP(hipMemsetAsync(s->d_timeline, 0, rows * kTimelineBuckets * sizeof(unsigned), s->stream));
-        k.timeline = s->d_timeline;
-        k.timeline_ticks = (unsigned)s->timeline_bucket_us * 100u; // the wall clock ticks at 100 MHz
-    }
-
-    const int blocks_per_cu = prm->trace_mode == FF_TRACE_BVH ? 1 : 2;
-    int grid = s->num_cus * blocks_per_cu;
-    const uint64_t max_useful = ((uint64_t)k.pix_items * (uint64_t)num_blocks + (uint64_t)block_threads - 1) / (uint64_t)block_threads;
-    if ((uint64_t)grid > max_useful) grid = (int)max_useful;
-    if (grid < 1) grid = 1;
-    k.primary_hits = nullptr;
-    k.reuse_quorum = s->sw.reuse_quorum;
-    // job-pool kernel: the defaults are where the same-box sweeps put them (profiles/r04_*pool_sweep*)
-    k.pool_quorum = s->sw.pool_quorum > 0 ? s->sw.pool_quorum : 40;
-    k.pool_quorum_min = std::min(k.pool_quorum, s->sw.pool_quorum_min > 0 ? s->sw.pool_quorum_min : 16);
-    k.pool_refill = s->sw.pool_refill > 0 ? s->sw.pool_refill : 16;
-    k.pool_slice = s->sw.pool_slice > 0 ? s->sw.pool_slice : 4;
-    k.pool_leave = s->sw.pool_leave >= 0 ? s->sw.pool_leave : 24;
-    k.pool_batch_min = s->sw.pool_batch_min > 0 ? s->sw.pool_batch_min : 48;
-    // (instrumented launches with a timeline run the lane-owned kernel, which keeps it; the LDS layout serves both)
-    const bool pool = s->use_pool && prm->trace_mode == FF_TRACE_BVH && !(s->collect_stats && s->timeline_bucket_us > 0);
-    // Every sample of a pixel starts with the same ray (kernel.cu:200-205 has no jitter): a pre-pass traces it once per pixel and the
-    // frame's samples start from the stored hit (trace_bvh_kernel).  One slot of 3 x 16 bytes per pixel item.
-    // The stored hits are KEPT: the next frame from the same camera, pixel mapping and scene starts from them without a pre-pass
-    // (a viewer that accumulates 1-spp frames with the camera at rest, kernel.cu:266,342).  A frame of 2 spp or more always runs on
-    // stored hits (the pre-pass pays within the frame: +1.3 % at 2 spp).  A 1-spp frame does when the hits are there already (+8 %),
-    // or when the frame before it had the same key - the camera has come to rest, so this frame's pre-pass (-4 % for this frame) is
-    // the last one; a one-off 1-spp frame traces its primary rays itself (profiles/r04_j_*).
-    const bool reuse_possible = prm->trace_mode == FF_TRACE_BVH && !debug && !s->sw.no_primary_reuse;
-    // (the stored normal is the interpolated one when the frame shades with vertex normals: part of the key)
-    FfState::PrimaryKey key;
-    std::memset(&key, 0, sizeof key);
-    if (reuse_possible) key = primary_key(k, k.trinormals != nullptr);
-    const bool keeping = reuse_possible && !s->sw.no_primary_cache;
-    const bool hits_kept = keeping && s->primary_valid && std::memcmp(&key, &s->primary_key, sizeof key) == 0;
-    const bool at_rest = keeping && s->last_key_valid && std::memcmp(&key, &s->last_key, sizeof key) == 0;
-    const bool reuse = reuse_possible && (spp >= s->sw.reuse_min_spp || hits_kept || at_rest);
-    s->last_key = key;
-    s->last_key_valid = reuse_possible;
-    if (reuse) {
-        if (s->primary_cache_bytes < (size_t)3 * (size_t)k.pix_items * sizeof(float4)) s->primary_valid = false; // (the buffer is about to move)
-        const int cst = ensure_bytes((void**)&s->d_primary_cache, &s->primary_cache_bytes, (size_t)3 * (size_t)k.pix_items * sizeof(float4));
-        if (cst != FF_OK) return cst;
-    }
-    // Start records: diffuse scenes of up to 32 geometries (the instantiation without the extras) on the lane-owned kernel start every
-    // sample from the pre-pass's SHADED hit (trace_bvh_kernel<..., START>).  The class of a pixel depends on the bounce count and the
-    // shade mode, so the kept records serve only a frame that agrees in both; the raw hits are written and kept as before (the job-pool
-    // kernel, ff_gbuffer and FF_NO_START_RECORDS read them).
-    const bool use_start = reuse && !pool && !s->sw.no_start_records && s->num_geoms <= kChunkGeometries && k.num_planes == k.num_quads &&
-                           k.has_specular == 0 && k.trinormals == nullptr;
-    bool start_kept = true;
-    if (use_start) {
-        const size_t need = (size_t)2 * (size_t)k.pix_items * sizeof(float4);
-        if (s->start_records_bytes < need) s->primary_has_start = false; // (the buffer is about to move)
-        const int sst = ensure_bytes((void**)&s->d_start_records, &s->start_records_bytes, need);
-        if (sst != FF_OK) return sst;
-        start_kept = s->primary_has_start && s->start_bounces == bounces && s->start_shade == prm->shade_mode;
-    }
-    k.park = nullptr;
-    if (pool) {
-        // where a lane's own path and query state waits between setup passes (trace_pool_kernel): 7 x 16 bytes per thread of the launch
-        const int pst = ensure_bytes((void**)&s->d_park, &s->park_bytes, (size_t)7 * (size_t)grid * (size_t)block_threads * sizeof(float4));
-        if (pst != FF_OK) return pst;
-        k.park = s->d_park;
-    }
-    if (prm->trace_mode == FF_TRACE_BVH) {
-        const int st = attach_stack_spill(s, k, grid, block_threads);
-        if (st != FF_OK) return st;
-    }
-
-    {
-        // Work queue (csrc/ff_k_shade.h acquire_pixel): 16 counters in different memory channels, and a wave takes at least
-        // queue_chunk consecutive items per atomic.  One counter asked for every item serves about 10^8 requests a second, which
-        // held every frame of short items far below the saturated rate (1080p C2, before -> after: the reference's own 1-ray frame
-        // 0.40 -> 0.19 ms, path-traced 1 spp 2.98 -> 1.33 ms, 4 spp 7.3 -> 4.8, 16 spp 20.8 -> 18.0; the 1 024-spp frame from the
-        // reference's default camera, whose 64-sample items are mostly one-ray paths, 164 -> 84 ms).  With 16 counters the chunk
-        // hardly matters for the atomics between 8 and 64 items (profiles/r02_q_queue_sweep.txt); what it decides is WHICH items a
-        // wave's lanes hold.  Whole 64-sample blocks: 64 items, i.e. the blocks of four neighbouring pixels (one 8x8 tile when a
-        // pixel has one block): the lanes' rays start from the same few surface points and walk the same corner of the trees
-        // (1 024 spp, ms with chunks of 4 / 16 / 64 / 128: C4, whose tree lives in L2, 570 / 530 / 491 / 488; C2 977 / 968 / 956 /
-        // 959; at 64-512 spp C4 gains 10-14 %, C2 1-2 %: profiles/r02_y_chunk_sweep_whole_blocks.txt).  Shorter items (frames of a few samples): 64
-        // samples of work, at most 32 items; there what a wave holds back at the end of the launch counts (1 spp: 1.33 ms with
-        // 16-32, 1.36 with 64).
-        const int samples_per_item = std::max(1, std::min(k.block_spp, k.spp_total));
-        // (the strips of a multi-GPU rank: 32; slowest of eight ranks 125.5 ms against 126.9 with 64 and 125.9 with 16)
-        k.queue_chunk = samples_per_item >= 64 ? (num_parts > 1 ? 32u : 64u) : (unsigned)std::min(32, std::max(4, 64 / samples_per_item));
-        if (s->sw.queue_chunk > 0) k.queue_chunk = (unsigned)s->sw.queue_chunk;
-        // The last items of every counter's share go out exactly as asked for (acquire_pixel: no private stock at the end of a launch):
-        // one per lane of the waves that draw from the counter where items are long (sample blocks), an eighth of that where they are
-        // short (a 1-spp frame's paths: single-item requests cost an atomic each, which is what the chunks are there to avoid).
-        // (measured on one box, profiles/r04_b_queue_tail.txt: long items 64 per wave; frames that drop most of their items at the
-        // queue - a camera outside the scene - lose with a long zone, every dropped item there being a request of its own: 8)
-        size_work_queue(s, k, grid, block_threads, samples_per_item >= 16 && !cull ? 64 : 8);
-    }
-    hipStream_t st = s->stream;
-    // cudaMemset(pbo, 0) of kernel.cu:340: untraced pixels read 0.  With the full grid the combine pass writes every pixel
-    // of the window (a missed pixel gets its zero sum), so the clears are only needed for the reference's floor grid.
-    if (prm->grid_mode == FF_GRID_REFERENCE_FLOOR) {
-        if (rgb8_dev) FF_HIP(hipMemsetAsync(rgb8_dev, 0, local_pixels * 3, st));
-        if (radiance_dev) FF_HIP(hipMemsetAsync(radiance_dev, 0, local_pixels * 3 * sizeof(float), st));
-    }
-    FF_HIP(hipMemsetAsync(s->d_counters, 0, (size_t)(1 + k.queue_counters) * kQueueStride * sizeof(unsigned), st)); // counters and the work queue behind them
-    FF_HIP(hipEventRecord(s->ev_begin, st));
-    // Fine-grained tail: in the launch that finishes the frame, the last sample block is traced as items of a few samples
-    // with per-sample storage (see KParams::tail_samples), so that the launch runs dry on short items.
-    k.tail_block = -1;
-    const int last_launch_blocks = num_blocks - (launches - 1) * blocks_per_launch;
-    // It pays where a launch is short against its items: the ranks of a multi-GPU frame (+3.3 % at eight ranks) and one-GPU
-    // frames of up to eight blocks (1080p C2 with / without, ms: 64 spp 66.0 / 71.4, 128 spp 128.4 / 132.3, 256 spp 247.8 / 251.1).
-    // It costs a per-sample buffer (2.1 GB written and read back at 1080p), which the 1 024-spp one-GPU frame does not earn back
-    // (+0.4 %, and 4x its HBM traffic): off there.  FF_TAIL_GROUP forces it (with that group size) wherever a launch has
-    // FF_TAIL_MIN_BLOCKS blocks.  Frames whose buffer would pass 16 GiB render without it (FfStats::flags).
-    const bool short_frame = num_parts == 1 && !s->tail_forced && num_blocks <= 8;
-    // How many of the frame's last blocks go out that way.  A lane that takes one of the last WHOLE blocks finishes up to two block
-    // times later (path lengths vary by that much between pixels); the short items must last that long for the launch to end on
-    // them, so a rank's strips - where a block time is 6 % of the launch - hand out TWO blocks in groups (eight ranks 94.5 -> 96 % of
-    // ideal, profiles/r04_n_*).  The kernels see one "tail block" of up to 2 x block_spp samples starting at block tail_block; the
-    // combine pass adds each block's samples in order.
-    // (two where a lane gets fewer than 24 whole blocks in the launch - eight ranks at 1080p and 1 024 spp: 16 -, one where it gets
-    // more: there the short items' own overhead outweighs the shorter end, 4 ranks 97.7 -> 97.3 %, 2 ranks 98.9 -> 98.5 %)
-    const double blocks_per_lane = (double)k.pix_items * (double)last_launch_blocks / ((double)grid * (double)block_threads);
-    const int tail_blocks_wanted = s->sw.tail_blocks > 0 ? s->sw.tail_blocks : (num_parts > 1 && blocks_per_lane < 24.0 ? 2 : 1);
-    const int tail_blocks = std::max(1, std::min(std::min(tail_blocks_wanted, 3), last_launch_blocks - 1));
-    const int tail_n = spp - (num_blocks - tail_blocks) * block_spp; // samples of the frame's last block(s)
-    // group size: the given one (multi-part frames: 32 samples), scaled with the block size beyond 1 024 spp and at least an
-    // eighth of the block; short one-GPU frames: a quarter of the block, at least 4 samples
-    const int tail_step = short_frame ? std::max(4, (tail_n + 3) / 4) : std::max(s->tail_group_spp * (block_spp / 64), (tail_n + 15) / 16);
-    const bool tail_wanted = !debug && prm->trace_mode == FF_TRACE_BVH && s->tail_group_spp > 0 && tail_step < tail_n &&
-                             (short_frame || ((num_parts > 1 || s->tail_forced) && last_launch_blocks >= s->tail_min_blocks));
-    const size_t tail_bytes = (size_t)k.pix_items * (size_t)tail_n * sizeof(float4); // [sample of the block][pixel item]
-    // The buffer stays allocated between frames.  Where the tail is this library's own choice (short one-GPU frames: a viewer at
-    // 64 spp) it may take at most 4 GiB and 2 % of the device's memory (1080p at up to 1 024 spp: 2.1 GB; a 64-spp 4K frame would
-    // need 8.5 GB and goes without); where the caller set up a multi-GPU frame or forced it, up to 16 GiB (also keeps slot indices
-    // in 31 bits; C5's ranks at eight GPUs need 4.2 GB).  FfStats::flags tells which way a frame went.
-    const size_t tail_cap = short_frame ? std::min<size_t>(4ull << 30, s->device_mem_bytes / 50) : (16ull << 30);
-    const bool tail_mode = tail_wanted && tail_bytes <= tail_cap;
-    if (!tail_mode && s->d_tail_samples && s->tail_samples_bytes > (256ull << 20)) {
-        // a frame that does not use it gives a large buffer back (the stream has drained: every render call is synchronous)
-        (void)hipFree(s->d_tail_samples);
-        s->d_tail_samples = nullptr;
-        s->tail_samples_bytes = 0;
-    }
-    s->pending_flags = (tail_mode ? FF_STATS_TAIL_ITEMS : 0u) | (tail_wanted && !tail_mode ? FF_STATS_TAIL_SKIPPED_TOO_LARGE : 0u);
-    if (tail_mode) {
-        int tst = ensure_bytes((void**)&s->d_tail_samples, &s->tail_samples_bytes, tail_bytes);
-        if (tst != FF_OK) return tst;
-        k.tail_samples = s->d_tail_samples;
-        k.tail_samples_in_block = tail_n;
-        // (Grading the groups down to an eighth of a block on multi-GPU ranks was measured: the 8-sample items cost more
-        // than the tail they save, 92.3 % instead of 93.3 % of ideal at eight ranks.)
-        int g = 0;
-        k.tail_start[0] = 0;
-        while (k.tail_start[g] < tail_n && g < 16) { k.tail_start[g + 1] = std::min(tail_n, k.tail_start[g] + tail_step); ++g; }
-        k.tail_groups = g;
-    }
-    // (after the tail decision: the tail block's samples are stored one by one and are not part of the cull - a frame whose only
-    // block is the tail block has nothing to drop and skips the mask pass.  Dropping tail items too was measured in round 4: a dropped
-    // item costs the queue what its 16 samples cost a lane that starts them from a stored miss; no gain, profiles/r04_f_*)
-    // (... and so does the reference's own frame - one primary ray per pixel, shaded by its normal: tracing a ray that misses
-    // everything costs what the mask pass costs, and the pass is a second launch: 0.089 instead of 0.064 ms at 1080p)
-    cull = cull && num_blocks - (tail_mode ? tail_blocks : 0) > 0 && !debug;
-    // ... and where a pre-pass stores every pixel's primary hit (below), it marks the pixels that hit NOTHING in the same mask: the
-    // exact version of the box test, also for a camera inside the scene's box (an open room seen from within)
-    const bool exact_cull = reuse && !s->sw.no_primary_cull && num_blocks - (tail_mode ? tail_blocks : 0) > 0;
-    // Can this frame start from the hits (and the mask) the last one stored?  Same camera, same pixel mapping, no change of the scene
-    // since (every upload / update clears primary_valid), and a mask there if this frame wants one.
-    const bool kept = reuse && hits_kept && (!(cull || exact_cull) || s->primary_has_mask) && start_kept;
-    s->pending_mask_reused = s->pending_mask_built = false;
-    if (cull || exact_cull) {
-        const size_t mask_bytes = ((size_t)k.pix_items / 64 + 2) * sizeof(unsigned long long);
-        if (!kept) {
-            const int mst = ensure_bytes((void**)&s->d_cull_mask, &s->cull_mask_bytes, mask_bytes);
-            if (mst != FF_OK) return mst;
-            if (cull) FF_HIP(launch_cull_mask(k, s->d_cull_mask, st));
-            else FF_HIP(hipMemsetAsync(s->d_cull_mask, 0, mask_bytes, st));
-            s->pending_mask_built = true;
-            if (!reuse) s->primary_has_mask = false; // (the mask that went with the stored hits has just been overwritten; the hits stay)
-        } else {
-            s->pending_mask_reused = true;
-        }
-        k.cull_mask = s->d_cull_mask;
-        // (a culled pixel's whole-block items are dropped; with a fine-grained tail its last block is still traced sample by sample)
-        s->pending_culled_rays_per_pixel = (unsigned)(spp - (tail_mode ? tail_n : 0));
-    }
-    if (reuse && kept) k.primary_hits = s->d_primary_cache;
-    k.start_records = use_start ? s->d_start_records : nullptr;
-    k.start_bounces = bounces;
-    if (reuse && !kept) {
-        const int pst = enqueue_prepass(s, k, s->d_primary_cache, exact_cull ? s->d_cull_mask : nullptr, num_blocks, grid, block_threads);
-        if (pst != FF_OK) return pst;
-        k.primary_hits = s->d_primary_cache;
-        s->primary_key = key;
-        s->primary_valid = true;
-        s->primary_has_mask = cull || exact_cull;
-        s->primary_has_start = use_start;
-        s->start_bounces = bounces;
-        s->start_shade = prm->shade_mode;
-    }
-    for (int l = 0; l < launches; ++l) {
-        k.block_begin = l * blocks_per_launch;
-        k.block_end = std::min(num_blocks, (l + 1) * blocks_per_launch);
-        k.whole_blocks = (unsigned)(k.block_end - k.block_begin);
-        k.total_items = k.pix_items * k.whole_blocks;
-        if (tail_mode && l == launches - 1) {
-            const unsigned groups = (unsigned)k.tail_groups;
-            k.tail_block = num_blocks - tail_blocks;
-            k.whole_blocks = (unsigned)(k.block_end - tail_blocks - k.block_begin);
-            k.tail_first_item = k.pix_items * k.whole_blocks;
-            k.total_items = k.tail_first_item + k.pix_items * groups;
-        }
-        if (l > 0) FF_HIP(hipMemsetAsync(s->d_queue, 0, (size_t)k.queue_counters * kQueueStride * sizeof(unsigned), st));
-        FF_HIP(launch_trace(k, prm->trace_mode, s->collect_stats, grid, block_threads, st, &s->last_kernel_name, pool, /*prepass=*/false, /*start=*/use_start,
-                            /*world_normals=*/!s->sw.no_world_normals));
-    }
-    FF_HIP(launch_combine(k, st));
-    FF_HIP(hipEventRecord(s->ev_end, st));
-    FF_HIP(hipMemcpyAsync(s->h_counters, s->d_counters, kCounterWords * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    if (k.timeline) {
-        const size_t rows = (size_t)s->num_cus * 2 * (kBlockThreads / 64);
-        s->h_timeline_rows.resize(rows * kTimelineBuckets);
-        FF_HIP(hipMemcpyAsync(s->h_timeline_rows.data(), s->d_timeline, rows * kTimelineBuckets * sizeof(unsigned), hipMemcpyDeviceToHost, st));
-    }
-    s->pending = true;
-    s->pending_launches = launches;
-    return FF_OK;
-}
-
-// (declared in ff_state.h)
-int frame_primary_hits(FfState* s, const FfCamera* camera, const FfRenderParams* params, PrimaryHits* out)
-{
-    const int W = params->width, H = params->height;
-    KParams k;
-    std::memset(&k, 0, sizeof k);
-    int st = fill_frame_mapping(s, k, camera, W, H, params->grid_mode, H, 0, 1, H, 0, 0, W, 1, "ff_gbuffer: ");
-    if (st != FF_OK) return st;
-    // The frame's stored hits serve if they were computed for this camera and pixel mapping: with either kind of stored normal, which
-    // the G-buffer's resolve does not read.
-    const size_t hits_bytes = (size_t)3 * (size_t)k.pix_items * sizeof(float4);
-    bool kept = false;
-    for (int smooth = 0; smooth < 2 && !kept; ++smooth) {
-        const FfState::PrimaryKey key = primary_key(k, smooth != 0);
-        kept = s->primary_valid && s->primary_cache_bytes >= hits_bytes && std::memcmp(&key, &s->primary_key, sizeof key) == 0;
-    }
-    *out = { s->d_primary_cache, !kept, k.pix_items, k.tiles_per_row, k.xlim, k.ylim };
-    if (kept) return FF_OK;
-    // a pre-pass of its own (geometric normals; the resolve recomputes a triangle's from its record anyway)
-    st = ensure_bytes((void**)&s->d_gb_hits, &s->gb_hits_bytes, hits_bytes);
-    if (st != FF_OK) return st;
-    out->hits = s->d_gb_hits;
-    const int block_threads = s->scene_block_threads;
-    const int grid = (int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)s->num_cus, ((uint64_t)k.pix_items + (uint64_t)block_threads - 1) / (uint64_t)block_threads));
-    fill_scene(s, k, false, block_threads);
-    st = attach_stack_spill(s, k, grid, block_threads);
-    if (st != FF_OK) return st;
-    k.reuse_quorum = s->sw.reuse_quorum;
-    k.queue = s->d_queue;
-    k.counters = s->d_counters;
-    k.timeline_ticks = 1;
-    size_work_queue(s, k, grid, block_threads, 8);
-    FF_HIP(hipMemsetAsync(s->d_counters, 0, (size_t)(1 + k.queue_counters) * kQueueStride * sizeof(unsigned), s->stream));
-    return enqueue_prepass(s, k, s->d_gb_hits, nullptr, 1, grid, block_threads);
-}
-
-int render_finish(FfState* s)
-{
-    if (!s->pending) return FF_OK; // nothing was enqueued (an empty part)
-    s->pending = false;
-    FF_HIP(hipStreamSynchronize(s->stream));
-    float ms = 0.f;
-    FF_HIP(hipEventElapsedTime(&ms, s->ev_begin, s->ev_end));
-    unsigned long long c[32];
-    std::memcpy(c, s->h_counters, sizeof c);
-    std::memcpy(s->raw_counters, c, sizeof c);
-    if (c[0] != 0)
-        return fail(FF_ERR_HIP, "the traversal loop guard cut %llu queries short (a malformed or absurdly deep tree): the frame is not valid", c[0]);
-    s->stats.rays_traced = 0;
-    for (int j = 0; j < kRaySlots; ++j) s->stats.rays_traced += s->h_counters[kRaySlotStride * (kRaySlotFirst + j)];
-    s->stats.rays_answered = 0;
-    {
-        // the rays of culled pixels: counted by the passes that built the mask - or, for a frame that took the mask over from the
-        // last one, as many pixels as that frame counted
-        unsigned long long culled = 0;
-        for (int j = 0; j < kRaySlots; ++j) culled += s->h_counters[kCulledPixelsWord + kRaySlotStride * j];
-        if (s->pending_mask_reused) culled = s->primary_culled_pixels;
-        else if (s->pending_mask_built) s->primary_culled_pixels = culled;
-        s->stats.rays_answered += culled * s->pending_culled_rays_per_pixel;
-    }
-    for (int j = 0; j < kRaySlots; ++j) s->stats.rays_answered += s->h_counters[kAnsweredWord + kRaySlotStride * j]; // + repeated primaries
-    s->stats.rays_cut_short = 0;
-    for (int j = 0; j < kRaySlots; ++j) s->stats.rays_cut_short += s->h_counters[kCutShortWord + kRaySlotStride * j];
-    s->raw_counters[0] = s->stats.rays_traced;
-    s->stats.nodes_visited = c[1];
-    s->stats.tris_tested = c[2];
-    s->stats.planes_tested = c[3];
-    s->stats.kernel_ms = ms;
-    s->stats.kernel_launches = (uint32_t)s->pending_launches;
-    s->stats.flags = s->pending_flags;
-    s->stats.scene_bytes_nodes = (uint64_t)s->num_nodes4 * sizeof(Bvh4Node);
-    s->stats.scene_bytes_tris = s->num_tris * sizeof(TriRecord);
-    return FF_OK;
-}
-
-} // namespace ff
-
-namespace {
 
 int render_local(FfState* s, const FfCamera* camera, const FfRenderParams* prm, int strip_rows, int part, int num_parts, int local_rows,
                  unsigned char* rgb8_dev, float* radiance_dev, int x0 = 0, int y0 = 0, int win_w = -1)

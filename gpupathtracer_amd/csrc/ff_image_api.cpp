@@ -2,7 +2,7 @@
 // ff_denoise, ff_denoise_temporal, ff_taa and ff_taa_upscale with their histories (kernels in ff_denoise.hip, ff_temporal.hip,
 // ff_taa.hip, ff_taa_upscale.hip), and
 // what they share with ff_display_api.cpp (ff_image.h).  No trace kernel is launched from here: ff_gbuffer's primary hits come
-// from frame_primary_hits (ff_api.cpp).
+// from frame_primary_hits (ff_frame.cpp).
 #include <algorithm>
 #include <cmath>
 #include <cstring>

@@ -263,16 +263,9 @@ int enqueue_nee(FfState* s, KParams& k, const FfCamera* camera, const FfRenderPa
     int grid = (int)std::min<uint64_t>((most_items + kBlockThreads - 1) / kBlockThreads, (uint64_t)s->num_cus * 8);
     if (grid < 1) grid = 1;
     k.stack_spill = nullptr;
-    if (prm->trace_mode == FF_TRACE_BVH && s->stack_lds_levels < s->stack_entries) {
-        const int sst = ensure_bytes((void**)&s->d_stack_spill, &s->stack_spill_bytes,
-                                     (size_t)(s->stack_entries - s->stack_lds_levels) * (size_t)grid * (size_t)kBlockThreads * sizeof(int));
-        if (sst != FF_OK) return sst;
-        k.stack_spill = s->d_stack_spill;
-    }
-    if (prm->grid_mode == FF_GRID_REFERENCE_FLOOR) {
-        if (k.rgb8) FF_HIP(hipMemsetAsync(k.rgb8, 0, local_pixels * 3, st));
-        if (k.radiance) FF_HIP(hipMemsetAsync(k.radiance, 0, local_pixels * 3 * sizeof(float), st));
-    }
+    int sst = prm->trace_mode == FF_TRACE_BVH ? attach_stack_spill(s, k, grid, kBlockThreads) : FF_OK;
+    if (sst == FF_OK) sst = clear_floor_grid(prm->grid_mode, k.rgb8, k.radiance, local_pixels, st);
+    if (sst != FF_OK) return sst;
     NeeParams np;
     std::memset(&np, 0, sizeof np);
     np.lights = s->d_nee_lights;
@@ -315,10 +308,7 @@ int enqueue_nee(FfState* s, KParams& k, const FfCamera* camera, const FfRenderPa
     FF_HIP(hipMemsetAsync(s->d_counters, 0, (size_t)kCounterWords * sizeof(unsigned long long), st));
     FF_HIP(hipEventRecord(s->ev_begin, st));
     for (int l = 0; l < launches; ++l) {
-        k.block_begin = l * blocks_per_launch;
-        k.block_end = std::min(k.num_blocks, (l + 1) * blocks_per_launch);
-        k.whole_blocks = (unsigned)(k.block_end - k.block_begin);
-        k.total_items = k.pix_items * k.whole_blocks;
+        set_launch_blocks(k, l, blocks_per_launch);
         np.k = k;
         np.items = k.total_items;
         FF_HIP(launch_nee(np, prm->trace_mode, env, tex, glossy, grid, st, &s->last_kernel_name));
@@ -326,11 +316,7 @@ int enqueue_nee(FfState* s, KParams& k, const FfCamera* camera, const FfRenderPa
     FF_HIP(launch_combine(k, st));
     FF_HIP(hipEventRecord(s->ev_end, st));
     FF_HIP(hipMemcpyAsync(s->h_counters, s->d_counters, kCounterWords * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    s->pending_culled_rays_per_pixel = 0;
-    s->pending_mask_reused = s->pending_mask_built = false;
-    s->pending_flags = 0u;
-    s->pending = true;
-    s->pending_launches = launches;
+    commit_pending(s, launches, 0u, 0u, false, false);
     return FF_OK;
 }
 

@@ -1,5 +1,5 @@
 // ff_state.h — the tracer state behind the opaque FfState handle and the internal render steps shared by the
-// translation units of the library (ff_api.cpp: single-device entry points; ff_dist.cpp: multi-GPU entry points;
+// translation units of the library (ff_api.cpp: single-device entry points; ff_frame.cpp: one frame; ff_dist.cpp: multi-GPU entry points;
 // ff_image_api.cpp and ff_display_api.cpp: the image-space entry points, whose own state is described in ff_image.h).
 #pragma once
 
@@ -286,6 +286,21 @@ int check_render_call(const FfState* s, const FfCamera* camera, const FfRenderPa
 int render_enqueue(FfState* s, const FfCamera* camera, const FfRenderParams* prm, int strip_rows, int part, int num_parts, int local_rows,
                    unsigned char* rgb8_dev, float* radiance_dev, int x0 = 0, int y0 = 0, int win_w = -1);
 int render_finish(FfState* s);
+
+// What render_enqueue's frame shares with enqueue_nee's and with frame_primary_hits (ff_frame.cpp), one copy each:
+// the camera's ray matrix into `k`;
+void set_camera_matrix(KParams& k, const FfMat4& cm);
+// d_stack_spill grown for a launch of grid x block_threads threads and attached to `k`, where the scene's stacks spill at all;
+int attach_stack_spill(FfState* s, KParams& k, int grid, int block_threads);
+// the clears of the local image that FF_GRID_REFERENCE_FLOOR needs (either pointer may be null);
+int clear_floor_grid(int grid_mode, unsigned char* rgb8_dev, float* radiance_dev, size_t local_pixels, hipStream_t stream);
+// the sample blocks of launch number `launch`: block_begin, block_end, whole_blocks, total_items;
+void set_launch_blocks(KParams& k, int launch, int blocks_per_launch);
+// what render_finish reads of an enqueued frame (the state's pending_* fields; sets `pending`).
+void commit_pending(FfState* s, int launches, uint32_t flags, unsigned culled_rays_per_pixel, bool mask_reused, bool mask_built);
+
+// Geometry records the BVH kernels keep in LDS: all of them up to kMaxLdsRecords, none beyond (read from global memory).
+inline int lds_records(const FfState* s) { return s->num_geoms > kMaxLdsRecords ? 0 : s->num_geoms; }
 
 // This camera's primary hits for a whole width x height frame (ff_render's pixel mapping: one part, strips of height rows, the
 // window is the image), for ff_gbuffer (ff_image_api.cpp): the hits the state keeps from its last frame if they were computed for
