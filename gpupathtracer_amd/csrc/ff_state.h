@@ -207,6 +207,22 @@ struct FfState {
     // Not reset by uploads.
     void* d_despeckle_work = nullptr;
     size_t despeckle_work_bytes = 0;
+    // adaptive sampling (ff_render_adaptive, ff_adaptive_api.cpp): the two running sums (W*H*3 floats each) and behind them the
+    // compact rectangle a pass renders into; per tile the error, the pass count and the list of tiles to check; the staging of host
+    // buffers (ff_adaptive_tile_error's inputs, the per-pixel pass counts).  The last call's grid and per-tile results stay for
+    // ff_adaptive_state.  Reset per call; not reset by uploads.
+    struct Adaptive {
+        float* d_planes = nullptr;
+        size_t planes_bytes = 0;
+        void* d_tiles = nullptr;
+        size_t tiles_bytes = 0;
+        void* d_stage = nullptr;
+        size_t stage_bytes = 0;
+        bool valid = false;                   // a call has completed: the fields below describe it
+        int width = 0, height = 0, tile = 0;
+        std::vector<uint16_t> tile_passes;    // n_t per tile, row-major
+        std::vector<float> tile_error;        // E_t of each tile's last check
+    } adaptive;
     unsigned* d_queue = nullptr;               // work-queue counter: lives right behind the counters (one memset clears both)
     unsigned long long* d_counters = nullptr;  // 28 counters + 4 queue words
     unsigned long long* h_counters = nullptr;  // pinned mirror for the per-frame read-back
@@ -343,6 +359,8 @@ void motion_blur_release(FfState* s);
 void dof_release(FfState* s);
 // Firefly clamp (ff_despeckle_api.cpp): frees the state's work buffer (ff_destroy).
 void despeckle_release(FfState* s);
+// Adaptive sampling (ff_adaptive_api.cpp): frees the state's buffers (ff_destroy).
+void adaptive_release(FfState* s);
 // The pixel buffer registered with ff_register_gl_pbo, mapped on the state's stream (kernel.cu:338-339) and unmapped again
 // (kernel.cu:344): what ff_render_to_pbo and ff_display_to_pbo write.  need_bytes: the least size the mapping must have.
 int map_pbo(FfState* s, size_t need_bytes, void** out_ptr);

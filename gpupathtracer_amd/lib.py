@@ -43,6 +43,7 @@ EXPORTS = [
     "ff_motion_blur_params_init", "ff_motion_blur", "ff_motion_blur_host",
     "ff_dof_params_init", "ff_dof_params_from_camera", "ff_depth_of_field", "ff_depth_of_field_host",
     "ff_despeckle_params_init", "ff_despeckle", "ff_despeckle_host",
+    "ff_adaptive_params_init", "ff_render_adaptive", "ff_adaptive_state", "ff_adaptive_tile_error", "ff_adaptive_tile_error_host", "ff_adaptive_plan_host",
 ]
 DIST_ID_BYTES = 128
 
@@ -239,6 +240,13 @@ def load():
     lib.ff_despeckle_params_init.restype = None
     lib.ff_despeckle.argtypes = [vp, i32, i32, P(T.FfDespeckleParams), vp, vp, vp, i32, vp, i32, vp, i32, P(C.c_uint32)]
     lib.ff_despeckle_host.argtypes = [i32, i32, P(T.FfDespeckleParams), vp, vp, vp, vp, vp, P(C.c_uint32)]
+    lib.ff_adaptive_params_init.argtypes = [P(T.FfAdaptiveParams)]
+    lib.ff_adaptive_params_init.restype = None
+    lib.ff_render_adaptive.argtypes = [vp, P(T.FfCamera), P(T.FfRenderParams), P(T.FfAdaptiveParams), vp, i32, vp, i32, vp, i32, P(T.FfAdaptiveInfo)]
+    lib.ff_adaptive_state.argtypes = [vp, vp, vp, vp, vp, i32]
+    lib.ff_adaptive_tile_error.argtypes = [vp, i32, i32, i32, i32, vp, vp, i32, vp]
+    lib.ff_adaptive_tile_error_host.argtypes = [i32, i32, i32, i32, vp, vp, vp]
+    lib.ff_adaptive_plan_host.argtypes = [i32, i32, vp, vp, i32]
     lib.ff_taa_upscale_params_init.argtypes = [P(T.FfTaaUpscaleParams)]
     lib.ff_taa_upscale_params_init.restype = None
     lib.ff_taa_upscale.argtypes = [vp, P(T.FfCamera), P(T.FfTaaUpscaleParams), i32, i32, vp, vp, i32, i32, vp, vp, i32, vp, i32, vp, i32]
@@ -744,6 +752,53 @@ def despeckle_host(radiance, gbuffer_or_planes, p=None, want_rgb8=True, want_out
     return rgb8, out, int(clamped.value)
 
 
+def adaptive_params(**overrides):
+    """ff_adaptive_params_init's defaults with the given fields replaced (any FfAdaptiveParams field)."""
+    p = T.FfAdaptiveParams()
+    load().ff_adaptive_params_init(C.byref(p))
+    for name, value in overrides.items():
+        if name not in dict(T.FfAdaptiveParams._fields_):
+            raise TypeError(f"FfAdaptiveParams has no field {name!r}")
+        setattr(p, name, value)
+    return p
+
+
+def _adaptive_sums(sum_all, sum_even, who):
+    """The two sum planes of the tile error as contiguous float32 [H,W,3] arrays, and (h, w)."""
+    a = np.ascontiguousarray(sum_all, dtype=np.float32)
+    b = np.ascontiguousarray(sum_even, dtype=np.float32)
+    h, w = a.shape[:2]
+    if a.shape != (h, w, 3) or b.shape != (h, w, 3):
+        raise ValueError(f"{who}: sum and sum_even must be [H,W,3]")
+    return a, b, (h, w)
+
+
+def adaptive_tile_grid(width, height, tile):
+    """(tiles_y, tiles_x) of ff_render_adaptive's tile grid."""
+    return (height + tile - 1) // tile, (width + tile - 1) // tile
+
+
+def adaptive_tile_error_host(sum_all, sum_even, tile, n):
+    """ff_adaptive_tile_error_host (no GPU): the running sums [H,W,3] after n passes -> E_t per tile, float32 [tiles_y, tiles_x]."""
+    a, b, (h, w) = _adaptive_sums(sum_all, sum_even, "adaptive_tile_error_host")
+    out = np.zeros(adaptive_tile_grid(w, h, tile) if tile > 0 else (1, 1), dtype=np.float32)
+    check(load().ff_adaptive_tile_error_host(w, h, tile, n, a.ctypes.data, b.ctypes.data, out.ctypes.data))
+    return out
+
+
+def adaptive_plan_host(active, max_rects=None):
+    """ff_adaptive_plan_host: a [tiles_y, tiles_x] array of flags -> the driver's rectangles, int32 [n, 4] of {tx0, ty0, tx1, ty1} in
+    tiles (half open).  max_rects: the room offered (default: one per tile); a list that does not fit raises."""
+    flags = np.ascontiguousarray(np.asarray(active) != 0, dtype=np.uint8)
+    ty, tx = flags.shape
+    room = flags.size if max_rects is None else max_rects
+    out = np.zeros((max(room, 1), 4), dtype=np.int32)
+    n = load().ff_adaptive_plan_host(tx, ty, flags.ctypes.data, out.ctypes.data, room)
+    if n < 0:
+        check(T.FF_ERR_INVALID_ARG)
+    return out[:n].copy()
+
+
 def display_params(**overrides):
     """ff_display_params_init's defaults with the given fields replaced (any FfDisplayParams field)."""
     p = T.FfDisplayParams()
@@ -978,6 +1033,46 @@ class Tracer:
         rad = np.zeros((h, w, 3), dtype=np.float32)
         check(self._lib.ff_render_tile(self._state, C.byref(camera), C.byref(params), x0, y0, w, h, rgb8.ctypes.data, 0, rad.ctypes.data, 0))
         return rgb8, rad
+
+    def render_adaptive(self, camera, params, ap=None):
+        """ff_render_adaptive: passes of params.spp samples (seed, seed + 1, ...) until every tile's error estimate is below
+        ap.threshold -> (rgb8 [H,W,3] uint8, radiance [H,W,3] float32, passes [H,W] uint16, FfAdaptiveInfo)."""
+        ap = ap if ap is not None else adaptive_params()
+        h, w = params.height, params.width
+        rgb8 = np.zeros((h, w, 3), dtype=np.uint8)
+        rad = np.zeros((h, w, 3), dtype=np.float32)
+        passes = np.zeros((h, w), dtype=np.uint16)
+        info = T.FfAdaptiveInfo()
+        check(self._lib.ff_render_adaptive(self._state, C.byref(camera), C.byref(params), C.byref(ap), rgb8.ctypes.data, 0, rad.ctypes.data, 0,
+                                           passes.ctypes.data, 0, C.byref(info)))
+        return rgb8, rad, passes, info
+
+    def render_adaptive_device(self, camera, params, ap=None, rgb8_ptr=None, radiance_ptr=None, passes_ptr=None):
+        """ff_render_adaptive into caller-owned DEVICE buffers (raw pointers; each may be None) -> FfAdaptiveInfo."""
+        ap = ap if ap is not None else adaptive_params()
+        vp = lambda q: C.c_void_p(q) if q else None  # noqa: E731
+        info = T.FfAdaptiveInfo()
+        check(self._lib.ff_render_adaptive(self._state, C.byref(camera), C.byref(params), C.byref(ap), vp(rgb8_ptr), 1, vp(radiance_ptr), 1, vp(passes_ptr), 1,
+                                           C.byref(info)))
+        return info
+
+    def adaptive_state(self, width, height, tile):
+        """ff_adaptive_state of the last render_adaptive call (its size and tile edge are the caller's to give) -> dict of numpy
+        arrays: sum / sum_even [H,W,3] float32, tile_passes [tiles_y,tiles_x] uint16, tile_error [tiles_y,tiles_x] float32."""
+        grid = adaptive_tile_grid(width, height, tile)
+        out = {"sum": np.zeros((height, width, 3), dtype=np.float32), "sum_even": np.zeros((height, width, 3), dtype=np.float32),
+               "tile_passes": np.zeros(grid, dtype=np.uint16), "tile_error": np.zeros(grid, dtype=np.float32)}
+        check(self._lib.ff_adaptive_state(self._state, out["sum"].ctypes.data, out["sum_even"].ctypes.data, out["tile_passes"].ctypes.data,
+                                          out["tile_error"].ctypes.data, 0))
+        return out
+
+    def adaptive_tile_error(self, sum_all, sum_even, tile, n):
+        """ff_adaptive_tile_error (the device kernel on planted sums): host sums [H,W,3] after n passes -> E_t per tile, float32
+        [tiles_y, tiles_x]."""
+        a, b, (h, w) = _adaptive_sums(sum_all, sum_even, "adaptive_tile_error")
+        out = np.zeros(adaptive_tile_grid(w, h, tile) if tile > 0 else (1, 1), dtype=np.float32)
+        check(self._lib.ff_adaptive_tile_error(self._state, w, h, tile, n, a.ctypes.data, b.ctypes.data, 0, out.ctypes.data))
+        return out
 
     def render_device(self, camera, params, rgb8_ptr=None, radiance_ptr=None):
         """Headless frame into caller-owned DEVICE buffers (raw pointers, e.g. torch tensor.data_ptr())."""

@@ -202,6 +202,23 @@ class FfDespeckleParams(C.Structure):
 DESPECKLE_PARAMS_BYTES = 28
 DESPECKLE_DEMODULATE_ALBEDO = 1
 
+
+class FfAdaptiveParams(C.Structure):
+    _fields_ = [("tile", C.c_int32), ("min_passes", C.c_int32), ("max_passes", C.c_int32), ("threshold", C.c_float), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+class FfAdaptiveInfo(C.Structure):
+    _fields_ = [("passes_run", C.c_int32), ("tiles", C.c_int32), ("tiles_stopped_early", C.c_int32), ("rectangles", C.c_int32),
+                ("samples", C.c_uint64), ("max_tile_error", C.c_float)]
+
+
+ADAPTIVE_PARAMS_BYTES, ADAPTIVE_INFO_BYTES = 24, 32
+ADAPTIVE_GUARD_NEIGHBOURS = 1
+ADAPTIVE_TILES = (16, 32, 64, 128)
+ADAPTIVE_MAX_PASSES = 65534
+assert C.sizeof(FfAdaptiveParams) == ADAPTIVE_PARAMS_BYTES and C.sizeof(FfAdaptiveInfo) == ADAPTIVE_INFO_BYTES
+
 BUILD_HOST_SAH, BUILD_GPU_LBVH, BUILD_GPU_PLOC = 0, 1, 2
 UPDATE_REFIT, UPDATE_REBUILD = 0, 1
 

@@ -1027,6 +1027,77 @@ FF_API int ff_despeckle(FfState* state, int width, int height, const FfDespeckle
 FF_API int ff_despeckle_host(int width, int height, const FfDespeckleParams* p, const float* radiance_in, const float* albedo,
                              const int32_t* ids, unsigned char* rgb8, float* radiance_out, uint32_t* out_clamped);
 
+/* ---- adaptive sampling (render until every tile's noise estimate is below a threshold) ------------- */
+
+/* Defaults: tile 64, min_passes 2, max_passes 64, threshold 0.0002 (the paper's value: a default for users, not a measured optimum
+ * for this renderer - tools/adaptive_bench.py sweeps it), no flags. */
+FF_API void ff_adaptive_params_init(FfAdaptiveParams* p);
+
+/* Renders a frame in passes and stops sampling the tiles of the image whose error estimate has fallen below ap->threshold: the
+ * stopping condition of Dammertz et al., "A Hierarchical Automatic Stopping Condition for Monte Carlo Global Illumination" (2010),
+ * on a fixed grid of ap->tile x ap->tile tiles (row-major, narrower and shorter at the right and bottom edges; the paper's block
+ * splitting is left out).  Pass k = 0, 1, 2, ... is an ordinary render of params->spp samples with seed params->seed + k -
+ * ff_render_progressive's seed sequence - restricted to the tiles that are still active; a rectangle of the frame renders bit for
+ * bit as the whole frame would (ff_render_tile).  Per pixel the call keeps two running float32 sums: `sum` over all of the pixel's
+ * passes and `sum_even` over its passes of even k (pass 0 writes both, later passes add).  A stopped tile never resumes, so a
+ * tile's passes are always 0 .. n_t - 1 and all pixels of a tile share n_t.
+ *   The error of a tile after n passes, n even.  float32 throughout, only + - * / sqrt and fabs, evaluated as written with the
+ *   parentheses shown, no fused multiply-add.  inv_n = 1.0f / (float)n, inv_h = 1.0f / (float)(n / 2).  Per pixel and channel
+ *   I_c = sum_c * inv_n and A_c = sum_even_c * inv_h; d = (I_r + I_g) + I_b; e_p = 0 where !(d > 0), otherwise
+ *   e_p = ((|I_r - A_r| + |I_g - A_g|) + |I_b - A_b|) / sqrt(d).  S is the sum of e_p over the tile's N_t pixels in a fixed order:
+ *   with the pixels in the tile's row-major order i = 0 .. N_t - 1, lane j of 256 adds e_j, e_(j+256), ... in that order starting
+ *   from 0.0f (a lane without a pixel holds 0.0f), then v[j] += v[j + off] for off = 128, 64, ..., 1, and S = v[0].
+ *   E_t = S * sqrt((float)N_t / (float)(W * H)) / (float)N_t, left to right.  The order does not depend on the launch shape:
+ *   ff_adaptive_tile_error, ff_adaptive_tile_error_host and a float32 restatement agree bit for bit.
+ *   A tile stops at a check iff E_t < threshold.  A NaN error is below nothing: such a tile stays active until max_passes.
+ *   The driver.  All tiles start active.  Each pass turns the active tiles into rectangles (ff_adaptive_plan_host), renders each
+ *   into a compact buffer and adds it to the sums.  After pass k, with n = k + 1: if n is even and n >= min_passes, E_t of the
+ *   active tiles is computed on the device and read back, and the tiles below the threshold stop.  Under
+ *   FF_ADAPTIVE_GUARD_NEIGHBOURS a tile stops only when it and all of its up to 8 neighbours are below the threshold at this same
+ *   check, a neighbour that has already stopped counting as below: no quiet tile stops beside a noisy one, which would leave a
+ *   seam.  The call ends when no tile is active or n == max_passes.  Each pixel then is sum * (1.0f / (float)n_t), and rgb8 the
+ *   rule of every rgb8 output here of that value.  threshold 0 is ff_render_progressive's frame max_passes - 1 bit for bit;
+ *   threshold +inf stops every tile with a finite error at min_passes.
+ * rgb8 (W*H*3 bytes), radiance (W*H*3 floats) and passes_out (W*H uint16, each pixel's n_t) follow ff_render's conventions and may
+ * each be NULL; out_info is a host pointer and may be NULL.  Because every pass goes through the frame's own code the call honours
+ * ff_set_pixel_jitter, ff_set_camera_sampling, textures, roughness and the environment.  Synchronous, on the state's stream.
+ * FfStats describes the last rectangle rendered.  The call leaves the progressive sum (a running ff_render_progressive sequence
+ * continues after it), every filter's history and the display exposure as they were; the stored primary hits follow the frames'
+ * own rule (a rectangle other than the whole frame replaces them).  Its own state is reset per call (buffers allocated on first
+ * use, regrown for a larger size, freed by ff_destroy).
+ * FF_ERR_INVALID_ARG, naming the field, before any device work, for: a NULL ap; tile not 16, 32, 64 or 128; min_passes odd or
+ * below 2; max_passes odd, below min_passes or above 65534; a NaN or -inf threshold; unknown flags; a nonzero reserved; then what
+ * ff_render refuses.
+ * Not offered: the multi-GPU entry points, a pixel-buffer twin, the paper's hierarchical block splitting. */
+FF_API int ff_render_adaptive(FfState* state, const FfCamera* camera, const FfRenderParams* params, const FfAdaptiveParams* ap,
+                              void* rgb8, int rgb8_on_device, float* radiance, int radiance_on_device,
+                              uint16_t* passes_out, int passes_on_device, FfAdaptiveInfo* out_info);
+
+/* The last ff_render_adaptive call's accumulators and per-tile results, for tests and tools: sum and sum_even (W*H*3 floats each),
+ * tile_passes (n_t per tile, uint16, row-major over the ceil(W / tile) x ceil(H / tile) grid) and tile_error (E_t of each tile's
+ * last check, float).  Each may be NULL; on_device covers all four.  FF_ERR_INVALID_ARG when no call has completed on this state. */
+FF_API int ff_adaptive_state(FfState* state, float* sum, float* sum_even, uint16_t* tile_passes, float* tile_error, int on_device);
+
+/* The device kernel of the error estimate on planted sums: E_t after n passes (even, 2 .. 65534) of every tile of a width x height
+ * image (1 .. 65535 each) under the tile edge `tile` (16, 32, 64 or 128), from sum and sum_even (W*H*3 floats each;
+ * inputs_on_device covers both) into out_error (a host pointer, one float per tile, row-major).  Leaves the last
+ * ff_render_adaptive call's results as they were. */
+FF_API int ff_adaptive_tile_error(FfState* state, int width, int height, int tile, int n, const float* sum, const float* sum_even,
+                                  int inputs_on_device, float* out_error);
+
+/* Host-only twin (no GPU, no state, host pointers), compiled from the same inline functions the kernel uses: the same checks, the
+ * same bits. */
+FF_API int ff_adaptive_tile_error_host(int width, int height, int tile, int n, const float* sum, const float* sum_even,
+                                       float* out_error);
+
+/* The driver's rectangle list for a tiles_x x tiles_y grid of flags (row-major, nonzero: active): first, per tile row, the maximal
+ * runs of active tiles; then runs of consecutive rows with the identical span [tx0, tx1) merge.  A rectangle is four ints
+ * {tx0, ty0, tx1, ty1} in tiles, half open, and the list is in the order of the rectangles' first rows, then of tx0.  All tiles
+ * active give one rectangle, the whole frame.  Returns the number of rectangles, or -1 with ff_last_error set for a NULL pointer,
+ * a grid size below 1 or a max_rects (the room in out_rects4, in rectangles) too small for the list.  ff_render_adaptive calls
+ * this very function. */
+FF_API int ff_adaptive_plan_host(int tiles_x, int tiles_y, const uint8_t* active, int32_t* out_rects4, int max_rects);
+
 /* ---- display transform (exposure, bloom, tone curve, sRGB) ------------------------------------- */
 
 /* Defaults: ACES, SRGB, flags 0, exposure 1, white 4, key 0.18, percentiles 0.5 / 0.95, min_exposure 2^-10, max_exposure 2^10,

@@ -356,6 +356,28 @@ typedef struct FfDespeckleParams {
     uint32_t reserved;        /* 0 */
 } FfDespeckleParams;          /* 28 bytes; every float must be finite */
 
+/* ff_render_adaptive: render in passes until every tile's error estimate is below a threshold.  ff_adaptive_params_init gives the
+ * defaults; the estimator and the driver are in ff_api.h. */
+#define FF_ADAPTIVE_GUARD_NEIGHBOURS 1     /* a tile stops only when its up to 8 neighbours are below the threshold too */
+typedef struct FfAdaptiveParams {
+    int32_t  tile;            /* the tile edge in pixels: 16, 32, 64 or 128 */
+    int32_t  min_passes;      /* no tile is judged before this many passes; even, >= 2 */
+    int32_t  max_passes;      /* no tile gets more; even, min_passes .. 65534 */
+    float    threshold;       /* a tile stops when its error is below this; finite or +inf (NaN is refused) */
+    uint32_t flags;           /* FF_ADAPTIVE_GUARD_NEIGHBOURS */
+    uint32_t reserved;        /* 0 */
+} FfAdaptiveParams;           /* 24 bytes */
+
+/* What a call of ff_render_adaptive did. */
+typedef struct FfAdaptiveInfo {
+    int32_t  passes_run;           /* passes the most persistent tile got: the largest n_t */
+    int32_t  tiles;                /* tiles of the grid */
+    int32_t  tiles_stopped_early;  /* tiles with fewer than max_passes passes */
+    int32_t  rectangles;           /* rectangles rendered, over all passes */
+    uint64_t samples;              /* camera samples traced: the sum over the rectangles of pixels * spp */
+    float    max_tile_error;       /* the largest of the tiles' last error estimates (NaN ones aside) */
+} FfAdaptiveInfo;                  /* 32 bytes (4 of padding at the end) */
+
 /* ff_texture_create: how a texture is addressed and filtered (the formulas are in ff_api.h).  0 = repeat, bilinear. */
 #define FF_TEX_REPEAT    0   /* coordinates wrap: c - floor(c) */
 #define FF_TEX_CLAMP     1   /* coordinates clamp to [0, 1] */
@@ -390,6 +412,8 @@ static_assert(sizeof(FfCameraSampling) == 16, "FfCameraSampling is 16 bytes");
 static_assert(sizeof(FfMotionBlurParams) == 24, "FfMotionBlurParams is 24 bytes");
 static_assert(sizeof(FfDofParams) == 32, "FfDofParams is 32 bytes");
 static_assert(sizeof(FfDespeckleParams) == 28, "FfDespeckleParams is 28 bytes");
+static_assert(sizeof(FfAdaptiveParams) == 24, "FfAdaptiveParams is 24 bytes");
+static_assert(sizeof(FfAdaptiveInfo) == 32, "FfAdaptiveInfo is 32 bytes");
 #else
 _Static_assert(sizeof(FfBXDF) == 60, "BXDF layout");
 _Static_assert(sizeof(FfTriangle) == 96, "Triangle layout");
@@ -402,6 +426,8 @@ _Static_assert(sizeof(FfCameraSampling) == 16, "FfCameraSampling layout");
 _Static_assert(sizeof(FfMotionBlurParams) == 24, "FfMotionBlurParams layout");
 _Static_assert(sizeof(FfDofParams) == 32, "FfDofParams layout");
 _Static_assert(sizeof(FfDespeckleParams) == 28, "FfDespeckleParams layout");
+_Static_assert(sizeof(FfAdaptiveParams) == 24, "FfAdaptiveParams layout");
+_Static_assert(sizeof(FfAdaptiveInfo) == 32, "FfAdaptiveInfo layout");
 #endif
 
 #endif /* FIREFLY_FF_TYPES_H */
