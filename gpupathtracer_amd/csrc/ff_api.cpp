@@ -455,6 +455,7 @@ int ff_destroy(FfState* s)
     motion_blur_release(s);
     dof_release(s);
     despeckle_release(s);
+    sharpen_release(s);
     adaptive_release(s);
     free_build_scratch(s->scratch);
     if (s->d_blocksums) (void)hipFree(s->d_blocksums);

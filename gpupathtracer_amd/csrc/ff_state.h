@@ -207,6 +207,9 @@ struct FfState {
     // Not reset by uploads.
     void* d_despeckle_work = nullptr;
     size_t despeckle_work_bytes = 0;
+    // sharpening (ff_sharpen): the staging of host buffers.  Not reset by uploads.
+    void* d_sharpen_work = nullptr;
+    size_t sharpen_work_bytes = 0;
     // adaptive sampling (ff_render_adaptive, ff_adaptive_api.cpp): the two running sums (W*H*3 floats each) and behind them the
     // compact rectangle a pass renders into; per tile the error, the pass count and the list of tiles to check; the staging of host
     // buffers (ff_adaptive_tile_error's inputs, the per-pixel pass counts).  The last call's grid and per-tile results stay for
@@ -359,6 +362,8 @@ void motion_blur_release(FfState* s);
 void dof_release(FfState* s);
 // Firefly clamp (ff_despeckle_api.cpp): frees the state's work buffer (ff_destroy).
 void despeckle_release(FfState* s);
+// Sharpening (ff_sharpen_api.cpp): frees the state's work buffer (ff_destroy).
+void sharpen_release(FfState* s);
 // Adaptive sampling (ff_adaptive_api.cpp): frees the state's buffers (ff_destroy).
 void adaptive_release(FfState* s);
 // The pixel buffer registered with ff_register_gl_pbo, mapped on the state's stream (kernel.cu:338-339) and unmapped again

@@ -43,6 +43,7 @@ EXPORTS = [
     "ff_motion_blur_params_init", "ff_motion_blur", "ff_motion_blur_host",
     "ff_dof_params_init", "ff_dof_params_from_camera", "ff_depth_of_field", "ff_depth_of_field_host",
     "ff_despeckle_params_init", "ff_despeckle", "ff_despeckle_host",
+    "ff_sharpen_params_init", "ff_sharpen", "ff_sharpen_host",
     "ff_adaptive_params_init", "ff_render_adaptive", "ff_adaptive_state", "ff_adaptive_tile_error", "ff_adaptive_tile_error_host", "ff_adaptive_plan_host",
 ]
 DIST_ID_BYTES = 128
@@ -240,6 +241,10 @@ def load():
     lib.ff_despeckle_params_init.restype = None
     lib.ff_despeckle.argtypes = [vp, i32, i32, P(T.FfDespeckleParams), vp, vp, vp, i32, vp, i32, vp, i32, P(C.c_uint32)]
     lib.ff_despeckle_host.argtypes = [i32, i32, P(T.FfDespeckleParams), vp, vp, vp, vp, vp, P(C.c_uint32)]
+    lib.ff_sharpen_params_init.argtypes = [P(T.FfSharpenParams)]
+    lib.ff_sharpen_params_init.restype = None
+    lib.ff_sharpen.argtypes = [vp, i32, i32, P(T.FfSharpenParams), vp, i32, vp, i32, vp, i32]
+    lib.ff_sharpen_host.argtypes = [i32, i32, P(T.FfSharpenParams), vp, vp, vp]
     lib.ff_adaptive_params_init.argtypes = [P(T.FfAdaptiveParams)]
     lib.ff_adaptive_params_init.restype = None
     lib.ff_render_adaptive.argtypes = [vp, P(T.FfCamera), P(T.FfRenderParams), P(T.FfAdaptiveParams), vp, i32, vp, i32, vp, i32, P(T.FfAdaptiveInfo)]
@@ -750,6 +755,35 @@ def despeckle_host(radiance, gbuffer_or_planes, p=None, want_rgb8=True, want_out
     check(load().ff_despeckle_host(w, h, C.byref(p), rad.ctypes.data, alb.ctypes.data if alb is not None else None, ids.ctypes.data,
                                    rgb8.ctypes.data if want_rgb8 else None, out.ctypes.data if want_out else None, C.byref(clamped)))
     return rgb8, out, int(clamped.value)
+
+
+def sharpen_params(**overrides):
+    """ff_sharpen_params_init's defaults with the given fields replaced (any FfSharpenParams field)."""
+    p = T.FfSharpenParams()
+    load().ff_sharpen_params_init(C.byref(p))
+    for name, value in overrides.items():
+        if name not in dict(T.FfSharpenParams._fields_):
+            raise TypeError(f"FfSharpenParams has no field {name!r}")
+        setattr(p, name, value)
+    return p
+
+
+def _sharpen_image(radiance, who):
+    """The input image of ff_sharpen as a contiguous float32 array, and (h, w)."""
+    rad = np.ascontiguousarray(radiance, dtype=np.float32)
+    if rad.ndim != 3 or rad.shape[2] != 3:
+        raise ValueError(f"{who}: radiance must be [H,W,3]")
+    return rad, rad.shape[:2]
+
+
+def sharpen_host(radiance, p=None, want_rgb8=True, want_out=True):
+    """ff_sharpen_host (no GPU): host radiance [H,W,3] -> (rgb8 [H,W,3] uint8, radiance [H,W,3] float32)."""
+    rad, (h, w) = _sharpen_image(radiance, "sharpen_host")
+    p = p if p is not None else sharpen_params()
+    rgb8 = np.zeros((h, w, 3), dtype=np.uint8) if want_rgb8 else None
+    out = np.zeros((h, w, 3), dtype=np.float32) if want_out else None
+    check(load().ff_sharpen_host(w, h, C.byref(p), rad.ctypes.data, rgb8.ctypes.data if want_rgb8 else None, out.ctypes.data if want_out else None))
+    return rgb8, out
 
 
 def adaptive_params(**overrides):
@@ -1324,6 +1358,33 @@ class Tracer:
         check(self._lib.ff_despeckle(self._state, width, height, C.byref(p), vp(radiance_ptr), vp(albedo_ptr), vp(ids_ptr), 1, vp(rgb8_ptr), 1,
                                      vp(radiance_out_ptr), 1, C.byref(clamped) if want_count else None))
         return int(clamped.value) if want_count else None
+
+    def sharpen(self, radiance, p=None, want_rgb8=True, want_out=True):
+        """ff_sharpen of radiance [H,W,3] -> (rgb8 [H,W,3] uint8, radiance [H,W,3] float32).  A host array gives host arrays; a
+        contiguous float32 device tensor (torch) gives device tensors."""
+        p = p if p is not None else sharpen_params()
+        if hasattr(radiance, "data_ptr"):
+            import torch
+            h, w = radiance.shape[:2]
+            if not radiance.is_cuda or radiance.dtype != torch.float32 or tuple(radiance.shape) != (h, w, 3) or not radiance.is_contiguous():
+                raise ValueError("sharpen: radiance must be a contiguous [H,W,3] float32 tensor on the device")
+            rgb8 = torch.zeros((h, w, 3), dtype=torch.uint8, device=radiance.device) if want_rgb8 else None
+            out = torch.zeros((h, w, 3), dtype=torch.float32, device=radiance.device) if want_out else None
+            torch.cuda.synchronize(radiance.device)
+            self.sharpen_device(w, h, radiance.data_ptr(), p, rgb8.data_ptr() if want_rgb8 else None, out.data_ptr() if want_out else None)
+            return rgb8, out
+        rad, (h, w) = _sharpen_image(radiance, "sharpen")
+        rgb8 = np.zeros((h, w, 3), dtype=np.uint8) if want_rgb8 else None
+        out = np.zeros((h, w, 3), dtype=np.float32) if want_out else None
+        check(self._lib.ff_sharpen(self._state, w, h, C.byref(p), rad.ctypes.data, 0, rgb8.ctypes.data if want_rgb8 else None, 0,
+                                   out.ctypes.data if want_out else None, 0))
+        return rgb8, out
+
+    def sharpen_device(self, width, height, radiance_ptr, p=None, rgb8_ptr=None, radiance_out_ptr=None):
+        """ff_sharpen on DEVICE buffers (raw pointers); the outputs must not overlap the input."""
+        p = p if p is not None else sharpen_params()
+        vp = lambda q: C.c_void_p(q) if q else None  # noqa: E731
+        check(self._lib.ff_sharpen(self._state, width, height, C.byref(p), vp(radiance_ptr), 1, vp(rgb8_ptr), 1, vp(radiance_out_ptr), 1))
 
     def display(self, radiance, p=None, want_rgb8=True, want_out=True):
         """ff_display of host radiance [H,W,3] -> (rgb8 [H,W,3] uint8, display_out [H,W,3] float32: the curve's output in [0, 1]);

@@ -203,6 +203,14 @@ DESPECKLE_PARAMS_BYTES = 28
 DESPECKLE_DEMODULATE_ALBEDO = 1
 
 
+class FfSharpenParams(C.Structure):
+    _fields_ = [("strength", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+SHARPEN_PARAMS_BYTES = 12
+SHARPEN_NOISE_AWARE = 1
+
+
 class FfAdaptiveParams(C.Structure):
     _fields_ = [("tile", C.c_int32), ("min_passes", C.c_int32), ("max_passes", C.c_int32), ("threshold", C.c_float), ("flags", C.c_uint32),
                 ("reserved", C.c_uint32)]

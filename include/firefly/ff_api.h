@@ -1027,6 +1027,65 @@ FF_API int ff_despeckle(FfState* state, int width, int height, const FfDespeckle
 FF_API int ff_despeckle_host(int width, int height, const FfDespeckleParams* p, const float* radiance_in, const float* albedo,
                              const int32_t* ids, unsigned char* rgb8, float* radiance_out, uint32_t* out_clamped);
 
+/* ---- sharpening (contrast-adaptive, after the temporal resolve) ------------------------------------ */
+
+/* Defaults: strength 0.5, FF_SHARPEN_NOISE_AWARE. */
+FF_API void ff_sharpen_params_init(FfSharpenParams* p);
+
+/* Sharpens a W x H float3 radiance image: a 5-tap contrast-adaptive filter (the cross B above, D left, F right, H below the pixel
+ * E) whose negative lobe is limited per pixel so that the result stays within what the taps span - it cannot ring - and which is
+ * evaluated in the range-compressed domain c / (1 + max c), so that an HDR highlight throws no dark halo.  ff_taa resamples and
+ * blends its history, ff_taa_upscale spreads one low sample over several pixels and ff_denoise low-passes what its edge-stopping
+ * lets through: this call sits directly after ff_taa / ff_taa_upscale (after ff_denoise in a purely spatial pipeline) and BEFORE
+ * ff_motion_blur, ff_depth_of_field and ff_display (after AMD FidelityFX CAS and the limited "robust" sharpening of FSR, by
+ * T. Lottes).  A pure image operation like ff_display: no scene, no G-buffer, no history.  All arithmetic is float32, evaluated as
+ * written with the parentheses shown, no fused multiply-add, IEEE division; exp, pow and sqrt appear nowhere, so ff_sharpen,
+ * ff_sharpen_host and a float32 restatement agree bit for bit.  min(a, b) is b < a ? b : a and max(a, b) is a < b ? b : a, nested
+ * left to right in the order written.  LIMIT = 0.1875f, CAP = 0.99999988f (1 - 2^-23), MAXC = 8388608.0f (2^23).
+ *   1 compress   a pixel is USABLE when its three channels are finite and >= 0 (a -0 passes) and m = max(max(c_r, c_g), c_b) <=
+ *                MAXC.  For a usable pixel t_k = (c_k / (1.0f + m)) + 0.0f per channel: the + 0.0f turns -0 into +0, so no min or
+ *                max below ever chooses between zeros of different sign (and 1.0f + m is 1 whichever zero m is); m <= 2^23 keeps
+ *                1 + m exact and every t_k <= CAP.  L = (0.2126f * t_r + 0.7152f * t_g) + 0.0722f * t_b
+ *   2 taps       for E at (x, y): B = (x, y-1), D = (x-1, y), F = (x+1, y), H = (x, y+1); a tap outside the image is E itself.
+ *                If E or any tap inside the image is not usable, the output pixel is the input pixel bit for bit.  If all four
+ *                taps (after that substitution) have E's three t exactly, the output is the input bit for bit as well: a constant
+ *                neighbourhood, the 1 x 1 image.  It is the COMPRESSED values that are compared
+ *   3 lobe       per channel k, of the taps' t_k: mn = min(min(b, d), min(f, h)), mx = max(max(b, d), max(f, h)).  lobe_k = -LIMIT
+ *                where mx == 0 (a channel that is black all round limits nothing); otherwise
+ *                lobe_k = max(-(mn / (4.0f * mx)), (1.0f - mx) / ((4.0f * mn) - 4.0f)).  (mn <= mx <= CAP: the divisors are never
+ *                0, both terms are <= -0, and the second is below 0.)  Then
+ *                lobe = max(-LIMIT, min(max(max(lobe_r, lobe_g), lobe_b), 0.0f)) * strength.  A channel with mn = 0 < mx gives
+ *                lobe_k = -0 and, being the largest, lobe = -0: a tap that is black in a channel in which another is not leaves
+ *                no room below it, and step 5 copies the pixel through
+ *   4 noise      (only under FF_SHARPEN_NOISE_AWARE, on step 3's lobe, strength included)
+ *                n = (0.25f * (((L_B + L_D) + L_F) + L_H)) - L_E; range = max - min of the five L, each nested in the order E, B,
+ *                D, F, H.  Where range > 0: a = min(fabs(n) / range, 1.0f) and lobe = lobe * (1.0f - 0.5f * a).  A lone outlier
+ *                (a = 1) is sharpened half as much as an edge
+ *   5 apply      where lobe == 0 (of either sign), the output is the input bit for bit.  Otherwise per channel
+ *                o_k = ((lobe * (((b_k + d_k) + f_k) + h_k)) + e_k) / ((4.0f * lobe) + 1.0f)   (the divisor is >= 0.25), then
+ *                o_k = min(max(o_k, 0.0f), CAP), then M = max(max(o_r, o_g), o_b) and out_k = o_k / (1.0f - M).  (The quotient is
+ *                never -0: its dividend is a sum whose exact zero is +0, and dividing by at most 1 does not underflow.)
+ *   6 rgb8 = trunc(clamp(out * 255)), the rule of every rgb8 output here.
+ * Consequences.  strength 0 returns the input bit for bit, NaN, Inf and -0 included; so does a constant image, a 1 x 1 image and
+ * every pixel with an unusable pixel in its cross.  A sharpened pixel is finite and >= 0, and at most CAP * 2^23.  A non-finite or
+ * negative pixel (or one above MAXC) spoils itself and at most its four cross neighbours, all of which are copied through.
+ * rgb8 (W*H*3 bytes) and radiance_out (W*H*3 floats) may each be NULL.  Neither may overlap the input (the taps read neighbours;
+ * radiance_out == radiance_in is refused), and the two outputs may not overlap each other.  Width and height are 1 .. 65535.
+ * Synchronous, on the state's stream; host buffers are staged.  The call leaves FfStats, the stored primary hits and their key, every
+ * filter's history, the display exposure and the progressive and adaptive sums as they were; its own state is a work buffer
+ * (allocated on first use, regrown for a larger size, freed by ff_destroy).  FF_ERR_INVALID_ARG, naming the field, before any
+ * device work for: a NULL state, params or radiance_in; a bad size; a strength outside 0 .. 1 or not finite; unknown flags or a
+ * nonzero reserved; an output that overlaps the input or the other output.
+ * Not offered: the 3 x 3 (9-tap) form, sharpening inside ff_taa_upscale's kernel, a G-buffer-guided form, a multi-GPU twin. */
+FF_API int ff_sharpen(FfState* state, int width, int height, const FfSharpenParams* p,
+                      const float* radiance_in, int input_on_device,
+                      void* rgb8, int rgb8_on_device, float* radiance_out, int radiance_out_on_device);
+
+/* Host-only twin (no GPU, no state, host pointers), compiled from the same inline per-pixel functions the kernel uses: the same
+ * image arguments, the same checks, the same bits. */
+FF_API int ff_sharpen_host(int width, int height, const FfSharpenParams* p, const float* radiance_in,
+                           unsigned char* rgb8, float* radiance_out);
+
 /* ---- adaptive sampling (render until every tile's noise estimate is below a threshold) ------------- */
 
 /* Defaults: tile 64, min_passes 2, max_passes 64, threshold 0.0002 (the paper's value: a default for users, not a measured optimum

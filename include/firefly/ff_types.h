@@ -356,6 +356,15 @@ typedef struct FfDespeckleParams {
     uint32_t reserved;        /* 0 */
 } FfDespeckleParams;          /* 28 bytes; every float must be finite */
 
+/* ff_sharpen: contrast-adaptive sharpening after the temporal resolve.  ff_sharpen_params_init gives the defaults; the operator is
+ * in ff_api.h. */
+#define FF_SHARPEN_NOISE_AWARE 1      /* a lone outlier is sharpened half as much as an edge (step 4) */
+typedef struct FfSharpenParams {
+    float    strength;   /* 0 .. 1; finite */
+    uint32_t flags;      /* FF_SHARPEN_NOISE_AWARE */
+    uint32_t reserved;   /* 0 */
+} FfSharpenParams;       /* 12 bytes */
+
 /* ff_render_adaptive: render in passes until every tile's error estimate is below a threshold.  ff_adaptive_params_init gives the
  * defaults; the estimator and the driver are in ff_api.h. */
 #define FF_ADAPTIVE_GUARD_NEIGHBOURS 1     /* a tile stops only when its up to 8 neighbours are below the threshold too */
@@ -412,6 +421,7 @@ static_assert(sizeof(FfCameraSampling) == 16, "FfCameraSampling is 16 bytes");
 static_assert(sizeof(FfMotionBlurParams) == 24, "FfMotionBlurParams is 24 bytes");
 static_assert(sizeof(FfDofParams) == 32, "FfDofParams is 32 bytes");
 static_assert(sizeof(FfDespeckleParams) == 28, "FfDespeckleParams is 28 bytes");
+static_assert(sizeof(FfSharpenParams) == 12, "FfSharpenParams is 12 bytes");
 static_assert(sizeof(FfAdaptiveParams) == 24, "FfAdaptiveParams is 24 bytes");
 static_assert(sizeof(FfAdaptiveInfo) == 32, "FfAdaptiveInfo is 32 bytes");
 #else
@@ -426,6 +436,7 @@ _Static_assert(sizeof(FfCameraSampling) == 16, "FfCameraSampling layout");
 _Static_assert(sizeof(FfMotionBlurParams) == 24, "FfMotionBlurParams layout");
 _Static_assert(sizeof(FfDofParams) == 32, "FfDofParams layout");
 _Static_assert(sizeof(FfDespeckleParams) == 28, "FfDespeckleParams layout");
+_Static_assert(sizeof(FfSharpenParams) == 12, "FfSharpenParams layout");
 _Static_assert(sizeof(FfAdaptiveParams) == 24, "FfAdaptiveParams layout");
 _Static_assert(sizeof(FfAdaptiveInfo) == 32, "FfAdaptiveInfo layout");
 #endif
