@@ -77,6 +77,11 @@ inline int check_disjoint(const Span (&outs)[2], const Span (&ins)[3], const cha
     return FF_OK;
 }
 
+// What the reprojecting filters and ff_interpolate prepare on the host (ff_image_api.cpp): the inverse of a 4x4 matrix in double
+// (column-major in and out; false if singular), and inverse(ff_camera_ray_matrix(c)) rounded to float, with the ray matrix itself.
+bool invert4(const double* m, double* out);
+bool inverse_ray_matrix(const FfCamera* c, float* out16, FfMat4* ray);
+
 // What a filter that reprojects its last result (ff_denoise_temporal, ff_taa) remembers between calls: two history sets in
 // d_work that swap by index (`cur`: the one the last call wrote; the layout is the filter's own), and the camera, image size and
 // per-geometry model matrices (caller's order) of that call.  `replaced` marks the meshes ff_update_mesh changed since.

@@ -42,7 +42,7 @@ int Staging::finish()
 
 } // namespace ff
 
-namespace {
+namespace ff {
 
 // inverse of a 4x4 matrix in double (Gauss-Jordan with partial pivoting); column-major in and out.  False if singular.
 bool invert4(const double* m, double* out)
@@ -72,6 +72,10 @@ bool invert4(const double* m, double* out)
         for (int c = 0; c < 4; ++c) out[c * 4 + r] = a[r][4 + c];
     return true;
 }
+
+} // namespace ff
+
+namespace {
 
 // the model matrix of a record as 12 floats (columns, xyz)
 void record_model(const GeomRecord& g, float* out12)
@@ -112,6 +116,10 @@ TemporalGeom temporal_row(const float* prev12, const GeomRecord& g, int flags)
     return row;
 }
 
+} // namespace
+
+namespace ff {
+
 // inverse(ff_camera_ray_matrix(c)) in double, rounded to float; false if singular
 bool inverse_ray_matrix(const FfCamera* c, float* out16, FfMat4* ray)
 {
@@ -122,10 +130,6 @@ bool inverse_ray_matrix(const FfCamera* c, float* out16, FfMat4* ray)
     for (int k = 0; k < 16; ++k) out16[k] = (float)inv[k];
     return true;
 }
-
-} // namespace
-
-namespace ff {
 
 int ReprojectionHistory::begin(const std::vector<GeomRecord>& records, int w, int h, size_t work_bytes_needed, hipStream_t stream, Frame* out)
 {

@@ -45,6 +45,19 @@ FF_PIXEL_HD uint32_t pixel_hash(int x, int y)
 
 FF_PIXEL_HD float pixel_u24(uint32_t h) { return (float)(h >> 8) * 5.9604644775390625e-08f - 0.5f; } // 2^-24; [-0.5, 0.5)
 
+// P(M, X) of ff_api.h (ff_taa, ff_taa_upscale, ff_interpolate): q = inverse(M) (X, 1), P the inverse, column-major; false when
+// q.w <= 0 (or NaN)
+FF_PIXEL_HD bool taa_project(const float* P, float x, float y, float z, float sw, float sh, float& fx, float& fy)
+{
+    const float qx = (P[0] * x + P[4] * y) + (P[8] * z + P[12]);
+    const float qy = (P[1] * x + P[5] * y) + (P[9] * z + P[13]);
+    const float qw = (P[3] * x + P[7] * y) + (P[11] * z + P[15]);
+    if (!(qw > 0.f)) return false;
+    fx = (qx / qw + 1.f) * 0.5f * sw;
+    fy = (1.f - qy / qw) * 0.5f * sh;
+    return true;
+}
+
 // Pixel i's result v[3] into the outputs that are there.
 FF_PIXEL_HD void store_rgb(size_t i, const float* v, unsigned char* rgb8, float* radiance_out)
 {

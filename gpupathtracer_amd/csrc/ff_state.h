@@ -210,6 +210,10 @@ struct FfState {
     // sharpening (ff_sharpen): the staging of host buffers.  Not reset by uploads.
     void* d_sharpen_work = nullptr;
     size_t sharpen_work_bytes = 0;
+    // frame interpolation (ff_interpolate): the five counts, the {rgb, state} work image (one float4 per pixel), then the geometry
+    // table and the staging of host buffers.  Not reset by uploads.
+    void* d_interpolate_work = nullptr;
+    size_t interpolate_work_bytes = 0;
     // adaptive sampling (ff_render_adaptive, ff_adaptive_api.cpp): the two running sums (W*H*3 floats each) and behind them the
     // compact rectangle a pass renders into; per tile the error, the pass count and the list of tiles to check; the staging of host
     // buffers (ff_adaptive_tile_error's inputs, the per-pixel pass counts).  The last call's grid and per-tile results stay for
@@ -364,6 +368,8 @@ void dof_release(FfState* s);
 void despeckle_release(FfState* s);
 // Sharpening (ff_sharpen_api.cpp): frees the state's work buffer (ff_destroy).
 void sharpen_release(FfState* s);
+// Frame interpolation (ff_interpolate_api.cpp): frees the state's work buffer (ff_destroy).
+void interpolate_release(FfState* s);
 // Adaptive sampling (ff_adaptive_api.cpp): frees the state's buffers (ff_destroy).
 void adaptive_release(FfState* s);
 // The pixel buffer registered with ff_register_gl_pbo, mapped on the state's stream (kernel.cu:338-339) and unmapped again

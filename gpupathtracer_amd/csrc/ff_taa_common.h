@@ -12,17 +12,7 @@ namespace ff {
 
 constexpr float kTaaMaxLength = 4096.f;
 
-// P(M, X) of ff_api.h: q = inverse(M) (X, 1); false when q.w <= 0 (or NaN)
-__device__ __forceinline__ bool taa_project(const float* P, float x, float y, float z, float sw, float sh, float& fx, float& fy)
-{
-    const float qx = (P[0] * x + P[4] * y) + (P[8] * z + P[12]);
-    const float qy = (P[1] * x + P[5] * y) + (P[9] * z + P[13]);
-    const float qw = (P[3] * x + P[7] * y) + (P[11] * z + P[15]);
-    if (!(qw > 0.f)) return false;
-    fx = (qx / qw + 1.f) * 0.5f * sw;
-    fy = (1.f - qy / qw) * 0.5f * sh;
-    return true;
-}
+// P(M, X) of ff_api.h is taa_project in ff_pixel.h (host and device: ff_interpolate.h projects with the same body).
 
 // Catmull-Rom weights of taps -1 .. 2 for fraction t (not renormalised; they sum to 1 up to rounding)
 __device__ __forceinline__ void taa_catmull_rom(float t, float* w)

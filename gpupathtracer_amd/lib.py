@@ -44,6 +44,7 @@ EXPORTS = [
     "ff_dof_params_init", "ff_dof_params_from_camera", "ff_depth_of_field", "ff_depth_of_field_host",
     "ff_despeckle_params_init", "ff_despeckle", "ff_despeckle_host",
     "ff_sharpen_params_init", "ff_sharpen", "ff_sharpen_host",
+    "ff_interpolate_params_init", "ff_interpolate", "ff_interpolate_host", "ff_interpolate_geometry_maps",
     "ff_adaptive_params_init", "ff_render_adaptive", "ff_adaptive_state", "ff_adaptive_tile_error", "ff_adaptive_tile_error_host", "ff_adaptive_plan_host",
 ]
 DIST_ID_BYTES = 128
@@ -245,6 +246,13 @@ def load():
     lib.ff_sharpen_params_init.restype = None
     lib.ff_sharpen.argtypes = [vp, i32, i32, P(T.FfSharpenParams), vp, i32, vp, i32, vp, i32]
     lib.ff_sharpen_host.argtypes = [i32, i32, P(T.FfSharpenParams), vp, vp, vp]
+    lib.ff_interpolate_params_init.argtypes = [P(T.FfInterpolateParams)]
+    lib.ff_interpolate_params_init.restype = None
+    cam = P(T.FfCamera)
+    lib.ff_interpolate.argtypes = [vp, i32, i32, P(T.FfInterpolateParams), cam, vp, vp, cam, vp, vp, vp, cam, vp, vp, vp, vp, i32, i32,
+                                   vp, i32, vp, i32, vp]
+    lib.ff_interpolate_host.argtypes = [i32, i32, P(T.FfInterpolateParams), cam, vp, vp, cam, vp, vp, vp, cam, vp, vp, vp, vp, i32, vp, vp, vp]
+    lib.ff_interpolate_geometry_maps.argtypes = [P(T.FfGeometry), P(T.FfGeometry), P(T.FfGeometry), i32, vp, vp]
     lib.ff_adaptive_params_init.argtypes = [P(T.FfAdaptiveParams)]
     lib.ff_adaptive_params_init.restype = None
     lib.ff_render_adaptive.argtypes = [vp, P(T.FfCamera), P(T.FfRenderParams), P(T.FfAdaptiveParams), vp, i32, vp, i32, vp, i32, P(T.FfAdaptiveInfo)]
@@ -784,6 +792,90 @@ def sharpen_host(radiance, p=None, want_rgb8=True, want_out=True):
     out = np.zeros((h, w, 3), dtype=np.float32) if want_out else None
     check(load().ff_sharpen_host(w, h, C.byref(p), rad.ctypes.data, rgb8.ctypes.data if want_rgb8 else None, out.ctypes.data if want_out else None))
     return rgb8, out
+
+
+def interpolate_params(**overrides):
+    """ff_interpolate_params_init's defaults with the given fields replaced (any FfInterpolateParams field)."""
+    p = T.FfInterpolateParams()
+    load().ff_interpolate_params_init(C.byref(p))
+    for name, value in overrides.items():
+        if name not in dict(T.FfInterpolateParams._fields_):
+            raise TypeError(f"FfInterpolateParams has no field {name!r}")
+        setattr(p, name, value)
+    return p
+
+
+def _interpolate_planes(gbuffer_or_planes):
+    """(position, ids) of a gbuffer() dict or of the pair itself."""
+    if isinstance(gbuffer_or_planes, dict):
+        return gbuffer_or_planes["position"], gbuffer_or_planes["ids"]
+    return gbuffer_or_planes
+
+
+def _interpolate_images(mid, a, b, who):
+    """The inputs of ff_interpolate: mid = (camera, gbuffer), a and b = (camera, radiance, gbuffer), a gbuffer being a gbuffer() dict
+    or the pair (position, ids) -> the three cameras, the eight images as contiguous host arrays in the C call's order, and (h, w)."""
+    cams = (mid[0], a[0], b[0])
+    pos, ids = _interpolate_planes(mid[1])
+    images = [np.ascontiguousarray(pos, dtype=np.float32), np.ascontiguousarray(ids, dtype=np.int32)]
+    for src in (a, b):
+        pos, ids = _interpolate_planes(src[2])
+        images += [np.ascontiguousarray(src[1], dtype=np.float32), np.ascontiguousarray(pos, dtype=np.float32), np.ascontiguousarray(ids, dtype=np.int32)]
+    shape = images[0].shape
+    if len(shape) != 3 or shape[2] != 3 or any(im.shape != shape for im in images):
+        raise ValueError(f"{who}: every image must be [H,W,3] and of one size")
+    return cams, images, shape[:2]
+
+
+def _interpolate_maps(geom_maps, who):
+    """geom_maps as a contiguous float32 [n,2,3,4] array (None stays None) and n."""
+    if geom_maps is None:
+        return None, 0
+    maps = np.ascontiguousarray(geom_maps, dtype=np.float32)
+    if maps.ndim != 4 or maps.shape[1:] != (2, 3, 4):
+        raise ValueError(f"{who}: geom_maps must be [n,2,3,4]")
+    return maps, maps.shape[0]
+
+
+def interpolate_host(mid, a, b, p=None, geom_maps=None, want_rgb8=True, want_out=True):
+    """ff_interpolate_host (no GPU): mid = (camera, gbuffer), a and b = (camera, radiance [H,W,3], gbuffer), a gbuffer being a gbuffer()
+    dict or the pair (position, ids); geom_maps [n,2,3,4] or None
+    -> (rgb8 [H,W,3] uint8, radiance [H,W,3] float32, counts [5] uint32: both, A only, B only, filled, fallback)."""
+    cams, im, (h, w) = _interpolate_images(mid, a, b, "interpolate_host")
+    maps, n = _interpolate_maps(geom_maps, "interpolate_host")
+    p = p if p is not None else interpolate_params()
+    rgb8 = np.zeros((h, w, 3), dtype=np.uint8) if want_rgb8 else None
+    out = np.zeros((h, w, 3), dtype=np.float32) if want_out else None
+    counts = np.zeros(5, dtype=np.uint32)
+    d = [x.ctypes.data for x in im]
+    check(load().ff_interpolate_host(w, h, C.byref(p), C.byref(cams[0]), d[0], d[1], C.byref(cams[1]), d[2], d[3], d[4], C.byref(cams[2]), d[5], d[6], d[7],
+                                     maps.ctypes.data if maps is not None else None, n, rgb8.ctypes.data if want_rgb8 else None,
+                                     out.ctypes.data if want_out else None, counts.ctypes.data))
+    return rgb8, out, counts
+
+
+def interpolate_geometry_maps(mid, a, b):
+    """ff_interpolate_geometry_maps (no GPU): the model matrices of a scene's n geometries at the three poses - each either a ctypes
+    array of FfGeometry or an [n,16] array of column-major matrices (FfGeometry.m_modelMatrix) -> (geom_maps [n,2,3,4] float32,
+    identity flags [n,2] int32)."""
+    def geometries(x):
+        if isinstance(x, C.Array) and x._type_ is T.FfGeometry:
+            return x
+        m = np.ascontiguousarray(x, dtype=np.float32)
+        if m.ndim != 2 or m.shape[1] != 16:
+            raise ValueError("interpolate_geometry_maps: model matrices must be [n,16]")
+        g = (T.FfGeometry * max(m.shape[0], 1))()
+        for i in range(m.shape[0]):
+            g[i].m_modelMatrix.m[:] = [float(v) for v in m[i]]
+        return g if m.shape[0] else None
+    gm, ga, gb = geometries(mid), geometries(a), geometries(b)
+    n = len(gm) if gm is not None else 0
+    if any(len(x) != n for x in (ga, gb) if x is not None):
+        raise ValueError("interpolate_geometry_maps: the three poses must have as many geometries")
+    maps = np.zeros((max(n, 1), 2, 3, 4), dtype=np.float32)
+    flags = np.zeros((max(n, 1), 2), dtype=np.int32)
+    check(load().ff_interpolate_geometry_maps(gm, ga, gb, n, maps.ctypes.data, flags.ctypes.data))
+    return maps[:n], flags[:n]
 
 
 def adaptive_params(**overrides):
@@ -1385,6 +1477,38 @@ class Tracer:
         p = p if p is not None else sharpen_params()
         vp = lambda q: C.c_void_p(q) if q else None  # noqa: E731
         check(self._lib.ff_sharpen(self._state, width, height, C.byref(p), vp(radiance_ptr), 1, vp(rgb8_ptr), 1, vp(radiance_out_ptr), 1))
+
+    def interpolate(self, mid, a, b, p=None, geom_maps=None, want_rgb8=True, want_out=True):
+        """ff_interpolate of host arrays: mid = (camera, gbuffer), a and b = (camera, radiance [H,W,3], gbuffer), a gbuffer being a
+        gbuffer() dict or the pair (position, ids); geom_maps [n,2,3,4] or None
+        -> (rgb8 [H,W,3] uint8, radiance [H,W,3] float32, counts [5] uint32: both, A only, B only, filled, fallback)."""
+        cams, im, (h, w) = _interpolate_images(mid, a, b, "interpolate")
+        maps, n = _interpolate_maps(geom_maps, "interpolate")
+        p = p if p is not None else interpolate_params()
+        rgb8 = np.zeros((h, w, 3), dtype=np.uint8) if want_rgb8 else None
+        out = np.zeros((h, w, 3), dtype=np.float32) if want_out else None
+        counts = np.zeros(5, dtype=np.uint32)
+        d = [x.ctypes.data for x in im]
+        check(self._lib.ff_interpolate(self._state, w, h, C.byref(p), C.byref(cams[0]), d[0], d[1], C.byref(cams[1]), d[2], d[3], d[4], C.byref(cams[2]),
+                                       d[5], d[6], d[7], maps.ctypes.data if maps is not None else None, n, 0, rgb8.ctypes.data if want_rgb8 else None, 0,
+                                       out.ctypes.data if want_out else None, 0, counts.ctypes.data))
+        return rgb8, out, counts
+
+    def interpolate_device(self, width, height, cameras, image_ptrs, p=None, geom_maps=None, rgb8_ptr=None, radiance_out_ptr=None, want_counts=True):
+        """ff_interpolate on DEVICE buffers (raw pointers): cameras = (mid, a, b); image_ptrs = the eight images in the C call's order
+        (position, ids, radiance_a, position_a, ids_a, radiance_b, position_b, ids_b); geom_maps a HOST [n,2,3,4] array or None; the
+        outputs must not overlap an input -> counts [5] uint32 (None without want_counts)."""
+        maps, n = _interpolate_maps(geom_maps, "interpolate_device")
+        p = p if p is not None else interpolate_params()
+        vp = lambda q: C.c_void_p(q) if q else None  # noqa: E731
+        d = [vp(q) for q in image_ptrs]
+        if len(d) != 8:
+            raise ValueError("interpolate_device: image_ptrs must name eight images")
+        counts = np.zeros(5, dtype=np.uint32)
+        check(self._lib.ff_interpolate(self._state, width, height, C.byref(p), C.byref(cameras[0]), d[0], d[1], C.byref(cameras[1]), d[2], d[3], d[4],
+                                       C.byref(cameras[2]), d[5], d[6], d[7], maps.ctypes.data if maps is not None else None, n, 1, vp(rgb8_ptr), 1,
+                                       vp(radiance_out_ptr), 1, counts.ctypes.data if want_counts else None))
+        return counts if want_counts else None
 
     def display(self, radiance, p=None, want_rgb8=True, want_out=True):
         """ff_display of host radiance [H,W,3] -> (rgb8 [H,W,3] uint8, display_out [H,W,3] float32: the curve's output in [0, 1]);

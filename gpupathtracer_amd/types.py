@@ -211,6 +211,15 @@ SHARPEN_PARAMS_BYTES = 12
 SHARPEN_NOISE_AWARE = 1
 
 
+class FfInterpolateParams(C.Structure):
+    _fields_ = [("t", C.c_float), ("surface_tolerance", C.c_float), ("fill_radius", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+INTERPOLATE_PARAMS_BYTES = 20
+INTERPOLATE_MAX_FILL_RADIUS = 8
+INTERPOLATE_COUNTS = ("both", "a_only", "b_only", "filled", "fallback")
+
+
 class FfAdaptiveParams(C.Structure):
     _fields_ = [("tile", C.c_int32), ("min_passes", C.c_int32), ("max_passes", C.c_int32), ("threshold", C.c_float), ("flags", C.c_uint32),
                 ("reserved", C.c_uint32)]

@@ -1086,6 +1086,95 @@ FF_API int ff_sharpen(FfState* state, int width, int height, const FfSharpenPara
 FF_API int ff_sharpen_host(int width, int height, const FfSharpenParams* p, const float* radiance_in,
                            unsigned char* rgb8, float* radiance_out);
 
+/* ---- frame interpolation (an in-between frame from two rendered neighbours) ----------------------- */
+
+/* Defaults: t 0.5, surface_tolerance 4 pixels, fill_radius 4, no flags. */
+FF_API void ff_interpolate_params_init(FfInterpolateParams* p);
+
+/* Makes the W x H frame of a pose between two rendered frames A and B: frames traced for frames shown, beside ff_upscale (pixels
+ * traced for pixels shown) and the temporal filters (samples for history).  ff_gbuffer gives the exact first hit of ANY pose for a
+ * fraction of a frame's cost, so the in-between ("mid") frame does not guess its geometry from motion vectors: each of its pixels
+ * knows its surface point, projects it through the camera of A and of B, and fetches its colour there - a backward gather, no
+ * scatter.  A pure image operation like ff_upscale: no scene is read and none is needed, no history is kept.  All images are W x H,
+ * row-major, top row first.  position and ids are ff_gbuffer's at camera_mid; radiance_S (at any stage of the pipeline),
+ * position_S and ids_S belong to the source S in {A, B} rendered at camera_S.  geom_maps (a HOST pointer, or NULL for a static
+ * scene) holds per geometry g and source S, at geom_maps + 12 (2 g + S), the row-major 3 x 4 affine map a_S,g that carries a
+ * world point of g at the mid pose to its place at S's pose (ff_interpolate_geometry_maps builds them); a map whose 12 floats are
+ * bitwise those of the identity (1 0 0 0, 0 1 0 0, 0 0 1 0) IS an identity: x^ = x exactly, nothing is multiplied.  All arithmetic
+ * is float32, evaluated as written with the parentheses shown, no fused multiply-add, IEEE division, floor and comparisons; exp and
+ * sqrt appear nowhere (distances are compared as squares), so ff_interpolate, ff_interpolate_host and a float32 restatement agree
+ * bit for bit.  P(M, X) is ff_taa's projection with that camera's m_screenWidth / m_screenHeight; M_mid, M_S: the UNJITTERED
+ * ff_camera_ray_matrix of each camera, inverted in double on the host (Gauss-Jordan elimination with partial pivoting) and rounded.  Per pixel p = (x, y) with x_p = position[p],
+ * g = ids[3p] (-1: a miss) and k = ids[3p + 2] (the bxdf type):
+ *   1 lookup     per source S.  A hit with maps given and g >= num_geometries: the lookup fails (ff_taa's "not known").  A hit:
+ *                x^ = x_p under an identity (or without maps), otherwise per row r
+ *                x^_r = (a_r.x * x_p.x + a_r.y * x_p.y) + (a_r.z * x_p.z + a_r.w).  If camera_S is bitwise camera_mid and the map is
+ *                an identity (a miss: the camera alone), h_S = (x, y) exactly and nothing is projected.  Otherwise
+ *                h_S = (x, y) + (P(M_S, X) - base), per axis (float)x + (f - base):  a hit has X = x^ and base = P(M_mid, x_p), which
+ *                cancels a pixel jitter in the mid G-buffer as ff_taa's motion does; a miss has X = the kernel.cu:203 far point of
+ *                the pixel's unjittered ray under M_mid (ff_taa's) and base = (x, y).  The lookup fails when either projection has
+ *                q.w <= 0 (or NaN) or unless 0 <= h_S.x <= W - 1 and 0 <= h_S.y <= H - 1
+ *   2 taps       i0 = floor(h_S.x), tx = h_S.x - i0; j0, ty likewise.  The taps are (i0 + {0, 1}, j0 + {0, 1}), row by row, each
+ *                coordinate clamped into the image, b_q = (1 - tx | tx) * (1 - ty | ty).  A tap counts when b_q > 0; ids_S there has
+ *                p's geometry index and bxdf type (a miss matches a miss); radiance_S there is finite in all three channels; and, for
+ *                a hit, it shows the same surface point: with d = position_S[q] - x^ and e = x^ - camera_S.m_position,
+ *                (d.x*d.x + d.y*d.y) + d.z*d.z <= (tol * tol) * (((e.x*e.x + e.y*e.y) + e.z*e.z) * (pix_S * pix_S)),  tol =
+ *                surface_tolerance, pix_S = 2 tan(m_fov / 2) / m_screenHeight of camera_S (the world size of a pixel at unit distance;
+ *                double on the host, rounded to float).  A NaN on either side does not count.  c_S = ff_upscale's "mean" over the
+ *                counting taps with w_q = b_q: c_0 + (sum w (c_q - c_0)) / sum w, c_0 the first of them, and c_0 itself for a single
+ *                tap - one tap, or a colour all taps share, comes back bit for bit.  S is VALID when a tap counts
+ *   3 combine    both valid: o = blend(c_A, c_B) per channel, where blend(a, b) = a if t == 0 or a == b, b if t == 1, and
+ *                (1.0f - t) * a + t * b otherwise.  (The two exceptions close what the formula leaves open: at t = 0 it would turn
+ *                a -0 of c_A into +0 and an overflowed c_B into NaN, and a colour both sources share would come back rounded.)
+ *                One valid: that source's c, bit for bit.  Neither: p is a HOLE
+ *   4 fill       (a second pass over step 3's output and validity)  a hole takes the mean, in the same form, over the pixels
+ *                q = (x + dx, y + dy), dy = -r .. r outer, dx = -r .. r inner, r = fill_radius, that lie in the image, are no holes
+ *                and whose ids geometry index and bxdf type in the MID G-buffer equal p's, with w = 1.0f / (float)(dx*dx + dy*dy):
+ *                o_0 + (sum w (o_q - o_0)) / sum w.  This is sum w o_q / sum w; such a pixel counts as "filled".  Without such a
+ *                pixel (always for fill_radius 0): o = blend(radiance_A[p], radiance_B[p]), the screen-space blend, counted as
+ *                "fallback"; a non-finite blend is written as it is - the rule of the other filters, its own pixel only
+ *   5 rgb8 = trunc(clamp(o * 255)), the rule of every rgb8 output here.
+ * counts (a HOST pointer to five uint32, may be NULL) receives the number of pixels resolved as {both, A only, B only, filled,
+ * fallback}; they sum to W * H.
+ * Consequences.  Three bitwise-equal cameras, no maps (or identities), the three G-buffers equal and A == B finite return A bit
+ * for bit (every pixel is its own single tap, and blend(a, a) = a).  t = 0 returns c_A wherever A is valid - bit for bit, a -0
+ * included - and t = 1 returns c_B wherever B is valid.  A constant finite colour in A and B returns that colour everywhere: the
+ * mean of equal colours and blend(a, a) are exact, in steps 2, 3 and 4 alike.  A non-finite source pixel never counts as a tap, so it
+ * reaches the output through step 4's fallback only; every other output pixel is finite as long as the means do not overflow.
+ * rgb8 (W*H*3 bytes) and radiance_out (W*H*3 floats) may each be NULL and must not overlap an input or each other.
+ * inputs_on_device covers the eight input images.  Host buffers are staged through the state's image staging buffer; the call keeps
+ * nothing else in the state and leaves FfStats, the stored primary hits and their key, every filter's history, the display
+ * exposure and the progressive and adaptive sums as they were; its own state is a work buffer (allocated on first use, regrown for
+ * a larger size, freed by ff_destroy).  Synchronous, on the state's stream.  FF_ERR_INVALID_ARG, naming the field, before any
+ * device work for: a NULL state, params, camera, position, ids or radiance; a width or height outside 1 .. 65535; t outside
+ * [0, 1] or NaN; a surface_tolerance that is not positive and finite; fill_radius outside 0 .. 8; nonzero flags or reserved;
+ * geom_maps given with num_geometries <= 0; an output that overlaps an input or the other output; a camera whose ray matrix is
+ * singular.
+ * Not offered: view-dependent re-shading (mirrors, glass and glossy highlights are fetched at their surface point, so a reflection
+ * lags), sources of a different size, extrapolation beyond [0, 1], a multi-GPU twin. */
+FF_API int ff_interpolate(FfState* state, int width, int height, const FfInterpolateParams* p,
+                          const FfCamera* camera_mid, const float* position, const int32_t* ids,
+                          const FfCamera* camera_a, const float* radiance_a, const float* position_a, const int32_t* ids_a,
+                          const FfCamera* camera_b, const float* radiance_b, const float* position_b, const int32_t* ids_b,
+                          const float* geom_maps, int num_geometries, int inputs_on_device,
+                          void* rgb8, int rgb8_on_device, float* radiance_out, int radiance_out_on_device, uint32_t* counts);
+
+/* Host-only twin (no GPU, no state, host pointers), compiled from the same inline per-pixel functions the kernels use: the same
+ * image arguments, the same checks, the same bits and the same counts. */
+FF_API int ff_interpolate_host(int width, int height, const FfInterpolateParams* p,
+                               const FfCamera* camera_mid, const float* position, const int32_t* ids,
+                               const FfCamera* camera_a, const float* radiance_a, const float* position_a, const int32_t* ids_a,
+                               const FfCamera* camera_b, const float* radiance_b, const float* position_b, const int32_t* ids_b,
+                               const float* geom_maps, int num_geometries,
+                               unsigned char* rgb8, float* radiance_out, uint32_t* counts);
+
+/* The geom_maps of ff_interpolate from the n geometries of a scene at the three poses (only m_modelMatrix is read): out receives
+ * n * 2 * 12 floats, a_S,g = M_S,g inverse(M_mid,g) composed in double and rounded (S = 0: a, 1: b).  A geometry whose model matrix
+ * at S is bitwise the one at mid gets the exact identity, which ff_interpolate applies as x^ = x; out_identity_flags (n * 2 int32,
+ * may be NULL) says which.  FF_ERR_INVALID_ARG for a NULL array, n <= 0 or a singular model matrix at mid.  No GPU, no state. */
+FF_API int ff_interpolate_geometry_maps(const FfGeometry* mid, const FfGeometry* a, const FfGeometry* b, int n, float* out,
+                                        int32_t* out_identity_flags);
+
 /* ---- adaptive sampling (render until every tile's noise estimate is below a threshold) ------------- */
 
 /* Defaults: tile 64, min_passes 2, max_passes 64, threshold 0.0002 (the paper's value: a default for users, not a measured optimum

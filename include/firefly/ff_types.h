@@ -365,6 +365,16 @@ typedef struct FfSharpenParams {
     uint32_t reserved;   /* 0 */
 } FfSharpenParams;       /* 12 bytes */
 
+/* ff_interpolate: an in-between frame from two rendered neighbours, gathered through the in-between pose's own G-buffer.
+ * ff_interpolate_params_init gives the defaults; the operator is in ff_api.h. */
+typedef struct FfInterpolateParams {
+    float   t;                  /* the in-between frame's place between A (0) and B (1); 0 .. 1 */
+    float   surface_tolerance;  /* how far, in pixels of the source, a tap's surface point may lie from the pixel's; > 0, finite */
+    int32_t fill_radius;        /* r: a hole is filled from its (2r+1)^2 window; 0 .. 8, 0 = no fill */
+    int32_t flags;              /* none defined yet: 0 */
+    int32_t reserved;           /* 0 */
+} FfInterpolateParams;          /* 20 bytes */
+
 /* ff_render_adaptive: render in passes until every tile's error estimate is below a threshold.  ff_adaptive_params_init gives the
  * defaults; the estimator and the driver are in ff_api.h. */
 #define FF_ADAPTIVE_GUARD_NEIGHBOURS 1     /* a tile stops only when its up to 8 neighbours are below the threshold too */
@@ -422,6 +432,7 @@ static_assert(sizeof(FfMotionBlurParams) == 24, "FfMotionBlurParams is 24 bytes"
 static_assert(sizeof(FfDofParams) == 32, "FfDofParams is 32 bytes");
 static_assert(sizeof(FfDespeckleParams) == 28, "FfDespeckleParams is 28 bytes");
 static_assert(sizeof(FfSharpenParams) == 12, "FfSharpenParams is 12 bytes");
+static_assert(sizeof(FfInterpolateParams) == 20, "FfInterpolateParams is 20 bytes");
 static_assert(sizeof(FfAdaptiveParams) == 24, "FfAdaptiveParams is 24 bytes");
 static_assert(sizeof(FfAdaptiveInfo) == 32, "FfAdaptiveInfo is 32 bytes");
 #else
@@ -437,6 +448,7 @@ _Static_assert(sizeof(FfMotionBlurParams) == 24, "FfMotionBlurParams layout");
 _Static_assert(sizeof(FfDofParams) == 32, "FfDofParams layout");
 _Static_assert(sizeof(FfDespeckleParams) == 28, "FfDespeckleParams layout");
 _Static_assert(sizeof(FfSharpenParams) == 12, "FfSharpenParams layout");
+_Static_assert(sizeof(FfInterpolateParams) == 20, "FfInterpolateParams layout");
 _Static_assert(sizeof(FfAdaptiveParams) == 24, "FfAdaptiveParams layout");
 _Static_assert(sizeof(FfAdaptiveInfo) == 32, "FfAdaptiveInfo layout");
 #endif
