@@ -456,6 +456,7 @@ int ff_destroy(FfState* s)
     dof_release(s);
     despeckle_release(s);
     sharpen_release(s);
+    local_tonemap_release(s);
     interpolate_release(s);
     adaptive_release(s);
     free_build_scratch(s->scratch);

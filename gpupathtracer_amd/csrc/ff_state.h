@@ -210,6 +210,10 @@ struct FfState {
     // sharpening (ff_sharpen): the staging of host buffers.  Not reset by uploads.
     void* d_sharpen_work = nullptr;
     size_t sharpen_work_bytes = 0;
+    // local tone mapping (ff_local_tonemap): the two bilateral grids (ceil(W/s) x ceil(H/s) x 40 cells of 8 bytes each; none for a
+    // call that only copies), then, from a multiple of 16 bytes on, the staging of host buffers.  Not reset by uploads.
+    void* d_ltm_work = nullptr;
+    size_t ltm_work_bytes = 0;
     // frame interpolation (ff_interpolate): the five counts, the {rgb, state} work image (one float4 per pixel), then the geometry
     // table and the staging of host buffers.  Not reset by uploads.
     void* d_interpolate_work = nullptr;
@@ -368,6 +372,8 @@ void dof_release(FfState* s);
 void despeckle_release(FfState* s);
 // Sharpening (ff_sharpen_api.cpp): frees the state's work buffer (ff_destroy).
 void sharpen_release(FfState* s);
+// Local tone mapping (ff_local_tonemap_api.cpp): frees the state's work buffer (ff_destroy).
+void local_tonemap_release(FfState* s);
 // Frame interpolation (ff_interpolate_api.cpp): frees the state's work buffer (ff_destroy).
 void interpolate_release(FfState* s);
 // Adaptive sampling (ff_adaptive_api.cpp): frees the state's buffers (ff_destroy).

@@ -44,6 +44,7 @@ EXPORTS = [
     "ff_dof_params_init", "ff_dof_params_from_camera", "ff_depth_of_field", "ff_depth_of_field_host",
     "ff_despeckle_params_init", "ff_despeckle", "ff_despeckle_host",
     "ff_sharpen_params_init", "ff_sharpen", "ff_sharpen_host",
+    "ff_local_tonemap_params_init", "ff_local_tonemap", "ff_local_tonemap_host", "ff_local_tonemap_grid_host",
     "ff_interpolate_params_init", "ff_interpolate", "ff_interpolate_host", "ff_interpolate_geometry_maps",
     "ff_adaptive_params_init", "ff_render_adaptive", "ff_adaptive_state", "ff_adaptive_tile_error", "ff_adaptive_tile_error_host", "ff_adaptive_plan_host",
 ]
@@ -246,6 +247,11 @@ def load():
     lib.ff_sharpen_params_init.restype = None
     lib.ff_sharpen.argtypes = [vp, i32, i32, P(T.FfSharpenParams), vp, i32, vp, i32, vp, i32]
     lib.ff_sharpen_host.argtypes = [i32, i32, P(T.FfSharpenParams), vp, vp, vp]
+    lib.ff_local_tonemap_params_init.argtypes = [P(T.FfLocalTonemapParams)]
+    lib.ff_local_tonemap_params_init.restype = None
+    lib.ff_local_tonemap.argtypes = [vp, i32, i32, P(T.FfLocalTonemapParams), vp, i32, vp, i32, vp, i32]
+    lib.ff_local_tonemap_host.argtypes = [i32, i32, P(T.FfLocalTonemapParams), vp, vp, vp]
+    lib.ff_local_tonemap_grid_host.argtypes = [i32, i32, P(T.FfLocalTonemapParams), vp, vp, vp]
     lib.ff_interpolate_params_init.argtypes = [P(T.FfInterpolateParams)]
     lib.ff_interpolate_params_init.restype = None
     cam = P(T.FfCamera)
@@ -792,6 +798,42 @@ def sharpen_host(radiance, p=None, want_rgb8=True, want_out=True):
     out = np.zeros((h, w, 3), dtype=np.float32) if want_out else None
     check(load().ff_sharpen_host(w, h, C.byref(p), rad.ctypes.data, rgb8.ctypes.data if want_rgb8 else None, out.ctypes.data if want_out else None))
     return rgb8, out
+
+
+def local_tonemap_params(**overrides):
+    """ff_local_tonemap_params_init's defaults with the given fields replaced (any FfLocalTonemapParams field but reserved)."""
+    p = T.FfLocalTonemapParams()
+    load().ff_local_tonemap_params_init(C.byref(p))
+    for name, value in overrides.items():
+        if name not in dict(T.FfLocalTonemapParams._fields_) or name == "reserved":
+            raise TypeError(f"FfLocalTonemapParams has no settable field {name!r}")
+        setattr(p, name, value)
+    return p
+
+
+def local_tonemap_host(radiance, p=None, want_rgb8=True, want_out=True, in_place=False):
+    """ff_local_tonemap_host (no GPU): host radiance [H,W,3] -> (rgb8 [H,W,3] uint8, radiance [H,W,3] float32).  in_place: the
+    radiance output is written over a copy of the input (radiance_out == radiance_in in the call)."""
+    rad, (h, w) = _sharpen_image(radiance, "local_tonemap_host")
+    p = p if p is not None else local_tonemap_params()
+    rgb8 = np.zeros((h, w, 3), dtype=np.uint8) if want_rgb8 else None
+    out = (rad.copy() if in_place else np.zeros((h, w, 3), dtype=np.float32)) if want_out else None
+    src = out if (in_place and want_out) else rad
+    check(load().ff_local_tonemap_host(w, h, C.byref(p), src.ctypes.data, rgb8.ctypes.data if want_rgb8 else None,
+                                       out.ctypes.data if want_out else None))
+    return rgb8, out
+
+
+def local_tonemap_grid_host(radiance, p=None):
+    """ff_local_tonemap_grid_host (no GPU): step 2's grid of host radiance [H,W,3] -> (n, S), each [gh, gw, 40] int32."""
+    rad, (h, w) = _sharpen_image(radiance, "local_tonemap_grid_host")
+    p = p if p is not None else local_tonemap_params()
+    s = int(p.cell) if int(p.cell) > 0 else 1
+    shape = ((h + s - 1) // s, (w + s - 1) // s, T.LOCAL_TONEMAP_BINS)
+    n = np.zeros(shape, dtype=np.int32)
+    S = np.zeros(shape, dtype=np.int32)
+    check(load().ff_local_tonemap_grid_host(w, h, C.byref(p), rad.ctypes.data, n.ctypes.data, S.ctypes.data))
+    return n, S
 
 
 def interpolate_params(**overrides):
@@ -1477,6 +1519,35 @@ class Tracer:
         p = p if p is not None else sharpen_params()
         vp = lambda q: C.c_void_p(q) if q else None  # noqa: E731
         check(self._lib.ff_sharpen(self._state, width, height, C.byref(p), vp(radiance_ptr), 1, vp(rgb8_ptr), 1, vp(radiance_out_ptr), 1))
+
+    def local_tonemap(self, radiance, p=None, want_rgb8=True, want_out=True, in_place=False):
+        """ff_local_tonemap of radiance [H,W,3] -> (rgb8 [H,W,3] uint8, radiance [H,W,3] float32).  A host array gives host arrays; a
+        contiguous float32 device tensor (torch) gives device tensors.  in_place: radiance_out is radiance_in in the call (a device
+        tensor is overwritten and returned; a host array is copied first)."""
+        p = p if p is not None else local_tonemap_params()
+        if hasattr(radiance, "data_ptr"):
+            import torch
+            h, w = radiance.shape[:2]
+            if not radiance.is_cuda or radiance.dtype != torch.float32 or tuple(radiance.shape) != (h, w, 3) or not radiance.is_contiguous():
+                raise ValueError("local_tonemap: radiance must be a contiguous [H,W,3] float32 tensor on the device")
+            rgb8 = torch.zeros((h, w, 3), dtype=torch.uint8, device=radiance.device) if want_rgb8 else None
+            out = (radiance if in_place else torch.zeros((h, w, 3), dtype=torch.float32, device=radiance.device)) if want_out else None
+            torch.cuda.synchronize(radiance.device)
+            self.local_tonemap_device(w, h, radiance.data_ptr(), p, rgb8.data_ptr() if want_rgb8 else None, out.data_ptr() if want_out else None)
+            return rgb8, out
+        rad, (h, w) = _sharpen_image(radiance, "local_tonemap")
+        rgb8 = np.zeros((h, w, 3), dtype=np.uint8) if want_rgb8 else None
+        out = (rad.copy() if in_place else np.zeros((h, w, 3), dtype=np.float32)) if want_out else None
+        src = out if (in_place and want_out) else rad
+        check(self._lib.ff_local_tonemap(self._state, w, h, C.byref(p), src.ctypes.data, 0, rgb8.ctypes.data if want_rgb8 else None, 0,
+                                         out.ctypes.data if want_out else None, 0))
+        return rgb8, out
+
+    def local_tonemap_device(self, width, height, radiance_ptr, p=None, rgb8_ptr=None, radiance_out_ptr=None):
+        """ff_local_tonemap on DEVICE buffers (raw pointers); radiance_out_ptr may be radiance_ptr."""
+        p = p if p is not None else local_tonemap_params()
+        vp = lambda q: C.c_void_p(q) if q else None  # noqa: E731
+        check(self._lib.ff_local_tonemap(self._state, width, height, C.byref(p), vp(radiance_ptr), 1, vp(rgb8_ptr), 1, vp(radiance_out_ptr), 1))
 
     def interpolate(self, mid, a, b, p=None, geom_maps=None, want_rgb8=True, want_out=True):
         """ff_interpolate of host arrays: mid = (camera, gbuffer), a and b = (camera, radiance [H,W,3], gbuffer), a gbuffer being a

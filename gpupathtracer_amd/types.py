@@ -211,6 +211,17 @@ SHARPEN_PARAMS_BYTES = 12
 SHARPEN_NOISE_AWARE = 1
 
 
+class FfLocalTonemapParams(C.Structure):
+    _fields_ = [("compression", C.c_float), ("detail", C.c_float), ("pivot", C.c_float), ("cell", C.c_int32), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32 * 3)]
+
+
+LOCAL_TONEMAP_PARAMS_BYTES = 32
+LOCAL_TONEMAP_CELLS = (8, 16, 32, 64)
+LOCAL_TONEMAP_BINS = 40
+assert C.sizeof(FfLocalTonemapParams) == LOCAL_TONEMAP_PARAMS_BYTES
+
+
 class FfInterpolateParams(C.Structure):
     _fields_ = [("t", C.c_float), ("surface_tolerance", C.c_float), ("fill_radius", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32)]
 

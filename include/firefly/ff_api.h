@@ -1086,6 +1086,75 @@ FF_API int ff_sharpen(FfState* state, int width, int height, const FfSharpenPara
 FF_API int ff_sharpen_host(int width, int height, const FfSharpenParams* p, const float* radiance_in,
                            unsigned char* rgb8, float* radiance_out);
 
+/* ---- local tone mapping (bilateral grid, directly before ff_display) ------------------------------ */
+
+/* Defaults: compression 0.5, detail 1, pivot 0.18, cell 32, no flags. */
+FF_API void ff_local_tonemap_params_init(FfLocalTonemapParams* p);
+
+/* Local tone mapping of a W x H float3 scene-referred radiance image, radiance out: the large-scale (base) log-luminance of the
+ * image is compressed about a pivot, the detail on top of it is kept or boosted, and every pixel's three channels are scaled by
+ * one ratio, which keeps hue and saturation.  The base comes from an edge-aware filter, a bilateral grid (J. Chen, S. Paris,
+ * F. Durand, "Real-time edge-aware image processing with the bilateral grid", SIGGRAPH 2007; the decomposition after F. Durand,
+ * J. Dorsey 2002): a strong luminance edge throws no halo.  ff_display handles dynamic range with one exposure and one curve for
+ * the frame; this call sits directly BEFORE it, after ff_sharpen / ff_motion_blur / ff_depth_of_field, and ff_display then applies
+ * exposure, curve and encoding as before.  A pure image operation like ff_sharpen: no scene, no G-buffer, no history.  All
+ * arithmetic is float32 + - * / and floor and integer operations on a float's bit pattern, evaluated as written with the
+ * parentheses shown, no fused multiply-add; log, exp and pow appear nowhere, and the grid is summed in integers, so
+ * ff_local_tonemap, ff_local_tonemap_host and a float32 restatement agree bit for bit.  s = cell; ">>" on a negative integer is
+ * the arithmetic shift (floor); gw = ceil(W / s), gh = ceil(H / s).
+ *   1 pseudo-log l = (0.2126f * r + 0.7152f * g) + 0.0722f * b.  A pixel is MAPPED when its three channels are finite and >= 0 (a
+ *                -0 passes) and l is finite and l >= 2^-16 (the floor of ff_display's histogram).  Every other pixel is copied
+ *                through bit for bit and contributes nothing.  With e = (bits(l) >> 23) - 127 and m = bits(l) & 0x7FFFFF:
+ *                q16 = e * 65536 + (m >> 7), the piecewise-linear log2 in 16.16 fixed point - exact, monotone in l - clamped
+ *                to [-16 * 65536, 24 * 65536 - 1].  q10 = q16 >> 6.  Lf = float(q16) * 2^-16 (exact)
+ *   2 splat      the grid has gw x gh columns of 40 cells of one stop; cell (cx, cy, z) is index (cy * gw + cx) * 40 + z.  A mapped
+ *                pixel (x, y) goes to cell (x / s, y / s, (q10 >> 10) + 16) (integer divisions).  A cell holds two int32: the count
+ *                n of its pixels and the sum S of their q10 (|q10| < 2^15 and at most 4 096 pixels: no overflow).  Integer adds:
+ *                the grid does not depend on their order
+ *   3 blur       n and S converted to float (round to nearest even: S can exceed 2^24), then per axis, x first, then y, then z, and
+ *                for n and S alike: v'(i) = ((v(i-1) + (2.0f * v(i))) + v(i+1)) * 0.25f, each pass on the whole result of the one
+ *                before; a tap outside the grid is 0.0f (dropped: n and S lose the same weight, so S / n is not biased)
+ *   4 slice      per mapped pixel fx = (((float)x + 0.5f) / s) - 0.5f and fy alike (the division is exact), fz = (Lf + 16.0f) -
+ *                0.5f.  Per axis with last = gw - 1, gh - 1, 39: f = f < 0 ? 0 : (f > last ? last : f); i0 = floor(f);
+ *                i1 = min(i0 + 1, last); t = f - i0 (exact).  lerp(a, b, t) = (a * (1.0f - t)) + (b * t).  For n and S alike, of the
+ *                eight taps v(x, y, z): along x first - v00 = lerp(v(x0,y0,z0), v(x1,y0,z0), tx), v10 = the same at (y1, z0), v01 at
+ *                (y0, z1), v11 at (y1, z1) - then along y - v0 = lerp(v00, v10, ty), v1 = lerp(v01, v11, ty) - then
+ *                v' = lerp(v0, v1, tz).  base = (S' / n') * 2^-10 where n' > 0, else base = Lf
+ *   5 gain       P = step 1's Lf of `pivot` (as if l = pivot).  g = ((compression - 1.0f) * (base - P)) + ((detail - 1.0f) * (Lf -
+ *                base)), then g = g < -32 ? -32 : (g > 32 ? 32 : g).  Where g == 0 (of either sign) the pixel is copied through
+ *                bit for bit.  Otherwise k = floor(g), f = g - k (exact), ratio = (1.0f + f) * 2^k, the power of two being the
+ *                float with bits (k + 127) << 23 (the inverse piecewise-linear exp2), and out_c = c * ratio per channel
+ *   6 rgb8 = trunc(clamp(out * 255)), the rule of every rgb8 output here.
+ * The piecewise-linear log2 and exp2 are within 0.086 stops and 6 % of the true ones; both are continuous and monotone.  This is accepted; tools/local_tonemap_bench.py reports the deviation
+ * from a float64 restatement with true log2 / exp2.
+ * Consequences.  compression 1 with detail 1 returns the input bit for bit (NaN, Inf and -0 included) and builds no grid.  A
+ * non-finite, negative or too dark pixel is copied and changes no other pixel: it is as if it were black.  Multiplying the image
+ * and the pivot by 2^k multiplies the output by 2^k (up to the clamps of steps 1 and 5).  A mapped pixel's output is >= 0; it
+ * can overflow to +Inf only for a channel above 2^94.
+ * rgb8 (W*H*3 bytes) and radiance_out (W*H*3 floats) may each be NULL.  radiance_out may be radiance_in itself (the grid is
+ * complete before any pixel is written and every pixel is read before it is written); any other overlap of an output with the
+ * input, and of the two outputs with each other, is refused.  Width and height are 1 .. 65535.  Synchronous, on the state's
+ * stream; host buffers are staged.  The call leaves FfStats, the stored primary hits and their key, every filter's history, the
+ * display exposure and the progressive and adaptive sums as they were; its own state is a work buffer (two grids and the staging;
+ * allocated on first use, regrown for a larger size, freed by ff_destroy).  FF_ERR_INVALID_ARG, naming the field, before any
+ * device work for: a NULL state, params or radiance_in; a bad size; a compression outside 0 .. 1, a detail outside 0 .. 4, a
+ * pivot outside [2^-16, 2^24) or any of them not finite; a cell other than 8, 16, 32, 64; nonzero flags or reserved; a refused
+ * overlap.
+ * Not offered: a multi-GPU twin, the call folded into ff_display, a bin other than one stop, temporal smoothing of the grid. */
+FF_API int ff_local_tonemap(FfState* state, int width, int height, const FfLocalTonemapParams* p,
+                            const float* radiance_in, int input_on_device,
+                            void* rgb8, int rgb8_on_device, float* radiance_out, int radiance_out_on_device);
+
+/* Host-only twin (no GPU, no state, host pointers), compiled from the same inline functions the kernels use: the same image
+ * arguments, the same checks, the same bits. */
+FF_API int ff_local_tonemap_host(int width, int height, const FfLocalTonemapParams* p, const float* radiance_in,
+                                 unsigned char* rgb8, float* radiance_out);
+
+/* Step 2's grid alone (host only): out_n and out_S take gw * gh * 40 int32 each, in step 2's cell order.  The parameter block is
+ * checked as above (compression, detail and pivot too, though only `cell` is used); built even for compression 1 with detail 1. */
+FF_API int ff_local_tonemap_grid_host(int width, int height, const FfLocalTonemapParams* p, const float* radiance_in,
+                                      int32_t* out_n, int32_t* out_S);
+
 /* ---- frame interpolation (an in-between frame from two rendered neighbours) ----------------------- */
 
 /* Defaults: t 0.5, surface_tolerance 4 pixels, fill_radius 4, no flags. */

@@ -365,6 +365,17 @@ typedef struct FfSharpenParams {
     uint32_t reserved;   /* 0 */
 } FfSharpenParams;       /* 12 bytes */
 
+/* ff_local_tonemap: bilateral-grid local tone mapping directly before ff_display.  ff_local_tonemap_params_init gives the
+ * defaults; the operator is in ff_api.h. */
+typedef struct FfLocalTonemapParams {
+    float    compression; /* what is left of the base layer's log-luminance range about the pivot: 0 .. 1, 1 = untouched */
+    float    detail;      /* the factor on the detail layer (log-luminance minus base): 0 .. 4, 1 = untouched */
+    float    pivot;       /* the luminance the compression leaves where it is; finite, in [2^-16, 2^24) */
+    int32_t  cell;        /* the grid cell's edge in pixels: 8, 16, 32 or 64 */
+    uint32_t flags;       /* none defined yet: 0 */
+    uint32_t reserved[3]; /* 0 */
+} FfLocalTonemapParams;   /* 32 bytes */
+
 /* ff_interpolate: an in-between frame from two rendered neighbours, gathered through the in-between pose's own G-buffer.
  * ff_interpolate_params_init gives the defaults; the operator is in ff_api.h. */
 typedef struct FfInterpolateParams {
@@ -432,6 +443,7 @@ static_assert(sizeof(FfMotionBlurParams) == 24, "FfMotionBlurParams is 24 bytes"
 static_assert(sizeof(FfDofParams) == 32, "FfDofParams is 32 bytes");
 static_assert(sizeof(FfDespeckleParams) == 28, "FfDespeckleParams is 28 bytes");
 static_assert(sizeof(FfSharpenParams) == 12, "FfSharpenParams is 12 bytes");
+static_assert(sizeof(FfLocalTonemapParams) == 32, "FfLocalTonemapParams is 32 bytes");
 static_assert(sizeof(FfInterpolateParams) == 20, "FfInterpolateParams is 20 bytes");
 static_assert(sizeof(FfAdaptiveParams) == 24, "FfAdaptiveParams is 24 bytes");
 static_assert(sizeof(FfAdaptiveInfo) == 32, "FfAdaptiveInfo is 32 bytes");
@@ -448,6 +460,7 @@ _Static_assert(sizeof(FfMotionBlurParams) == 24, "FfMotionBlurParams layout");
 _Static_assert(sizeof(FfDofParams) == 32, "FfDofParams layout");
 _Static_assert(sizeof(FfDespeckleParams) == 28, "FfDespeckleParams layout");
 _Static_assert(sizeof(FfSharpenParams) == 12, "FfSharpenParams layout");
+_Static_assert(sizeof(FfLocalTonemapParams) == 32, "FfLocalTonemapParams layout");
 _Static_assert(sizeof(FfInterpolateParams) == 20, "FfInterpolateParams layout");
 _Static_assert(sizeof(FfAdaptiveParams) == 24, "FfAdaptiveParams layout");
 _Static_assert(sizeof(FfAdaptiveInfo) == 32, "FfAdaptiveInfo layout");

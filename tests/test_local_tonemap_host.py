@@ -1,0 +1,215 @@
+"""ff_local_tonemap on the host side: exports, defaults, every argument check (all before any device work), the host twins
+ff_local_tonemap_host and ff_local_tonemap_grid_host - the kernels' inline functions compiled for the host - bit for bit against
+the numpy float32 restatement (tests/local_tonemap_ref.py) over sizes, every cell size, three compressions and three details, and
+the consequences the header states: the identity, spoiled pixels, hand-derived values on a two-region image (no halo), detail kept,
+power-of-two equivariance."""
+import ctypes as C
+import os
+import re
+
+import numpy as np
+import pytest
+
+from gpupathtracer_amd import lib
+from gpupathtracer_amd import types as T
+import local_tonemap_ref as R
+from local_tonemap_cases import (CELLS, COMPRESSIONS, DETAILS, HOST_SIZES, SPOILED, TOL, TWO_REGION_PARAMS, assert_same, bits, hdr, midrange, params,
+                                 reference, spoiled, two_regions)
+
+F = np.float32
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def test_new_entry_points_are_exported_and_declared(ff):
+    handle = ff.load()
+    header = open(os.path.join(ROOT, "include", "firefly", "ff_api.h")).read()
+    declared = set(re.findall(r"FF_API\s+[\w\s\*]+?\b(ff_\w+)\s*\(", header))
+    for name in ("ff_local_tonemap_params_init", "ff_local_tonemap", "ff_local_tonemap_host", "ff_local_tonemap_grid_host"):
+        assert name in ff.EXPORTS and name in declared and hasattr(handle, name), name
+
+
+def test_params_defaults_and_size():
+    p = params()
+    assert (p.compression, p.detail, p.pivot, p.cell, p.flags, tuple(p.reserved)) == (0.5, 1.0, float(F(0.18)), 32, 0, (0, 0, 0))
+    assert C.sizeof(T.FfLocalTonemapParams) == T.LOCAL_TONEMAP_PARAMS_BYTES == 32
+    types_h = open(os.path.join(ROOT, "include", "firefly", "ff_types.h")).read()
+    assert "static_assert(sizeof(FfLocalTonemapParams) == 32" in types_h and "_Static_assert(sizeof(FfLocalTonemapParams) == 32" in types_h
+    q = params(compression=1.0, cell=8)
+    assert q.compression == 1.0 and q.cell == 8
+    with pytest.raises(TypeError):
+        params(radius=3)
+
+
+def raw_host(p, rad, rgb8=None, out=None, w=None, h=None):
+    ptr = lambda a: a.ctypes.data if a is not None else None  # noqa: E731
+    hh, ww = rad.shape[:2] if rad is not None else (9, 17)
+    return lib.load().ff_local_tonemap_host(ww if w is None else w, hh if h is None else h, C.byref(p) if p is not None else None, ptr(rad), ptr(rgb8),
+                                            ptr(out))
+
+
+def test_every_refused_argument_names_its_field():
+    rad = np.array(hdr(17, 15))
+    out = np.full(rad.shape, 7.0, F)
+    last = lambda: lib.load().ff_last_error().decode()  # noqa: E731
+    nan, inf = float("nan"), float("inf")
+    cases = [("compression", -0.25), ("compression", 1.5), ("compression", nan), ("compression", inf), ("detail", -0.5), ("detail", 4.5), ("detail", nan),
+             ("detail", inf), ("pivot", 0.0), ("pivot", 2.0 ** -17), ("pivot", 2.0 ** 24), ("pivot", -1.0), ("pivot", nan), ("pivot", inf), ("cell", 0),
+             ("cell", 4), ("cell", 24), ("cell", 128), ("cell", -8), ("flags", 1), ("flags", 0x80000000)]
+    for field, value in cases:
+        assert raw_host(params(**{field: value}), rad, None, out) == T.FF_ERR_INVALID_ARG, (field, value)
+        assert field in last(), (field, value, last())
+    for k in range(3):
+        p = params()
+        p.reserved[k] = 1
+        assert raw_host(p, rad, None, out) == T.FF_ERR_INVALID_ARG and "reserved" in last()
+    assert (out == 7.0).all()
+    for field, value in [("compression", 0.0), ("compression", 1.0), ("detail", 0.0), ("detail", 4.0), ("pivot", 2.0 ** -16), ("pivot", 16777215.0)]:
+        assert raw_host(params(**{field: value}), rad, None, out) == T.FF_OK, (field, value)  # (both ends are allowed)
+    p = params()
+    for args, word in [((None, rad), "params"), ((p, None), "radiance_in")]:
+        assert raw_host(*args, None, out, w=17, h=15) == T.FF_ERR_INVALID_ARG and word in last(), (word, last())
+    for w, h in [(0, 15), (17, 0), (65536, 1), (1, 65536), (-1, 3)]:
+        assert raw_host(p, rad, None, out, w=w, h=h) == T.FF_ERR_INVALID_ARG and "size" in last()
+    # overlapping buffers: the float output partly on the input, the bytes on the input and on the floats
+    tail = rad.reshape(-1)[3:]  # (it starts inside radiance_in)
+    assert raw_host(p, rad, None, tail) == T.FF_ERR_INVALID_ARG and "radiance_out overlaps radiance_in" in last()
+    assert raw_host(p, rad, rad.view(np.uint8), out) == T.FF_ERR_INVALID_ARG and "rgb8 overlaps radiance_in" in last()
+    assert raw_host(p, rad, rad.view(np.uint8), rad) == T.FF_ERR_INVALID_ARG and "rgb8 overlaps radiance_in" in last()
+    assert raw_host(p, rad, out.view(np.uint8), out) == T.FF_ERR_INVALID_ARG and "rgb8 overlaps radiance_out" in last()
+    assert np.array_equal(bits(rad), bits(hdr(17, 15)))
+    # the grid twin checks the same block and its own outputs
+    g = lib.load().ff_local_tonemap_grid_host
+    n = np.zeros((2, 3, 40), np.int32)
+    assert g(17, 15, C.byref(params(cell=5)), rad.ctypes.data, n.ctypes.data, n.ctypes.data) == T.FF_ERR_INVALID_ARG and "cell" in last()
+    assert g(17, 15, C.byref(params(cell=8)), rad.ctypes.data, None, n.ctypes.data) == T.FF_ERR_INVALID_ARG and "out_n" in last()
+    assert g(17, 15, C.byref(params(cell=8)), rad.ctypes.data, n.ctypes.data, None) == T.FF_ERR_INVALID_ARG and "out_S" in last()
+    # the device entry point refuses a NULL state, and the same arguments, before it touches a device
+    d = lib.load().ff_local_tonemap
+    assert d(None, 17, 15, C.byref(p), rad.ctypes.data, 0, None, 0, out.ctypes.data, 0) == T.FF_ERR_INVALID_ARG
+    assert "state" in last()
+
+
+def test_in_place_gives_the_same_bits_as_separate_buffers():
+    for w, h in [(33, 17), (65, 33)]:
+        rad = spoiled(w, h)[0]
+        for cell in (8, 32):
+            p = params(cell=cell, detail=2.0)
+            assert_same(lib.local_tonemap_host(rad, p, in_place=True), lib.local_tonemap_host(rad, p))
+
+
+@pytest.mark.parametrize("cell", CELLS)
+@pytest.mark.parametrize("w,h", HOST_SIZES, ids=[f"{w}x{h}" for w, h in HOST_SIZES])
+def test_twin_and_grid_match_the_reference_bit_for_bit(w, h, cell):
+    rad = hdr(w, h)
+    n, S = lib.local_tonemap_grid_host(rad, params(cell=cell))
+    rn, rS = R.splat(rad, cell)
+    assert n.shape == (-(-h // cell), -(-w // cell), 40)
+    assert np.array_equal(n, rn) and np.array_equal(S, rS)
+    assert int(n.sum()) == w * h  # (every pixel of hdr() is mapped)
+    changed = 0
+    for compression in COMPRESSIONS:
+        for detail in DETAILS:
+            p = params(cell=cell, compression=compression, detail=detail)
+            got = lib.local_tonemap_host(rad, p)
+            assert_same(got, reference(rad, p, "hdr"))
+            changed += int((bits(got[1]) != bits(rad)).sum())
+    assert changed
+
+
+def test_grid_of_spoiled_pixels_and_bin_edges():
+    """The grid counts exactly the mapped pixels, and a pixel on a bin's lower edge (an exact power of two) lands in that bin."""
+    rad, places = spoiled(33, 17)
+    n, S = lib.local_tonemap_grid_host(rad, params(cell=16))
+    rn, rS = R.splat(rad, 16)
+    assert np.array_equal(n, rn) and np.array_equal(S, rS) and int(n.sum()) == 33 * 17 - len(places)
+    one = np.zeros((1, 3, 3), F)
+    one[0, 0] = 2.0 ** -16   # the lowest bin's lower edge
+    one[0, 1] = 1.0          # bin 16, q10 0
+    one[0, 2] = 3.0e38       # above 2^24: clamped into the highest bin
+    n, S = lib.local_tonemap_grid_host(one, params(cell=8))
+    assert n[0, 0].nonzero()[0].tolist() == [0, 16, 39]
+    assert (S[0, 0, 0], S[0, 0, 16], S[0, 0, 39]) == (-16 * 1024, 0, 24 * 1024 - 1)
+
+
+def test_identity_returns_the_input_bit_for_bit():
+    rad = np.array(spoiled(65, 33)[0])
+    rad[0, 0] = np.array([0x7FC01234, 0xFF800000, 0x80000000], np.uint32).view(F)  # a NaN with a payload, -Inf, -0
+    for cell in CELLS:
+        rgb8, out = lib.local_tonemap_host(rad, params(compression=1.0, detail=1.0, cell=cell))
+        assert np.array_equal(bits(out), bits(rad)) and np.array_equal(rgb8, R.rgb8_of(rad))
+        assert_same((rgb8, out), R.local_tonemap(rad, 1.0, 1.0, 0.18, cell))
+
+
+def test_spoiled_pixels_are_copied_and_change_nothing_else():
+    rad, places = spoiled(65, 33)
+    assert len(places) >= len(SPOILED)
+    black = np.array(rad)
+    for y, x in places:
+        black[y, x] = 0.0
+    mask = np.ones(rad.shape[:2], bool)
+    mask[tuple(np.array(places).T)] = False
+    for cell in (8, 32):
+        p = params(cell=cell, detail=2.0)
+        got = lib.local_tonemap_host(rad, p)
+        assert_same(got, R.local_tonemap(rad, 0.5, 2.0, 0.18, cell))
+        for y, x in places:
+            assert np.array_equal(bits(got[1][y, x]), bits(rad[y, x]))
+        clean = lib.local_tonemap_host(black, p)
+        assert np.array_equal(bits(got[1])[mask], bits(clean[1])[mask]) and np.array_equal(got[0][mask], clean[0][mask])
+        assert (bits(got[1])[mask] != bits(rad)[mask]).any()
+
+
+def close(a, b):
+    return np.abs(np.asarray(a, np.float64) / b - 1.0).max() <= TOL
+
+
+@pytest.mark.parametrize("who", ["restatement", "twin"])
+def test_two_regions_hand_derived_values_and_no_halo(who):
+    """128 x 64 grey, left l = 0.125 (Lf = -3), right l = 32 (Lf = 5); pivot 1 (P = 0), compression 0.5, detail 1, cell 16.  The sides
+    are 8 bins apart and blur plus trilinear tap reach 2, so base = Lf on each side: g = -0.5 * -3 = 1.5 -> ratio (1 + 0.5) * 2 = 3,
+    and g = -0.5 * 5 = -2.5 -> k = -3, f = 0.5, ratio 1.5 / 8 = 0.1875.  EVERY left pixel is 0.125 * 3 = 0.375 and every right
+    pixel 32 * 0.1875 = 6, the columns at the edge included."""
+    rad = two_regions()
+    run = (lambda r, **kw: R.local_tonemap(r, **kw)) if who == "restatement" else (lambda r, **kw: lib.local_tonemap_host(r, params(**kw)))
+    rgb8, out = run(rad, **TWO_REGION_PARAMS)
+    assert close(out[:, :64], 0.375) and close(out[:, 64:], 6.0)
+    assert close(out[:, 62:64], 0.375) and close(out[:, 64:66], 6.0)
+    assert (rgb8[:, :64] == int(0.375 * 255)).all() and (rgb8[:, 64:] == 255).all()
+
+
+@pytest.mark.parametrize("who", ["restatement", "twin"])
+def test_detail_is_kept_and_boosted_by_hand_derived_gains(who):
+    """The right half a 1-pixel checker of l = 32 (Lf 5) and l = 40 (Lf 5.25): both in one bin, base 5.125.  Detail 1: one gain
+    -0.5 * 5.125 for both, so out(40) / out(32) = 1.25.  Detail 2: g = -2.5625 + (Lf - 5.125) = -2.6875 and -2.4375, k = -3,
+    ratios 1.3125 / 8 and 1.5625 / 8, outputs 32 * 0.1640625 = 5.25 and 40 * 0.1953125 = 7.8125."""
+    rad = two_regions(True)
+    run = (lambda r, **kw: R.local_tonemap(r, **kw)) if who == "restatement" else (lambda r, **kw: lib.local_tonemap_host(r, params(**kw)))
+    # the issue asks for the pixels at least 2 cells from the image border and from the edge; a 16 x 16 cell holds as many 32s as
+    # 40s wherever it lies and dropped blur taps scale n and S alike, so the whole right half is held to it
+    inner = np.zeros((64, 128), bool)
+    inner[:, 64:] = True
+    hi = (rad[..., 0] == 40.0) & inner
+    lo = (rad[..., 0] == 32.0) & inner
+    assert hi.sum() == lo.sum() > 0
+    _, out = run(rad, **TWO_REGION_PARAMS)
+    assert close(out[hi], 40.0 * (1.4375 / 8)) and close(out[lo], 32.0 * (1.4375 / 8))  # g = -2.5625: k = -3, f = 0.4375
+    for y, x in np.argwhere(hi & (np.arange(128) > 64)[None, :])[::7]:
+        assert close(out[y, x] / out[y, x - 1], 1.25)  # (its left neighbour is a 32)
+    _, out2 = run(rad, **dict(TWO_REGION_PARAMS, detail=2.0))
+    assert close(out2[lo], 5.25) and close(out2[hi], 7.8125)
+    # the left half still has its hand-derived value
+    assert close(out[:, :64], 0.375) and close(out2[:, :64], 0.375)
+
+
+@pytest.mark.parametrize("k", [-3, 4])
+def test_power_of_two_equivariance(k):
+    rad = midrange(65, 33)
+    assert rad.min() * 2.0 ** -3 >= 2.0 ** -10 and rad.max() * 2.0 ** 4 <= 2.0 ** 16
+    scale = F(2.0 ** k)
+    for cell, detail in [(8, 1.0), (32, 2.0)]:
+        p = params(cell=cell, detail=detail, pivot=0.75)
+        q = params(cell=cell, detail=detail, pivot=0.75 * 2.0 ** k)
+        base = lib.local_tonemap_host(rad, p)[1]
+        scaled = lib.local_tonemap_host(rad * scale, q)[1]
+        assert np.abs(scaled.astype(np.float64) / (base.astype(np.float64) * 2.0 ** k) - 1.0).max() <= TOL
+        assert_same(lib.local_tonemap_host(rad, p), reference(rad, p, "midrange"))
