@@ -234,6 +234,12 @@ struct FfState {
         std::vector<uint16_t> tile_passes;    // n_t per tile, row-major
         std::vector<float> tile_error;        // E_t of each tile's last check
     } adaptive;
+    // video planes (ff_encode_yuv): the knot tables of the three transfers (ff_yuv.h kYuvKnotStride floats apart, each uploaded on
+    // its first use) and the staging of host buffers.  Not reset by uploads.
+    void* d_yuv_knots = nullptr;
+    bool yuv_knots_loaded[3] = { false, false, false };
+    void* d_yuv_work = nullptr;
+    size_t yuv_work_bytes = 0;
     unsigned* d_queue = nullptr;               // work-queue counter: lives right behind the counters (one memset clears both)
     unsigned long long* d_counters = nullptr;  // 28 counters + 4 queue words
     unsigned long long* h_counters = nullptr;  // pinned mirror for the per-frame read-back
@@ -378,6 +384,8 @@ void local_tonemap_release(FfState* s);
 void interpolate_release(FfState* s);
 // Adaptive sampling (ff_adaptive_api.cpp): frees the state's buffers (ff_destroy).
 void adaptive_release(FfState* s);
+// Video planes (ff_yuv_api.cpp): frees the knot tables and the work buffer (ff_destroy).
+void yuv_release(FfState* s);
 // The pixel buffer registered with ff_register_gl_pbo, mapped on the state's stream (kernel.cu:338-339) and unmapped again
 // (kernel.cu:344): what ff_render_to_pbo and ff_display_to_pbo write.  need_bytes: the least size the mapping must have.
 int map_pbo(FfState* s, size_t need_bytes, void** out_ptr);

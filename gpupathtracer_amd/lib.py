@@ -47,6 +47,7 @@ EXPORTS = [
     "ff_local_tonemap_params_init", "ff_local_tonemap", "ff_local_tonemap_host", "ff_local_tonemap_grid_host",
     "ff_interpolate_params_init", "ff_interpolate", "ff_interpolate_host", "ff_interpolate_geometry_maps",
     "ff_adaptive_params_init", "ff_render_adaptive", "ff_adaptive_state", "ff_adaptive_tile_error", "ff_adaptive_tile_error_host", "ff_adaptive_plan_host",
+    "ff_yuv_params_init", "ff_yuv_plane_bytes", "ff_yuv_knots", "ff_encode_yuv", "ff_encode_yuv_host", "ff_save_y4m",
 ]
 DIST_ID_BYTES = 128
 
@@ -266,6 +267,13 @@ def load():
     lib.ff_adaptive_tile_error.argtypes = [vp, i32, i32, i32, i32, vp, vp, i32, vp]
     lib.ff_adaptive_tile_error_host.argtypes = [i32, i32, i32, i32, vp, vp, vp]
     lib.ff_adaptive_plan_host.argtypes = [i32, i32, vp, vp, i32]
+    lib.ff_yuv_params_init.argtypes = [P(T.FfYuvParams)]
+    lib.ff_yuv_params_init.restype = None
+    lib.ff_yuv_plane_bytes.argtypes = [i32, i32, P(T.FfYuvParams), P(C.c_uint64), P(C.c_uint64)]
+    lib.ff_yuv_knots.argtypes = [i32, vp]
+    lib.ff_encode_yuv.argtypes = [vp, i32, i32, P(T.FfYuvParams), vp, i32, vp, vp, i32]
+    lib.ff_encode_yuv_host.argtypes = [i32, i32, P(T.FfYuvParams), vp, vp, vp]
+    lib.ff_save_y4m.argtypes = [C.c_char_p, i32, i32, i32, P(T.FfYuvParams), vp, vp]
     lib.ff_taa_upscale_params_init.argtypes = [P(T.FfTaaUpscaleParams)]
     lib.ff_taa_upscale_params_init.restype = None
     lib.ff_taa_upscale.argtypes = [vp, P(T.FfCamera), P(T.FfTaaUpscaleParams), i32, i32, vp, vp, i32, i32, vp, vp, i32, vp, i32, vp, i32]
@@ -834,6 +842,61 @@ def local_tonemap_grid_host(radiance, p=None):
     S = np.zeros(shape, dtype=np.int32)
     check(load().ff_local_tonemap_grid_host(w, h, C.byref(p), rad.ctypes.data, n.ctypes.data, S.ctypes.data))
     return n, S
+
+
+def yuv_params(**overrides):
+    """ff_yuv_params_init's defaults with the given fields replaced (any FfYuvParams field)."""
+    p = T.FfYuvParams()
+    load().ff_yuv_params_init(C.byref(p))
+    for name, value in overrides.items():
+        if name not in dict(T.FfYuvParams._fields_):
+            raise TypeError(f"FfYuvParams has no field {name!r}")
+        setattr(p, name, value)
+    return p
+
+
+def yuv_plane_bytes(width, height, p=None):
+    """ff_yuv_plane_bytes -> (luma bytes, chroma bytes) of a width x height image under p."""
+    p = p if p is not None else yuv_params()
+    luma, chroma = C.c_uint64(0), C.c_uint64(0)
+    check(load().ff_yuv_plane_bytes(width, height, C.byref(p), C.byref(luma), C.byref(chroma)))
+    return int(luma.value), int(chroma.value)
+
+
+def yuv_knots(transfer):
+    """ff_yuv_knots -> K_0 .. K_4096 of a transfer, float32 [4097]."""
+    out = np.zeros(T.YUV_KNOTS, dtype=np.float32)
+    check(load().ff_yuv_knots(transfer, out.ctypes.data))
+    return out
+
+
+def _yuv_planes(h, w, p):
+    """Empty host planes of ff_encode_yuv: luma [H,W] and chroma [ceil(H/2),ceil(W/2),2], uint8 at depth 8 and uint16 otherwise (a
+    depth the library refuses gets uint16 planes: the call names it)."""
+    dtype = np.uint8 if int(p.depth) == 8 else np.uint16
+    return np.zeros((h, w), dtype=dtype), np.zeros(((h + 1) // 2, (w + 1) // 2, 2), dtype=dtype)
+
+
+def encode_yuv_host(linear, p=None):
+    """ff_encode_yuv_host (no GPU): host display-linear [H,W,3] -> (luma [H,W], chroma [ceil(H/2),ceil(W/2),2] of Cb Cr pairs);
+    uint8 codes at depth 8 (NV12), uint16 codes << 6 at depth 10 (P010)."""
+    img, (h, w) = _sharpen_image(linear, "encode_yuv_host")
+    p = p if p is not None else yuv_params()
+    luma, chroma = _yuv_planes(h, w, p)
+    check(load().ff_encode_yuv_host(w, h, C.byref(p), img.ctypes.data, luma.ctypes.data, chroma.ctypes.data))
+    return luma, chroma
+
+
+def save_y4m(path, luma, chroma, p=None, append=False):
+    """ff_save_y4m: one YUV4MPEG2 frame of encode_yuv's host planes; append=False writes the stream header first."""
+    p = p if p is not None else yuv_params()
+    dtype = np.uint8 if int(p.depth) == 8 else np.uint16
+    lum = np.ascontiguousarray(luma, dtype=dtype)
+    chr_ = np.ascontiguousarray(chroma, dtype=dtype)
+    h, w = lum.shape[:2]
+    if lum.ndim != 2 or chr_.shape != ((h + 1) // 2, (w + 1) // 2, 2):
+        raise ValueError("save_y4m: luma must be [H,W] and chroma [ceil(H/2),ceil(W/2),2]")
+    check(load().ff_save_y4m(os.fsencode(path), 1 if append else 0, w, h, C.byref(p), lum.ctypes.data, chr_.ctypes.data))
 
 
 def interpolate_params(**overrides):
@@ -1548,6 +1611,39 @@ class Tracer:
         p = p if p is not None else local_tonemap_params()
         vp = lambda q: C.c_void_p(q) if q else None  # noqa: E731
         check(self._lib.ff_local_tonemap(self._state, width, height, C.byref(p), vp(radiance_ptr), 1, vp(rgb8_ptr), 1, vp(radiance_out_ptr), 1))
+
+    def encode_yuv(self, linear, p=None):
+        """ff_encode_yuv of host display-linear [H,W,3] -> (luma [H,W], chroma [ceil(H/2),ceil(W/2),2] of Cb Cr pairs), host arrays:
+        uint8 codes at depth 8 (NV12), uint16 codes << 6 at depth 10 (P010)."""
+        img, (h, w) = _sharpen_image(linear, "encode_yuv")
+        p = p if p is not None else yuv_params()
+        luma, chroma = _yuv_planes(h, w, p)
+        check(self._lib.ff_encode_yuv(self._state, w, h, C.byref(p), img.ctypes.data, 0, luma.ctypes.data, chroma.ctypes.data, 0))
+        return luma, chroma
+
+    def encode_yuv_device(self, linear, p=None, luma=None, chroma=None):
+        """ff_encode_yuv on DEVICE tensors (torch): linear a contiguous [H,W,3] float32 tensor -> (luma, chroma) tensors laid out as
+        encode_yuv's arrays (uint8 at depth 8, int16 holding the uint16 bit patterns otherwise).  luma / chroma: contiguous tensors
+        of at least the planes' bytes to write into (any dtype and shape; returned as given); they must not overlap the input or
+        each other."""
+        import torch
+        p = p if p is not None else yuv_params()
+        h, w = linear.shape[:2]
+        if not linear.is_cuda or linear.dtype != torch.float32 or tuple(linear.shape) != (h, w, 3) or not linear.is_contiguous():
+            raise ValueError("encode_yuv_device: linear must be a contiguous [H,W,3] float32 tensor on the device")
+        need = yuv_plane_bytes(w, h, p)
+        dtype = torch.uint8 if int(p.depth) == 8 else torch.int16
+        if luma is None:
+            luma = torch.zeros((h, w), dtype=dtype, device=linear.device)
+        if chroma is None:
+            chroma = torch.zeros(((h + 1) // 2, (w + 1) // 2, 2), dtype=dtype, device=linear.device)
+        for name, t, n in (("luma", luma, need[0]), ("chroma", chroma, need[1])):
+            if not t.is_cuda or not t.is_contiguous() or t.numel() * t.element_size() < n:
+                raise ValueError(f"encode_yuv_device: {name} must be a contiguous device tensor of at least {n} bytes")
+        torch.cuda.synchronize(linear.device)
+        check(self._lib.ff_encode_yuv(self._state, w, h, C.byref(p), C.c_void_p(linear.data_ptr()), 1, C.c_void_p(luma.data_ptr()),
+                                      C.c_void_p(chroma.data_ptr()), 1))
+        return luma, chroma
 
     def interpolate(self, mid, a, b, p=None, geom_maps=None, want_rgb8=True, want_out=True):
         """ff_interpolate of host arrays: mid = (camera, gbuffer), a and b = (camera, radiance [H,W,3], gbuffer), a gbuffer being a

@@ -247,6 +247,20 @@ ADAPTIVE_TILES = (16, 32, 64, 128)
 ADAPTIVE_MAX_PASSES = 65534
 assert C.sizeof(FfAdaptiveParams) == ADAPTIVE_PARAMS_BYTES and C.sizeof(FfAdaptiveInfo) == ADAPTIVE_INFO_BYTES
 
+
+class FfYuvParams(C.Structure):
+    _fields_ = [("transfer", C.c_int32), ("matrix", C.c_int32), ("range", C.c_int32), ("depth", C.c_int32), ("siting", C.c_int32),
+                ("reference_white_nits", C.c_float)]
+
+
+YUV_PARAMS_BYTES = 24
+YUV_TRANSFER_BT709, YUV_TRANSFER_SRGB, YUV_TRANSFER_PQ = 0, 1, 2
+YUV_MATRIX_BT709, YUV_MATRIX_BT2020 = 0, 1
+YUV_RANGE_LIMITED, YUV_RANGE_FULL = 0, 1
+YUV_SITING_CENTER, YUV_SITING_LEFT = 0, 1
+YUV_KNOTS = 4097
+assert C.sizeof(FfYuvParams) == YUV_PARAMS_BYTES
+
 BUILD_HOST_SAH, BUILD_GPU_LBVH, BUILD_GPU_PLOC = 0, 1, 2
 UPDATE_REFIT, UPDATE_REBUILD = 0, 1
 

@@ -1405,6 +1405,73 @@ FF_API void ff_free_ppm(unsigned char* rgb8);
  * ((s + 0.055) / 1.055)^2.4), a 256-entry table computed in double; srgb == 0: out = float(b / 255.0). */
 FF_API int ff_rgb8_to_linear(const unsigned char* bytes, int n, int srgb, float* out_floats);
 
+/* ---- video planes (Y'CbCr 4:2:0 for an encoder, after ff_display or ff_local_tonemap) ------------- */
+
+/* Defaults: BT709 transfer, BT709 matrix, LIMITED range, depth 8, LEFT siting, reference_white_nits 203. */
+FF_API void ff_yuv_params_init(FfYuvParams* p);
+
+/* The sizes of the two planes ff_encode_yuv writes for a width x height image under p (step 8); either output may be NULL.  The
+ * checks are ff_encode_yuv's for the size and the parameters. */
+FF_API int ff_yuv_plane_bytes(int width, int height, const FfYuvParams* p, uint64_t* luma_bytes, uint64_t* chroma_bytes);
+
+/* K_0 .. K_4096 of step 4 for FF_YUV_TRANSFER_*: 4097 floats.  FF_ERR_UNSUPPORTED if they do not rise strictly from exactly 0 to
+ * exactly 1 on this host (every later step relies on it). */
+FF_API int ff_yuv_knots(int transfer, float* out4097);
+
+/* The stage that leaves the pipeline for a video encoder or a stream: turns a W x H image of float3 DISPLAY-LINEAR values into
+ * Y'CbCr 4:2:0 planes - NV12 at depth 8, P010 at depth 10.  For SDR the input is ff_display's display_out under FF_ENCODE_LINEAR
+ * semantics (1 = peak white; the chain is ff_display(display_out) -> ff_encode_yuv); for PQ it is radiance after exposure, 1.0
+ * being reference white (ff_local_tonemap -> ff_encode_yuv with PQ, BT2020, depth 10 is HDR10).  A pure image operation like
+ * ff_display: no scene, no G-buffer, no history.  All per-pixel arithmetic is float32 + - * / and floor, every formula evaluated
+ * left to right as written with the parentheses shown, no fused multiply-add, IEEE division; pow appears only where the knots are
+ * made (double, host), so ff_encode_yuv, ff_encode_yuv_host and a float32 restatement agree bit for bit.  Per pixel and channel:
+ *   1 sanitise   NaN and every value that is not > 0 (negative, -Inf, either zero) become +0; then c = min(c, 65536).  All later
+ *                steps see finite numbers
+ *   2 gamut      (only with FF_YUV_MATRIX_BT2020)  linear BT.709 primaries to BT.2020 (BT.2087, rounded to float):
+ *                r' = (0.6274 r + 0.3293 g) + 0.0433 b, g' = (0.0691 r + 0.9195 g) + 0.0114 b, b' = (0.0164 r + 0.0880 g) + 0.8956 b
+ *   3 scale      PQ: v = c * (reference_white_nits / 10000), the quotient formed once in float; otherwise v = c.  Then v = min(v, 1)
+ *   4 transfer   knots K_j = float(eotf(j / 4096)), j = 0 .. 4096, in double on the host (ff_yuv_knots); K_0 = 0, K_4096 = 1, strictly
+ *                increasing.  eotf(s): SRGB s / 12.92 for s <= 0.04045, else ((s + 0.055) / 1.055)^2.4 (ff_display's); BT709
+ *                s / 4.5 for s < 0.081, else max(((s + 0.099) / 1.099)^(1 / 0.45), 0.081 / 4.5) (BT.709's OETF steps from 0.081 to
+ *                0.08125 at 0.018 and its inverse is level across that gap; without the max K_332 would lie below K_331); PQ (ST 2084, 10 000 nits = 1) p = s^(1 / m2),
+ *                (max(p - c1, 0) / (c2 - c3 p))^(1 / m1) with m1 = 2610 / 16384, m2 = 2523 / 4096 * 128, c1 = 3424 / 4096,
+ *                c2 = 2413 / 4096 * 32, c3 = 2392 / 4096 * 32.  v >= 1: e = 1.  Otherwise j = the number of K_1 .. K_4095 that are
+ *                <= v (twelve halving steps: for step = 2048, 1024 .. 1: if K_{j+step} <= v then j += step) and
+ *                e = (float(j) + (v - K_j) / (K_{j+1} - K_j)) * (1 / 4096): the piecewise-linear inverse of the EOTF.  e and the
+ *                true OETF value lie in the same cell of 1 / 4096, under a quarter of a 10-bit code apart
+ *   5 luma       (Kr, Kg, Kb, Dcb, Dcr) = BT709 (0.2126, 0.7152, 0.0722, 1.8556, 1.5748), BT2020 (0.2627, 0.6780, 0.0593, 1.8814,
+ *                1.4746), float constants; with r, g, b step 4's outputs: y = (Kr r + Kg g) + Kb b, cb = (b - y) / Dcb,
+ *                cr = (r - y) / Dcr
+ *   6 chroma     the chroma planes are ceil(W/2) x ceil(H/2); every tap coordinate is clamped into the image; cb and cr are
+ *                filtered unquantised, c(x, y) being either.  CENTER: ((c(2X, 2Y) + c(2X+1, 2Y)) + (c(2X, 2Y+1) + c(2X+1, 2Y+1))) *
+ *                0.25.  LEFT: h(row) = (c(2X-1, row) * 0.25 + c(2X, row) * 0.5) + c(2X+1, row) * 0.25, the sample is
+ *                (h(2Y) + h(2Y+1)) * 0.5
+ *   7 quantise   s = 2^(depth - 8), m = 2^depth - 1.  LIMITED: Y = floor((219 y + 16) * s + 0.5), C = floor((224 c + 128) * s + 0.5)
+ *                clamped to [16 s, 240 s].  FULL: Y = floor(y * m + 0.5), C = floor((c * m + 2^(depth-1)) + 0.5) clamped to [0, m]
+ *   8 store      depth 8, NV12: luma is W x H bytes; chroma is ceil(H/2) rows of ceil(W/2) interleaved Cb Cr byte pairs.  Depth 10,
+ *                P010: the same layout in little-endian uint16 with the code in the high ten bits (code << 6).  Rows are tightly
+ *                packed (ff_yuv_plane_bytes gives the sizes).
+ * Width and height are 1 .. 65535.  Synchronous, on the state's stream; host buffers are staged (input_on_device covers linear_in,
+ * outputs_on_device both planes).  The knots of a transfer are uploaded on its first use and kept in the state; ff_destroy frees
+ * them and the staging buffer.  The call leaves FfStats, the stored primary hits and their key, every filter's history, the display
+ * exposure and the progressive and adaptive sums as they were.  FF_ERR_INVALID_ARG, naming the field, before any device work for: a
+ * NULL state, params, linear_in, luma or chroma; a bad size; an unknown transfer, matrix, range or siting; a depth other than 8 or
+ * 10; a reference_white_nits that is not finite or outside (0, 10000]; an output that overlaps the input or the other output.
+ * Not offered: 4:4:4 and 4:2:2 output, HLG, dithering, top-left (type 2) siting, row pitches other than tight. */
+FF_API int ff_encode_yuv(FfState* state, int width, int height, const FfYuvParams* p, const float* linear_in, int input_on_device,
+                         void* luma, void* chroma, int outputs_on_device);
+
+/* Host-only twin (no GPU, no state, host pointers), compiled from the same inline functions the kernel uses: the same image
+ * arguments, the same checks, the same bytes. */
+FF_API int ff_encode_yuv_host(int width, int height, const FfYuvParams* p, const float* linear_in, void* luma, void* chroma);
+
+/* One YUV4MPEG2 frame of ff_encode_yuv's host planes, to pipe into any encoder.  append == 0 starts the file with the stream header
+ * "YUV4MPEG2 W<w> H<h> F30:1 Ip A1:1 <C> XCOLORRANGE=<LIMITED|FULL>", <C> being C420p10 at depth 10, else C420mpeg2 for LEFT and
+ * C420jpeg for CENTER; append != 0 adds a frame to an existing file.  A frame is "FRAME\n" and the planar Y, Cb, Cr samples; depth
+ * 10 as low-aligned little-endian 16-bit codes (the P010 sample >> 6), as Y4M expects.  The parameter checks are ff_encode_yuv's;
+ * FF_ERR_IO when the file cannot be written. */
+FF_API int ff_save_y4m(const char* path, int append, int width, int height, const FfYuvParams* p, const void* luma, const void* chroma);
+
 /* ---- measurement -------------------------------------------------------------------------------- */
 
 /* Turn per-launch node/triangle visit counters on (1) or off (0, default).  Ray counting is always on. */

@@ -408,6 +408,26 @@ typedef struct FfAdaptiveInfo {
     float    max_tile_error;       /* the largest of the tiles' last error estimates (NaN ones aside) */
 } FfAdaptiveInfo;                  /* 32 bytes (4 of padding at the end) */
 
+/* ff_encode_yuv: display-linear float3 into the Y'CbCr 4:2:0 planes of a video encoder (NV12, P010).  ff_yuv_params_init gives the
+ * defaults; the operator is in ff_api.h. */
+#define FF_YUV_TRANSFER_BT709 0   /* the BT.709 OETF: SDR video */
+#define FF_YUV_TRANSFER_SRGB  1   /* ff_display's sRGB curve */
+#define FF_YUV_TRANSFER_PQ    2   /* SMPTE ST 2084, 10 000 nits = 1: HDR10 */
+#define FF_YUV_MATRIX_BT709   0
+#define FF_YUV_MATRIX_BT2020  1   /* non-constant luminance; the input's BT.709 primaries are converted first */
+#define FF_YUV_RANGE_LIMITED  0   /* 16 .. 235 / 16 .. 240 (times 4 at depth 10) */
+#define FF_YUV_RANGE_FULL     1   /* 0 .. 2^depth - 1 */
+#define FF_YUV_SITING_CENTER  0   /* a chroma sample in the middle of its 2 x 2 luma block (JPEG, MPEG-1) */
+#define FF_YUV_SITING_LEFT    1   /* co-sited with the even luma column, midway between the rows (MPEG-2, H.264, HEVC) */
+typedef struct FfYuvParams {
+    int32_t transfer;              /* FF_YUV_TRANSFER_* */
+    int32_t matrix;                /* FF_YUV_MATRIX_* */
+    int32_t range;                 /* FF_YUV_RANGE_* */
+    int32_t depth;                 /* 8 (NV12) or 10 (P010) */
+    int32_t siting;                /* FF_YUV_SITING_* */
+    float   reference_white_nits;  /* PQ: the luminance of input 1.0; finite, within (0, 10000] */
+} FfYuvParams;                     /* 24 bytes */
+
 /* ff_texture_create: how a texture is addressed and filtered (the formulas are in ff_api.h).  0 = repeat, bilinear. */
 #define FF_TEX_REPEAT    0   /* coordinates wrap: c - floor(c) */
 #define FF_TEX_CLAMP     1   /* coordinates clamp to [0, 1] */
@@ -447,6 +467,7 @@ static_assert(sizeof(FfLocalTonemapParams) == 32, "FfLocalTonemapParams is 32 by
 static_assert(sizeof(FfInterpolateParams) == 20, "FfInterpolateParams is 20 bytes");
 static_assert(sizeof(FfAdaptiveParams) == 24, "FfAdaptiveParams is 24 bytes");
 static_assert(sizeof(FfAdaptiveInfo) == 32, "FfAdaptiveInfo is 32 bytes");
+static_assert(sizeof(FfYuvParams) == 24, "FfYuvParams is 24 bytes");
 #else
 _Static_assert(sizeof(FfBXDF) == 60, "BXDF layout");
 _Static_assert(sizeof(FfTriangle) == 96, "Triangle layout");
@@ -464,6 +485,7 @@ _Static_assert(sizeof(FfLocalTonemapParams) == 32, "FfLocalTonemapParams layout"
 _Static_assert(sizeof(FfInterpolateParams) == 20, "FfInterpolateParams layout");
 _Static_assert(sizeof(FfAdaptiveParams) == 24, "FfAdaptiveParams layout");
 _Static_assert(sizeof(FfAdaptiveInfo) == 32, "FfAdaptiveInfo layout");
+_Static_assert(sizeof(FfYuvParams) == 24, "FfYuvParams layout");
 #endif
 
 #endif /* FIREFLY_FF_TYPES_H */
