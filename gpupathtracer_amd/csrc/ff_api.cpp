@@ -460,6 +460,7 @@ int ff_destroy(FfState* s)
     interpolate_release(s);
     adaptive_release(s);
     yuv_release(s);
+    resize_release(s);
     free_build_scratch(s->scratch);
     if (s->d_blocksums) (void)hipFree(s->d_blocksums);
     if (s->d_rgb8) (void)hipFree(s->d_rgb8);

@@ -240,6 +240,20 @@ struct FfState {
     bool yuv_knots_loaded[3] = { false, false, false };
     void* d_yuv_work = nullptr;
     size_t yuv_work_bytes = 0;
+    // resampling (ff_resize): the intermediate image of the horizontal pass (W' x H float3), the staging of host buffers and, per
+    // axis (0: horizontal, 1: vertical), the table uploaded last - first[out_size], then from a multiple of 16 bytes on the
+    // weights - with its key (in_size, out_size, filter): rebuilt and uploaded only when the key changes.  Not reset by uploads.
+    void* d_resize_mid = nullptr;
+    size_t resize_mid_bytes = 0;
+    void* d_resize_work = nullptr;
+    size_t resize_work_bytes = 0;
+    struct ResizeTable {
+        void* d_table = nullptr;
+        size_t bytes = 0;
+        bool valid = false;
+        int in_size = 0, out_size = 0, filter = 0;
+        int taps = 0, span = 0; // T, and for axis 0 the longest input span of a tile (ff_resize.h ResizeAxis)
+    } resize_table[2];
     unsigned* d_queue = nullptr;               // work-queue counter: lives right behind the counters (one memset clears both)
     unsigned long long* d_counters = nullptr;  // 28 counters + 4 queue words
     unsigned long long* h_counters = nullptr;  // pinned mirror for the per-frame read-back
@@ -386,6 +400,8 @@ void interpolate_release(FfState* s);
 void adaptive_release(FfState* s);
 // Video planes (ff_yuv_api.cpp): frees the knot tables and the work buffer (ff_destroy).
 void yuv_release(FfState* s);
+// Resampling (ff_resize_api.cpp): frees the intermediate image, the work buffer and the two tables (ff_destroy).
+void resize_release(FfState* s);
 // The pixel buffer registered with ff_register_gl_pbo, mapped on the state's stream (kernel.cu:338-339) and unmapped again
 // (kernel.cu:344): what ff_render_to_pbo and ff_display_to_pbo write.  need_bytes: the least size the mapping must have.
 int map_pbo(FfState* s, size_t need_bytes, void** out_ptr);

@@ -48,6 +48,7 @@ EXPORTS = [
     "ff_interpolate_params_init", "ff_interpolate", "ff_interpolate_host", "ff_interpolate_geometry_maps",
     "ff_adaptive_params_init", "ff_render_adaptive", "ff_adaptive_state", "ff_adaptive_tile_error", "ff_adaptive_tile_error_host", "ff_adaptive_plan_host",
     "ff_yuv_params_init", "ff_yuv_plane_bytes", "ff_yuv_knots", "ff_encode_yuv", "ff_encode_yuv_host", "ff_save_y4m",
+    "ff_resize_params_init", "ff_resize_taps", "ff_resize_weights", "ff_resize", "ff_resize_host",
 ]
 DIST_ID_BYTES = 128
 
@@ -274,6 +275,12 @@ def load():
     lib.ff_encode_yuv.argtypes = [vp, i32, i32, P(T.FfYuvParams), vp, i32, vp, vp, i32]
     lib.ff_encode_yuv_host.argtypes = [i32, i32, P(T.FfYuvParams), vp, vp, vp]
     lib.ff_save_y4m.argtypes = [C.c_char_p, i32, i32, i32, P(T.FfYuvParams), vp, vp]
+    lib.ff_resize_params_init.argtypes = [P(T.FfResizeParams)]
+    lib.ff_resize_params_init.restype = None
+    lib.ff_resize_taps.argtypes = [i32, i32, i32, P(i32)]
+    lib.ff_resize_weights.argtypes = [i32, i32, i32, vp, vp]
+    lib.ff_resize.argtypes = [vp, P(T.FfResizeParams), i32, i32, vp, i32, i32, i32, vp, i32, vp, i32]
+    lib.ff_resize_host.argtypes = [P(T.FfResizeParams), i32, i32, vp, i32, i32, vp, vp]
     lib.ff_taa_upscale_params_init.argtypes = [P(T.FfTaaUpscaleParams)]
     lib.ff_taa_upscale_params_init.restype = None
     lib.ff_taa_upscale.argtypes = [vp, P(T.FfCamera), P(T.FfTaaUpscaleParams), i32, i32, vp, vp, i32, i32, vp, vp, i32, vp, i32, vp, i32]
@@ -897,6 +904,45 @@ def save_y4m(path, luma, chroma, p=None, append=False):
     if lum.ndim != 2 or chr_.shape != ((h + 1) // 2, (w + 1) // 2, 2):
         raise ValueError("save_y4m: luma must be [H,W] and chroma [ceil(H/2),ceil(W/2),2]")
     check(load().ff_save_y4m(os.fsencode(path), 1 if append else 0, w, h, C.byref(p), lum.ctypes.data, chr_.ctypes.data))
+
+
+def resize_params(**overrides):
+    """ff_resize_params_init's defaults with the given fields replaced (any FfResizeParams field)."""
+    p = T.FfResizeParams()
+    load().ff_resize_params_init(C.byref(p))
+    for name, value in overrides.items():
+        if name not in dict(T.FfResizeParams._fields_):
+            raise TypeError(f"FfResizeParams has no field {name!r}")
+        setattr(p, name, value)
+    return p
+
+
+def resize_taps(in_size, out_size, filter):
+    """ff_resize_taps -> T of an axis of in_size input and out_size output samples under filter."""
+    taps = C.c_int(0)
+    check(load().ff_resize_taps(in_size, out_size, filter, C.byref(taps)))
+    return int(taps.value)
+
+
+def resize_weights(in_size, out_size, filter):
+    """ff_resize_weights -> (first int32 [out_size], weights float32 [out_size, T]) of one axis."""
+    taps = resize_taps(in_size, out_size, filter)
+    first = np.zeros(out_size, dtype=np.int32)
+    weights = np.zeros((out_size, taps), dtype=np.float32)
+    check(load().ff_resize_weights(in_size, out_size, filter, first.ctypes.data, weights.ctypes.data))
+    return first, weights
+
+
+def resize_host(radiance, out_width, out_height, p=None, want_rgb8=True, want_out=True):
+    """ff_resize_host (no GPU): host radiance [H,W,3] -> (rgb8 [H',W',3] uint8, radiance [H',W',3] float32)."""
+    rad, (h, w) = _sharpen_image(radiance, "resize_host")
+    p = p if p is not None else resize_params()
+    shape = (max(int(out_height), 0), max(int(out_width), 0), 3)  # (a size the library refuses still gets arrays: the call names it)
+    rgb8 = np.zeros(shape, dtype=np.uint8) if want_rgb8 else None
+    out = np.zeros(shape, dtype=np.float32) if want_out else None
+    check(load().ff_resize_host(C.byref(p), w, h, rad.ctypes.data, out_width, out_height, rgb8.ctypes.data if want_rgb8 else None,
+                                out.ctypes.data if want_out else None))
+    return rgb8, out
 
 
 def interpolate_params(**overrides):
@@ -1644,6 +1690,36 @@ class Tracer:
         check(self._lib.ff_encode_yuv(self._state, w, h, C.byref(p), C.c_void_p(linear.data_ptr()), 1, C.c_void_p(luma.data_ptr()),
                                       C.c_void_p(chroma.data_ptr()), 1))
         return luma, chroma
+
+    def resize(self, radiance, out_width, out_height, p=None, want_rgb8=True, want_out=True):
+        """ff_resize of radiance [H,W,3] -> (rgb8 [H',W',3] uint8, radiance [H',W',3] float32).  A host array gives host arrays; a
+        contiguous float32 device tensor (torch) gives device tensors."""
+        p = p if p is not None else resize_params()
+        shape = (max(int(out_height), 0), max(int(out_width), 0), 3)
+        if hasattr(radiance, "data_ptr"):
+            import torch
+            h, w = radiance.shape[:2]
+            if not radiance.is_cuda or radiance.dtype != torch.float32 or tuple(radiance.shape) != (h, w, 3) or not radiance.is_contiguous():
+                raise ValueError("resize: radiance must be a contiguous [H,W,3] float32 tensor on the device")
+            rgb8 = torch.zeros(shape, dtype=torch.uint8, device=radiance.device) if want_rgb8 else None
+            out = torch.zeros(shape, dtype=torch.float32, device=radiance.device) if want_out else None
+            torch.cuda.synchronize(radiance.device)
+            self.resize_device(w, h, radiance.data_ptr(), out_width, out_height, p, rgb8.data_ptr() if want_rgb8 else None,
+                               out.data_ptr() if want_out else None)
+            return rgb8, out
+        rad, (h, w) = _sharpen_image(radiance, "resize")
+        rgb8 = np.zeros(shape, dtype=np.uint8) if want_rgb8 else None
+        out = np.zeros(shape, dtype=np.float32) if want_out else None
+        check(self._lib.ff_resize(self._state, C.byref(p), w, h, rad.ctypes.data, 0, out_width, out_height, rgb8.ctypes.data if want_rgb8 else None, 0,
+                                  out.ctypes.data if want_out else None, 0))
+        return rgb8, out
+
+    def resize_device(self, in_width, in_height, radiance_ptr, out_width, out_height, p=None, rgb8_ptr=None, radiance_out_ptr=None):
+        """ff_resize on DEVICE buffers (raw pointers); the outputs must not overlap the input or each other."""
+        p = p if p is not None else resize_params()
+        vp = lambda q: C.c_void_p(q) if q else None  # noqa: E731
+        check(self._lib.ff_resize(self._state, C.byref(p), in_width, in_height, vp(radiance_ptr), 1, out_width, out_height, vp(rgb8_ptr), 1,
+                                  vp(radiance_out_ptr), 1))
 
     def interpolate(self, mid, a, b, p=None, geom_maps=None, want_rgb8=True, want_out=True):
         """ff_interpolate of host arrays: mid = (camera, gbuffer), a and b = (camera, radiance [H,W,3], gbuffer), a gbuffer being a

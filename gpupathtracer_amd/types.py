@@ -261,6 +261,17 @@ YUV_SITING_CENTER, YUV_SITING_LEFT = 0, 1
 YUV_KNOTS = 4097
 assert C.sizeof(FfYuvParams) == YUV_PARAMS_BYTES
 
+
+class FfResizeParams(C.Structure):
+    _fields_ = [("filter", C.c_int32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+RESIZE_PARAMS_BYTES = 12
+RESIZE_BOX, RESIZE_TRIANGLE, RESIZE_MITCHELL, RESIZE_LANCZOS3 = 0, 1, 2, 3
+RESIZE_ANTI_RING = 1
+RESIZE_MAX_RATIO, RESIZE_MAX_TAPS = 16, 96
+assert C.sizeof(FfResizeParams) == RESIZE_PARAMS_BYTES
+
 BUILD_HOST_SAH, BUILD_GPU_LBVH, BUILD_GPU_PLOC = 0, 1, 2
 UPDATE_REFIT, UPDATE_REBUILD = 0, 1
 

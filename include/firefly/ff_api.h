@@ -1472,6 +1472,81 @@ FF_API int ff_encode_yuv_host(int width, int height, const FfYuvParams* p, const
  * FF_ERR_IO when the file cannot be written. */
 FF_API int ff_save_y4m(const char* path, int append, int width, int height, const FfYuvParams* p, const void* luma, const void* chroma);
 
+/* ---- resampling (separable polyphase, to any size within a factor of 16) -------------------------- */
+
+/* Defaults: FF_RESIZE_LANCZOS3, FF_RESIZE_ANTI_RING, reserved 0. */
+FF_API void ff_resize_params_init(FfResizeParams* p);
+
+/* T, the number of taps every output sample of an axis of in_size input and out_size output samples has under `filter` (below):
+ * at most 96.  FF_ERR_INVALID_ARG for a size or a ratio ff_resize refuses, an unknown filter or a NULL out_taps. */
+FF_API int ff_resize_taps(int in_size, int out_size, int filter, int* out_taps);
+
+/* The table of one axis as ff_resize and ff_resize_host use it: out_first[X] for X = 0 .. out_size - 1, and out_weights[X * T + j]
+ * for tap j = 0 .. T - 1 (T from ff_resize_taps).  The checks are ff_resize_taps'; neither pointer may be NULL. */
+FF_API int ff_resize_weights(int in_size, int out_size, int filter, int32_t* out_first, float* out_weights);
+
+/* Resamples a W x H float3 radiance image to W' x H', each size within a factor of 16 of the other, under a reconstruction filter
+ * that is stretched when it minifies: what makes an image SMALLER (supersampling - render k times the pixels, filter down -,
+ * thumbnails and proxies, the size of the planes ff_encode_yuv writes, host-side mip chains for ff_texture_create) or gives it an
+ * arbitrary size, where ff_upscale and ff_taa_upscale only enlarge, need G-buffers and stop at 8 times.  A pure image operation like
+ * ff_sharpen: no scene, no G-buffer, no history; it works on linear radiance, so it sits BEFORE ff_local_tonemap and ff_display
+ * (or on display_out ahead of ff_encode_yuv).  Two passes, the horizontal one always first, W x H -> W' x H, then the vertical one;
+ * neither is skipped, even at equal size, because MITCHELL at equal size is a blur.
+ * WEIGHTS.  Per axis, on the host, in double, every formula evaluated left to right as written.  For an axis of n input and N
+ * output samples:
+ *   1 s = (double)n / (double)N
+ *   2 f = max(s, 1): the filter is stretched when minifying
+ *   3 the radius R is 0.5 for BOX, 1 for TRIANGLE, 2 for MITCHELL and 3 for LANCZOS3
+ *   4 r = R * f
+ *   5 T = (int)ceil(2 * r), the same for every output sample of the axis (ff_resize_taps); at the limits it is at most 96
+ *   6 for output X: c = ((double)X + 0.5) * s - 0.5; first_X = (int)ceil(c - r); t_j = ((double)(first_X + j) - c) / f for tap
+ *     j = 0 .. T-1; k_j = k(t_j); S is the sum of k_j from j = 0 upward; w_j = (float)(k_j / S)
+ * k(t) with a = |t|:
+ *   BOX        1 for -0.5 <= t < 0.5, else 0
+ *   TRIANGLE   1 - a for a < 1, else 0
+ *   MITCHELL   (B = C = 1.0 / 3.0)
+ *              for a < 1: ((12 - 9B - 6C) a a a + (-18 + 12B + 6C) a a + (6 - 2B)) / 6
+ *              for a < 2: ((-B - 6C) a a a + (6B + 30C) a a + (-12B - 48C) a + (8B + 24C)) / 6
+ *              else 0
+ *   LANCZOS3   0 for a >= 3; 1 for t == 0; 0 for every other t that equals its own floor, so that an equal-size pass has the single
+ *              weight 1; else 3 sin(pi t) sin(pi t / 3) / (pi pi t t)
+ * No tap outside first_X .. first_X + T - 1 has a nonzero k, S > 0 always, and the rounded weights of an output sample sum to 1
+ * within 2^-24.  With n = N, BOX, TRIANGLE and LANCZOS3 each give exactly one weight of 1, at input X.  (BOX, TRIANGLE and MITCHELL
+ * use only + - * / and are the same bits wherever they are computed; sin is not correctly rounded, so a LANCZOS3 weight of another
+ * libm may differ by a float ulp.  ff_resize and ff_resize_host use this library's, the one ff_resize_weights returns.)
+ * PIXELS.  All arithmetic is float32 with no fused multiply-add; min(a, b) is b < a ? b : a and max(a, b) is a < b ? b : a.  In
+ * each pass, per output sample and channel:
+ *   1 tap j reads input index clamp(first_X + j, 0, n - 1).  A clamped tap keeps its weight and counts as often as it is named
+ *   2 a non-finite value reads as +0 in everything below - in the vertical pass too, where the value is an intermediate
+ *   3 acc = 0; for j = 0 .. T-1: acc = acc + w_j * v_j
+ *   4 with FF_RESIZE_ANTI_RING: lo and hi are the min and max of v_j over the taps with w_j != 0, taken in the order of j, and
+ *     out = min(max(acc, lo), hi).  Without the flag out = acc: the negative lobes of MITCHELL and LANCZOS3 may then produce
+ *     NEGATIVE radiance beside an edge (and values above the brightest input)
+ *   5 rgb8 = trunc(clamp(out * 255)), the rule of every rgb8 output here.
+ * Consequences.  An equal-size call under BOX, TRIANGLE or LANCZOS3 returns a finite image value for value (a -0 may come back as
+ * +0).  With ANTI_RING a constant image returns bit for bit at every size and filter.  A non-finite input sample affects only the
+ * outputs whose taps name it.  No output is non-finite: the absolute weights of an output sample sum to less than 2, so this holds
+ * for finite input up to 2^125 in magnitude, which two passes cannot carry past FLT_MAX.
+ * rgb8 (W'*H'*3 bytes) and radiance_out (W'*H'*3 floats) may each be NULL.  Neither may overlap the input, and the two may not
+ * overlap each other; each span is sized by its own image.  Every size is 1 .. 65535, and on each axis out <= 16 in and
+ * in <= 16 out.  Synchronous, on the state's stream; host buffers are staged.  The call leaves FfStats, the stored primary hits and
+ * their key, every filter's history, the display exposure and the progressive and adaptive sums as they were, and ff_upload_scene
+ * resets nothing of it; its own state is the intermediate image, the staging buffer and, per axis, the table uploaded last with its
+ * key (in, out, filter) - rebuilt and uploaded only when the key changes -, all allocated on first use, regrown for a larger size
+ * and freed by ff_destroy.  FF_ERR_INVALID_ARG, naming the field, before any device work for: a NULL state, params or radiance_in;
+ * a size outside 1 .. 65535; sizes more than a factor of 16 apart on an axis; an unknown filter; unknown flags or a nonzero
+ * reserved; an output that overlaps the input or the other output.
+ * Not offered: other channel counts, a G-buffer-aware form, gamma-space resampling, a row pitch, a multi-GPU twin, a resize fused
+ * into ff_encode_yuv. */
+FF_API int ff_resize(FfState* state, const FfResizeParams* p, int in_width, int in_height,
+                     const float* radiance_in, int input_on_device, int out_width, int out_height,
+                     void* rgb8, int rgb8_on_device, float* radiance_out, int radiance_out_on_device);
+
+/* Host-only twin (no GPU, no state, host pointers), compiled from the same inline per-tap functions the kernels use: the same
+ * image arguments, the same checks, the same bits. */
+FF_API int ff_resize_host(const FfResizeParams* p, int in_width, int in_height, const float* radiance_in,
+                          int out_width, int out_height, unsigned char* rgb8, float* radiance_out);
+
 /* ---- measurement -------------------------------------------------------------------------------- */
 
 /* Turn per-launch node/triangle visit counters on (1) or off (0, default).  Ray counting is always on. */

@@ -428,6 +428,16 @@ typedef struct FfYuvParams {
     float   reference_white_nits;  /* PQ: the luminance of input 1.0; finite, within (0, 10000] */
 } FfYuvParams;                     /* 24 bytes */
 
+/* ff_resize: separable polyphase resampling of a float3 image to any size within a factor of 16.  ff_resize_params_init gives the
+ * defaults; the operator is in ff_api.h. */
+enum { FF_RESIZE_BOX = 0, FF_RESIZE_TRIANGLE = 1, FF_RESIZE_MITCHELL = 2, FF_RESIZE_LANCZOS3 = 3 };
+#define FF_RESIZE_ANTI_RING 1u        /* an output sample is clamped to the range of the samples its taps read (step 4) */
+typedef struct FfResizeParams {
+    int32_t  filter;     /* FF_RESIZE_* */
+    uint32_t flags;      /* FF_RESIZE_ANTI_RING */
+    uint32_t reserved;   /* 0 */
+} FfResizeParams;        /* 12 bytes */
+
 /* ff_texture_create: how a texture is addressed and filtered (the formulas are in ff_api.h).  0 = repeat, bilinear. */
 #define FF_TEX_REPEAT    0   /* coordinates wrap: c - floor(c) */
 #define FF_TEX_CLAMP     1   /* coordinates clamp to [0, 1] */
@@ -468,6 +478,7 @@ static_assert(sizeof(FfInterpolateParams) == 20, "FfInterpolateParams is 20 byte
 static_assert(sizeof(FfAdaptiveParams) == 24, "FfAdaptiveParams is 24 bytes");
 static_assert(sizeof(FfAdaptiveInfo) == 32, "FfAdaptiveInfo is 32 bytes");
 static_assert(sizeof(FfYuvParams) == 24, "FfYuvParams is 24 bytes");
+static_assert(sizeof(FfResizeParams) == 12, "FfResizeParams is 12 bytes");
 #else
 _Static_assert(sizeof(FfBXDF) == 60, "BXDF layout");
 _Static_assert(sizeof(FfTriangle) == 96, "Triangle layout");
@@ -486,6 +497,7 @@ _Static_assert(sizeof(FfInterpolateParams) == 20, "FfInterpolateParams layout");
 _Static_assert(sizeof(FfAdaptiveParams) == 24, "FfAdaptiveParams layout");
 _Static_assert(sizeof(FfAdaptiveInfo) == 32, "FfAdaptiveInfo layout");
 _Static_assert(sizeof(FfYuvParams) == 24, "FfYuvParams layout");
+_Static_assert(sizeof(FfResizeParams) == 12, "FfResizeParams layout");
 #endif
 
 #endif /* FIREFLY_FF_TYPES_H */
