@@ -443,7 +443,7 @@ int ff_destroy(FfState* s)
     if (s->d_frame) (void)hipFree(s->d_frame);
     if (s->d_mean) (void)hipFree(s->d_mean);
     if (s->d_gb_hits) (void)hipFree(s->d_gb_hits);
-    if (s->d_img_stage) (void)hipFree(s->d_img_stage);
+    if (s->d_img_work) (void)hipFree(s->d_img_work);
     if (s->d_dn_work) (void)hipFree(s->d_dn_work);
     for (ReprojectionHistory& h : s->history) h.release();
     if (s->d_nee_lights) (void)hipFree(s->d_nee_lights);
@@ -452,12 +452,6 @@ int ff_destroy(FfState* s)
     tex_release(s);
     glossy_release(s);
     display_release(s);
-    motion_blur_release(s);
-    dof_release(s);
-    despeckle_release(s);
-    sharpen_release(s);
-    local_tonemap_release(s);
-    interpolate_release(s);
     adaptive_release(s);
     yuv_release(s);
     resize_release(s);

@@ -1,7 +1,7 @@
-// ff_despeckle_api.cpp — host side of ff_despeckle (include/firefly/ff_api.h): the argument checks, the work buffer (the partial counts of
-// clamped pixels, then the staging of host buffers through ff_image.h's helpers), the one launch (kernel in ff_despeckle.hip) and the
-// loops of the host-only twin ff_despeckle_host over ff_despeckle.h's per-pixel functions.  A pure image operation: no scene, no
-// history, nothing kept in the state but the work buffer.
+// ff_despeckle_api.cpp — host side of ff_despeckle (include/firefly/ff_api.h): the argument checks, its use of the state's image work
+// buffer (the partial counts of clamped pixels, then the staging of host buffers through ff_image.h's helpers), the one launch (kernel
+// in ff_despeckle.hip) and the loops of the host-only twin ff_despeckle_host over ff_despeckle.h's per-pixel functions.  A pure
+// image operation: no scene, no history, nothing kept in the state.
 #include <cmath>
 #include <vector>
 
@@ -40,10 +40,10 @@ int check_despeckle(int width, int height, const FfDespeckleParams* p, const flo
     if (demodulate && !albedo) return fail(FF_ERR_INVALID_ARG, "%s: albedo is null under FF_DESPECKLE_DEMODULATE_ALBEDO", who);
     if (!ids) return fail(FF_ERR_INVALID_ARG, "%s: ids is null", who);
     const size_t px = (size_t)width * (size_t)height;
-    const Span out[2] = { { rgb8, px * 3, "rgb8" }, { radiance_out, px * 12, "radiance_out" } };
     // (an albedo that is not read may lie anywhere)
-    const Span in[3] = { { radiance_in, px * 12, "radiance_in" }, { demodulate ? albedo : nullptr, demodulate ? px * 12 : 0, "albedo" }, { ids, px * 12, "ids" } };
-    if (check_disjoint(out, in, who) != FF_OK) return FF_ERR_INVALID_ARG;
+    const Span albedo_read = { demodulate ? albedo : nullptr, demodulate ? px * 12 : 0, "albedo" };
+    if (check_outputs_disjoint(rgb8, radiance_out, px, { { radiance_in, px * 12, "radiance_in" }, albedo_read, { ids, px * 12, "ids" } }, who) != FF_OK)
+        return FF_ERR_INVALID_ARG;
     a->width = width;
     a->height = height;
     a->radius = p->radius;
@@ -82,17 +82,6 @@ uint32_t despeckle_rows(const DespeckleArgs& a, const std::vector<DespeckleCell>
 
 } // namespace
 
-namespace ff {
-
-void despeckle_release(FfState* s)
-{
-    if (s->d_despeckle_work) (void)hipFree(s->d_despeckle_work);
-    s->d_despeckle_work = nullptr;
-    s->despeckle_work_bytes = 0;
-}
-
-} // namespace ff
-
 extern "C" {
 
 void ff_despeckle_params_init(FfDespeckleParams* p)
@@ -119,22 +108,19 @@ int ff_despeckle(FfState* s, int width, int height, const FfDespeckleParams* p, 
     FF_HIP(hipSetDevice(s->device));
     hipStream_t stream = s->stream;
     const size_t px = (size_t)width * (size_t)height;
-    unsigned char* d_rgb8 = (unsigned char*)rgb8;
-    float* d_out = radiance_out;
     if (!a.demodulate) albedo = nullptr;
-    Staging stage(&s->d_despeckle_work, &s->despeckle_work_bytes, kCountBytes);
+    Staging stage(&s->d_img_work, &s->img_work_bytes, kCountBytes);
     if (!inputs_on_device) {
         stage.in(&radiance_in, radiance_in, px * 12);
         if (albedo) stage.in(&albedo, albedo, px * 12);
         stage.in(&ids, ids, px * 12);
     }
-    if (rgb8 && !rgb8_on_device) stage.out(&d_rgb8, rgb8, px * 3);
-    if (radiance_out && !radiance_out_on_device) stage.out(&d_out, radiance_out, px * 12);
+    StagedOutputs out(stage, px, rgb8, rgb8_on_device, radiance_out, radiance_out_on_device);
     const int staged = stage.commit(stream, "ff_despeckle: staging the inputs failed");
     if (staged != FF_OK) return staged;
-    uint32_t* d_count = (uint32_t*)s->d_despeckle_work;
+    uint32_t* d_count = (uint32_t*)s->d_img_work;
     FF_HIP(hipMemsetAsync(d_count, 0, kCountBytes, stream));
-    FF_HIP(launch_despeckle(a, radiance_in, albedo, ids, d_rgb8, d_out, d_count, stream));
+    FF_HIP(launch_despeckle(a, radiance_in, albedo, ids, out.rgb8, out.radiance, d_count, stream));
     FF_HIP(hipStreamSynchronize(stream));
     if (out_clamped) {
         std::vector<uint32_t> slots(kCountBytes / sizeof(uint32_t));

@@ -132,7 +132,7 @@ int display_run(FfState* s, int width, int height, const FfDisplayParams* p, con
     FF_HIP(hipSetDevice(s->device));
     hipStream_t stream = s->stream;
     const size_t px = (size_t)width * (size_t)height;
-    const bool in_host = !input_on_device, rgb_host = rgb8 && !rgb8_on_device, out_host = display_out && !display_out_on_device;
+    const bool in_host = !input_on_device, out_host = display_out && !display_out_on_device;
     const bool automatic = (p->flags & FF_DISPLAY_AUTO_EXPOSURE) != 0, bloom = (p->flags & FF_DISPLAY_BLOOM) != 0;
     // a device display_out that overlaps radiance_in without being it: the kernel reads a copy of the input
     const char* rin = (const char*)radiance_in;
@@ -149,7 +149,8 @@ int display_run(FfState* s, int width, int height, const FfDisplayParams* p, con
         }
     }
     unsigned* d_counters = (unsigned*)s->d_disp_const;
-    // the work buffer: the pyramid's levels, then the staging of host buffers (and the copy of an overlapping input)
+    // its use of the state's image work buffer: the pyramid's levels ({rgb, 0} float4 per texel, levels 1 .. n one after another),
+    // then the staging of host buffers (and the copy of an overlapping input)
     BloomLevel level[kDisplayMaxLevels + 1] = {};
     size_t need = 0, level_at[kDisplayMaxLevels + 1] = {};
     const int levels = bloom ? p->bloom_levels : 0;
@@ -163,15 +164,12 @@ int display_run(FfState* s, int width, int height, const FfDisplayParams* p, con
         need += ((size_t)lw * (size_t)lh * sizeof(float4) + 15) & ~(size_t)15;
     }
     const float* d_in = radiance_in;
-    unsigned char* d_rgb8 = (unsigned char*)rgb8;
-    float* d_out = display_out;
-    Staging stage(&s->d_disp_work, &s->disp_work_bytes, need);
+    Staging stage(&s->d_img_work, &s->img_work_bytes, need);
     if (in_host || overlap) stage.in(&d_in, radiance_in, px * 12, in_host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice);
-    if (rgb_host) stage.out(&d_rgb8, rgb8, px * 3);
-    if (out_host) stage.out(&d_out, display_out, px * 12);
+    StagedOutputs out(stage, px, rgb8, rgb8_on_device, display_out, display_out_on_device);
     const int sst = stage.commit(stream, nullptr);
     if (sst != FF_OK) return sst;
-    for (int j = 1; j <= levels; ++j) level[j].texels = (float4*)((char*)s->d_disp_work + level_at[j]);
+    for (int j = 1; j <= levels; ++j) level[j].texels = (float4*)((char*)s->d_img_work + level_at[j]);
     // steps 1 and 2
     uint32_t hist[kDisplayBins] = {};
     if (automatic) {
@@ -204,7 +202,7 @@ int display_run(FfState* s, int width, int height, const FfDisplayParams* p, con
         a.u1_w = level[1].w;
         a.u1_h = level[1].h;
     }
-    if (d_rgb8 || d_out) FF_HIP(launch_display(a, d_in, d_rgb8, d_out, stream));
+    if (out.rgb8 || out.radiance) FF_HIP(launch_display(a, d_in, out.rgb8, out.radiance, stream));
     FF_HIP(hipStreamSynchronize(stream));
     const int fst = stage.finish();
     if (fst != FF_OK) return fst;
@@ -226,8 +224,7 @@ int check_display_call(FfState* s, int width, int height, const FfDisplayParams*
     const int st = check_params(p, who);
     if (st != FF_OK) return st;
     if (!radiance_in) return fail(FF_ERR_INVALID_ARG, "%s: radiance_in is null", who);
-    if (width < 1 || height < 1 || width > 65535 || height > 65535) return fail(FF_ERR_INVALID_ARG, "%s: image size %dx%d is invalid", who, width, height);
-    return FF_OK;
+    return check_image_size(width, height, who);
 }
 
 } // namespace
@@ -237,9 +234,8 @@ namespace ff {
 void display_release(FfState* s)
 {
     if (s->d_disp_const) (void)hipFree(s->d_disp_const);
-    if (s->d_disp_work) (void)hipFree(s->d_disp_work);
-    s->d_disp_const = s->d_disp_work = nullptr;
-    s->disp_const_bytes = s->disp_work_bytes = 0;
+    s->d_disp_const = nullptr;
+    s->disp_const_bytes = 0;
 }
 
 } // namespace ff

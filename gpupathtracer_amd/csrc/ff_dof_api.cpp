@@ -1,7 +1,7 @@
 // ff_dof_api.cpp — host side of ff_depth_of_field (include/firefly/ff_api.h): the argument checks, the parameters of a thin lens
-// (ff_dof_params_from_camera) and the entry points.  The work buffer, the staging of host buffers, the three launches (kernels in
-// ff_dof.hip) and the loops of the host-only twin ff_depth_of_field_host are ff_tile_filter.h's, over ff_dof.h's per-pixel
-// functions.  A pure image operation: no scene, no history, nothing kept in the state but the work buffer.
+// (ff_dof_params_from_camera) and the entry points.  The use of the state's image work buffer, the staging of host buffers, the
+// three launches (kernels in ff_dof.hip) and the loops of the host-only twin ff_depth_of_field_host are ff_tile_filter.h's, over
+// ff_dof.h's per-pixel functions.  A pure image operation: no scene, no history, nothing kept in the state.
 #include <cmath>
 
 #include <hip/hip_runtime.h>
@@ -42,9 +42,8 @@ int check_dof(const FfCamera* camera, int width, int height, const FfDofParams* 
     if (!position) return fail(FF_ERR_INVALID_ARG, "%s: position is null", who);
     if (!depth) return fail(FF_ERR_INVALID_ARG, "%s: depth is null", who);
     const size_t px = (size_t)width * (size_t)height;
-    const Span out[2] = { { rgb8, px * 3, "rgb8" }, { radiance_out, px * 12, "radiance_out" } };
-    const Span in[3] = { { radiance_in, px * 12, "radiance_in" }, { position, px * 12, "position" }, { depth, px * 4, "depth" } };
-    if (check_disjoint(out, in, who) != FF_OK) return FF_ERR_INVALID_ARG;
+    if (check_outputs_disjoint(rgb8, radiance_out, px, { { radiance_in, px * 12, "radiance_in" }, { position, px * 12, "position" }, { depth, px * 4, "depth" } }, who) != FF_OK)
+        return FF_ERR_INVALID_ARG;
     a->grid = make_tile_grid(width, height, p->max_radius);
     a->g = p->grid;
     a->fi = 1.f / p->focus_distance;
@@ -58,17 +57,6 @@ int check_dof(const FfCamera* camera, int width, int height, const FfDofParams* 
 }
 
 } // namespace
-
-namespace ff {
-
-void dof_release(FfState* s)
-{
-    if (s->d_dof_work) (void)hipFree(s->d_dof_work);
-    s->d_dof_work = nullptr;
-    s->dof_work_bytes = 0;
-}
-
-} // namespace ff
 
 extern "C" {
 
@@ -115,8 +103,8 @@ int ff_depth_of_field(FfState* s, const FfCamera* camera, int width, int height,
     DofArgs a;
     const int st = check_dof(camera, width, height, p, radiance_in, position, depth, rgb8, radiance_out, &a, "ff_depth_of_field");
     if (st != FF_OK) return st;
-    return tile_filter_device<DofFilter>(s, &s->d_dof_work, &s->dof_work_bytes, a, radiance_in, position, depth, inputs_on_device, rgb8, rgb8_on_device, radiance_out,
-                                         radiance_out_on_device, "ff_depth_of_field");
+    return tile_filter_device<DofFilter>(s, a, radiance_in, position, depth, inputs_on_device, rgb8, rgb8_on_device, radiance_out, radiance_out_on_device,
+                                         "ff_depth_of_field");
 }
 
 int ff_depth_of_field_host(const FfCamera* camera, int width, int height, const FfDofParams* p, const float* radiance_in, const float* position,

@@ -1,9 +1,10 @@
 // ff_image.h — what the image-space entry points (ff_image_api.cpp: ff_gbuffer, ff_denoise, ff_denoise_temporal, ff_taa;
-// ff_display_api.cpp; the gather filters ff_motion_blur_api.cpp and ff_dof_api.cpp) keep in the tracer state and share: the
-// staging of host buffers, the gather filters' size and overlap checks, and the reprojection history.  Nothing here reaches a
-// trace kernel.
+// ff_display_api.cpp; ff_upscale_api.cpp; the filters of the ff_*_api.cpp files behind them) keep in the tracer state and share:
+// the staging of host buffers through the state's one image work buffer, the size and overlap checks, and the reprojection
+// history.  Nothing here reaches a trace kernel.
 #pragma once
 
+#include <initializer_list>
 #include <vector>
 
 #include <hip/hip_runtime.h>
@@ -14,7 +15,8 @@ namespace ff {
 
 struct TemporalGeom; // ff_temporal.h
 
-// Host buffers travel through a device buffer the state owns, in 16-byte aligned pieces from `first_byte` on.  The caller names
+// Host buffers travel through a device buffer the state owns (FfState::d_img_work for every image-space entry point; the bytes
+// before `first_byte` are the entry point's own scratch), in 16-byte aligned pieces from `first_byte` on.  The caller names
 // its pieces once - in(): copied to the device by commit(), out(): copied back by finish() - so the size of the buffer and every
 // piece's place in it come from the same list.  commit() grows the buffer, stores each piece's device address through the pointer
 // it was registered with and enqueues the copies in; finish() runs after the caller's synchronize.
@@ -46,7 +48,23 @@ private:
     std::vector<Piece> pieces;
 };
 
-// What the gather filters (ff_motion_blur, ff_depth_of_field) refuse before they look at a buffer: an image size out of range ...
+// The two optional outputs of an image filter of `px` output pixels, as the kernel gets them: the caller's device pointers, or
+// pieces of `stage` that finish() copies back to the caller's host buffers.  Null stays null.  (Not copyable: commit() stores the
+// pieces' addresses through the two members.)
+struct StagedOutputs {
+    unsigned char* rgb8;
+    float* radiance;
+    StagedOutputs(Staging& stage, size_t px, void* rgb8_out, int rgb8_on_device, float* radiance_out, int radiance_out_on_device)
+        : rgb8((unsigned char*)rgb8_out), radiance(radiance_out)
+    {
+        if (rgb8_out && !rgb8_on_device) stage.out(&rgb8, rgb8_out, px * 3);
+        if (radiance_out && !radiance_out_on_device) stage.out(&radiance, radiance_out, px * 12);
+    }
+    StagedOutputs(const StagedOutputs&) = delete;
+    StagedOutputs& operator=(const StagedOutputs&) = delete;
+};
+
+// What the filters refuse before they look at a buffer: an image size out of range ...
 inline int check_image_size(int width, int height, const char* who)
 {
     if (width < 1 || height < 1 || width > 65535 || height > 65535) return fail(FF_ERR_INVALID_ARG, "%s: image size %dx%d is invalid", who, width, height);
@@ -68,13 +86,20 @@ inline bool overlaps(const Span& a, const Span& b)
     return p < q + b.bytes && q < p + a.bytes;
 }
 
-inline int check_disjoint(const Span (&outs)[2], const Span (&ins)[3], const char* who)
+inline int check_disjoint(const Span (&outs)[2], std::initializer_list<Span> ins, const char* who)
 {
     for (const Span& o : outs)
         for (const Span& i : ins)
             if (o.ptr && overlaps(o, i)) return fail(FF_ERR_INVALID_ARG, "%s: %s overlaps %s", who, o.name, i.name);
     if (outs[0].ptr && outs[1].ptr && overlaps(outs[0], outs[1])) return fail(FF_ERR_INVALID_ARG, "%s: %s overlaps %s", who, outs[0].name, outs[1].name);
     return FF_OK;
+}
+
+// ... for the usual pair of outputs: rgb8 and radiance_out of `px` pixels.
+inline int check_outputs_disjoint(const void* rgb8, const float* radiance_out, size_t px, std::initializer_list<Span> ins, const char* who)
+{
+    const Span outs[2] = { { rgb8, px * 3, "rgb8" }, { radiance_out, px * 12, "radiance_out" } };
+    return check_disjoint(outs, ins, who);
 }
 
 // What the reprojecting filters and ff_interpolate prepare on the host (ff_image_api.cpp): the inverse of a 4x4 matrix in double

@@ -203,8 +203,7 @@ int check_image_call(const FfState* s, bool takes_camera, const FfCamera* camera
     if (!s) return fail(FF_ERR_INVALID_ARG, "%s: state is null", who);
     if (takes_camera && !camera) return fail(FF_ERR_INVALID_ARG, "%s: camera is null", who);
     if (!params) return fail(FF_ERR_INVALID_ARG, "%s: params are null", who);
-    if (width <= 0 || height <= 0 || width > 65535 || height > 65535) return fail(FF_ERR_INVALID_ARG, "%s: image size %dx%d is invalid", who, width, height);
-    return FF_OK;
+    return check_image_size(width, height, who);
 }
 
 int check_iterations(int iterations, const char* who)
@@ -286,7 +285,7 @@ int history_readback(FfState* s, int which, const char* who, const char* filter,
     const size_t px = (size_t)h.width * (size_t)h.height;
     float* d_motion = motion;
     float* d_length = length;
-    Staging stage(&s->d_img_stage, &s->img_stage_bytes);
+    Staging stage(&s->d_img_work, &s->img_work_bytes);
     if (!on_device && motion) stage.out(&d_motion, motion, px * 8);
     if (!on_device && length) stage.out(&d_length, length, px * 4);
     const int st = stage.commit(s->stream, nullptr);
@@ -336,7 +335,7 @@ int ff_gbuffer(FfState* s, const FfCamera* camera, const FfRenderParams* params,
     r.normal = normal;
     r.albedo = albedo;
     r.ids = ids;
-    Staging stage(&s->d_img_stage, &s->img_stage_bytes);
+    Staging stage(&s->d_img_work, &s->img_work_bytes);
     if (!on_device) {
         if (depth) stage.out(&r.depth, depth, px * 4);
         if (position) stage.out(&r.position, position, px * 12);
@@ -389,9 +388,7 @@ int ff_denoise(FfState* s, int width, int height, const FfDenoiseParams* dn, con
     const float* d_nrm = normal;
     const float* d_alb = demod ? albedo : nullptr;
     const int* d_ids = ids;
-    unsigned char* d_rgb8 = (unsigned char*)rgb8;
-    float* d_out = radiance_out;
-    Staging stage(&s->d_img_stage, &s->img_stage_bytes);
+    Staging stage(&s->d_img_work, &s->img_work_bytes);
     if (!inputs_on_device) {
         stage.in(&d_rad, radiance_in, px * 12);
         if (filter) {
@@ -401,8 +398,7 @@ int ff_denoise(FfState* s, int width, int height, const FfDenoiseParams* dn, con
             stage.in(&d_ids, ids, px * 12);
         }
     }
-    if (rgb8 && !rgb8_on_device) stage.out(&d_rgb8, rgb8, px * 3);
-    if (radiance_out && !radiance_out_on_device) stage.out(&d_out, radiance_out, px * 12);
+    StagedOutputs out(stage, px, rgb8, rgb8_on_device, radiance_out, radiance_out_on_device);
     st = stage.commit(stream, "ff_denoise: staging the inputs failed");
     if (st != FF_OK) return st;
     DenoiseBuffers b;
@@ -427,7 +423,7 @@ int ff_denoise(FfState* s, int width, int height, const FfDenoiseParams* dn, con
             src = 1 - src;
         }
     }
-    FF_HIP(launch_denoise_finish(b, src, d_rad, d_alb, demod, d_rgb8, d_out, stream));
+    FF_HIP(launch_denoise_finish(b, src, d_rad, d_alb, demod, out.rgb8, out.radiance, stream));
     FF_HIP(hipStreamSynchronize(stream));
     return stage.finish();
 }
@@ -479,9 +475,7 @@ int ff_denoise_temporal(FfState* s, const FfCamera* camera, int width, int heigh
     const float* d_nrm = normal;
     const float* d_alb = demod ? albedo : nullptr;
     const int* d_ids = ids;
-    unsigned char* d_rgb8 = (unsigned char*)rgb8;
-    float* d_out = radiance_out;
-    Staging stage(&s->d_img_stage, &s->img_stage_bytes);
+    Staging stage(&s->d_img_work, &s->img_work_bytes);
     if (!inputs_on_device) {
         stage.in(&d_rad, radiance_in, px * 12);
         stage.in(&d_pos, position, px * 12);
@@ -489,8 +483,7 @@ int ff_denoise_temporal(FfState* s, const FfCamera* camera, int width, int heigh
         if (demod) stage.in(&d_alb, albedo, px * 12);
         stage.in(&d_ids, ids, px * 12);
     }
-    if (rgb8 && !rgb8_on_device) stage.out(&d_rgb8, rgb8, px * 3);
-    if (radiance_out && !radiance_out_on_device) stage.out(&d_out, radiance_out, px * 12);
+    StagedOutputs out(stage, px, rgb8, rgb8_on_device, radiance_out, radiance_out_on_device);
     st = stage.commit(stream, "ff_denoise_temporal: staging the inputs failed");
     if (st != FF_OK) return st;
     // history: kept only for the same image size (a new size, a reset or a new scene start afresh)
@@ -541,7 +534,7 @@ int ff_denoise_temporal(FfState* s, const FfCamera* camera, int width, int heigh
     fb.guide_nrm = b.nrm[r.cur];
     fb.color[0] = b.work[src];
     fb.color[1] = b.work[1 - src];
-    FF_HIP(launch_denoise_finish(fb, 0, d_rad, d_alb, demod, d_rgb8, d_out, stream));
+    FF_HIP(launch_denoise_finish(fb, 0, d_rad, d_alb, demod, out.rgb8, out.radiance, stream));
     FF_HIP(hipStreamSynchronize(stream));
     hist.commit(s->h_geoms, camera, width, height, f);
     return stage.finish();
@@ -593,9 +586,7 @@ int ff_taa(FfState* s, const FfCamera* camera, int width, int height, const FfTa
     const float* d_rad = radiance_in;
     const float* d_pos = position;
     const int* d_ids = ids;
-    unsigned char* d_rgb8 = (unsigned char*)rgb8;
-    float* d_out = radiance_out;
-    Staging stage(&s->d_img_stage, &s->img_stage_bytes);
+    Staging stage(&s->d_img_work, &s->img_work_bytes);
     if (in_host) {
         stage.in(&d_rad, radiance_in, px * 12);
         stage.in(&d_pos, position, px * 12);
@@ -603,8 +594,7 @@ int ff_taa(FfState* s, const FfCamera* camera, int width, int height, const FfTa
     } else if (alias) {
         stage.in(&d_rad, radiance_in, px * 12, hipMemcpyDeviceToDevice);
     }
-    if (rgb8 && !rgb8_on_device) stage.out(&d_rgb8, rgb8, px * 3);
-    if (out_host) stage.out(&d_out, radiance_out, px * 12);
+    StagedOutputs out(stage, px, rgb8, rgb8_on_device, radiance_out, radiance_out_on_device);
     st = stage.commit(stream, in_host ? "ff_taa: staging the inputs failed" : "ff_taa: copying the input failed");
     if (st != FF_OK) return st;
     // history: kept only for the same image size (a new size, a reset or a new scene start afresh); the per-geometry table holds
@@ -634,7 +624,7 @@ int ff_taa(FfState* s, const FfCamera* camera, int width, int height, const FfTa
         a.prev_screen_w = hist.camera.m_screenWidth;
         a.prev_screen_h = hist.camera.m_screenHeight;
     }
-    FF_HIP(launch_taa(a, d_rad, d_pos, d_ids, d_rgb8, d_out, stream));
+    FF_HIP(launch_taa(a, d_rad, d_pos, d_ids, out.rgb8, out.radiance, stream));
     FF_HIP(hipStreamSynchronize(stream));
     hist.commit(s->h_geoms, camera, width, height, f);
     return stage.finish();
@@ -710,17 +700,14 @@ int ff_taa_upscale(FfState* s, const FfCamera* camera, const FfTaaUpscaleParams*
     const int* d_ids_lo = ids_lo;
     const float* d_pos = position;
     const int* d_ids = ids;
-    unsigned char* d_rgb8 = (unsigned char*)rgb8;
-    float* d_out = radiance_out;
-    Staging stage(&s->d_img_stage, &s->img_stage_bytes);
+    Staging stage(&s->d_img_work, &s->img_work_bytes);
     if (!inputs_on_device) {
         stage.in(&d_rad, radiance_lo, lo_px * 12);
         stage.in(&d_ids_lo, ids_lo, lo_px * 12);
         stage.in(&d_pos, position, px * 12);
         stage.in(&d_ids, ids, px * 12);
     }
-    if (rgb8 && !rgb8_on_device) stage.out(&d_rgb8, rgb8, px * 3);
-    if (radiance_out && !radiance_out_on_device) stage.out(&d_out, radiance_out, px * 12);
+    StagedOutputs out(stage, px, rgb8, rgb8_on_device, radiance_out, radiance_out_on_device);
     int st = stage.commit(stream, "ff_taa_upscale: staging the inputs failed");
     if (st != FF_OK) return st;
     // history: ff_taa's, on the high grid; kept only while both sizes stay what they were
@@ -758,7 +745,7 @@ int ff_taa_upscale(FfState* s, const FfCamera* camera, const FfTaaUpscaleParams*
     a.lo_jy = p->lo_jitter[1];
     a.sx = (float)width / (float)lo_width;
     a.sy = (float)height / (float)lo_height;
-    FF_HIP(launch_taa_upscale(a, d_rad, d_ids_lo, d_pos, d_ids, d_rgb8, d_out, stream));
+    FF_HIP(launch_taa_upscale(a, d_rad, d_ids_lo, d_pos, d_ids, out.rgb8, out.radiance, stream));
     FF_HIP(hipStreamSynchronize(stream));
     hist.commit(s->h_geoms, camera, width, height, f);
     s->taa_upscale_lo_width = lo_width;

@@ -1,8 +1,8 @@
 // ff_interpolate_api.cpp — host side of ff_interpolate (include/firefly/ff_api.h): the argument checks, what is prepared in double on
-// the host (the cameras' inverse ray matrices, the pixel size, the geometry table), the work buffer (the five counts, the {rgb, state}
-// work image, then the staging of host buffers through ff_image.h's helpers), the two launches (kernels in ff_interpolate.hip), the
-// loops of the host-only twin ff_interpolate_host over ff_interpolate.h's per-pixel functions, and ff_interpolate_geometry_maps.  A
-// pure image operation: no scene, no history, nothing kept in the state but the work buffer.
+// the host (the cameras' inverse ray matrices, the pixel size, the geometry table), its use of the state's image work buffer (the five
+// counts, the {rgb, state} work image, then the staging of host buffers through ff_image.h's helpers), the two launches (kernels in
+// ff_interpolate.hip), the loops of the host-only twin ff_interpolate_host over ff_interpolate.h's per-pixel functions, and
+// ff_interpolate_geometry_maps.  A pure image operation: no scene, no history, nothing kept in the state.
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -51,15 +51,13 @@ int check_interpolate(int width, int height, const FfInterpolateParams* p, const
     }
     if (geom_maps && num_geometries <= 0) return fail(FF_ERR_INVALID_ARG, "%s: geom_maps given with num_geometries %d", who, num_geometries);
     const size_t px = (size_t)width * (size_t)height;
-    const Span outs[2] = { { rgb8, px * 3, "rgb8" }, { radiance_out, px * 12, "radiance_out" } };
-    const Span ins[8] = { { b.position[0], px * 12, "position" },     { b.ids[0], px * 12, "ids" },
-                          { b.radiance[0], px * 12, "radiance_a" },   { b.position[1], px * 12, "position_a" },
-                          { b.ids[1], px * 12, "ids_a" },             { b.radiance[1], px * 12, "radiance_b" },
-                          { b.position[2], px * 12, "position_b" },   { b.ids[2], px * 12, "ids_b" } };
-    for (const Span& o : outs)
-        for (const Span& i : ins)
-            if (o.ptr && overlaps(o, i)) return fail(FF_ERR_INVALID_ARG, "%s: %s overlaps %s", who, o.name, i.name);
-    if (outs[0].ptr && outs[1].ptr && overlaps(outs[0], outs[1])) return fail(FF_ERR_INVALID_ARG, "%s: rgb8 overlaps radiance_out", who);
+    if (check_outputs_disjoint(rgb8, radiance_out, px,
+                               { { b.position[0], px * 12, "position" },   { b.ids[0], px * 12, "ids" },
+                                 { b.radiance[0], px * 12, "radiance_a" }, { b.position[1], px * 12, "position_a" },
+                                 { b.ids[1], px * 12, "ids_a" },           { b.radiance[1], px * 12, "radiance_b" },
+                                 { b.position[2], px * 12, "position_b" }, { b.ids[2], px * 12, "ids_b" } },
+                               who) != FF_OK)
+        return FF_ERR_INVALID_ARG;
 
     a->width = width;
     a->height = height;
@@ -114,17 +112,6 @@ void set_buffers(InterpArgs* a, const InterpBuffers& b)
 
 } // namespace
 
-namespace ff {
-
-void interpolate_release(FfState* s)
-{
-    if (s->d_interpolate_work) (void)hipFree(s->d_interpolate_work);
-    s->d_interpolate_work = nullptr;
-    s->interpolate_work_bytes = 0;
-}
-
-} // namespace ff
-
 extern "C" {
 
 void ff_interpolate_params_init(FfInterpolateParams* p)
@@ -153,9 +140,7 @@ int ff_interpolate(FfState* s, int width, int height, const FfInterpolateParams*
     FF_HIP(hipSetDevice(s->device));
     hipStream_t stream = s->stream;
     const size_t px = (size_t)width * (size_t)height;
-    unsigned char* d_rgb8 = (unsigned char*)rgb8;
-    float* d_out = radiance_out;
-    Staging stage(&s->d_interpolate_work, &s->interpolate_work_bytes, kCountBytes + px * sizeof(float4));
+    Staging stage(&s->d_img_work, &s->img_work_bytes, kCountBytes + px * sizeof(float4));
     if (!table.empty()) stage.in(&a.maps, table.data(), table.size() * sizeof(InterpMap));
     if (!inputs_on_device) {
         for (int i = 0; i < 3; ++i) {
@@ -164,15 +149,14 @@ int ff_interpolate(FfState* s, int width, int height, const FfInterpolateParams*
         }
         for (int S = 0; S < 2; ++S) stage.in(&b.radiance[S], b.radiance[S], px * 12);
     }
-    if (rgb8 && !rgb8_on_device) stage.out(&d_rgb8, rgb8, px * 3);
-    if (radiance_out && !radiance_out_on_device) stage.out(&d_out, radiance_out, px * 12);
+    StagedOutputs out(stage, px, rgb8, rgb8_on_device, radiance_out, radiance_out_on_device);
     const int staged = stage.commit(stream, "ff_interpolate: staging the inputs failed");
     if (staged != FF_OK) return staged;
     set_buffers(&a, b);
-    uint32_t* d_count = (uint32_t*)s->d_interpolate_work;
-    float4* d_work = (float4*)((char*)s->d_interpolate_work + kCountBytes);
+    uint32_t* d_count = (uint32_t*)s->d_img_work;
+    float4* d_work = (float4*)((char*)s->d_img_work + kCountBytes);
     FF_HIP(hipMemsetAsync(d_count, 0, kCountBytes, stream));
-    FF_HIP(launch_interpolate(a, d_work, d_rgb8, d_out, d_count, stream));
+    FF_HIP(launch_interpolate(a, d_work, out.rgb8, out.radiance, d_count, stream));
     FF_HIP(hipStreamSynchronize(stream));
     if (counts) FF_HIP(hipMemcpy(counts, d_count, 5 * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return stage.finish();

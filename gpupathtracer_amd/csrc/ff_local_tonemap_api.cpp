@@ -1,7 +1,7 @@
-// ff_local_tonemap_api.cpp — host side of ff_local_tonemap (include/firefly/ff_api.h): the argument checks, the work buffer (the
-// two grids, then the staging of host buffers through ff_image.h's helpers), the launches (kernels in ff_local_tonemap.hip) and
-// the loops of the host-only twins ff_local_tonemap_host and ff_local_tonemap_grid_host over ff_local_tonemap.h's functions.  A
-// pure image operation: no scene, no G-buffer, no history, nothing kept in the state but the work buffer.
+// ff_local_tonemap_api.cpp — host side of ff_local_tonemap (include/firefly/ff_api.h): the argument checks, its use of the state's
+// image work buffer (the two grids, then the staging of host buffers through ff_image.h's helpers), the launches (kernels in
+// ff_local_tonemap.hip) and the loops of the host-only twins ff_local_tonemap_host and ff_local_tonemap_grid_host over
+// ff_local_tonemap.h's functions.  A pure image operation: no scene, no G-buffer, no history, nothing kept in the state.
 #include <cmath>
 #include <vector>
 
@@ -56,14 +56,13 @@ int check_ltm(int width, int height, const FfLocalTonemapParams* p, const float*
     const int st = check_ltm_params(width, height, p, radiance_in, a, who);
     if (st != FF_OK) return st;
     const size_t px = (size_t)width * (size_t)height;
-    const Span out[2] = { { rgb8, px * 3, "rgb8" }, { radiance_out, px * 12, "radiance_out" } };
+    const Span in = { radiance_in, px * 12, "radiance_in" };
     // (in place: every pixel is read before it is written, and the grid is complete before any pixel is written)
-    const Span in[3] = { { radiance_in, px * 12, "radiance_in" }, { nullptr, 0, "" }, { nullptr, 0, "" } };
     if (radiance_out == radiance_in) {
-        if (rgb8 && overlaps(out[0], in[0])) return fail(FF_ERR_INVALID_ARG, "%s: rgb8 overlaps radiance_in", who);
+        if (rgb8 && overlaps({ rgb8, px * 3, "rgb8" }, in)) return fail(FF_ERR_INVALID_ARG, "%s: rgb8 overlaps radiance_in", who);
         return FF_OK;
     }
-    return check_disjoint(out, in, who);
+    return check_outputs_disjoint(rgb8, radiance_out, px, { in }, who);
 }
 
 // Steps 1 and 2 on the host: the grid of int32 cells.
@@ -101,17 +100,6 @@ void ltm_blur_host(const LtmArgs& a, int axis, const std::vector<LtmCellF>& src,
 
 } // namespace
 
-namespace ff {
-
-void local_tonemap_release(FfState* s)
-{
-    if (s->d_ltm_work) (void)hipFree(s->d_ltm_work);
-    s->d_ltm_work = nullptr;
-    s->ltm_work_bytes = 0;
-}
-
-} // namespace ff
-
 extern "C" {
 
 void ff_local_tonemap_params_init(FfLocalTonemapParams* p)
@@ -137,17 +125,14 @@ int ff_local_tonemap(FfState* s, int width, int height, const FfLocalTonemapPara
     FF_HIP(hipSetDevice(s->device));
     hipStream_t stream = s->stream;
     const size_t px = (size_t)width * (size_t)height;
-    unsigned char* d_rgb8 = (unsigned char*)rgb8;
-    float* d_out = radiance_out;
     // the two grids at the head of the work buffer (none for a copy); the staging follows from a multiple of 16 bytes on
     const size_t grid_bytes = a.identity ? 0 : 2 * ltm_grid_cells(a) * sizeof(LtmCellF);
-    Staging stage(&s->d_ltm_work, &s->ltm_work_bytes, (grid_bytes + 15) & ~(size_t)15);
+    Staging stage(&s->d_img_work, &s->img_work_bytes, (grid_bytes + 15) & ~(size_t)15);
     if (!input_on_device) stage.in(&radiance_in, radiance_in, px * 12);
-    if (rgb8 && !rgb8_on_device) stage.out(&d_rgb8, rgb8, px * 3);
-    if (radiance_out && !radiance_out_on_device) stage.out(&d_out, radiance_out, px * 12);
+    StagedOutputs out(stage, px, rgb8, rgb8_on_device, radiance_out, radiance_out_on_device);
     const int staged = stage.commit(stream, "ff_local_tonemap: staging the input failed");
     if (staged != FF_OK) return staged;
-    FF_HIP(launch_local_tonemap(a, radiance_in, s->d_ltm_work, d_rgb8, d_out, stream));
+    FF_HIP(launch_local_tonemap(a, radiance_in, s->d_img_work, out.rgb8, out.radiance, stream));
     FF_HIP(hipStreamSynchronize(stream));
     return stage.finish();
 }

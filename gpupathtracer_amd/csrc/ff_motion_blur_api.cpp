@@ -1,7 +1,7 @@
-// ff_motion_blur_api.cpp — host side of ff_motion_blur (include/firefly/ff_api.h): the argument checks and the entry points.  The work
-// buffer, the staging of host buffers, the three launches (kernels in ff_motion_blur.hip) and the loops of the host-only twin
-// ff_motion_blur_host are ff_tile_filter.h's, over ff_motion_blur.h's per-pixel functions.  A pure image operation: no scene, no
-// history, nothing kept in the state but the work buffer.
+// ff_motion_blur_api.cpp — host side of ff_motion_blur (include/firefly/ff_api.h): the argument checks and the entry points.  The use
+// of the state's image work buffer, the staging of host buffers, the three launches (kernels in ff_motion_blur.hip) and the loops of
+// the host-only twin ff_motion_blur_host are ff_tile_filter.h's, over ff_motion_blur.h's per-pixel functions.  A pure image
+// operation: no scene, no history, nothing kept in the state.
 #include <cmath>
 
 #include <hip/hip_runtime.h>
@@ -31,9 +31,8 @@ int check_motion_blur(int width, int height, const FfMotionBlurParams* p, const 
     if (!motion) return fail(FF_ERR_INVALID_ARG, "%s: motion is null", who);
     if (!depth) return fail(FF_ERR_INVALID_ARG, "%s: depth is null", who);
     const size_t px = (size_t)width * (size_t)height;
-    const Span out[2] = { { rgb8, px * 3, "rgb8" }, { radiance_out, px * 12, "radiance_out" } };
-    const Span in[3] = { { radiance_in, px * 12, "radiance_in" }, { motion, px * 8, "motion" }, { depth, px * 4, "depth" } };
-    if (check_disjoint(out, in, who) != FF_OK) return FF_ERR_INVALID_ARG;
+    if (check_outputs_disjoint(rgb8, radiance_out, px, { { radiance_in, px * 12, "radiance_in" }, { motion, px * 8, "motion" }, { depth, px * 4, "depth" } }, who) != FF_OK)
+        return FF_ERR_INVALID_ARG;
     a->grid = make_tile_grid(width, height, p->max_radius);
     a->samples = p->samples;
     a->half_shutter = 0.5f * p->shutter;
@@ -42,17 +41,6 @@ int check_motion_blur(int width, int height, const FfMotionBlurParams* p, const 
 }
 
 } // namespace
-
-namespace ff {
-
-void motion_blur_release(FfState* s)
-{
-    if (s->d_mblur_work) (void)hipFree(s->d_mblur_work);
-    s->d_mblur_work = nullptr;
-    s->mblur_work_bytes = 0;
-}
-
-} // namespace ff
 
 extern "C" {
 
@@ -76,8 +64,8 @@ int ff_motion_blur(FfState* s, int width, int height, const FfMotionBlurParams* 
     MotionBlurArgs a;
     const int st = check_motion_blur(width, height, p, radiance_in, motion, depth, rgb8, radiance_out, &a, "ff_motion_blur");
     if (st != FF_OK) return st;
-    return tile_filter_device<MotionBlurFilter>(s, &s->d_mblur_work, &s->mblur_work_bytes, a, radiance_in, motion, depth, inputs_on_device, rgb8, rgb8_on_device,
-                                                radiance_out, radiance_out_on_device, "ff_motion_blur");
+    return tile_filter_device<MotionBlurFilter>(s, a, radiance_in, motion, depth, inputs_on_device, rgb8, rgb8_on_device, radiance_out, radiance_out_on_device,
+                                                "ff_motion_blur");
 }
 
 int ff_motion_blur_host(int width, int height, const FfMotionBlurParams* p, const float* radiance_in, const float* motion, const float* depth,

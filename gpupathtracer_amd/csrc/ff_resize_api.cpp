@@ -1,6 +1,6 @@
 // ff_resize_api.cpp — host side of ff_resize (include/firefly/ff_api.h): the argument checks, the per-axis tables (computed here in
-// double, cached in the state under their key), the intermediate image and the staging of host buffers (ff_image.h's helpers), the
-// two launches (kernels in ff_resize.hip) and the loops of the host-only twin ff_resize_host over ff_resize.h's per-tap functions.
+// double, cached in the state under their key), the intermediate image, the staging of host buffers in the state's image work
+// buffer (ff_image.h's helpers), the two launches (kernels in ff_resize.hip) and the loops of the host-only twin ff_resize_host over ff_resize.h's per-tap functions.
 // A pure image operation: no scene, no G-buffer, no history.
 #include <cmath>
 #include <vector>
@@ -98,9 +98,7 @@ int check_resize(const FfResizeParams* p, int in_width, int in_height, const flo
     if (p->reserved != 0) return fail(FF_ERR_INVALID_ARG, "%s: reserved must be 0", who);
     if (!radiance_in) return fail(FF_ERR_INVALID_ARG, "%s: radiance_in is null", who);
     const size_t in_px = (size_t)in_width * (size_t)in_height, out_px = (size_t)out_width * (size_t)out_height;
-    const Span out[2] = { { rgb8, out_px * 3, "rgb8" }, { radiance_out, out_px * 12, "radiance_out" } };
-    const Span in[3] = { { radiance_in, in_px * 12, "radiance_in" }, { nullptr, 0, "" }, { nullptr, 0, "" } };
-    return check_disjoint(out, in, who);
+    return check_outputs_disjoint(rgb8, radiance_out, out_px, { { radiance_in, in_px * 12, "radiance_in" } }, who);
 }
 
 // One pass of the twin over one axis: `count` lines of n samples (of 3 floats, `step` samples apart, lines `line` samples apart)
@@ -188,9 +186,8 @@ namespace ff {
 void resize_release(FfState* s)
 {
     if (s->d_resize_mid) (void)hipFree(s->d_resize_mid);
-    if (s->d_resize_work) (void)hipFree(s->d_resize_work);
-    s->d_resize_mid = s->d_resize_work = nullptr;
-    s->resize_mid_bytes = s->resize_work_bytes = 0;
+    s->d_resize_mid = nullptr;
+    s->resize_mid_bytes = 0;
     for (FfState::ResizeTable& t : s->resize_table) {
         if (t.d_table) (void)hipFree(t.d_table);
         t = FfState::ResizeTable();
@@ -249,15 +246,12 @@ int ff_resize(FfState* s, const FfResizeParams* p, int in_width, int in_height, 
     const int mst = ensure_bytes(&s->d_resize_mid, &s->resize_mid_bytes, (size_t)out_width * (size_t)in_height * 12);
     if (mst != FF_OK) return mst;
     const size_t in_px = (size_t)in_width * (size_t)in_height, out_px = (size_t)out_width * (size_t)out_height;
-    unsigned char* d_rgb8 = (unsigned char*)rgb8;
-    float* d_out = radiance_out;
-    Staging stage(&s->d_resize_work, &s->resize_work_bytes);
+    Staging stage(&s->d_img_work, &s->img_work_bytes);
     if (!input_on_device) stage.in(&radiance_in, radiance_in, in_px * 12);
-    if (rgb8 && !rgb8_on_device) stage.out(&d_rgb8, rgb8, out_px * 3);
-    if (radiance_out && !radiance_out_on_device) stage.out(&d_out, radiance_out, out_px * 12);
+    StagedOutputs out(stage, out_px, rgb8, rgb8_on_device, radiance_out, radiance_out_on_device);
     const int staged = stage.commit(stream, "ff_resize: staging the input failed");
     if (staged != FF_OK) return staged;
-    FF_HIP(launch_resize(a, radiance_in, (float*)s->d_resize_mid, d_rgb8, d_out, stream));
+    FF_HIP(launch_resize(a, radiance_in, (float*)s->d_resize_mid, out.rgb8, out.radiance, stream));
     FF_HIP(hipStreamSynchronize(stream));
     return stage.finish();
 }

@@ -1,7 +1,7 @@
-// ff_sharpen_api.cpp — host side of ff_sharpen (include/firefly/ff_api.h): the argument checks, the work buffer (the staging of
-// host buffers through ff_image.h's helpers), the one launch (kernel in ff_sharpen.hip) and the loops of the host-only twin
-// ff_sharpen_host over ff_sharpen.h's per-pixel functions.  A pure image operation: no scene, no G-buffer, no history, nothing
-// kept in the state but the work buffer.
+// ff_sharpen_api.cpp — host side of ff_sharpen (include/firefly/ff_api.h): the argument checks, the staging of host buffers in
+// the state's image work buffer (ff_image.h's helpers), the one launch (kernel in ff_sharpen.hip) and the loops of the host-only
+// twin ff_sharpen_host over ff_sharpen.h's per-pixel functions.  A pure image operation: no scene, no G-buffer, no history,
+// nothing kept in the state.
 #include <cmath>
 #include <vector>
 
@@ -27,9 +27,7 @@ int check_sharpen(int width, int height, const FfSharpenParams* p, const float* 
     if (p->reserved != 0) return fail(FF_ERR_INVALID_ARG, "%s: reserved must be 0", who);
     if (!radiance_in) return fail(FF_ERR_INVALID_ARG, "%s: radiance_in is null", who);
     const size_t px = (size_t)width * (size_t)height;
-    const Span out[2] = { { rgb8, px * 3, "rgb8" }, { radiance_out, px * 12, "radiance_out" } };
-    const Span in[3] = { { radiance_in, px * 12, "radiance_in" }, { nullptr, 0, "" }, { nullptr, 0, "" } };
-    if (check_disjoint(out, in, who) != FF_OK) return FF_ERR_INVALID_ARG;
+    if (check_outputs_disjoint(rgb8, radiance_out, px, { { radiance_in, px * 12, "radiance_in" } }, who) != FF_OK) return FF_ERR_INVALID_ARG;
     a->width = width;
     a->height = height;
     a->strength = p->strength;
@@ -60,17 +58,6 @@ void sharpen_rows(const SharpenArgs& a, const std::vector<SharpenCell>& cells, c
 
 } // namespace
 
-namespace ff {
-
-void sharpen_release(FfState* s)
-{
-    if (s->d_sharpen_work) (void)hipFree(s->d_sharpen_work);
-    s->d_sharpen_work = nullptr;
-    s->sharpen_work_bytes = 0;
-}
-
-} // namespace ff
-
 extern "C" {
 
 void ff_sharpen_params_init(FfSharpenParams* p)
@@ -93,15 +80,12 @@ int ff_sharpen(FfState* s, int width, int height, const FfSharpenParams* p, cons
     FF_HIP(hipSetDevice(s->device));
     hipStream_t stream = s->stream;
     const size_t px = (size_t)width * (size_t)height;
-    unsigned char* d_rgb8 = (unsigned char*)rgb8;
-    float* d_out = radiance_out;
-    Staging stage(&s->d_sharpen_work, &s->sharpen_work_bytes);
+    Staging stage(&s->d_img_work, &s->img_work_bytes);
     if (!input_on_device) stage.in(&radiance_in, radiance_in, px * 12);
-    if (rgb8 && !rgb8_on_device) stage.out(&d_rgb8, rgb8, px * 3);
-    if (radiance_out && !radiance_out_on_device) stage.out(&d_out, radiance_out, px * 12);
+    StagedOutputs out(stage, px, rgb8, rgb8_on_device, radiance_out, radiance_out_on_device);
     const int staged = stage.commit(stream, "ff_sharpen: staging the input failed");
     if (staged != FF_OK) return staged;
-    FF_HIP(launch_sharpen(a, radiance_in, d_rgb8, d_out, stream));
+    FF_HIP(launch_sharpen(a, radiance_in, out.rgb8, out.radiance, stream));
     FF_HIP(hipStreamSynchronize(stream));
     return stage.finish();
 }

@@ -113,13 +113,17 @@ struct FfState {
     float* d_mean = nullptr;
     size_t mean_bytes = 0;
     int accum_width = 0, accum_height = 0, accum_frames = 0;
+    // The image work buffer, the one device buffer every image-space entry point (ff_gbuffer, the denoisers, ff_taa*, ff_upscale,
+    // ff_display, ff_motion_blur, ff_depth_of_field, ff_despeckle, ff_sharpen, ff_local_tonemap, ff_interpolate, ff_encode_yuv,
+    // ff_resize) works in: the running entry point's own scratch at the head (counts, grids, a packed plane, the bloom pyramid; each
+    // *_api.cpp says what), the staging of host buffers behind it (ff::Staging).  Grown on demand, and nothing in it outlives the
+    // call that put it there.  Not reset by uploads.
+    void* d_img_work = nullptr;
+    size_t img_work_bytes = 0;
     // G-buffer and denoiser (ff_gbuffer / ff_denoise, ff_image_api.cpp, ff_denoise.hip): ff_gbuffer's own primary hits ([3][pix_items]
-    // float4, never the frame's d_primary_cache), staging for host buffers (ff::Staging), the filter's packed guides and its two
-    // colour buffers
+    // float4, never the frame's d_primary_cache), the filter's packed guides and its two colour buffers
     float4* d_gb_hits = nullptr;
     size_t gb_hits_bytes = 0;
-    void* d_img_stage = nullptr;
-    size_t img_stage_bytes = 0;
     float4* d_dn_work = nullptr; // 4 float4 per pixel: guide_pos, guide_nrm, colour 0, colour 1
     size_t dn_work_bytes = 0;
     // The reprojection histories (ff_image.h).  ff_denoise_temporal (ff_temporal.hip): two sets of 4 float4 per pixel (guide position
@@ -184,40 +188,13 @@ struct FfState {
     float* d_glossy_alpha = nullptr; // ff::NeeParams::glossy_alpha
     size_t glossy_alpha_bytes = 0;
     // display transform (ff_display, ff_display.hip): the adapted exposure, the last call's results (ff_display_state) and the
-    // device buffers - 256 histogram counters and the 255 sRGB thresholds in d_disp_const, the bloom pyramid ({rgb, 0} float4 per
-    // texel, levels 1 .. n one after another) and the staging of host buffers in d_disp_work.  Not reset by uploads.
+    // 256 histogram counters and the 255 sRGB thresholds in d_disp_const.  Not reset by uploads.
     void* d_disp_const = nullptr;
     size_t disp_const_bytes = 0;
-    void* d_disp_work = nullptr;
-    size_t disp_work_bytes = 0;
     bool disp_has_prev = false, disp_called = false;
     float disp_prev_exposure = 0.f;           // E of the last automatic call (the next one adapts from it)
     float disp_exposure = 0.f, disp_target = 0.f;
     uint32_t disp_histogram[256] = {};
-    // motion blur (ff_motion_blur): ff_tile_filter.h's work buffer under MotionBlurFilter - the packed {v, l, z} plane (one float4 per
-    // pixel), the tile and neighbour maxima (one float4 per tile each), then, from a multiple of 16 bytes on, the staging of host
-    // buffers.  Not reset by uploads.
-    void* d_mblur_work = nullptr;
-    size_t mblur_work_bytes = 0;
-    // depth of field (ff_depth_of_field): the same under DofFilter - the packed {l, z} plane (one float2 per pixel), the tile and
-    // neighbour maxima (one float per tile each), then the staging.  A buffer of its own.  Not reset by uploads.
-    void* d_dof_work = nullptr;
-    size_t dof_work_bytes = 0;
-    // firefly clamp (ff_despeckle): the partial counts of clamped pixels (ff_despeckle.h kDespeckleSlots), then the staging of host buffers.
-    // Not reset by uploads.
-    void* d_despeckle_work = nullptr;
-    size_t despeckle_work_bytes = 0;
-    // sharpening (ff_sharpen): the staging of host buffers.  Not reset by uploads.
-    void* d_sharpen_work = nullptr;
-    size_t sharpen_work_bytes = 0;
-    // local tone mapping (ff_local_tonemap): the two bilateral grids (ceil(W/s) x ceil(H/s) x 40 cells of 8 bytes each; none for a
-    // call that only copies), then, from a multiple of 16 bytes on, the staging of host buffers.  Not reset by uploads.
-    void* d_ltm_work = nullptr;
-    size_t ltm_work_bytes = 0;
-    // frame interpolation (ff_interpolate): the five counts, the {rgb, state} work image (one float4 per pixel), then the geometry
-    // table and the staging of host buffers.  Not reset by uploads.
-    void* d_interpolate_work = nullptr;
-    size_t interpolate_work_bytes = 0;
     // adaptive sampling (ff_render_adaptive, ff_adaptive_api.cpp): the two running sums (W*H*3 floats each) and behind them the
     // compact rectangle a pass renders into; per tile the error, the pass count and the list of tiles to check; the staging of host
     // buffers (ff_adaptive_tile_error's inputs, the per-pixel pass counts).  The last call's grid and per-tile results stay for
@@ -235,18 +212,14 @@ struct FfState {
         std::vector<float> tile_error;        // E_t of each tile's last check
     } adaptive;
     // video planes (ff_encode_yuv): the knot tables of the three transfers (ff_yuv.h kYuvKnotStride floats apart, each uploaded on
-    // its first use) and the staging of host buffers.  Not reset by uploads.
+    // its first use).  Not reset by uploads.
     void* d_yuv_knots = nullptr;
     bool yuv_knots_loaded[3] = { false, false, false };
-    void* d_yuv_work = nullptr;
-    size_t yuv_work_bytes = 0;
-    // resampling (ff_resize): the intermediate image of the horizontal pass (W' x H float3), the staging of host buffers and, per
-    // axis (0: horizontal, 1: vertical), the table uploaded last - first[out_size], then from a multiple of 16 bytes on the
-    // weights - with its key (in_size, out_size, filter): rebuilt and uploaded only when the key changes.  Not reset by uploads.
+    // resampling (ff_resize): the intermediate image of the horizontal pass (W' x H float3) and, per axis (0: horizontal, 1:
+    // vertical), the table uploaded last - first[out_size], then from a multiple of 16 bytes on the weights - with its key
+    // (in_size, out_size, filter): rebuilt and uploaded only when the key changes.  Not reset by uploads.
     void* d_resize_mid = nullptr;
     size_t resize_mid_bytes = 0;
-    void* d_resize_work = nullptr;
-    size_t resize_work_bytes = 0;
     struct ResizeTable {
         void* d_table = nullptr;
         size_t bytes = 0;
@@ -382,25 +355,13 @@ void tex_release(FfState* s);
 void glossy_drop_bindings(FfState* s);
 int glossy_sync_table(FfState* s);
 void glossy_release(FfState* s);
-// Display transform (ff_display_api.cpp): frees the state's device buffers (ff_destroy).
+// Display transform (ff_display_api.cpp): frees the counters and the threshold table (ff_destroy).
 void display_release(FfState* s);
-// Motion blur (ff_motion_blur_api.cpp): frees the state's work buffer (ff_destroy).
-void motion_blur_release(FfState* s);
-// Depth of field (ff_dof_api.cpp): frees the state's work buffer (ff_destroy).
-void dof_release(FfState* s);
-// Firefly clamp (ff_despeckle_api.cpp): frees the state's work buffer (ff_destroy).
-void despeckle_release(FfState* s);
-// Sharpening (ff_sharpen_api.cpp): frees the state's work buffer (ff_destroy).
-void sharpen_release(FfState* s);
-// Local tone mapping (ff_local_tonemap_api.cpp): frees the state's work buffer (ff_destroy).
-void local_tonemap_release(FfState* s);
-// Frame interpolation (ff_interpolate_api.cpp): frees the state's work buffer (ff_destroy).
-void interpolate_release(FfState* s);
 // Adaptive sampling (ff_adaptive_api.cpp): frees the state's buffers (ff_destroy).
 void adaptive_release(FfState* s);
-// Video planes (ff_yuv_api.cpp): frees the knot tables and the work buffer (ff_destroy).
+// Video planes (ff_yuv_api.cpp): frees the knot tables (ff_destroy).
 void yuv_release(FfState* s);
-// Resampling (ff_resize_api.cpp): frees the intermediate image, the work buffer and the two tables (ff_destroy).
+// Resampling (ff_resize_api.cpp): frees the intermediate image and the two tables (ff_destroy).
 void resize_release(FfState* s);
 // The pixel buffer registered with ff_register_gl_pbo, mapped on the state's stream (kernel.cu:338-339) and unmapped again
 // (kernel.cu:344): what ff_render_to_pbo and ff_display_to_pbo write.  need_bytes: the least size the mapping must have.

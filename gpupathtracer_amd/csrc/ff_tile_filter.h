@@ -202,34 +202,31 @@ hipError_t launch_gather_kernel(Kernel kernel, const Args& a, hipStream_t stream
 
 #endif // __HIPCC__
 
-// The device entry point behind the checks: the filter's work buffer (the packed plane, T and N, then, from a multiple of 16 bytes
-// on, the staging of host buffers), the three launches, the wait.  rgb8 and radiance_out may be null.
+// The device entry point behind the checks: the filter's use of the state's image work buffer (the packed plane, T and N, then,
+// from a multiple of 16 bytes on, the staging of host buffers), the three launches, the wait.  rgb8 and radiance_out may be null.
 template <class F>
-int tile_filter_device(FfState* s, void** work, size_t* work_bytes, const typename F::Args& a, const float* radiance_in, const float* guide,
-                       const float* depth, int inputs_on_device, void* rgb8, int rgb8_on_device, float* radiance_out, int radiance_out_on_device, const char* who)
+int tile_filter_device(FfState* s, const typename F::Args& a, const float* radiance_in, const float* guide, const float* depth, int inputs_on_device,
+                       void* rgb8, int rgb8_on_device, float* radiance_out, int radiance_out_on_device, const char* who)
 {
     FF_HIP(hipSetDevice(s->device));
     hipStream_t stream = s->stream;
     const size_t px = (size_t)a.grid.width * (size_t)a.grid.height, tiles = tile_count(a.grid);
     const size_t own_bytes = (px * sizeof(typename F::Packed) + 2 * tiles * sizeof(typename F::Tile) + 15) & ~(size_t)15;
-    unsigned char* d_rgb8 = (unsigned char*)rgb8;
-    float* d_out = radiance_out;
-    Staging stage(work, work_bytes, own_bytes);
+    Staging stage(&s->d_img_work, &s->img_work_bytes, own_bytes);
     if (!inputs_on_device) {
         stage.in(&radiance_in, radiance_in, px * 12);
         stage.in(&guide, guide, px * 4 * F::kGuideFloats);
         stage.in(&depth, depth, px * 4);
     }
-    if (rgb8 && !rgb8_on_device) stage.out(&d_rgb8, rgb8, px * 3);
-    if (radiance_out && !radiance_out_on_device) stage.out(&d_out, radiance_out, px * 12);
+    StagedOutputs out(stage, px, rgb8, rgb8_on_device, radiance_out, radiance_out_on_device);
     const int st = stage.commit(stream, (std::string(who) + ": staging the inputs failed").c_str());
     if (st != FF_OK) return st;
-    typename F::Packed* plane = (typename F::Packed*)*work;
+    typename F::Packed* plane = (typename F::Packed*)s->d_img_work;
     typename F::Tile* tile_max = (typename F::Tile*)(plane + px);
     typename F::Tile* neighbour_max = tile_max + tiles;
     FF_HIP(launch_pack_tile_max<F>(a, guide, depth, plane, tile_max, stream));
     FF_HIP(launch_neighbour_max<F>(a, tile_max, neighbour_max, stream));
-    if (d_rgb8 || d_out) FF_HIP(F::launch_gather(a, plane, neighbour_max, radiance_in, d_rgb8, d_out, stream));
+    if (out.rgb8 || out.radiance) FF_HIP(F::launch_gather(a, plane, neighbour_max, radiance_in, out.rgb8, out.radiance, stream));
     FF_HIP(hipStreamSynchronize(stream));
     return stage.finish();
 }

@@ -1,6 +1,6 @@
 // ff_upscale_api.cpp — host side of ff_upscale (include/firefly/ff_api.h): the argument checks, the staging of host buffers and the
 // launch (kernel in ff_upscale.hip), and the host-only twin ff_upscale_host, which runs ff_upscale.h's per-pixel function in a loop.
-// A pure image operation: no scene, no history, nothing kept in the state but the staging buffer every image call shares.
+// A pure image operation: no scene, no history, nothing kept in the state.
 #include <cmath>
 
 #include <hip/hip_runtime.h>
@@ -100,9 +100,7 @@ int ff_upscale(FfState* s, const FfUpscaleParams* p, int lo_width, int lo_height
     const size_t lo_px = (size_t)lo_width * (size_t)lo_height, px = (size_t)width * (size_t)height;
     hipStream_t stream = s->stream;
     // host buffers are staged, as in ff_denoise: the inputs the call reads, the outputs it writes
-    unsigned char* d_rgb8 = (unsigned char*)rgb8;
-    float* d_out = radiance_out;
-    Staging stage(&s->d_img_stage, &s->img_stage_bytes);
+    Staging stage(&s->d_img_work, &s->img_work_bytes);
     if (!inputs_on_device) {
         stage.in(&a.radiance_lo, radiance_lo, lo_px * 12);
         stage.in(&a.position_lo, position_lo, lo_px * 12);
@@ -114,11 +112,10 @@ int ff_upscale(FfState* s, const FfUpscaleParams* p, int lo_width, int lo_height
         if (a.demodulate) stage.in(&a.albedo, albedo, px * 12);
         stage.in(&a.ids, ids, px * 12);
     }
-    if (rgb8 && !rgb8_on_device) stage.out(&d_rgb8, rgb8, px * 3);
-    if (radiance_out && !radiance_out_on_device) stage.out(&d_out, radiance_out, px * 12);
+    StagedOutputs out(stage, px, rgb8, rgb8_on_device, radiance_out, radiance_out_on_device);
     st = stage.commit(stream, "ff_upscale: staging the inputs failed");
     if (st != FF_OK) return st;
-    FF_HIP(launch_upscale(a, d_rgb8, d_out, stream));
+    FF_HIP(launch_upscale(a, out.rgb8, out.radiance, stream));
     FF_HIP(hipStreamSynchronize(stream));
     return stage.finish();
 }

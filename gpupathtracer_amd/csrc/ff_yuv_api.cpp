@@ -1,7 +1,7 @@
 // ff_yuv_api.cpp — host side of ff_encode_yuv (include/firefly/ff_api.h): the knots of the three transfers (double, once), the
-// argument checks, the knot tables and the staging of host buffers in the state, the one launch (kernel in ff_yuv.hip), the loops of
-// the host-only twin ff_encode_yuv_host over ff_yuv.h's functions, and the YUV4MPEG2 writer.  A pure image operation: no scene, no
-// G-buffer, no history.
+// argument checks, the knot tables in the state and the staging of host buffers in its image work buffer, the one launch (kernel in
+// ff_yuv.hip), the loops of the host-only twin ff_encode_yuv_host over ff_yuv.h's functions, and the YUV4MPEG2 writer.  A pure
+// image operation: no scene, no G-buffer, no history.
 #include <cerrno>
 #include <cmath>
 #include <cstdio>
@@ -89,8 +89,7 @@ int check_yuv(int width, int height, const FfYuvParams* p, const float* linear_i
     size_t lb, cb;
     plane_bytes(width, height, p->depth, &lb, &cb);
     const Span out[2] = { { luma, lb, "luma" }, { chroma, cb, "chroma" } };
-    const Span in[3] = { { linear_in, (size_t)width * (size_t)height * 12, "linear_in" }, { nullptr, 0, "" }, { nullptr, 0, "" } };
-    if (check_disjoint(out, in, who) != FF_OK) return FF_ERR_INVALID_ARG;
+    if (check_disjoint(out, { { linear_in, (size_t)width * (size_t)height * 12, "linear_in" } }, who) != FF_OK) return FF_ERR_INVALID_ARG;
     a->width = width;
     a->height = height;
     a->bt2020 = p->matrix == FF_YUV_MATRIX_BT2020;
@@ -149,10 +148,7 @@ namespace ff {
 void yuv_release(FfState* s)
 {
     if (s->d_yuv_knots) (void)hipFree(s->d_yuv_knots);
-    if (s->d_yuv_work) (void)hipFree(s->d_yuv_work);
     s->d_yuv_knots = nullptr;
-    s->d_yuv_work = nullptr;
-    s->yuv_work_bytes = 0;
     s->yuv_knots_loaded[0] = s->yuv_knots_loaded[1] = s->yuv_knots_loaded[2] = false;
 }
 
@@ -224,7 +220,7 @@ int ff_encode_yuv(FfState* s, int width, int height, const FfYuvParams* p, const
     plane_bytes(width, height, p->depth, &lb, &cb);
     void* d_luma = luma;
     void* d_chroma = chroma;
-    Staging stage(&s->d_yuv_work, &s->yuv_work_bytes);
+    Staging stage(&s->d_img_work, &s->img_work_bytes);
     if (!input_on_device) stage.in(&linear_in, linear_in, (size_t)width * (size_t)height * 12);
     if (!outputs_on_device) {
         stage.out(&d_luma, luma, lb);

@@ -584,59 +584,70 @@ def render_params(width, height, bounces=1, spp=1, seed=1234, trace_mode=T.TRACE
     return T.FfRenderParams(width, height, bounces, spp, seed, trace_mode, shade_mode, grid_mode, spp_per_launch)
 
 
+def _params(struct, init, overrides, arrays=None, fixed=()):
+    """What every *_params(**overrides) returns: a `struct` with the defaults of the library's `init` function and the given fields
+    replaced.  arrays: field -> ctypes array type, for the fields given as a sequence; fixed: fields that may not be set."""
+    p = struct()
+    getattr(load(), init)(C.byref(p))
+    fields = dict(struct._fields_)
+    for name, value in overrides.items():
+        if name not in fields or name in fixed:
+            raise TypeError(f"{struct.__name__} has no {'settable ' if fixed else ''}field {name!r}")
+        setattr(p, name, arrays[name](*value) if arrays and name in arrays else value)
+    return p
+
+
+def _vp(q):
+    """A raw device pointer (an int; 0 or None: none) as ctypes passes it."""
+    return C.c_void_p(q) if q else None
+
+
+def _image_outputs(h, w, want_rgb8=True, want_out=True, device=None, out=None):
+    """The two optional outputs of an image filter for an h x w image: (rgb8 [h,w,3] uint8, out [h,w,3] float32, and the pointer to
+    pass for each) - numpy arrays, or torch tensors on `device`; None for an output that is not wanted.  out: the array or tensor
+    to use as the float output where one is wanted (an in-place call's)."""
+    if device is None:
+        new, ptr = (lambda dtype: np.zeros((h, w, 3), dtype=dtype)), (lambda a: a.ctypes.data)
+    else:
+        import torch
+        new, ptr = (lambda dtype: torch.zeros((h, w, 3), dtype=getattr(torch, dtype), device=device)), (lambda a: a.data_ptr())
+    rgb8 = new("uint8") if want_rgb8 else None
+    out = (out if out is not None else new("float32")) if want_out else None
+    return rgb8, out, ptr(rgb8) if want_rgb8 else None, ptr(out) if want_out else None
+
+
+def _device_image(t, dtype, what, spelled, hw=None):
+    """(h, w) of the device tensor `t`, which must be contiguous, on the device, of the torch `dtype` and [H,W,3] (of the size hw,
+    where one is given); what and spelled: the tensor and its type as the error names them."""
+    h, w = hw if hw is not None else t.shape[:2]
+    if not t.is_cuda or t.dtype != dtype or tuple(t.shape) != (h, w, 3) or not t.is_contiguous():
+        raise ValueError(f"{what} must be a contiguous [H,W,3] {spelled} tensor on the device")
+    return h, w
+
+
 def denoise_params(**overrides):
     """ff_denoise_params_init's defaults with the given fields replaced (iterations, sigma_color, sigma_normal, sigma_plane, flags)."""
-    dn = T.FfDenoiseParams()
-    load().ff_denoise_params_init(C.byref(dn))
-    for name, value in overrides.items():
-        if name not in dict(T.FfDenoiseParams._fields_):
-            raise TypeError(f"FfDenoiseParams has no field {name!r}")
-        setattr(dn, name, value)
-    return dn
+    return _params(T.FfDenoiseParams, "ff_denoise_params_init", overrides)
 
 
 def temporal_params(**overrides):
     """ff_temporal_params_init's defaults with the given fields replaced (any FfTemporalParams field)."""
-    tp = T.FfTemporalParams()
-    load().ff_temporal_params_init(C.byref(tp))
-    for name, value in overrides.items():
-        if name not in dict(T.FfTemporalParams._fields_):
-            raise TypeError(f"FfTemporalParams has no field {name!r}")
-        setattr(tp, name, value)
-    return tp
+    return _params(T.FfTemporalParams, "ff_temporal_params_init", overrides)
 
 
 def taa_params(**overrides):
     """ff_taa_params_init's defaults with the given fields replaced (any FfTaaParams field)."""
-    p = T.FfTaaParams()
-    load().ff_taa_params_init(C.byref(p))
-    for name, value in overrides.items():
-        if name not in dict(T.FfTaaParams._fields_):
-            raise TypeError(f"FfTaaParams has no field {name!r}")
-        setattr(p, name, value)
-    return p
+    return _params(T.FfTaaParams, "ff_taa_params_init", overrides)
 
 
 def upscale_params(**overrides):
     """ff_upscale_params_init's defaults with the given fields replaced (any FfUpscaleParams field; a jitter as a pair)."""
-    p = T.FfUpscaleParams()
-    load().ff_upscale_params_init(C.byref(p))
-    for name, value in overrides.items():
-        if name not in dict(T.FfUpscaleParams._fields_):
-            raise TypeError(f"FfUpscaleParams has no field {name!r}")
-        setattr(p, name, (C.c_float * 2)(*value) if name in ("lo_jitter", "hi_jitter") else value)
-    return p
+    return _params(T.FfUpscaleParams, "ff_upscale_params_init", overrides, arrays={"lo_jitter": C.c_float * 2, "hi_jitter": C.c_float * 2})
 
 
 def taa_upscale_params(**overrides):
     """ff_taa_upscale_params_init's defaults with the given fields replaced (any FfTaaUpscaleParams field; lo_jitter as a pair)."""
-    p = T.FfTaaUpscaleParams()
-    load().ff_taa_upscale_params_init(C.byref(p))
-    for name, value in overrides.items():
-        if name not in dict(T.FfTaaUpscaleParams._fields_):
-            raise TypeError(f"FfTaaUpscaleParams has no field {name!r}")
-        setattr(p, name, (C.c_float * 2)(*value) if name == "lo_jitter" else value)
-    return p
+    return _params(T.FfTaaUpscaleParams, "ff_taa_upscale_params_init", overrides, arrays={"lo_jitter": C.c_float * 2})
 
 
 def _upscale_images(radiance_lo, gbuffer_lo, gbuffer_hi, who):
@@ -657,23 +668,16 @@ def upscale_host(radiance_lo, gbuffer_lo, gbuffer_hi, p=None):
     -> (rgb8 [H,W,3] uint8, radiance [H,W,3] float32)."""
     rad, lo, hi, (h, w), (H, W) = _upscale_images(radiance_lo, gbuffer_lo, gbuffer_hi, "upscale_host")
     p = p if p is not None else upscale_params()
-    rgb8 = np.zeros((H, W, 3), dtype=np.uint8)
-    out = np.zeros((H, W, 3), dtype=np.float32)
+    rgb8, out, rgb8_ptr, out_ptr = _image_outputs(H, W)
     check(load().ff_upscale_host(C.byref(p), w, h, rad.ctypes.data, lo["position"].ctypes.data, lo["normal"].ctypes.data, lo["albedo"].ctypes.data,
                                  lo["ids"].ctypes.data, W, H, hi["position"].ctypes.data, hi["normal"].ctypes.data, hi["albedo"].ctypes.data,
-                                 hi["ids"].ctypes.data, rgb8.ctypes.data, out.ctypes.data))
+                                 hi["ids"].ctypes.data, rgb8_ptr, out_ptr))
     return rgb8, out
 
 
 def motion_blur_params(**overrides):
     """ff_motion_blur_params_init's defaults with the given fields replaced (any FfMotionBlurParams field)."""
-    p = T.FfMotionBlurParams()
-    load().ff_motion_blur_params_init(C.byref(p))
-    for name, value in overrides.items():
-        if name not in dict(T.FfMotionBlurParams._fields_):
-            raise TypeError(f"FfMotionBlurParams has no field {name!r}")
-        setattr(p, name, value)
-    return p
+    return _params(T.FfMotionBlurParams, "ff_motion_blur_params_init", overrides)
 
 
 def _motion_blur_images(radiance, motion, depth, who):
@@ -692,22 +696,14 @@ def motion_blur_host(radiance, motion, depth, p=None, want_rgb8=True, want_out=T
     -> (rgb8 [H,W,3] uint8, radiance [H,W,3] float32)."""
     rad, mot, dep, (h, w) = _motion_blur_images(radiance, motion, depth, "motion_blur_host")
     p = p if p is not None else motion_blur_params()
-    rgb8 = np.zeros((h, w, 3), dtype=np.uint8) if want_rgb8 else None
-    out = np.zeros((h, w, 3), dtype=np.float32) if want_out else None
-    check(load().ff_motion_blur_host(w, h, C.byref(p), rad.ctypes.data, mot.ctypes.data, dep.ctypes.data, rgb8.ctypes.data if want_rgb8 else None,
-                                     out.ctypes.data if want_out else None))
+    rgb8, out, rgb8_ptr, out_ptr = _image_outputs(h, w, want_rgb8, want_out)
+    check(load().ff_motion_blur_host(w, h, C.byref(p), rad.ctypes.data, mot.ctypes.data, dep.ctypes.data, rgb8_ptr, out_ptr))
     return rgb8, out
 
 
 def dof_params(**overrides):
     """ff_dof_params_init's defaults with the given fields replaced (any FfDofParams field; reserved: a pair)."""
-    p = T.FfDofParams()
-    load().ff_dof_params_init(C.byref(p))
-    for name, value in overrides.items():
-        if name not in dict(T.FfDofParams._fields_):
-            raise TypeError(f"FfDofParams has no field {name!r}")
-        setattr(p, name, (C.c_int32 * 2)(*value) if name == "reserved" else value)
-    return p
+    return _params(T.FfDofParams, "ff_dof_params_init", overrides, arrays={"reserved": C.c_int32 * 2})
 
 
 def dof_params_from_camera(camera, cs, **overrides):
@@ -736,22 +732,15 @@ def depth_of_field_host(radiance, gbuffer_or_planes, camera, p=None, want_rgb8=T
     -> (rgb8 [H,W,3] uint8, radiance [H,W,3] float32)."""
     rad, pos, dep, (h, w) = _dof_images(radiance, gbuffer_or_planes, "depth_of_field_host")
     p = p if p is not None else dof_params()
-    rgb8 = np.zeros((h, w, 3), dtype=np.uint8) if want_rgb8 else None
-    out = np.zeros((h, w, 3), dtype=np.float32) if want_out else None
+    rgb8, out, rgb8_ptr, out_ptr = _image_outputs(h, w, want_rgb8, want_out)
     check(load().ff_depth_of_field_host(C.byref(camera), w, h, C.byref(p), rad.ctypes.data, pos.ctypes.data, dep.ctypes.data,
-                                        rgb8.ctypes.data if want_rgb8 else None, out.ctypes.data if want_out else None))
+                                        rgb8_ptr, out_ptr))
     return rgb8, out
 
 
 def despeckle_params(**overrides):
     """ff_despeckle_params_init's defaults with the given fields replaced (any FfDespeckleParams field)."""
-    p = T.FfDespeckleParams()
-    load().ff_despeckle_params_init(C.byref(p))
-    for name, value in overrides.items():
-        if name not in dict(T.FfDespeckleParams._fields_):
-            raise TypeError(f"FfDespeckleParams has no field {name!r}")
-        setattr(p, name, value)
-    return p
+    return _params(T.FfDespeckleParams, "ff_despeckle_params_init", overrides)
 
 
 def _despeckle_planes(gbuffer_or_planes):
@@ -778,27 +767,21 @@ def despeckle_host(radiance, gbuffer_or_planes, p=None, want_rgb8=True, want_out
     FF_DESPECKLE_DEMODULATE_ALBEDO) -> (rgb8 [H,W,3] uint8, radiance [H,W,3] float32, the number of clamped pixels)."""
     rad, alb, ids, (h, w) = _despeckle_images(radiance, gbuffer_or_planes, "despeckle_host")
     p = p if p is not None else despeckle_params()
-    rgb8 = np.zeros((h, w, 3), dtype=np.uint8) if want_rgb8 else None
-    out = np.zeros((h, w, 3), dtype=np.float32) if want_out else None
+    rgb8, out, rgb8_ptr, out_ptr = _image_outputs(h, w, want_rgb8, want_out)
     clamped = C.c_uint32(0)
     check(load().ff_despeckle_host(w, h, C.byref(p), rad.ctypes.data, alb.ctypes.data if alb is not None else None, ids.ctypes.data,
-                                   rgb8.ctypes.data if want_rgb8 else None, out.ctypes.data if want_out else None, C.byref(clamped)))
+                                   rgb8_ptr, out_ptr, C.byref(clamped)))
     return rgb8, out, int(clamped.value)
 
 
 def sharpen_params(**overrides):
     """ff_sharpen_params_init's defaults with the given fields replaced (any FfSharpenParams field)."""
-    p = T.FfSharpenParams()
-    load().ff_sharpen_params_init(C.byref(p))
-    for name, value in overrides.items():
-        if name not in dict(T.FfSharpenParams._fields_):
-            raise TypeError(f"FfSharpenParams has no field {name!r}")
-        setattr(p, name, value)
-    return p
+    return _params(T.FfSharpenParams, "ff_sharpen_params_init", overrides)
 
 
-def _sharpen_image(radiance, who):
-    """The input image of ff_sharpen as a contiguous float32 array, and (h, w)."""
+def _float3_image(radiance, who):
+    """An [H,W,3] input image (ff_sharpen's, ff_local_tonemap's, ff_encode_yuv's, ff_resize's, ff_display's) as a contiguous float32
+    array, and (h, w)."""
     rad = np.ascontiguousarray(radiance, dtype=np.float32)
     if rad.ndim != 3 or rad.shape[2] != 3:
         raise ValueError(f"{who}: radiance must be [H,W,3]")
@@ -807,41 +790,32 @@ def _sharpen_image(radiance, who):
 
 def sharpen_host(radiance, p=None, want_rgb8=True, want_out=True):
     """ff_sharpen_host (no GPU): host radiance [H,W,3] -> (rgb8 [H,W,3] uint8, radiance [H,W,3] float32)."""
-    rad, (h, w) = _sharpen_image(radiance, "sharpen_host")
+    rad, (h, w) = _float3_image(radiance, "sharpen_host")
     p = p if p is not None else sharpen_params()
-    rgb8 = np.zeros((h, w, 3), dtype=np.uint8) if want_rgb8 else None
-    out = np.zeros((h, w, 3), dtype=np.float32) if want_out else None
-    check(load().ff_sharpen_host(w, h, C.byref(p), rad.ctypes.data, rgb8.ctypes.data if want_rgb8 else None, out.ctypes.data if want_out else None))
+    rgb8, out, rgb8_ptr, out_ptr = _image_outputs(h, w, want_rgb8, want_out)
+    check(load().ff_sharpen_host(w, h, C.byref(p), rad.ctypes.data, rgb8_ptr, out_ptr))
     return rgb8, out
 
 
 def local_tonemap_params(**overrides):
     """ff_local_tonemap_params_init's defaults with the given fields replaced (any FfLocalTonemapParams field but reserved)."""
-    p = T.FfLocalTonemapParams()
-    load().ff_local_tonemap_params_init(C.byref(p))
-    for name, value in overrides.items():
-        if name not in dict(T.FfLocalTonemapParams._fields_) or name == "reserved":
-            raise TypeError(f"FfLocalTonemapParams has no settable field {name!r}")
-        setattr(p, name, value)
-    return p
+    return _params(T.FfLocalTonemapParams, "ff_local_tonemap_params_init", overrides, fixed=("reserved",))
 
 
 def local_tonemap_host(radiance, p=None, want_rgb8=True, want_out=True, in_place=False):
     """ff_local_tonemap_host (no GPU): host radiance [H,W,3] -> (rgb8 [H,W,3] uint8, radiance [H,W,3] float32).  in_place: the
     radiance output is written over a copy of the input (radiance_out == radiance_in in the call)."""
-    rad, (h, w) = _sharpen_image(radiance, "local_tonemap_host")
+    rad, (h, w) = _float3_image(radiance, "local_tonemap_host")
     p = p if p is not None else local_tonemap_params()
-    rgb8 = np.zeros((h, w, 3), dtype=np.uint8) if want_rgb8 else None
-    out = (rad.copy() if in_place else np.zeros((h, w, 3), dtype=np.float32)) if want_out else None
+    rgb8, out, rgb8_ptr, out_ptr = _image_outputs(h, w, want_rgb8, want_out, out=rad.copy() if in_place else None)
     src = out if (in_place and want_out) else rad
-    check(load().ff_local_tonemap_host(w, h, C.byref(p), src.ctypes.data, rgb8.ctypes.data if want_rgb8 else None,
-                                       out.ctypes.data if want_out else None))
+    check(load().ff_local_tonemap_host(w, h, C.byref(p), src.ctypes.data, rgb8_ptr, out_ptr))
     return rgb8, out
 
 
 def local_tonemap_grid_host(radiance, p=None):
     """ff_local_tonemap_grid_host (no GPU): step 2's grid of host radiance [H,W,3] -> (n, S), each [gh, gw, 40] int32."""
-    rad, (h, w) = _sharpen_image(radiance, "local_tonemap_grid_host")
+    rad, (h, w) = _float3_image(radiance, "local_tonemap_grid_host")
     p = p if p is not None else local_tonemap_params()
     s = int(p.cell) if int(p.cell) > 0 else 1
     shape = ((h + s - 1) // s, (w + s - 1) // s, T.LOCAL_TONEMAP_BINS)
@@ -853,13 +827,7 @@ def local_tonemap_grid_host(radiance, p=None):
 
 def yuv_params(**overrides):
     """ff_yuv_params_init's defaults with the given fields replaced (any FfYuvParams field)."""
-    p = T.FfYuvParams()
-    load().ff_yuv_params_init(C.byref(p))
-    for name, value in overrides.items():
-        if name not in dict(T.FfYuvParams._fields_):
-            raise TypeError(f"FfYuvParams has no field {name!r}")
-        setattr(p, name, value)
-    return p
+    return _params(T.FfYuvParams, "ff_yuv_params_init", overrides)
 
 
 def yuv_plane_bytes(width, height, p=None):
@@ -887,7 +855,7 @@ def _yuv_planes(h, w, p):
 def encode_yuv_host(linear, p=None):
     """ff_encode_yuv_host (no GPU): host display-linear [H,W,3] -> (luma [H,W], chroma [ceil(H/2),ceil(W/2),2] of Cb Cr pairs);
     uint8 codes at depth 8 (NV12), uint16 codes << 6 at depth 10 (P010)."""
-    img, (h, w) = _sharpen_image(linear, "encode_yuv_host")
+    img, (h, w) = _float3_image(linear, "encode_yuv_host")
     p = p if p is not None else yuv_params()
     luma, chroma = _yuv_planes(h, w, p)
     check(load().ff_encode_yuv_host(w, h, C.byref(p), img.ctypes.data, luma.ctypes.data, chroma.ctypes.data))
@@ -908,13 +876,7 @@ def save_y4m(path, luma, chroma, p=None, append=False):
 
 def resize_params(**overrides):
     """ff_resize_params_init's defaults with the given fields replaced (any FfResizeParams field)."""
-    p = T.FfResizeParams()
-    load().ff_resize_params_init(C.byref(p))
-    for name, value in overrides.items():
-        if name not in dict(T.FfResizeParams._fields_):
-            raise TypeError(f"FfResizeParams has no field {name!r}")
-        setattr(p, name, value)
-    return p
+    return _params(T.FfResizeParams, "ff_resize_params_init", overrides)
 
 
 def resize_taps(in_size, out_size, filter):
@@ -935,25 +897,17 @@ def resize_weights(in_size, out_size, filter):
 
 def resize_host(radiance, out_width, out_height, p=None, want_rgb8=True, want_out=True):
     """ff_resize_host (no GPU): host radiance [H,W,3] -> (rgb8 [H',W',3] uint8, radiance [H',W',3] float32)."""
-    rad, (h, w) = _sharpen_image(radiance, "resize_host")
+    rad, (h, w) = _float3_image(radiance, "resize_host")
     p = p if p is not None else resize_params()
-    shape = (max(int(out_height), 0), max(int(out_width), 0), 3)  # (a size the library refuses still gets arrays: the call names it)
-    rgb8 = np.zeros(shape, dtype=np.uint8) if want_rgb8 else None
-    out = np.zeros(shape, dtype=np.float32) if want_out else None
-    check(load().ff_resize_host(C.byref(p), w, h, rad.ctypes.data, out_width, out_height, rgb8.ctypes.data if want_rgb8 else None,
-                                out.ctypes.data if want_out else None))
+    # (a size the library refuses still gets arrays: the call names it)
+    rgb8, out, rgb8_ptr, out_ptr = _image_outputs(max(int(out_height), 0), max(int(out_width), 0), want_rgb8, want_out)
+    check(load().ff_resize_host(C.byref(p), w, h, rad.ctypes.data, out_width, out_height, rgb8_ptr, out_ptr))
     return rgb8, out
 
 
 def interpolate_params(**overrides):
     """ff_interpolate_params_init's defaults with the given fields replaced (any FfInterpolateParams field)."""
-    p = T.FfInterpolateParams()
-    load().ff_interpolate_params_init(C.byref(p))
-    for name, value in overrides.items():
-        if name not in dict(T.FfInterpolateParams._fields_):
-            raise TypeError(f"FfInterpolateParams has no field {name!r}")
-        setattr(p, name, value)
-    return p
+    return _params(T.FfInterpolateParams, "ff_interpolate_params_init", overrides)
 
 
 def _interpolate_planes(gbuffer_or_planes):
@@ -995,13 +949,12 @@ def interpolate_host(mid, a, b, p=None, geom_maps=None, want_rgb8=True, want_out
     cams, im, (h, w) = _interpolate_images(mid, a, b, "interpolate_host")
     maps, n = _interpolate_maps(geom_maps, "interpolate_host")
     p = p if p is not None else interpolate_params()
-    rgb8 = np.zeros((h, w, 3), dtype=np.uint8) if want_rgb8 else None
-    out = np.zeros((h, w, 3), dtype=np.float32) if want_out else None
+    rgb8, out, rgb8_ptr, out_ptr = _image_outputs(h, w, want_rgb8, want_out)
     counts = np.zeros(5, dtype=np.uint32)
     d = [x.ctypes.data for x in im]
     check(load().ff_interpolate_host(w, h, C.byref(p), C.byref(cams[0]), d[0], d[1], C.byref(cams[1]), d[2], d[3], d[4], C.byref(cams[2]), d[5], d[6], d[7],
-                                     maps.ctypes.data if maps is not None else None, n, rgb8.ctypes.data if want_rgb8 else None,
-                                     out.ctypes.data if want_out else None, counts.ctypes.data))
+                                     maps.ctypes.data if maps is not None else None, n, rgb8_ptr, out_ptr,
+                                     counts.ctypes.data))
     return rgb8, out, counts
 
 
@@ -1031,13 +984,7 @@ def interpolate_geometry_maps(mid, a, b):
 
 def adaptive_params(**overrides):
     """ff_adaptive_params_init's defaults with the given fields replaced (any FfAdaptiveParams field)."""
-    p = T.FfAdaptiveParams()
-    load().ff_adaptive_params_init(C.byref(p))
-    for name, value in overrides.items():
-        if name not in dict(T.FfAdaptiveParams._fields_):
-            raise TypeError(f"FfAdaptiveParams has no field {name!r}")
-        setattr(p, name, value)
-    return p
+    return _params(T.FfAdaptiveParams, "ff_adaptive_params_init", overrides)
 
 
 def _adaptive_sums(sum_all, sum_even, who):
@@ -1078,13 +1025,7 @@ def adaptive_plan_host(active, max_rects=None):
 
 def display_params(**overrides):
     """ff_display_params_init's defaults with the given fields replaced (any FfDisplayParams field)."""
-    p = T.FfDisplayParams()
-    load().ff_display_params_init(C.byref(p))
-    for name, value in overrides.items():
-        if name not in dict(T.FfDisplayParams._fields_):
-            raise TypeError(f"FfDisplayParams has no field {name!r}")
-        setattr(p, name, value)
-    return p
+    return _params(T.FfDisplayParams, "ff_display_params_init", overrides)
 
 
 def srgb_thresholds():
@@ -1327,9 +1268,8 @@ class Tracer:
     def render_adaptive_device(self, camera, params, ap=None, rgb8_ptr=None, radiance_ptr=None, passes_ptr=None):
         """ff_render_adaptive into caller-owned DEVICE buffers (raw pointers; each may be None) -> FfAdaptiveInfo."""
         ap = ap if ap is not None else adaptive_params()
-        vp = lambda q: C.c_void_p(q) if q else None  # noqa: E731
         info = T.FfAdaptiveInfo()
-        check(self._lib.ff_render_adaptive(self._state, C.byref(camera), C.byref(params), C.byref(ap), vp(rgb8_ptr), 1, vp(radiance_ptr), 1, vp(passes_ptr), 1,
+        check(self._lib.ff_render_adaptive(self._state, C.byref(camera), C.byref(params), C.byref(ap), _vp(rgb8_ptr), 1, _vp(radiance_ptr), 1, _vp(passes_ptr), 1,
                                            C.byref(info)))
         return info
 
@@ -1376,18 +1316,16 @@ class Tracer:
         h, w = rad.shape[:2]
         dn = dn if dn is not None else denoise_params()
         g = {k: np.ascontiguousarray(gbuffer[k], dtype=np.int32 if k == "ids" else np.float32) for k in ("position", "normal", "albedo", "ids")}
-        rgb8 = np.zeros((h, w, 3), dtype=np.uint8)
-        out = np.zeros((h, w, 3), dtype=np.float32)
+        rgb8, out, rgb8_ptr, out_ptr = _image_outputs(h, w)
         check(self._lib.ff_denoise(self._state, w, h, C.byref(dn), rad.ctypes.data, g["position"].ctypes.data, g["normal"].ctypes.data,
-                                   g["albedo"].ctypes.data, g["ids"].ctypes.data, 0, rgb8.ctypes.data, 0, out.ctypes.data, 0))
+                                   g["albedo"].ctypes.data, g["ids"].ctypes.data, 0, rgb8_ptr, 0, out_ptr, 0))
         return rgb8, out
 
     def denoise_device(self, width, height, radiance_ptr, position_ptr, normal_ptr, albedo_ptr, ids_ptr, dn=None, rgb8_ptr=None, radiance_out_ptr=None):
         """ff_denoise on DEVICE buffers (raw pointers); radiance_out_ptr may equal radiance_ptr."""
         dn = dn if dn is not None else denoise_params()
-        vp = lambda p: C.c_void_p(p) if p else None  # noqa: E731
-        check(self._lib.ff_denoise(self._state, width, height, C.byref(dn), vp(radiance_ptr), vp(position_ptr), vp(normal_ptr), vp(albedo_ptr),
-                                   vp(ids_ptr), 1, vp(rgb8_ptr), 1, vp(radiance_out_ptr), 1))
+        check(self._lib.ff_denoise(self._state, width, height, C.byref(dn), _vp(radiance_ptr), _vp(position_ptr), _vp(normal_ptr), _vp(albedo_ptr),
+                                   _vp(ids_ptr), 1, _vp(rgb8_ptr), 1, _vp(radiance_out_ptr), 1))
 
     def denoise_temporal(self, radiance, gbuffer, camera, tp=None):
         """ff_denoise_temporal of this frame's host radiance [H,W,3] guided by gbuffer() of `camera`; the history stays in the state
@@ -1398,11 +1336,9 @@ class Tracer:
             raise ValueError("denoise_temporal: radiance must be [H,W,3] and the G-buffer of the same size")
         tp = tp if tp is not None else temporal_params()
         g = {k: np.ascontiguousarray(gbuffer[k], dtype=np.int32 if k == "ids" else np.float32) for k in ("position", "normal", "albedo", "ids")}
-        rgb8 = np.zeros((h, w, 3), dtype=np.uint8)
-        out = np.zeros((h, w, 3), dtype=np.float32)
+        rgb8, out, rgb8_ptr, out_ptr = _image_outputs(h, w)
         check(self._lib.ff_denoise_temporal(self._state, C.byref(camera), w, h, C.byref(tp), rad.ctypes.data, g["position"].ctypes.data,
-                                            g["normal"].ctypes.data, g["albedo"].ctypes.data, g["ids"].ctypes.data, 0, rgb8.ctypes.data, 0,
-                                            out.ctypes.data, 0))
+                                            g["normal"].ctypes.data, g["albedo"].ctypes.data, g["ids"].ctypes.data, 0, rgb8_ptr, 0, out_ptr, 0))
         self._temporal_size = (h, w)
         return rgb8, out
 
@@ -1410,9 +1346,8 @@ class Tracer:
                                 radiance_out_ptr=None):
         """ff_denoise_temporal on DEVICE buffers (raw pointers); radiance_out_ptr may equal radiance_ptr."""
         tp = tp if tp is not None else temporal_params()
-        vp = lambda p: C.c_void_p(p) if p else None  # noqa: E731
-        check(self._lib.ff_denoise_temporal(self._state, C.byref(camera), width, height, C.byref(tp), vp(radiance_ptr), vp(position_ptr),
-                                            vp(normal_ptr), vp(albedo_ptr), vp(ids_ptr), 1, vp(rgb8_ptr), 1, vp(radiance_out_ptr), 1))
+        check(self._lib.ff_denoise_temporal(self._state, C.byref(camera), width, height, C.byref(tp), _vp(radiance_ptr), _vp(position_ptr),
+                                            _vp(normal_ptr), _vp(albedo_ptr), _vp(ids_ptr), 1, _vp(rgb8_ptr), 1, _vp(radiance_out_ptr), 1))
         self._temporal_size = (height, width)
 
     def temporal_reset(self):
@@ -1441,19 +1376,17 @@ class Tracer:
         p = p if p is not None else taa_params()
         pos = np.ascontiguousarray(gbuffer["position"], dtype=np.float32)
         ids = np.ascontiguousarray(gbuffer["ids"], dtype=np.int32)
-        rgb8 = np.zeros((h, w, 3), dtype=np.uint8)
-        out = np.zeros((h, w, 3), dtype=np.float32)
+        rgb8, out, rgb8_ptr, out_ptr = _image_outputs(h, w)
         check(self._lib.ff_taa(self._state, C.byref(camera), w, h, C.byref(p), rad.ctypes.data, pos.ctypes.data, ids.ctypes.data, 0,
-                               rgb8.ctypes.data, 0, out.ctypes.data, 0))
+                               rgb8_ptr, 0, out_ptr, 0))
         self._taa_size = (h, w)
         return rgb8, out
 
     def taa_device(self, camera, width, height, radiance_ptr, position_ptr, ids_ptr, p=None, rgb8_ptr=None, radiance_out_ptr=None):
         """ff_taa on DEVICE buffers (raw pointers); radiance_out_ptr may equal radiance_ptr."""
         p = p if p is not None else taa_params()
-        vp = lambda q: C.c_void_p(q) if q else None  # noqa: E731
-        check(self._lib.ff_taa(self._state, C.byref(camera), width, height, C.byref(p), vp(radiance_ptr), vp(position_ptr), vp(ids_ptr), 1,
-                               vp(rgb8_ptr), 1, vp(radiance_out_ptr), 1))
+        check(self._lib.ff_taa(self._state, C.byref(camera), width, height, C.byref(p), _vp(radiance_ptr), _vp(position_ptr), _vp(ids_ptr), 1,
+                               _vp(rgb8_ptr), 1, _vp(radiance_out_ptr), 1))
         self._taa_size = (height, width)
 
     def taa_reset(self):
@@ -1473,21 +1406,19 @@ class Tracer:
         jitters both were made with) -> (rgb8 [H,W,3] uint8, radiance [H,W,3] float32)."""
         rad, lo, hi, (h, w), (H, W) = _upscale_images(radiance_lo, gbuffer_lo, gbuffer_hi, "upscale")
         p = p if p is not None else upscale_params()
-        rgb8 = np.zeros((H, W, 3), dtype=np.uint8)
-        out = np.zeros((H, W, 3), dtype=np.float32)
+        rgb8, out, rgb8_ptr, out_ptr = _image_outputs(H, W)
         check(self._lib.ff_upscale(self._state, C.byref(p), w, h, rad.ctypes.data, lo["position"].ctypes.data, lo["normal"].ctypes.data,
                                    lo["albedo"].ctypes.data, lo["ids"].ctypes.data, W, H, hi["position"].ctypes.data, hi["normal"].ctypes.data,
-                                   hi["albedo"].ctypes.data, hi["ids"].ctypes.data, 0, rgb8.ctypes.data, 0, out.ctypes.data, 0))
+                                   hi["albedo"].ctypes.data, hi["ids"].ctypes.data, 0, rgb8_ptr, 0, out_ptr, 0))
         return rgb8, out
 
     def upscale_device(self, lo_width, lo_height, radiance_lo_ptr, position_lo_ptr, normal_lo_ptr, albedo_lo_ptr, ids_lo_ptr, width, height, position_ptr,
                        normal_ptr, albedo_ptr, ids_ptr, p=None, rgb8_ptr=None, radiance_out_ptr=None):
         """ff_upscale on DEVICE buffers (raw pointers); the outputs must not overlap an input."""
         p = p if p is not None else upscale_params()
-        vp = lambda q: C.c_void_p(q) if q else None  # noqa: E731
-        check(self._lib.ff_upscale(self._state, C.byref(p), lo_width, lo_height, vp(radiance_lo_ptr), vp(position_lo_ptr), vp(normal_lo_ptr),
-                                   vp(albedo_lo_ptr), vp(ids_lo_ptr), width, height, vp(position_ptr), vp(normal_ptr), vp(albedo_ptr), vp(ids_ptr), 1,
-                                   vp(rgb8_ptr), 1, vp(radiance_out_ptr), 1))
+        check(self._lib.ff_upscale(self._state, C.byref(p), lo_width, lo_height, _vp(radiance_lo_ptr), _vp(position_lo_ptr), _vp(normal_lo_ptr),
+                                   _vp(albedo_lo_ptr), _vp(ids_lo_ptr), width, height, _vp(position_ptr), _vp(normal_ptr), _vp(albedo_ptr), _vp(ids_ptr), 1,
+                                   _vp(rgb8_ptr), 1, _vp(radiance_out_ptr), 1))
 
     def taa_upscale(self, radiance_lo, gbuffer_lo, gbuffer_hi, camera, p=None):
         """ff_taa_upscale of this frame's host radiance [h,w,3], rendered under p.lo_jitter, with the ids of its gbuffer() (same
@@ -1502,10 +1433,9 @@ class Tracer:
         if rad.shape != (h, w, 3) or ids_lo.shape != (h, w, 3) or pos.shape != (H, W, 3) or ids.shape != (H, W, 3):
             raise ValueError("taa_upscale: radiance_lo and gbuffer_lo must be [h,w,3] and gbuffer_hi [H,W,3]")
         p = p if p is not None else taa_upscale_params()
-        rgb8 = np.zeros((H, W, 3), dtype=np.uint8)
-        out = np.zeros((H, W, 3), dtype=np.float32)
+        rgb8, out, rgb8_ptr, out_ptr = _image_outputs(H, W)
         check(self._lib.ff_taa_upscale(self._state, C.byref(camera), C.byref(p), w, h, rad.ctypes.data, ids_lo.ctypes.data, W, H, pos.ctypes.data,
-                                       ids.ctypes.data, 0, rgb8.ctypes.data, 0, out.ctypes.data, 0))
+                                       ids.ctypes.data, 0, rgb8_ptr, 0, out_ptr, 0))
         self._taa_upscale_size = (H, W)
         return rgb8, out
 
@@ -1513,9 +1443,8 @@ class Tracer:
                            radiance_out_ptr=None):
         """ff_taa_upscale on DEVICE buffers (raw pointers); the outputs must not overlap an input."""
         p = p if p is not None else taa_upscale_params()
-        vp = lambda q: C.c_void_p(q) if q else None  # noqa: E731
-        check(self._lib.ff_taa_upscale(self._state, C.byref(camera), C.byref(p), lo_width, lo_height, vp(radiance_lo_ptr), vp(ids_lo_ptr), width, height,
-                                       vp(position_ptr), vp(ids_ptr), 1, vp(rgb8_ptr), 1, vp(radiance_out_ptr), 1))
+        check(self._lib.ff_taa_upscale(self._state, C.byref(camera), C.byref(p), lo_width, lo_height, _vp(radiance_lo_ptr), _vp(ids_lo_ptr), width, height,
+                                       _vp(position_ptr), _vp(ids_ptr), 1, _vp(rgb8_ptr), 1, _vp(radiance_out_ptr), 1))
         self._taa_upscale_size = (height, width)
 
     def taa_upscale_reset(self):
@@ -1535,36 +1464,32 @@ class Tracer:
         -> (rgb8 [H,W,3] uint8, radiance [H,W,3] float32)."""
         rad, mot, dep, (h, w) = _motion_blur_images(radiance, motion, depth, "motion_blur")
         p = p if p is not None else motion_blur_params()
-        rgb8 = np.zeros((h, w, 3), dtype=np.uint8) if want_rgb8 else None
-        out = np.zeros((h, w, 3), dtype=np.float32) if want_out else None
+        rgb8, out, rgb8_ptr, out_ptr = _image_outputs(h, w, want_rgb8, want_out)
         check(self._lib.ff_motion_blur(self._state, w, h, C.byref(p), rad.ctypes.data, mot.ctypes.data, dep.ctypes.data, 0,
-                                       rgb8.ctypes.data if want_rgb8 else None, 0, out.ctypes.data if want_out else None, 0))
+                                       rgb8_ptr, 0, out_ptr, 0))
         return rgb8, out
 
     def motion_blur_device(self, width, height, radiance_ptr, motion_ptr, depth_ptr, p=None, rgb8_ptr=None, radiance_out_ptr=None):
         """ff_motion_blur on DEVICE buffers (raw pointers); the outputs must not overlap an input."""
         p = p if p is not None else motion_blur_params()
-        vp = lambda q: C.c_void_p(q) if q else None  # noqa: E731
-        check(self._lib.ff_motion_blur(self._state, width, height, C.byref(p), vp(radiance_ptr), vp(motion_ptr), vp(depth_ptr), 1, vp(rgb8_ptr), 1,
-                                       vp(radiance_out_ptr), 1))
+        check(self._lib.ff_motion_blur(self._state, width, height, C.byref(p), _vp(radiance_ptr), _vp(motion_ptr), _vp(depth_ptr), 1, _vp(rgb8_ptr), 1,
+                                       _vp(radiance_out_ptr), 1))
 
     def depth_of_field(self, radiance, gbuffer_or_planes, camera, p=None, want_rgb8=True, want_out=True):
         """ff_depth_of_field of host radiance [H,W,3] with a gbuffer() dict of `camera` (or its (position [H,W,3], depth [H,W])
         planes) -> (rgb8 [H,W,3] uint8, radiance [H,W,3] float32)."""
         rad, pos, dep, (h, w) = _dof_images(radiance, gbuffer_or_planes, "depth_of_field")
         p = p if p is not None else dof_params()
-        rgb8 = np.zeros((h, w, 3), dtype=np.uint8) if want_rgb8 else None
-        out = np.zeros((h, w, 3), dtype=np.float32) if want_out else None
+        rgb8, out, rgb8_ptr, out_ptr = _image_outputs(h, w, want_rgb8, want_out)
         check(self._lib.ff_depth_of_field(self._state, C.byref(camera), w, h, C.byref(p), rad.ctypes.data, pos.ctypes.data, dep.ctypes.data, 0,
-                                          rgb8.ctypes.data if want_rgb8 else None, 0, out.ctypes.data if want_out else None, 0))
+                                          rgb8_ptr, 0, out_ptr, 0))
         return rgb8, out
 
     def depth_of_field_device(self, camera, width, height, radiance_ptr, position_ptr, depth_ptr, p=None, rgb8_ptr=None, radiance_out_ptr=None):
         """ff_depth_of_field on DEVICE buffers (raw pointers); the outputs must not overlap an input."""
         p = p if p is not None else dof_params()
-        vp = lambda q: C.c_void_p(q) if q else None  # noqa: E731
-        check(self._lib.ff_depth_of_field(self._state, C.byref(camera), width, height, C.byref(p), vp(radiance_ptr), vp(position_ptr), vp(depth_ptr), 1,
-                                          vp(rgb8_ptr), 1, vp(radiance_out_ptr), 1))
+        check(self._lib.ff_depth_of_field(self._state, C.byref(camera), width, height, C.byref(p), _vp(radiance_ptr), _vp(position_ptr), _vp(depth_ptr), 1,
+                                          _vp(rgb8_ptr), 1, _vp(radiance_out_ptr), 1))
 
     def despeckle(self, radiance, gbuffer_or_planes, p=None, want_rgb8=True, want_out=True):
         """ff_despeckle of radiance [H,W,3] with a gbuffer() dict (or its (albedo, ids) planes; albedo None without
@@ -1576,30 +1501,27 @@ class Tracer:
             albedo, ids = _despeckle_planes(gbuffer_or_planes)
             h, w = radiance.shape[:2]
             for name, t, dtype in (("radiance", radiance, torch.float32), ("albedo", albedo, torch.float32), ("ids", ids, torch.int32)):
-                if t is not None and (not t.is_cuda or t.dtype != dtype or tuple(t.shape) != (h, w, 3) or not t.is_contiguous()):
-                    raise ValueError(f"despeckle: {name} must be a contiguous [H,W,3] {dtype} tensor on the device")
-            rgb8 = torch.zeros((h, w, 3), dtype=torch.uint8, device=radiance.device) if want_rgb8 else None
-            out = torch.zeros((h, w, 3), dtype=torch.float32, device=radiance.device) if want_out else None
+                if t is not None:
+                    _device_image(t, dtype, f"despeckle: {name}", dtype, (h, w))
+            rgb8, out, rgb8_ptr, out_ptr = _image_outputs(h, w, want_rgb8, want_out, radiance.device)
             torch.cuda.synchronize(radiance.device)
-            clamped = self.despeckle_device(w, h, radiance.data_ptr(), albedo.data_ptr() if albedo is not None else None, ids.data_ptr(), p,
-                                            rgb8.data_ptr() if want_rgb8 else None, out.data_ptr() if want_out else None)
+            clamped = self.despeckle_device(w, h, radiance.data_ptr(), albedo.data_ptr() if albedo is not None else None, ids.data_ptr(), p, rgb8_ptr,
+                                            out_ptr)
             return rgb8, out, clamped
         rad, alb, idp, (h, w) = _despeckle_images(radiance, gbuffer_or_planes, "despeckle")
-        rgb8 = np.zeros((h, w, 3), dtype=np.uint8) if want_rgb8 else None
-        out = np.zeros((h, w, 3), dtype=np.float32) if want_out else None
+        rgb8, out, rgb8_ptr, out_ptr = _image_outputs(h, w, want_rgb8, want_out)
         clamped = C.c_uint32(0)
         check(self._lib.ff_despeckle(self._state, w, h, C.byref(p), rad.ctypes.data, alb.ctypes.data if alb is not None else None, idp.ctypes.data, 0,
-                                     rgb8.ctypes.data if want_rgb8 else None, 0, out.ctypes.data if want_out else None, 0, C.byref(clamped)))
+                                     rgb8_ptr, 0, out_ptr, 0, C.byref(clamped)))
         return rgb8, out, int(clamped.value)
 
     def despeckle_device(self, width, height, radiance_ptr, albedo_ptr, ids_ptr, p=None, rgb8_ptr=None, radiance_out_ptr=None, want_count=True):
         """ff_despeckle on DEVICE buffers (raw pointers); the outputs must not overlap an input -> the number of clamped pixels
         (None with want_count=False: out_clamped is passed as NULL)."""
         p = p if p is not None else despeckle_params()
-        vp = lambda q: C.c_void_p(q) if q else None  # noqa: E731
         clamped = C.c_uint32(0)
-        check(self._lib.ff_despeckle(self._state, width, height, C.byref(p), vp(radiance_ptr), vp(albedo_ptr), vp(ids_ptr), 1, vp(rgb8_ptr), 1,
-                                     vp(radiance_out_ptr), 1, C.byref(clamped) if want_count else None))
+        check(self._lib.ff_despeckle(self._state, width, height, C.byref(p), _vp(radiance_ptr), _vp(albedo_ptr), _vp(ids_ptr), 1, _vp(rgb8_ptr), 1,
+                                     _vp(radiance_out_ptr), 1, C.byref(clamped) if want_count else None))
         return int(clamped.value) if want_count else None
 
     def sharpen(self, radiance, p=None, want_rgb8=True, want_out=True):
@@ -1608,26 +1530,20 @@ class Tracer:
         p = p if p is not None else sharpen_params()
         if hasattr(radiance, "data_ptr"):
             import torch
-            h, w = radiance.shape[:2]
-            if not radiance.is_cuda or radiance.dtype != torch.float32 or tuple(radiance.shape) != (h, w, 3) or not radiance.is_contiguous():
-                raise ValueError("sharpen: radiance must be a contiguous [H,W,3] float32 tensor on the device")
-            rgb8 = torch.zeros((h, w, 3), dtype=torch.uint8, device=radiance.device) if want_rgb8 else None
-            out = torch.zeros((h, w, 3), dtype=torch.float32, device=radiance.device) if want_out else None
+            h, w = _device_image(radiance, torch.float32, "sharpen: radiance", "float32")
+            rgb8, out, rgb8_ptr, out_ptr = _image_outputs(h, w, want_rgb8, want_out, radiance.device)
             torch.cuda.synchronize(radiance.device)
-            self.sharpen_device(w, h, radiance.data_ptr(), p, rgb8.data_ptr() if want_rgb8 else None, out.data_ptr() if want_out else None)
+            self.sharpen_device(w, h, radiance.data_ptr(), p, rgb8_ptr, out_ptr)
             return rgb8, out
-        rad, (h, w) = _sharpen_image(radiance, "sharpen")
-        rgb8 = np.zeros((h, w, 3), dtype=np.uint8) if want_rgb8 else None
-        out = np.zeros((h, w, 3), dtype=np.float32) if want_out else None
-        check(self._lib.ff_sharpen(self._state, w, h, C.byref(p), rad.ctypes.data, 0, rgb8.ctypes.data if want_rgb8 else None, 0,
-                                   out.ctypes.data if want_out else None, 0))
+        rad, (h, w) = _float3_image(radiance, "sharpen")
+        rgb8, out, rgb8_ptr, out_ptr = _image_outputs(h, w, want_rgb8, want_out)
+        check(self._lib.ff_sharpen(self._state, w, h, C.byref(p), rad.ctypes.data, 0, rgb8_ptr, 0, out_ptr, 0))
         return rgb8, out
 
     def sharpen_device(self, width, height, radiance_ptr, p=None, rgb8_ptr=None, radiance_out_ptr=None):
         """ff_sharpen on DEVICE buffers (raw pointers); the outputs must not overlap the input."""
         p = p if p is not None else sharpen_params()
-        vp = lambda q: C.c_void_p(q) if q else None  # noqa: E731
-        check(self._lib.ff_sharpen(self._state, width, height, C.byref(p), vp(radiance_ptr), 1, vp(rgb8_ptr), 1, vp(radiance_out_ptr), 1))
+        check(self._lib.ff_sharpen(self._state, width, height, C.byref(p), _vp(radiance_ptr), 1, _vp(rgb8_ptr), 1, _vp(radiance_out_ptr), 1))
 
     def local_tonemap(self, radiance, p=None, want_rgb8=True, want_out=True, in_place=False):
         """ff_local_tonemap of radiance [H,W,3] -> (rgb8 [H,W,3] uint8, radiance [H,W,3] float32).  A host array gives host arrays; a
@@ -1636,32 +1552,26 @@ class Tracer:
         p = p if p is not None else local_tonemap_params()
         if hasattr(radiance, "data_ptr"):
             import torch
-            h, w = radiance.shape[:2]
-            if not radiance.is_cuda or radiance.dtype != torch.float32 or tuple(radiance.shape) != (h, w, 3) or not radiance.is_contiguous():
-                raise ValueError("local_tonemap: radiance must be a contiguous [H,W,3] float32 tensor on the device")
-            rgb8 = torch.zeros((h, w, 3), dtype=torch.uint8, device=radiance.device) if want_rgb8 else None
-            out = (radiance if in_place else torch.zeros((h, w, 3), dtype=torch.float32, device=radiance.device)) if want_out else None
+            h, w = _device_image(radiance, torch.float32, "local_tonemap: radiance", "float32")
+            rgb8, out, rgb8_ptr, out_ptr = _image_outputs(h, w, want_rgb8, want_out, radiance.device, out=radiance if in_place else None)
             torch.cuda.synchronize(radiance.device)
-            self.local_tonemap_device(w, h, radiance.data_ptr(), p, rgb8.data_ptr() if want_rgb8 else None, out.data_ptr() if want_out else None)
+            self.local_tonemap_device(w, h, radiance.data_ptr(), p, rgb8_ptr, out_ptr)
             return rgb8, out
-        rad, (h, w) = _sharpen_image(radiance, "local_tonemap")
-        rgb8 = np.zeros((h, w, 3), dtype=np.uint8) if want_rgb8 else None
-        out = (rad.copy() if in_place else np.zeros((h, w, 3), dtype=np.float32)) if want_out else None
+        rad, (h, w) = _float3_image(radiance, "local_tonemap")
+        rgb8, out, rgb8_ptr, out_ptr = _image_outputs(h, w, want_rgb8, want_out, out=rad.copy() if in_place else None)
         src = out if (in_place and want_out) else rad
-        check(self._lib.ff_local_tonemap(self._state, w, h, C.byref(p), src.ctypes.data, 0, rgb8.ctypes.data if want_rgb8 else None, 0,
-                                         out.ctypes.data if want_out else None, 0))
+        check(self._lib.ff_local_tonemap(self._state, w, h, C.byref(p), src.ctypes.data, 0, rgb8_ptr, 0, out_ptr, 0))
         return rgb8, out
 
     def local_tonemap_device(self, width, height, radiance_ptr, p=None, rgb8_ptr=None, radiance_out_ptr=None):
         """ff_local_tonemap on DEVICE buffers (raw pointers); radiance_out_ptr may be radiance_ptr."""
         p = p if p is not None else local_tonemap_params()
-        vp = lambda q: C.c_void_p(q) if q else None  # noqa: E731
-        check(self._lib.ff_local_tonemap(self._state, width, height, C.byref(p), vp(radiance_ptr), 1, vp(rgb8_ptr), 1, vp(radiance_out_ptr), 1))
+        check(self._lib.ff_local_tonemap(self._state, width, height, C.byref(p), _vp(radiance_ptr), 1, _vp(rgb8_ptr), 1, _vp(radiance_out_ptr), 1))
 
     def encode_yuv(self, linear, p=None):
         """ff_encode_yuv of host display-linear [H,W,3] -> (luma [H,W], chroma [ceil(H/2),ceil(W/2),2] of Cb Cr pairs), host arrays:
         uint8 codes at depth 8 (NV12), uint16 codes << 6 at depth 10 (P010)."""
-        img, (h, w) = _sharpen_image(linear, "encode_yuv")
+        img, (h, w) = _float3_image(linear, "encode_yuv")
         p = p if p is not None else yuv_params()
         luma, chroma = _yuv_planes(h, w, p)
         check(self._lib.ff_encode_yuv(self._state, w, h, C.byref(p), img.ctypes.data, 0, luma.ctypes.data, chroma.ctypes.data, 0))
@@ -1674,9 +1584,7 @@ class Tracer:
         each other."""
         import torch
         p = p if p is not None else yuv_params()
-        h, w = linear.shape[:2]
-        if not linear.is_cuda or linear.dtype != torch.float32 or tuple(linear.shape) != (h, w, 3) or not linear.is_contiguous():
-            raise ValueError("encode_yuv_device: linear must be a contiguous [H,W,3] float32 tensor on the device")
+        h, w = _device_image(linear, torch.float32, "encode_yuv_device: linear", "float32")
         need = yuv_plane_bytes(w, h, p)
         dtype = torch.uint8 if int(p.depth) == 8 else torch.int16
         if luma is None:
@@ -1695,31 +1603,24 @@ class Tracer:
         """ff_resize of radiance [H,W,3] -> (rgb8 [H',W',3] uint8, radiance [H',W',3] float32).  A host array gives host arrays; a
         contiguous float32 device tensor (torch) gives device tensors."""
         p = p if p is not None else resize_params()
-        shape = (max(int(out_height), 0), max(int(out_width), 0), 3)
+        oh, ow = max(int(out_height), 0), max(int(out_width), 0)
         if hasattr(radiance, "data_ptr"):
             import torch
-            h, w = radiance.shape[:2]
-            if not radiance.is_cuda or radiance.dtype != torch.float32 or tuple(radiance.shape) != (h, w, 3) or not radiance.is_contiguous():
-                raise ValueError("resize: radiance must be a contiguous [H,W,3] float32 tensor on the device")
-            rgb8 = torch.zeros(shape, dtype=torch.uint8, device=radiance.device) if want_rgb8 else None
-            out = torch.zeros(shape, dtype=torch.float32, device=radiance.device) if want_out else None
+            h, w = _device_image(radiance, torch.float32, "resize: radiance", "float32")
+            rgb8, out, rgb8_ptr, out_ptr = _image_outputs(oh, ow, want_rgb8, want_out, radiance.device)
             torch.cuda.synchronize(radiance.device)
-            self.resize_device(w, h, radiance.data_ptr(), out_width, out_height, p, rgb8.data_ptr() if want_rgb8 else None,
-                               out.data_ptr() if want_out else None)
+            self.resize_device(w, h, radiance.data_ptr(), out_width, out_height, p, rgb8_ptr, out_ptr)
             return rgb8, out
-        rad, (h, w) = _sharpen_image(radiance, "resize")
-        rgb8 = np.zeros(shape, dtype=np.uint8) if want_rgb8 else None
-        out = np.zeros(shape, dtype=np.float32) if want_out else None
-        check(self._lib.ff_resize(self._state, C.byref(p), w, h, rad.ctypes.data, 0, out_width, out_height, rgb8.ctypes.data if want_rgb8 else None, 0,
-                                  out.ctypes.data if want_out else None, 0))
+        rad, (h, w) = _float3_image(radiance, "resize")
+        rgb8, out, rgb8_ptr, out_ptr = _image_outputs(oh, ow, want_rgb8, want_out)
+        check(self._lib.ff_resize(self._state, C.byref(p), w, h, rad.ctypes.data, 0, out_width, out_height, rgb8_ptr, 0, out_ptr, 0))
         return rgb8, out
 
     def resize_device(self, in_width, in_height, radiance_ptr, out_width, out_height, p=None, rgb8_ptr=None, radiance_out_ptr=None):
         """ff_resize on DEVICE buffers (raw pointers); the outputs must not overlap the input or each other."""
         p = p if p is not None else resize_params()
-        vp = lambda q: C.c_void_p(q) if q else None  # noqa: E731
-        check(self._lib.ff_resize(self._state, C.byref(p), in_width, in_height, vp(radiance_ptr), 1, out_width, out_height, vp(rgb8_ptr), 1,
-                                  vp(radiance_out_ptr), 1))
+        check(self._lib.ff_resize(self._state, C.byref(p), in_width, in_height, _vp(radiance_ptr), 1, out_width, out_height, _vp(rgb8_ptr), 1,
+                                  _vp(radiance_out_ptr), 1))
 
     def interpolate(self, mid, a, b, p=None, geom_maps=None, want_rgb8=True, want_out=True):
         """ff_interpolate of host arrays: mid = (camera, gbuffer), a and b = (camera, radiance [H,W,3], gbuffer), a gbuffer being a
@@ -1728,13 +1629,12 @@ class Tracer:
         cams, im, (h, w) = _interpolate_images(mid, a, b, "interpolate")
         maps, n = _interpolate_maps(geom_maps, "interpolate")
         p = p if p is not None else interpolate_params()
-        rgb8 = np.zeros((h, w, 3), dtype=np.uint8) if want_rgb8 else None
-        out = np.zeros((h, w, 3), dtype=np.float32) if want_out else None
+        rgb8, out, rgb8_ptr, out_ptr = _image_outputs(h, w, want_rgb8, want_out)
         counts = np.zeros(5, dtype=np.uint32)
         d = [x.ctypes.data for x in im]
         check(self._lib.ff_interpolate(self._state, w, h, C.byref(p), C.byref(cams[0]), d[0], d[1], C.byref(cams[1]), d[2], d[3], d[4], C.byref(cams[2]),
-                                       d[5], d[6], d[7], maps.ctypes.data if maps is not None else None, n, 0, rgb8.ctypes.data if want_rgb8 else None, 0,
-                                       out.ctypes.data if want_out else None, 0, counts.ctypes.data))
+                                       d[5], d[6], d[7], maps.ctypes.data if maps is not None else None, n, 0, rgb8_ptr, 0, out_ptr,
+                                       0, counts.ctypes.data))
         return rgb8, out, counts
 
     def interpolate_device(self, width, height, cameras, image_ptrs, p=None, geom_maps=None, rgb8_ptr=None, radiance_out_ptr=None, want_counts=True):
@@ -1743,35 +1643,28 @@ class Tracer:
         outputs must not overlap an input -> counts [5] uint32 (None without want_counts)."""
         maps, n = _interpolate_maps(geom_maps, "interpolate_device")
         p = p if p is not None else interpolate_params()
-        vp = lambda q: C.c_void_p(q) if q else None  # noqa: E731
-        d = [vp(q) for q in image_ptrs]
+        d = [_vp(q) for q in image_ptrs]
         if len(d) != 8:
             raise ValueError("interpolate_device: image_ptrs must name eight images")
         counts = np.zeros(5, dtype=np.uint32)
         check(self._lib.ff_interpolate(self._state, width, height, C.byref(p), C.byref(cameras[0]), d[0], d[1], C.byref(cameras[1]), d[2], d[3], d[4],
-                                       C.byref(cameras[2]), d[5], d[6], d[7], maps.ctypes.data if maps is not None else None, n, 1, vp(rgb8_ptr), 1,
-                                       vp(radiance_out_ptr), 1, counts.ctypes.data if want_counts else None))
+                                       C.byref(cameras[2]), d[5], d[6], d[7], maps.ctypes.data if maps is not None else None, n, 1, _vp(rgb8_ptr), 1,
+                                       _vp(radiance_out_ptr), 1, counts.ctypes.data if want_counts else None))
         return counts if want_counts else None
 
     def display(self, radiance, p=None, want_rgb8=True, want_out=True):
         """ff_display of host radiance [H,W,3] -> (rgb8 [H,W,3] uint8, display_out [H,W,3] float32: the curve's output in [0, 1]);
         the adapted exposure stays in the state."""
-        rad = np.ascontiguousarray(radiance, dtype=np.float32)
-        if rad.ndim != 3 or rad.shape[2] != 3:
-            raise ValueError("display: radiance must be [H,W,3]")
-        h, w = rad.shape[:2]
+        rad, (h, w) = _float3_image(radiance, "display")
         p = p if p is not None else display_params()
-        rgb8 = np.zeros((h, w, 3), dtype=np.uint8) if want_rgb8 else None
-        out = np.zeros((h, w, 3), dtype=np.float32) if want_out else None
-        check(self._lib.ff_display(self._state, w, h, C.byref(p), rad.ctypes.data, 0, rgb8.ctypes.data if want_rgb8 else None, 0,
-                                   out.ctypes.data if want_out else None, 0))
+        rgb8, out, rgb8_ptr, out_ptr = _image_outputs(h, w, want_rgb8, want_out)
+        check(self._lib.ff_display(self._state, w, h, C.byref(p), rad.ctypes.data, 0, rgb8_ptr, 0, out_ptr, 0))
         return rgb8, out
 
     def display_device(self, width, height, radiance_ptr, p=None, rgb8_ptr=None, display_out_ptr=None):
         """ff_display on DEVICE buffers (raw pointers); display_out_ptr may equal radiance_ptr."""
         p = p if p is not None else display_params()
-        vp = lambda q: C.c_void_p(q) if q else None  # noqa: E731
-        check(self._lib.ff_display(self._state, width, height, C.byref(p), vp(radiance_ptr), 1, vp(rgb8_ptr), 1, vp(display_out_ptr), 1))
+        check(self._lib.ff_display(self._state, width, height, C.byref(p), _vp(radiance_ptr), 1, _vp(rgb8_ptr), 1, _vp(display_out_ptr), 1))
 
     def display_to_pbo(self, radiance, p=None):
         """ff_display_to_pbo of host radiance [H,W,3] into the buffer registered with ff_register_gl_pbo."""
