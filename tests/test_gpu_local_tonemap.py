@@ -1,14 +1,16 @@
 """ff_local_tonemap on the GPU: bit for bit, radiance and bytes, against the host twin ff_local_tonemap_host (and through it the
 numpy restatement, tests/test_local_tonemap_host.py) with host buffers, device buffers and in place, over the shapes that take each
 path of the kernels - a one-pixel image, one partial cell, partial last rows and columns of cells, a column of cells one pixel
-wide, several small tiles packed per workgroup - and on an empty grid, a grid of one pixel, the two-region image, the identity and
-a work buffer that regrows."""
+wide, several small tiles packed per workgroup, every cell size over several cell rows and columns with partial last cells - and
+on an empty grid, a grid of one pixel, the two-region image, cell sums beyond float precision, a checker that leaves the splat no
+run to merge, cells emptied between two calls on one state, the identity and a work buffer that regrows."""
 import numpy as np
 import pytest
 
 from gpupathtracer_amd import lib
 import local_tonemap_ref as R
-from local_tonemap_cases import GPU_SHAPES, TOL, TWO_REGION_PARAMS, assert_same, bits, hdr, params, spoiled, two_regions
+from local_tonemap_cases import (CELLS, EXTREME_STOPS, GPU_SHAPES, TOL, TWO_REGION_PARAMS, assert_same, bin_checker, bits, extreme, hdr, longest_run, params,
+                                 spoiled, stale_bases, stale_pair, two_regions)
 
 pytestmark = pytest.mark.gpu
 
@@ -41,6 +43,61 @@ def test_kernels_match_the_twin_bit_for_bit(tracer, w, h, cell):
         out = check_every_buffer_kind(tracer, rad, p)[1]
         changed += int((bits(out) != bits(rad)).sum())
     assert changed
+
+
+@pytest.mark.parametrize("cell", CELLS)
+@pytest.mark.parametrize("stop", list(EXTREME_STOPS))
+def test_long_runs_and_sums_beyond_float_precision(tracer, stop, cell):
+    """Flat and two-level 128 x 128 images in the top stop and in the bottom mapped stop: a splat thread of cell 64 merges its 16
+    pixels into one add, a full cell of 64 sums q10 beyond +-2^24 and the x blur's (float)int rounds it (asserted here for cell 64
+    through the grid twin; tests/test_local_tonemap_host.py holds the twin against the restatement on the same images)."""
+    for two_level in (False, True):
+        rad = extreme(stop, two_level)
+        _, S = lib.local_tonemap_grid_host(rad, params(cell=64))
+        assert (np.abs(S.astype(np.int64)).max(axis=2) > 2 ** 24).all()
+        if two_level:
+            assert (S.astype(F).astype(np.int64) != S).any()
+        assert longest_run(rad, 64) == 16
+        for compression, detail in [(0.5, 1.0), (0.0, 2.0)]:
+            out = check_every_buffer_kind(tracer, rad, params(cell=cell, compression=compression, detail=detail))[1]
+            assert (bits(out) != bits(rad)).any()
+
+
+@pytest.mark.parametrize("cell", CELLS)
+def test_checker_of_two_bins(tracer, cell):
+    """A one-pixel checker of two adjacent bins, plain and shifted every 256 / cell rows, so that no run of a splat thread of cell 32
+    or 64 is longer than one pixel: every add is a thread's own."""
+    rows = 256 // cell if cell * cell > 256 else 0
+    assert longest_run(bin_checker(rows), cell) == 1
+    for rad in {0: bin_checker(), rows: bin_checker(rows)}.values():
+        check_every_buffer_kind(tracer, rad, params(cell=cell, detail=2.0))
+
+
+@pytest.mark.parametrize("cell", CELLS)
+def test_emptied_cells_are_written_again(tracer, cell):
+    """The splat writes empty cells, so the grid is never cleared: on one state a fully mapped 130 x 70 image, then the same size
+    with chosen cells wholly unmapped (for cell 8 one tile of the four in a workgroup, and the last, partial workgroup) - host
+    buffers, then device buffers.  The second result is the twin's bit for bit; that a stale cell would change it is asserted
+    through the grid twin: the cells are empty, and a mapped pixel next to each gets another base than the first image's cell
+    would give it."""
+    import torch
+    first, second, cells = stale_pair(cell)
+    p = params(cell=cell, detail=2.0)
+    n1, _ = lib.local_tonemap_grid_host(first, p)
+    n2, _ = lib.local_tonemap_grid_host(second, p)
+    for cy, cx in cells:
+        assert n1[cy, cx].any() and not n2[cy, cx].any()
+    for at, true, stale in stale_bases(cell):
+        assert true != stale, (at, true, stale)
+    want1, want2 = lib.local_tonemap_host(first, p), lib.local_tonemap_host(second, p)
+    assert (bits(want1[1]) != bits(want2[1]))[second[..., 0] >= 0].any()
+    assert_same(tracer.local_tonemap(first, p), want1)
+    assert_same(tracer.local_tonemap(second, p), want2)
+    d_first, d_second = (torch.from_numpy(np.array(a)).cuda() for a in (first, second))
+    rgb8, out = tracer.local_tonemap(d_first, p)
+    assert_same((rgb8.cpu().numpy(), out.cpu().numpy()), want1)
+    rgb8, out = tracer.local_tonemap(d_second, p)
+    assert_same((rgb8.cpu().numpy(), out.cpu().numpy()), want2)
 
 
 def test_only_one_output_at_a_time(tracer):

@@ -13,8 +13,8 @@ import pytest
 from gpupathtracer_amd import lib
 from gpupathtracer_amd import types as T
 import local_tonemap_ref as R
-from local_tonemap_cases import (CELLS, COMPRESSIONS, DETAILS, HOST_SIZES, SPOILED, TOL, TWO_REGION_PARAMS, assert_same, bits, hdr, midrange, params,
-                                 reference, spoiled, two_regions)
+from local_tonemap_cases import (CELLS, COMPRESSIONS, DETAILS, EXTREME_STOPS, HOST_SIZES, SPOILED, TOL, TWO_REGION_PARAMS, assert_same, bin_checker, bits,
+                                 extreme, hdr, longest_run, midrange, params, reference, spoiled, stale_bases, stale_pair, two_regions)
 
 F = np.float32
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -129,6 +129,62 @@ def test_grid_of_spoiled_pixels_and_bin_edges():
     n, S = lib.local_tonemap_grid_host(one, params(cell=8))
     assert n[0, 0].nonzero()[0].tolist() == [0, 16, 39]
     assert (S[0, 0, 0], S[0, 0, 16], S[0, 0, 39]) == (-16 * 1024, 0, 24 * 1024 - 1)
+
+
+@pytest.mark.parametrize("stop", list(EXTREME_STOPS))
+def test_cell_sums_beyond_float_precision(stop):
+    """A full 64 x 64 cell in the top or the bottom stop sums q10 beyond +-2^24, and with two levels to a sum that (float)int rounds in
+    the x blur: what the GPU file's test of the same images is for.  Twin and restatement agree bit for bit for every cell size."""
+    for two_level in (False, True):
+        rad = extreme(stop, two_level)
+        n, S = lib.local_tonemap_grid_host(rad, params(cell=64))
+        assert n.shape == (2, 2, 40) and int(n.sum()) == 128 * 128 and (n[..., 39 if stop == "top" else 0] == 4096).all()
+        assert (np.abs(S.astype(np.int64)).max(axis=2) > 2 ** 24).all()
+        if two_level:
+            assert (S.astype(F).astype(np.int64) != S).any()   # (the conversion of some cell's sum is not exact)
+        assert longest_run(rad, 64) == 16 and longest_run(rad, 32) == 4
+        for cell in CELLS:
+            gn, gS = lib.local_tonemap_grid_host(rad, params(cell=cell))
+            rn, rS = R.splat(rad, cell)
+            assert np.array_equal(gn, rn) and np.array_equal(gS, rS)
+            for compression, detail in [(0.5, 1.0), (0.0, 2.0)]:
+                p = params(cell=cell, compression=compression, detail=detail)
+                got = lib.local_tonemap_host(rad, p)
+                assert_same(got, reference(rad, p))
+                assert (bits(got[1]) != bits(rad)).any()
+
+
+def test_checker_of_two_bins_leaves_no_run():
+    """The one-pixel checker of bins 16 and 17: plain, a splat thread of cell 32 or 64 sees one level only; shifted every 8 (4) rows,
+    no run of a thread of cell 32 (64) is longer than one pixel."""
+    assert longest_run(bin_checker(), 64) == 16 and longest_run(bin_checker(), 32) == 4
+    assert longest_run(bin_checker(4), 64) == 1 and longest_run(bin_checker(8), 32) == 1 and longest_run(bin_checker(), 16) == 1
+    for rows in (0, 4, 8):
+        rad = bin_checker(rows)
+        n, _ = lib.local_tonemap_grid_host(rad, params(cell=64))
+        assert (n[..., 16] == 2048).all() and (n[..., 17] == 2048).all() and int(n.sum()) == 128 * 128
+        for cell in CELLS:
+            p = params(cell=cell, detail=2.0)
+            assert_same(lib.local_tonemap_host(rad, p), reference(rad, p))
+
+
+@pytest.mark.parametrize("cell", CELLS)
+def test_emptied_cells_change_their_neighbours_base(cell):
+    """stale_pair(): the second image's chosen cells are empty in the grid, full in the first image's, and a mapped pixel next to each
+    gets another base than it would if the cell still held the first image's sums - a kernel that left such a cell unwritten between
+    two calls would show."""
+    first, second, cells = stale_pair(cell)
+    p = params(cell=cell)
+    n1, _ = lib.local_tonemap_grid_host(first, p)
+    n2, S2 = lib.local_tonemap_grid_host(second, p)
+    assert int(n1.sum()) == first.shape[0] * first.shape[1]
+    for cy, cx in cells:
+        assert n1[cy, cx].any() and not n2[cy, cx].any() and not S2[cy, cx].any()
+    assert int(n2.sum()) == int(n1.sum()) - sum(int(n1[cy, cx].sum()) for cy, cx in cells)
+    for at, true, stale in stale_bases(cell):
+        assert true != stale, (at, true, stale)
+    q = params(cell=cell, detail=2.0)
+    assert_same(lib.local_tonemap_host(second, q), reference(second, q))
 
 
 def test_identity_returns_the_input_bit_for_bit():

@@ -1,6 +1,7 @@
 """ff_encode_yuv without a GPU: the host twin ff_encode_yuv_host against the numpy float32 restatement (tests/yuv_ref.py) byte for byte
 over every parameter combination; the knots; the textbook colour-bar codes; neutral greys; the deviation from the float64 true form;
-hand-derived siting weights; sanitising; the refusals; the YUV4MPEG2 writer."""
+hand-derived siting weights; sanitising; the helpers that the GPU file's tests of tall images stand on; the refusals; the YUV4MPEG2
+writer."""
 import ctypes as C
 import math
 
@@ -10,7 +11,8 @@ import pytest
 from gpupathtracer_amd import lib
 from gpupathtracer_amd import types as T
 import yuv_ref as R
-from yuv_cases import ALL_COMBINATIONS, DEPTHS, HOST_SIZES, MATRICES, RANGES, SITINGS, TRANSFERS, assert_same, inputs, name_of, params, unshift
+from yuv_cases import (ALL_COMBINATIONS, DEPTHS, HOST_SIZES, MATRICES, PLANTS, RANGES, SITINGS, TRANSFERS, assert_same, black_planes, blue_on_black,
+                       gpu_param_sets, inputs, large_input, name_of, params, planes_below, planted_samples, unshift)
 
 F = np.float32
 
@@ -181,9 +183,6 @@ def test_siting_weights():
         assert tuple(chroma[1, 1]) == W[0.5] and tuple(chroma[0, 1]) == W[0] and tuple(chroma[1, 0]) == W[0]
 
 
-PLANTS = [(float("nan"), 0.0), (-1.0, 0.0), (float("-inf"), 0.0), (float("inf"), 65536.0), (1e30, 65536.0)]
-
-
 @pytest.mark.parametrize("combo", [(T.YUV_TRANSFER_BT709, T.YUV_MATRIX_BT709, T.YUV_RANGE_LIMITED, 8, T.YUV_SITING_LEFT),
                                    (T.YUV_TRANSFER_PQ, T.YUV_MATRIX_BT2020, T.YUV_RANGE_FULL, 10, T.YUV_SITING_CENTER)], ids=name_of)
 def test_sanitising(combo):
@@ -208,6 +207,36 @@ def test_sanitising(combo):
     clean = lib.encode_yuv_host(base, p)[0]
     assert np.array_equal(got[0][untouched], clean[untouched])
     assert (got[0][~untouched] != clean[~untouched]).any()
+
+
+@pytest.mark.parametrize("name", list(gpu_param_sets()))
+def test_planted_pixels_below_a_black_top(name):
+    """What the GPU file's test of the second tile trip relies on, held here on an image small enough to restate whole: blue pixels
+    either side of column 63 | 64 in the last rows of an odd height change exactly planted_samples(), and planes_below() is the
+    whole image's planes, for the restatement and for the twin."""
+    p = gpu_param_sets()[name]
+    w, h, first = 67, 83, 62
+    black = black_planes(w, h, p)
+    assert_same(black, R.encode(np.zeros((h, w, 3), F), p))
+    assert_same(black, lib.encode_yuv_host(np.zeros((h, w, 3), F), p))
+    every = [(x, y) for y in (64, 65, 82) for x in (63, 64)]
+    for points in [[q] for q in every] + [every]:
+        img = blue_on_black(w, h, points)
+        want = R.encode(img, p)
+        assert_same(planes_below(img, p, first), want, f"{points} restatement")
+        assert_same(planes_below(img, p, first, lib.encode_yuv_host), want, f"{points} twin")
+        for plane in (0, 1):
+            touched = np.argwhere((want[1] != black[1])[..., plane])
+            assert {tuple(t) for t in touched.tolist()} == planted_samples(points, p.siting), (points, plane)
+        assert {tuple(t) for t in np.argwhere(want[0] != black[0]).tolist()} == {(y, x) for x, y in points}
+
+
+def test_large_input_holds_every_transfers_knots():
+    img = large_input(65, 99)
+    assert img.shape == (99, 65, 3) and not img.flags.writeable and img.max() > 50 and img.min() >= 0
+    for band, transfer in enumerate(TRANSFERS):
+        K = R.knots(transfer) / (F(203) / F(10000)) if transfer == T.YUV_TRANSFER_PQ else R.knots(transfer)
+        assert np.isin(img[33 * band:33 * band + 33], K.astype(F)).sum() > 100
 
 
 def _host_status(w, h, p, img, luma, chroma):

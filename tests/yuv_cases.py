@@ -1,4 +1,5 @@
 """What tests/test_yuv_host.py and tests/test_gpu_yuv.py share: the parameter sets, the input images and the comparison."""
+import functools
 import itertools
 
 import numpy as np
@@ -16,11 +17,25 @@ DEPTHS = (8, 10)
 SITINGS = (T.YUV_SITING_CENTER, T.YUV_SITING_LEFT)
 ALL_COMBINATIONS = list(itertools.product(TRANSFERS, MATRICES, RANGES, DEPTHS, SITINGS))
 
-HOST_SIZES = [(1, 1), (2, 2), (3, 3), (5, 2), (7, 5), (66, 19)]
+# widths that are a multiple of 4 take the kernel's whole-dword path where the buffers are 16-byte aligned: with one row, with an odd
+# height (the row below the image repeats the last one), below, at and past the 64-pixel tile
+VECTOR_SIZES = [(4, 1), (4, 3), (8, 2), (64, 17), (68, 19)]
+HOST_SIZES = [(1, 1), (2, 2), (3, 3), (5, 2), (7, 5), (66, 19)] + VECTOR_SIZES
 # around the lane's 4 x 2 block and the kernel's 64 x 32 tile (and every smaller power-of-two edge)
-GPU_SIZES = [(1, 1), (2, 2), (3, 3), (5, 2), (7, 5), (64, 16), (65, 17), (67, 19), (130, 35)]
+GPU_SIZES = [(1, 1), (2, 2), (3, 3), (5, 2), (7, 5), (64, 16), (65, 17), (67, 19), (130, 35)] + VECTOR_SIZES
+# every parameter combination runs on the device at an odd height with two tile columns: the scalar path and the vector path
+COMBINATION_SIZES = [(67, 19), (68, 19)]
 SEAM_SIZE = (130, 35)
 SEAM_COLUMNS, SEAM_ROWS = (63, 64, 65, 127, 128), (15, 16, 17)
+# more tiles than the kernel's 2 048 workgroups, so that some take a second trip of the tile loop: 2 x 1025 tiles (workgroups 0 and
+# 1 come back for a last tile row of 19 rows), scalar and vector, and 1024 x 3 tiles (a whole tile row of second trips)
+TALL_SIZES = [(65, 32787), (68, 32787)]
+WIDE_SIZE = (65535, 65)
+TALL_PLANT_COLUMNS, TALL_PLANT_ROWS = (63, 64), (32768, 32769, 32786)  # either side of the tile seam; rows of the second trip
+# where two lanes (4 x 2 pixels) or two tiles (64 x 32) meet in SEAM_SIZE, the last column and the last row
+MEET_COLUMNS, MEET_ROWS = (3, 4, 63, 64, 127, 128, 129), (1, 2, 31, 32, 34)
+# what step 1 replaces: (planted value, the value that stands for it)
+PLANTS = [(float("nan"), 0.0), (-1.0, 0.0), (float("-inf"), 0.0), (float("inf"), 65536.0), (1e30, 65536.0)]
 
 
 def params(transfer=T.YUV_TRANSFER_BT709, matrix=T.YUV_MATRIX_BT709, range_=T.YUV_RANGE_LIMITED, depth=8, siting=T.YUV_SITING_LEFT, **more):
@@ -32,6 +47,7 @@ def gpu_param_sets():
         "nv12-bt709-limited-left": params(),
         "p010-pq-bt2020-limited-left": params(T.YUV_TRANSFER_PQ, T.YUV_MATRIX_BT2020, T.YUV_RANGE_LIMITED, 10, T.YUV_SITING_LEFT),
         "nv12-srgb-full-center": params(T.YUV_TRANSFER_SRGB, T.YUV_MATRIX_BT709, T.YUV_RANGE_FULL, 8, T.YUV_SITING_CENTER),
+        "p010-bt709-bt2020-full-center": params(T.YUV_TRANSFER_BT709, T.YUV_MATRIX_BT2020, T.YUV_RANGE_FULL, 10, T.YUV_SITING_CENTER),
     }
 
 
@@ -57,6 +73,55 @@ def inputs(w, h, transfer=T.YUV_TRANSFER_BT709, seed=0):
     img = np.where(pick == 0, low, np.where(pick == 1, high, k)).astype(F)
     img = np.maximum(img, F(0))
     return np.ascontiguousarray(img.reshape(h, w, 3))
+
+
+@functools.lru_cache(maxsize=None)
+def large_input(w, h):
+    """One read-only w x h image for the sizes of more than 2 048 tiles, made once per session: three bands of rows, each inputs() of
+    one transfer, so that every parameter set finds its own knots in it."""
+    cuts = [0, h // 3, 2 * (h // 3), h]
+    img = np.concatenate([inputs(w, b - a, t, seed=3) for t, a, b in zip(TRANSFERS, cuts, cuts[1:])])
+    assert img.shape == (h, w, 3)
+    img.setflags(write=False)
+    return img
+
+
+def black_planes(w, h, p):
+    """The planes of a black w x h image: one code each, from the restatement of a 2 x 2 one."""
+    luma, chroma = R.encode(np.zeros((2, 2, 3), F), p)
+    return np.full((h, w), luma[0, 0], luma.dtype), np.broadcast_to(chroma[0, 0], ((h + 1) // 2, (w + 1) // 2, 2)).copy()
+
+
+def blue_on_black(w, h, points):
+    """A black w x h image with a saturated-blue pixel at each (x, y) of points."""
+    img = np.zeros((h, w, 3), F)
+    for x, y in points:
+        img[y, x, 2] = 1.0
+    return img
+
+
+def planes_below(img, p, first_row, encode=R.encode):
+    """The planes of an image that is black above the even row first_row: black_planes() there, and `encode` of the rows from
+    first_row on below.  A chroma sample takes rows 2Y and 2Y + 1 and nothing above them, so the planes of the lower part alone are
+    the lower part of the whole image's planes (tests/test_yuv_host.py holds this against the whole image's)."""
+    h, w = img.shape[:2]
+    assert first_row % 2 == 0 and not img[:first_row].any()
+    luma, chroma = black_planes(w, h, p)
+    low = encode(np.ascontiguousarray(img[first_row:]), p)
+    luma[first_row:] = np.asarray(low[0]).view(luma.dtype)
+    chroma[first_row // 2:] = np.asarray(low[1]).view(chroma.dtype)
+    return luma, chroma
+
+
+def planted_samples(points, siting):
+    """The chroma samples (row, column) that pixels (x, y) of another colour on a flat image change: the pixel's own, and under LEFT
+    the next one too for an odd column (its tap at 2X - 1)."""
+    want = set()
+    for x, y in points:
+        want.add((y // 2, x // 2))
+        if siting == T.YUV_SITING_LEFT and x % 2 == 1:
+            want.add((y // 2, x // 2 + 1))
+    return want
 
 
 def assert_same(got, want, what=""):
