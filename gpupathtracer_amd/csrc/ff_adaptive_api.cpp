@@ -179,19 +179,9 @@ int ff_render_adaptive(FfState* s, const FfCamera* camera, const FfRenderParams*
     TileBuffers tb;
     st = tile_buffers(s, tiles, &tb);
     if (st != FF_OK) return st;
-    unsigned char* rgb8_dev = (unsigned char*)rgb8;
-    float* rad_dev = radiance;
+    RenderOutputs out(s, px, rgb8, rgb8_on_device, radiance, radiance_on_device);
+    if (out.status != FF_OK) return out.status;
     uint16_t* passes_dev = passes_out;
-    if (rgb8 && !rgb8_on_device) {
-        st = ensure_bytes((void**)&s->d_rgb8, &s->rgb8_bytes, px * 3 + 16);
-        if (st != FF_OK) return st;
-        rgb8_dev = s->d_rgb8;
-    }
-    if (radiance && !radiance_on_device) {
-        st = ensure_bytes((void**)&s->d_radiance, &s->radiance_bytes, plane * sizeof(float) + 16);
-        if (st != FF_OK) return st;
-        rad_dev = s->d_radiance;
-    }
     if (passes_out && !passes_on_device) {
         st = ensure_bytes(&ad.d_stage, &ad.stage_bytes, px * sizeof(uint16_t) + 16);
         if (st != FF_OK) return st;
@@ -244,10 +234,10 @@ int ff_render_adaptive(FfState* s, const FfCamera* camera, const FfRenderParams*
 
     // resolve: the means, the 8-bit image and the pass counts
     FF_HIP(hipMemcpyAsync(tb.passes, tile_passes.data(), tiles * sizeof(uint16_t), hipMemcpyHostToDevice, stream));
-    if (rad_dev || rgb8_dev || passes_dev) FF_HIP(launch_adaptive_resolve(grid, d_sum, tb.passes, rad_dev, rgb8_dev, passes_dev, stream));
+    if (out.radiance || out.rgb8 || passes_dev) FF_HIP(launch_adaptive_resolve(grid, d_sum, tb.passes, out.radiance, out.rgb8, passes_dev, stream));
     FF_HIP(hipStreamSynchronize(stream));
-    if (rgb8 && !rgb8_on_device) FF_HIP(hipMemcpy(rgb8, rgb8_dev, px * 3, hipMemcpyDeviceToHost));
-    if (radiance && !radiance_on_device) FF_HIP(hipMemcpy(radiance, rad_dev, plane * sizeof(float), hipMemcpyDeviceToHost));
+    st = out.copy_back();
+    if (st != FF_OK) return st;
     if (passes_out && !passes_on_device) FF_HIP(hipMemcpy(passes_out, passes_dev, px * sizeof(uint16_t), hipMemcpyDeviceToHost));
 
     for (size_t t = 0; t < tiles; ++t) {

@@ -132,44 +132,6 @@ int default_strip_rows(int world, int height)
     return best;
 }
 
-// Device buffers for the frame's final outputs on the gathering device when the caller passed host pointers (or null).
-struct RootOutputs {
-    unsigned char* rgb8 = nullptr;
-    float* radiance = nullptr;
-};
-
-int root_outputs(FfState* s, const FfRenderParams* prm, void* rgb8, int rgb8_on_device, float* radiance, int radiance_on_device, RootOutputs& out)
-{
-    const size_t pixels = (size_t)prm->width * (size_t)prm->height;
-    if (rgb8) {
-        if (rgb8_on_device) out.rgb8 = (unsigned char*)rgb8;
-        else {
-            const int st = ensure_bytes((void**)&s->d_rgb8, &s->rgb8_bytes, pixels * 3 + 16);
-            if (st != FF_OK) return st;
-            out.rgb8 = s->d_rgb8;
-        }
-    }
-    if (radiance) {
-        if (radiance_on_device) out.radiance = radiance;
-        else {
-            const int st = ensure_bytes((void**)&s->d_radiance, &s->radiance_bytes, pixels * 12 + 16);
-            if (st != FF_OK) return st;
-            out.radiance = s->d_radiance;
-        }
-    }
-    return FF_OK;
-}
-
-int copy_root_outputs_to_host(FfState* s, const FfRenderParams* prm, void* rgb8, int rgb8_on_device, float* radiance, int radiance_on_device,
-                              const RootOutputs& out)
-{
-    const size_t pixels = (size_t)prm->width * (size_t)prm->height;
-    if (rgb8 && !rgb8_on_device) FF_HIP(hipMemcpy(rgb8, out.rgb8, pixels * 3, hipMemcpyDeviceToHost));
-    if (radiance && !radiance_on_device) FF_HIP(hipMemcpy(radiance, out.radiance, pixels * 12, hipMemcpyDeviceToHost));
-    (void)s;
-    return FF_OK;
-}
-
 } // namespace
 
 // One rank of a process-per-GPU job.
@@ -393,7 +355,7 @@ int ff_render_distributed(FfState* s, const FfCamera* camera, const FfRenderPara
 
     // (1) local work
     PackLayout L;
-    RootOutputs out;
+    RenderOutputs out; // the frame's final outputs on the gathering device (rank 0)
     unsigned char* pack = nullptr;
     int local = check_render_call(s, camera, params, "ff_render_distributed");
     if (local == FF_OK && params->shade_mode == FF_SHADE_DIFFUSE_PATH_NEE)
@@ -414,7 +376,8 @@ int ff_render_distributed(FfState* s, const FfCamera* camera, const FfRenderPara
         L.strip_rows = strip_rows;
         L.num_parts = world;
         if (root) {
-            local = root_outputs(s, params, rgb8, rgb8_on_device, radiance, radiance_on_device, out);
+            out = RenderOutputs(s, (size_t)L.width * (size_t)L.height, rgb8, rgb8_on_device, radiance, radiance_on_device);
+            local = out.status;
             if (local == FF_OK) local = ensure_bytes((void**)&d->d_gather, &d->gather_bytes, L.total_bytes() + 16);
             pack = d->d_gather; // part 0 sits at offset 0: rendered in place
         }
@@ -478,7 +441,7 @@ int ff_render_distributed(FfState* s, const FfCamera* camera, const FfRenderPara
     if (st != FF_OK) return st;
     d->last_gather_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_gather).count();
     if (root) {
-        st = copy_root_outputs_to_host(s, params, rgb8, rgb8_on_device, radiance, radiance_on_device, out);
+        st = out.copy_back();
         if (st != FF_OK) return st;
     }
     s->stats.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -706,12 +669,11 @@ int ff_multi_render(FfMulti* m, const FfCamera* camera, const FfRenderParams* pa
             if (s->cam_active()) return fail(FF_ERR_UNSUPPORTED, "ff_multi_render: frames with per-sample camera rays (ff_set_camera_sampling) render on one device only");
     FfState* root = m->states[0];
     FF_HIP(hipSetDevice(root->device));
-    RootOutputs out;
-    int st = root_outputs(root, params, rgb8, rgb8_on_device, radiance, radiance_on_device, out);
+    RenderOutputs out(root, (size_t)params->width * (size_t)params->height, rgb8, rgb8_on_device, radiance, radiance_on_device);
+    if (out.status != FF_OK) return out.status;
+    int st = multi_render_core(m, camera, params, strip_rows, out.rgb8, out.radiance);
     if (st != FF_OK) return st;
-    st = multi_render_core(m, camera, params, strip_rows, out.rgb8, out.radiance);
-    if (st != FF_OK) return st;
-    st = copy_root_outputs_to_host(root, params, rgb8, rgb8_on_device, radiance, radiance_on_device, out);
+    st = out.copy_back();
     if (st != FF_OK) return st;
     m->stats.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return FF_OK;

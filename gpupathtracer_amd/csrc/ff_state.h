@@ -1,6 +1,7 @@
 // ff_state.h — the tracer state behind the opaque FfState handle and the internal render steps shared by the
-// translation units of the library (ff_api.cpp: single-device entry points; ff_frame.cpp: one frame; ff_dist.cpp: multi-GPU entry points;
-// ff_image_api.cpp and ff_display_api.cpp: the image-space entry points, whose own state is described in ff_image.h).
+// translation units of the library (ff_api.cpp: the handle's lifetime and measurement; ff_scene_api.cpp: the scene on the device;
+// ff_render_api.cpp: the single-device render entry points; ff_frame.cpp: one frame; ff_dist.cpp: multi-GPU entry points;
+// ff_adaptive_api.cpp: ff_render_adaptive; the image-space *_api.cpp files, whose own state is described in ff_image.h).
 #pragma once
 
 #include <vector>
@@ -94,6 +95,7 @@ struct FfState {
     // work buffers (device)
     float* d_blocksums = nullptr;
     size_t blocksums_bytes = 0;
+    // where a render call's outputs go when the caller gave host buffers (ff::RenderOutputs): filled and copied back within the call
     unsigned char* d_rgb8 = nullptr;
     size_t rgb8_bytes = 0;
     float* d_radiance = nullptr;
@@ -110,8 +112,6 @@ struct FfState {
     size_t accum_bytes = 0;
     float* d_frame = nullptr;
     size_t frame_bytes = 0;
-    float* d_mean = nullptr;
-    size_t mean_bytes = 0;
     int accum_width = 0, accum_height = 0, accum_frames = 0;
     // The image work buffer, the one device buffer every image-space entry point (ff_gbuffer, the denoisers, ff_taa*, ff_upscale,
     // ff_display, ff_motion_blur, ff_depth_of_field, ff_despeckle, ff_sharpen, ff_local_tonemap, ff_interpolate, ff_encode_yuv,
@@ -284,7 +284,6 @@ struct FfState {
     std::vector<unsigned> h_timeline_rows; // one row per wave, added up by ff_debug_timeline
 };
 
-
 #define FF_HIP(call)                                                                                          \
     do {                                                                                                      \
         hipError_t _e = (call);                                                                               \
@@ -306,6 +305,48 @@ int check_render_call(const FfState* s, const FfCamera* camera, const FfRenderPa
 int render_enqueue(FfState* s, const FfCamera* camera, const FfRenderParams* prm, int strip_rows, int part, int num_parts, int local_rows,
                    unsigned char* rgb8_dev, float* radiance_dev, int x0 = 0, int y0 = 0, int win_w = -1);
 int render_finish(FfState* s);
+
+// The two optional outputs of a render entry point of `pixels` pixels, as the frame gets them: the caller's device pointers, or the
+// state's d_rgb8 / d_radiance grown to size, which copy_back() copies to the caller's host buffers after the frame.  Null stays
+// null.  status: FF_OK, or what ensure_bytes returned for a failed allocation (its message is the thread's last error).  The
+// render-side twin of StagedOutputs (ff_image.h).
+struct RenderOutputs {
+    unsigned char* rgb8 = nullptr;
+    float* radiance = nullptr;
+    int status = FF_OK;
+    RenderOutputs() = default; // no outputs (a rank that gathers nothing)
+    RenderOutputs(FfState* s, size_t pixels, void* rgb8_out, int rgb8_on_device, float* radiance_out, int radiance_on_device)
+        : rgb8((unsigned char*)rgb8_out), radiance(radiance_out)
+    {
+        if (rgb8_out && !rgb8_on_device) {
+            status = ensure_bytes((void**)&s->d_rgb8, &s->rgb8_bytes, pixels * 3 + 16);
+            if (status != FF_OK) return;
+            rgb8 = s->d_rgb8;
+            host_rgb8 = rgb8_out;
+            rgb8_bytes = pixels * 3;
+        }
+        if (radiance_out && !radiance_on_device) {
+            status = ensure_bytes((void**)&s->d_radiance, &s->radiance_bytes, pixels * 12 + 16);
+            if (status != FF_OK) return;
+            radiance = s->d_radiance;
+            host_radiance = radiance_out;
+            radiance_bytes = pixels * 12;
+        }
+    }
+    // After the frame has finished: the outputs placed in the state's buffers, to the host (an output of no bytes - a part without
+    // rows - is skipped).
+    int copy_back() const
+    {
+        if (rgb8_bytes) FF_HIP(hipMemcpy(host_rgb8, rgb8, rgb8_bytes, hipMemcpyDeviceToHost));
+        if (radiance_bytes) FF_HIP(hipMemcpy(host_radiance, radiance, radiance_bytes, hipMemcpyDeviceToHost));
+        return FF_OK;
+    }
+
+private:
+    void* host_rgb8 = nullptr;
+    float* host_radiance = nullptr;
+    size_t rgb8_bytes = 0, radiance_bytes = 0; // what copy_back() copies (0: a device output, or none)
+};
 
 // What render_enqueue's frame shares with enqueue_nee's and with frame_primary_hits (ff_frame.cpp), one copy each:
 // the camera's ray matrix into `k`;
@@ -364,11 +405,14 @@ void yuv_release(FfState* s);
 // Resampling (ff_resize_api.cpp): frees the intermediate image and the two tables (ff_destroy).
 void resize_release(FfState* s);
 // The pixel buffer registered with ff_register_gl_pbo, mapped on the state's stream (kernel.cu:338-339) and unmapped again
-// (kernel.cu:344): what ff_render_to_pbo and ff_display_to_pbo write.  need_bytes: the least size the mapping must have.
+// (kernel.cu:344): what ff_render_to_pbo and ff_display_to_pbo write (ff_render_api.cpp).  need_bytes: the least size the mapping
+// must have.
 int map_pbo(FfState* s, size_t need_bytes, void** out_ptr);
 int unmap_pbo(FfState* s, int status);
 
-// ff_upload_scene for a scene already compiled on the host (ff_api.cpp).
+// ff_upload_scene for a scene already compiled on the host (ff_scene_api.cpp).
 int upload_compiled_scene(FfState* s, const CompiledScene& cs, double build_ms);
+// The scene on the device (ff_scene_api.cpp): frees its arrays and forgets it (an upload's first step; ff_destroy).
+void free_scene(FfState* s);
 
 } // namespace ff

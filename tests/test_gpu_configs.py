@@ -1,7 +1,7 @@
 """GPU tests (`-m gpu`) that pin what BASELINE.json's configs[2..4] add over the headline config and round 1 never exercised:
 
   * the sample-block rule beyond 1 024 spp (`block_spp = 64 * ceil(spp / 1024)`, oracle/ff_oracle.c orc_render vs
-    csrc/ff_api.cpp render_local) against the CPU oracle, radiance bits equal;
+    csrc/ff_render_api.cpp render_local, csrc/ff_frame.cpp plan_sample_blocks) against the CPU oracle, radiance bits equal;
   * C5's shape: 3840x2160 (16-bit packed pixel coordinates, 8.3 M work items per block), 16 bounces;
   * C4 in path mode: 8 diffuse bounces on the 983 040-triangle sphere, where secondary rays leave the tessellated surface
     with the 1e-4 offset — BVH (all three builders) against the brute-force loop and against the oracle.

@@ -294,7 +294,7 @@ def test_fine_grained_tail_is_bit_identical(monkeypatch):
             _, rad = t.render_strips(cam, p300, 4, part, 3)
             rows = ffdist.strip_row_indices(90, 4, part, 3)
             assert np.array_equal(rad.view(np.uint32), full[rows].view(np.uint32)), part
-    # ... whether the frame's last one, two or three sample blocks go out as short items (csrc/ff_api.cpp: two where a rank's launch is
+    # ... whether the frame's last one, two or three sample blocks go out as short items (csrc/ff_frame.cpp plan_tail: two where a rank's launch is
     # short, FF_TAIL_BLOCKS forces a number; a partial last block, and a frame all of whose blocks are tail blocks)
     for blocks in ("1", "2", "3"):
         monkeypatch.setenv("FF_TAIL_BLOCKS", blocks)
@@ -525,7 +525,7 @@ def test_culled_pixels_have_a_stored_primary_hit_for_their_tail_items():
 def test_primary_rays_are_answered_from_the_pixel_s_stored_hit(tracer, monkeypatch):
     """Every sample of a pixel starts with the same ray (kernel.cu:200-205 has no jitter): a pre-pass of the frame traces every
     pixel's primary ray once and stores its closest hit per pixel; every sample of the frame starts from there (csrc/ff_kernels.hip
-    trace_bvh_kernel, csrc/ff_k_shade.h settle_hit; csrc/ff_api.cpp render_enqueue).  Same bits and the same number of path segments as with the
+    trace_bvh_kernel, csrc/ff_k_shade.h settle_hit; csrc/ff_frame.cpp render_enqueue).  Same bits and the same number of path segments as with the
     reuse off (FF_NO_PRIMARY_REUSE=1) and as the brute-force kernel, which traces every one of them; FfStats::rays_answered counts
     exactly the primary segments: one per sample (camera inside the box: no pixel is culled); with diffuse, mirror and glass
     surfaces, one bounce (every path is its primary segment), partial last blocks, several launches per frame and interpolated
@@ -688,7 +688,7 @@ def test_job_pool_kernel_equals_the_lane_owned_kernel(monkeypatch):
 
 def test_stored_primary_hits_are_kept_while_camera_and_scene_stay(monkeypatch):
     """The pixels' stored primary hits (and the mask of pixels that see nothing) belong to a camera, a pixel mapping and a scene: the
-    next frame from the same ones starts from them without a pre-pass (csrc/ff_api.cpp render_enqueue) - a viewer that accumulates
+    next frame from the same ones starts from them without a pre-pass (csrc/ff_frame.cpp render_enqueue) - a viewer that accumulates
     1-spp frames with the camera at rest (kernel.cu:266,342).  Frames rendered that way equal the frames of a state that keeps nothing
     (FF_NO_PRIMARY_CACHE=1) and the brute-force kernel's, bits and ray / answered counts; a new camera, another frame size, a tile, a
     transform update and a mesh refit each make the next frame compute its own.  A 1-spp frame starts from stored hits when they are

@@ -1,4 +1,4 @@
-"""Start records (csrc/ff_k_shade.h settle_hit<PREPASS>, scatter_start; csrc/ff_kernels.hip trace_bvh_kernel<..., START>; csrc/ff_api.cpp
+"""Start records (csrc/ff_k_shade.h settle_hit<PREPASS>, scatter_start; csrc/ff_kernels.hip trace_bvh_kernel<..., START>; csrc/ff_frame.cpp
 render_enqueue): the pre-pass of a frame shades every pixel's stored primary hit once, and on diffuse scenes of up to 32 geometries
 every sample of the frame starts from that record inside the shading pass that ended the sample before it.  Nothing a frame
 computes may change: every case compares radiance bits, rgb8 bytes and the ray counters of three renderings -

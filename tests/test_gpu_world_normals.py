@@ -1,5 +1,5 @@
 """Normal tables (csrc/ff_frame_kernels.hip world_normals_kernel; csrc/ff_k_shade.h unit_world_normal; csrc/ff_k_traverse.h
-finish_segment<WN>; csrc/ff_kernels.hip trace_bvh_kernel<..., WN>; csrc/ff_api.cpp finalize_layout): the unit world normal of every
+finish_segment<WN>; csrc/ff_kernels.hip trace_bvh_kernel<..., WN>; csrc/ff_scene_api.cpp finalize_layout): the unit world normal of every
 triangle and plane is computed once, where the scene changes, by the function the shading pass calls, and the diffuse small-scene
 kernels fetch it with the winner's record instead of computing it per hit.  Nothing a frame computes may change: every case compares
 radiance bits, rgb8 bytes and the ray counters of three renderings -
