@@ -61,6 +61,7 @@ void read_switches(FfState* s)
     if (const char* e = std::getenv("FF_QUEUE_TAIL")) w.queue_tail = std::max(0, std::min(4096, std::atoi(e)));
     if (const char* e = std::getenv("FF_POOL_LEAVE")) w.pool_leave = std::max(0, std::min(64, std::atoi(e)));
     if (const char* e = std::getenv("FF_POOL_STACK_LEVELS")) w.pool_stack_levels = std::max(1, std::min(64, std::atoi(e)));
+    w.grade_no_lds = std::getenv("FF_GRADE_NO_LDS") != nullptr;
     s->sw = w;
 }
 
@@ -158,6 +159,7 @@ int ff_destroy(FfState* s)
     adaptive_release(s);
     yuv_release(s);
     resize_release(s);
+    grade_release(s);
     free_build_scratch(s->scratch);
     if (s->d_blocksums) (void)hipFree(s->d_blocksums);
     if (s->d_rgb8) (void)hipFree(s->d_rgb8);

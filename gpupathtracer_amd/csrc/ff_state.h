@@ -115,7 +115,7 @@ struct FfState {
     int accum_width = 0, accum_height = 0, accum_frames = 0;
     // The image work buffer, the one device buffer every image-space entry point (ff_gbuffer, the denoisers, ff_taa*, ff_upscale,
     // ff_display, ff_motion_blur, ff_depth_of_field, ff_despeckle, ff_sharpen, ff_local_tonemap, ff_interpolate, ff_encode_yuv,
-    // ff_resize) works in: the running entry point's own scratch at the head (counts, grids, a packed plane, the bloom pyramid; each
+    // ff_resize, ff_color_grade) works in: the running entry point's own scratch at the head (counts, grids, a packed plane, the bloom pyramid; each
     // *_api.cpp says what), the staging of host buffers behind it (ff::Staging).  Grown on demand, and nothing in it outlives the
     // call that put it there.  Not reset by uploads.
     void* d_img_work = nullptr;
@@ -227,6 +227,15 @@ struct FfState {
         int in_size = 0, out_size = 0, filter = 0;
         int taps = 0, span = 0; // T, and for axis 0 the longest input span of a tile (ff_resize.h ResizeAxis)
     } resize_table[2];
+    // colour grade (ff_color_grade, ff_grade_api.cpp): the LUT objects (id = index; neither device array: a free id).  d_table holds
+    // the lattice as float4 texels, d_curves the 3 K knots; `desc` is the caller's descriptor without its pointers.  They belong to
+    // the state: not reset by uploads.
+    struct GradeLut {
+        float4* d_table = nullptr;
+        float* d_curves = nullptr;
+        FfGradeLut desc = {};
+    };
+    std::vector<GradeLut> grade_luts;
     unsigned* d_queue = nullptr;               // work-queue counter: lives right behind the counters (one memset clears both)
     unsigned long long* d_counters = nullptr;  // 28 counters + 4 queue words
     unsigned long long* h_counters = nullptr;  // pinned mirror for the per-frame read-back
@@ -257,6 +266,7 @@ struct FfState {
         int lds_node_cap = -1;         // FF_DEBUG_LDS_NODE_CAP: at most this many tree nodes in LDS (experiments on partial residency)
         int pool_leave = -1;           // FF_POOL_LEAVE: jobs a wave may still hold when it leaves the traverse role for a setup pass (they are put down)
         int pool_stack_levels = 0;     // FF_POOL_STACK_LEVELS: traversal stack levels kept in LDS (the deeper ones spill)
+        bool grade_no_lds = false;     // FF_GRADE_NO_LDS: ff_color_grade reads every lattice from global memory
     } sw;
     int block_threads = ff::kBlockThreadsMax; // BVH kernel workgroup size (512 or 1024); FF_BLOCK_THREADS overrides for experiments
     bool setup_threshold_forced = false;
@@ -404,6 +414,8 @@ void adaptive_release(FfState* s);
 void yuv_release(FfState* s);
 // Resampling (ff_resize_api.cpp): frees the intermediate image and the two tables (ff_destroy).
 void resize_release(FfState* s);
+// Colour grade (ff_grade_api.cpp): frees the LUT objects (ff_destroy).
+void grade_release(FfState* s);
 // The pixel buffer registered with ff_register_gl_pbo, mapped on the state's stream (kernel.cu:338-339) and unmapped again
 // (kernel.cu:344): what ff_render_to_pbo and ff_display_to_pbo write (ff_render_api.cpp).  need_bytes: the least size the mapping
 // must have.

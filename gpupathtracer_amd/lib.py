@@ -49,6 +49,8 @@ EXPORTS = [
     "ff_adaptive_params_init", "ff_render_adaptive", "ff_adaptive_state", "ff_adaptive_tile_error", "ff_adaptive_tile_error_host", "ff_adaptive_plan_host",
     "ff_yuv_params_init", "ff_yuv_plane_bytes", "ff_yuv_knots", "ff_encode_yuv", "ff_encode_yuv_host", "ff_save_y4m",
     "ff_resize_params_init", "ff_resize_taps", "ff_resize_weights", "ff_resize", "ff_resize_host",
+    "ff_grade_params_init", "ff_grade_lut_create", "ff_grade_lut_destroy", "ff_color_grade", "ff_color_grade_host",
+    "ff_load_cube", "ff_free_cube", "ff_save_cube",
 ]
 DIST_ID_BYTES = 128
 
@@ -281,6 +283,16 @@ def load():
     lib.ff_resize_weights.argtypes = [i32, i32, i32, vp, vp]
     lib.ff_resize.argtypes = [vp, P(T.FfResizeParams), i32, i32, vp, i32, i32, i32, vp, i32, vp, i32]
     lib.ff_resize_host.argtypes = [P(T.FfResizeParams), i32, i32, vp, i32, i32, vp, vp]
+    lib.ff_grade_params_init.argtypes = [P(T.FfGradeParams)]
+    lib.ff_grade_params_init.restype = None
+    lib.ff_grade_lut_create.argtypes = [vp, P(T.FfGradeLut), P(i32)]
+    lib.ff_grade_lut_destroy.argtypes = [vp, i32]
+    lib.ff_color_grade.argtypes = [vp, P(T.FfGradeParams), i32, i32, vp, i32, vp, i32, vp, i32]
+    lib.ff_color_grade_host.argtypes = [P(T.FfGradeParams), P(T.FfGradeLut), i32, i32, vp, vp, vp]
+    lib.ff_load_cube.argtypes = [C.c_char_p, P(T.FfCubeFile)]
+    lib.ff_free_cube.argtypes = [P(T.FfCubeFile)]
+    lib.ff_free_cube.restype = None
+    lib.ff_save_cube.argtypes = [C.c_char_p, P(T.FfCubeFile)]
     lib.ff_taa_upscale_params_init.argtypes = [P(T.FfTaaUpscaleParams)]
     lib.ff_taa_upscale_params_init.restype = None
     lib.ff_taa_upscale.argtypes = [vp, P(T.FfCamera), P(T.FfTaaUpscaleParams), i32, i32, vp, vp, i32, i32, vp, vp, i32, vp, i32, vp, i32]
@@ -780,7 +792,8 @@ def sharpen_params(**overrides):
 
 
 def _float3_image(radiance, who):
-    """An [H,W,3] input image (ff_sharpen's, ff_local_tonemap's, ff_encode_yuv's, ff_resize's, ff_display's) as a contiguous float32
+    """An [H,W,3] input image (ff_sharpen's, ff_local_tonemap's, ff_encode_yuv's, ff_resize's, ff_color_grade's,
+    ff_display's) as a contiguous float32
     array, and (h, w)."""
     rad = np.ascontiguousarray(radiance, dtype=np.float32)
     if rad.ndim != 3 or rad.shape[2] != 3:
@@ -903,6 +916,90 @@ def resize_host(radiance, out_width, out_height, p=None, want_rgb8=True, want_ou
     rgb8, out, rgb8_ptr, out_ptr = _image_outputs(max(int(out_height), 0), max(int(out_width), 0), want_rgb8, want_out)
     check(load().ff_resize_host(C.byref(p), w, h, rad.ctypes.data, out_width, out_height, rgb8_ptr, out_ptr))
     return rgb8, out
+
+
+def grade_params(**overrides):
+    """ff_grade_params_init's defaults with the given fields replaced (any FfGradeParams field; matrix a sequence of 9 row-major,
+    offset of 3)."""
+    return _params(T.FfGradeParams, "ff_grade_params_init", overrides, arrays={"matrix": C.c_float * 9, "offset": C.c_float * 3})
+
+
+class GradeLut:
+    """An FfGradeLut descriptor with the arrays it points to: .desc is what the library takes; .curves [3, K] and .table
+    [N, N, N, 3] (indexed [b, g, r]: red fastest) are the float32 arrays, None for a half that is absent."""
+
+    def __init__(self, desc, curves, table):
+        self.desc, self.curves, self.table = desc, curves, table
+
+
+def grade_lut(curves=None, curve_lo=0.0, curve_hi=1.0, curve_axis=T.GRADE_AXIS_LINEAR, curve_shift=0, table=None,
+              domain_min=(0.0, 0.0, 0.0), domain_max=(1.0, 1.0, 1.0)):
+    """A LUT descriptor (GradeLut) from curves [3, K] and / or a lattice table [N, N, N, 3] (or [N^3, 3], red fastest).  The sizes
+    come from the arrays; nothing is checked here: the library names what it refuses."""
+    d = T.FfGradeLut()
+    cv = tb = None
+    if curves is not None:
+        cv = np.ascontiguousarray(curves, dtype=np.float32)
+        if cv.ndim != 2 or cv.shape[0] != 3:
+            raise ValueError("grade_lut: curves must be [3, K]")
+        d.curve_size, d.curve_axis, d.curve_shift = cv.shape[1], curve_axis, curve_shift
+        d.curve_lo, d.curve_hi = curve_lo, curve_hi
+        d.curves = cv.ctypes.data
+    if table is not None:
+        tb = np.ascontiguousarray(table, dtype=np.float32)
+        if tb.ndim == 2 and tb.shape[1] == 3:
+            n = round(tb.shape[0] ** (1.0 / 3.0))
+            if n ** 3 != tb.shape[0]:
+                raise ValueError("grade_lut: a [M, 3] table must have M = N^3 rows")
+            tb = tb.reshape(n, n, n, 3)
+        if tb.ndim != 4 or tb.shape[3] != 3 or not (tb.shape[0] == tb.shape[1] == tb.shape[2]):
+            raise ValueError("grade_lut: table must be [N, N, N, 3] or [N^3, 3]")
+        d.size = tb.shape[0]
+        d.domain_min = (C.c_float * 3)(*domain_min)
+        d.domain_max = (C.c_float * 3)(*domain_max)
+        d.table = tb.ctypes.data
+    return GradeLut(d, cv, tb)
+
+
+def _lut_ref(lut):
+    return C.byref(lut.desc) if lut is not None else None
+
+
+def color_grade_host(radiance, p=None, lut=None, want_rgb8=True, want_out=True, in_place=False):
+    """ff_color_grade_host (no GPU): host radiance [H,W,3], a GradeLut or None -> (rgb8 [H,W,3] uint8, radiance [H,W,3] float32).
+    in_place: the radiance output is written over a copy of the input (radiance_out == radiance_in in the call)."""
+    rad, (h, w) = _float3_image(radiance, "color_grade_host")
+    p = p if p is not None else grade_params()
+    rgb8, out, rgb8_ptr, out_ptr = _image_outputs(h, w, want_rgb8, want_out, out=rad.copy() if in_place else None)
+    src = out if (in_place and want_out) else rad
+    check(load().ff_color_grade_host(C.byref(p), _lut_ref(lut), w, h, src.ctypes.data, rgb8_ptr, out_ptr))
+    return rgb8, out
+
+
+def load_cube(path):
+    """ff_load_cube -> (GradeLut, title): a 1D .cube file as curves on the linear axis, a 3D one as the lattice."""
+    lib = load()
+    f = T.FfCubeFile()
+    check(lib.ff_load_cube(os.fsencode(path), C.byref(f)))
+    try:
+        d = f.lut
+        title = f.title.decode("utf-8", "replace")
+        if d.curve_size:
+            cv = np.ctypeslib.as_array(C.cast(d.curves, C.POINTER(C.c_float)), shape=(3, d.curve_size)).copy()
+            return grade_lut(curves=cv, curve_lo=d.curve_lo, curve_hi=d.curve_hi), title
+        n = d.size
+        tb = np.ctypeslib.as_array(C.cast(d.table, C.POINTER(C.c_float)), shape=(n, n, n, 3)).copy()
+        return grade_lut(table=tb, domain_min=tuple(d.domain_min), domain_max=tuple(d.domain_max)), title
+    finally:
+        lib.ff_free_cube(C.byref(f))
+
+
+def save_cube(path, lut, title=""):
+    """ff_save_cube: a GradeLut with exactly one half (curves on the linear axis, or the lattice) as a .cube file."""
+    f = T.FfCubeFile()
+    f.title = title.encode("utf-8")
+    f.lut = lut.desc
+    check(load().ff_save_cube(os.fsencode(path), C.byref(f)))
 
 
 def interpolate_params(**overrides):
@@ -1621,6 +1718,38 @@ class Tracer:
         p = p if p is not None else resize_params()
         check(self._lib.ff_resize(self._state, C.byref(p), in_width, in_height, _vp(radiance_ptr), 1, out_width, out_height, _vp(rgb8_ptr), 1,
                                   _vp(radiance_out_ptr), 1))
+
+    def grade_lut_create(self, lut):
+        """ff_grade_lut_create of a GradeLut (lib.grade_lut, lib.load_cube) -> the LUT's id, for FfGradeParams.lut_id."""
+        out = C.c_int(-1)
+        check(self._lib.ff_grade_lut_create(self._state, C.byref(lut.desc), C.byref(out)))
+        return int(out.value)
+
+    def grade_lut_destroy(self, lut_id):
+        check(self._lib.ff_grade_lut_destroy(self._state, lut_id))
+
+    def color_grade(self, radiance, p=None, want_rgb8=True, want_out=True, in_place=False):
+        """ff_color_grade of radiance [H,W,3] -> (rgb8 [H,W,3] uint8, radiance [H,W,3] float32).  A host array gives host arrays; a
+        contiguous float32 device tensor (torch) gives device tensors.  in_place: radiance_out is radiance_in in the call (a device
+        tensor is overwritten and returned; a host array is copied first)."""
+        p = p if p is not None else grade_params()
+        if hasattr(radiance, "data_ptr"):
+            import torch
+            h, w = _device_image(radiance, torch.float32, "color_grade: radiance", "float32")
+            rgb8, out, rgb8_ptr, out_ptr = _image_outputs(h, w, want_rgb8, want_out, radiance.device, out=radiance if in_place else None)
+            torch.cuda.synchronize(radiance.device)
+            self.color_grade_device(w, h, radiance.data_ptr(), p, rgb8_ptr, out_ptr)
+            return rgb8, out
+        rad, (h, w) = _float3_image(radiance, "color_grade")
+        rgb8, out, rgb8_ptr, out_ptr = _image_outputs(h, w, want_rgb8, want_out, out=rad.copy() if in_place else None)
+        src = out if (in_place and want_out) else rad
+        check(self._lib.ff_color_grade(self._state, C.byref(p), w, h, src.ctypes.data, 0, rgb8_ptr, 0, out_ptr, 0))
+        return rgb8, out
+
+    def color_grade_device(self, width, height, radiance_ptr, p=None, rgb8_ptr=None, radiance_out_ptr=None):
+        """ff_color_grade on DEVICE buffers (raw pointers); radiance_out_ptr may be radiance_ptr."""
+        p = p if p is not None else grade_params()
+        check(self._lib.ff_color_grade(self._state, C.byref(p), width, height, _vp(radiance_ptr), 1, _vp(rgb8_ptr), 1, _vp(radiance_out_ptr), 1))
 
     def interpolate(self, mid, a, b, p=None, geom_maps=None, want_rgb8=True, want_out=True):
         """ff_interpolate of host arrays: mid = (camera, gbuffer), a and b = (camera, radiance [H,W,3], gbuffer), a gbuffer being a

@@ -272,6 +272,31 @@ RESIZE_ANTI_RING = 1
 RESIZE_MAX_RATIO, RESIZE_MAX_TAPS = 16, 96
 assert C.sizeof(FfResizeParams) == RESIZE_PARAMS_BYTES
 
+
+class FfGradeParams(C.Structure):
+    _fields_ = [("flags", C.c_uint32), ("matrix", C.c_float * 9), ("offset", C.c_float * 3), ("saturation", C.c_float), ("lut_id", C.c_int32),
+                ("reserved", C.c_uint32)]
+
+
+class FfGradeLut(C.Structure):
+    _fields_ = [("curve_size", C.c_int32), ("curve_axis", C.c_int32), ("curve_shift", C.c_int32), ("curve_lo", C.c_float), ("curve_hi", C.c_float),
+                ("size", C.c_int32), ("domain_min", C.c_float * 3), ("domain_max", C.c_float * 3), ("curves", C.c_void_p), ("table", C.c_void_p)]
+
+
+class FfCubeFile(C.Structure):
+    _fields_ = [("title", C.c_char * 128), ("lut", FfGradeLut)]
+
+
+GRADE_PARAMS_BYTES, GRADE_LUT_BYTES, CUBE_FILE_BYTES = 64, 64, 192
+GRADE_PRIMARY, GRADE_CURVES, GRADE_LUT3D, GRADE_TRILINEAR = 1, 2, 4, 8
+GRADE_AXIS_LINEAR, GRADE_AXIS_LOG = 0, 1
+GRADE_MAX_LUTS, GRADE_MAX_CURVE, GRADE_MAX_SIZE = 16, 4096, 65
+# the kernels' launch (csrc/ff_grade.h): the largest lattice kept in LDS and the LDS bytes a workgroup may take; a fixed grid of at
+# most GRADE_MAX_BLOCKS workgroups of GRADE_THREADS lanes, a lane on GRADE_PIXELS_PER_LANE consecutive pixels per pass
+GRADE_LDS_MAX_SIZE, GRADE_LDS_BYTES = 17, 65536
+GRADE_THREADS, GRADE_PIXELS_PER_LANE, GRADE_MAX_BLOCKS = 256, 4, 512
+assert (C.sizeof(FfGradeParams), C.sizeof(FfGradeLut), C.sizeof(FfCubeFile)) == (GRADE_PARAMS_BYTES, GRADE_LUT_BYTES, CUBE_FILE_BYTES)
+
 BUILD_HOST_SAH, BUILD_GPU_LBVH, BUILD_GPU_PLOC = 0, 1, 2
 UPDATE_REFIT, UPDATE_REBUILD = 0, 1
 

@@ -1547,6 +1547,102 @@ FF_API int ff_resize(FfState* state, const FfResizeParams* p, int in_width, int 
 FF_API int ff_resize_host(const FfResizeParams* p, int in_width, int in_height, const float* radiance_in,
                           int out_width, int out_height, unsigned char* rgb8, float* radiance_out);
 
+/* ---- colour grade (primary grade, 1D curves, 3D lattice, .cube files) ---------------------------- */
+
+/* Defaults: flags 0, the identity matrix, offset 0, saturation 1, lut_id -1, reserved 0. */
+FF_API void ff_grade_params_init(FfGradeParams* p);
+
+/* A LUT object from a descriptor of host arrays: the three curves, the lattice, or both (a half is absent when its size is 0 and its
+ * pointer NULL).  LUTs belong to the state like textures: at most 16 at a time, an id freed by ff_grade_lut_destroy is given out
+ * again (the lowest free one first), ff_upload_scene leaves them alone and ff_destroy frees them.  The arrays are copied; the
+ * caller's may go.  FF_ERR_INVALID_ARG, naming the field, for: a NULL state, descriptor or out_id; a descriptor with neither
+ * half; curve_size outside 2 .. 4096, or not the K its FF_GRADE_AXIS_LOG axis gives; an unknown curve_axis; curve_lo or curve_hi
+ * not finite, not curve_lo < curve_hi, or curve_hi - curve_lo not finite; on the LOG axis curve_lo <= 0, curve_shift outside
+ * 8 .. 23 or low `curve_shift` bits of either end's bit pattern set; on the LINEAR axis a nonzero curve_shift; size outside
+ * 2 .. 65; a domain_min or domain_max that is not finite, not domain_min < domain_max, or whose difference is not finite; a size
+ * without its pointer or a pointer without its size; a curve knot or a lattice value that is not finite or exceeds FLT_MAX / 2
+ * in magnitude (so that no difference of two overflows); a 17th LUT. */
+FF_API int ff_grade_lut_create(FfState* state, const FfGradeLut* lut, int* out_id);
+/* Frees LUT `id` (after the stream's work has completed).  FF_ERR_INVALID_ARG for an id that names no LUT. */
+FF_API int ff_grade_lut_destroy(FfState* state, int id);
+
+/* The colour grade: the one stage that changes the COLOUR of the picture - white balance, channel gains, a channel mixer, gamut
+ * conversion, CDL slope and offset, desaturation (stage 1); a camera-log shaper, contrast curves (stage 2); a "look" from any
+ * grading tool, a .cube file (stage 3).  A pure per-pixel operation on a W x H float3 image: no scene, no G-buffer, no history,
+ * no neighbours.  It works on whatever it is given - scene-linear radiance ahead of ff_local_tonemap and ff_display, or
+ * display_out ahead of ff_encode_yuv.
+ * All arithmetic is float32 with no fused multiply-add, every formula evaluated left to right as written; max(a, b) is
+ * a > b ? a : b and min(a, b) is a < b ? a : b, so a NaN in first place reads as the bound (only a stage 1 that overflowed makes
+ * one); bits(x) is the float's bit pattern as an unsigned integer.  Three stages in this order, each run only when its flag is
+ * set; flags = 0 copies the image bit for bit.
+ *   1 FF_GRADE_PRIMARY  (matrix[9] row-major m, offset[3] o, saturation s; all finite, s >= 0)
+ *       c'_r = ((m[0] r + m[1] g) + m[2] b) + o[0], c'_g and c'_b likewise from rows 1 and 2
+ *       l = (0.2126 c'_r + 0.7152 c'_g) + 0.0722 c'_b        (ff_display's weights)
+ *       c''_i = l + s (c'_i - l)
+ *   2 FF_GRADE_CURVES   (the LUT's K knots C per channel, over curve_lo .. curve_hi = lo .. hi); per channel
+ *       x' = min(max(x, lo), hi)
+ *       FF_GRADE_AXIS_LINEAR:  p = ((x' - lo) / (hi - lo)) float(K - 1); k = min(int(floor p), K - 2); t = p - float(k)
+ *       FF_GRADE_AXIS_LOG:     (for scene-linear HDR ahead of a lattice: the knots are evenly spaced in the float's bit pattern, 2^(23 -
+ *                              shift) to a binade, as in ff_display's histogram.  0 < lo < hi, shift in 8 .. 23, the low `shift`
+ *                              bits of bits(lo) and bits(hi) zero so that no cell straddles a binade, K = ((bits(hi) - bits(lo)) >>
+ *                              shift) + 1)
+ *                              d = bits(x') - bits(lo); k = min(d >> shift, K - 2); t = float(d - (k << shift)) / float(1 << shift)
+ *                              (exact)
+ *       y = C[k] + t (C[k + 1] - C[k])
+ *   3 FF_GRADE_LUT3D    (the LUT's N^3 texels V, red fastest - texel i + N (j + N k), the .cube order - over domain_min ..
+ *                       domain_max); per channel, with that channel's dmin and dmax:
+ *       u = (min(max(x, dmin), dmax) - dmin) / (dmax - dmin); p = u float(N - 1); i = min(int(floor p), N - 2); f = p - float(i)
+ *     giving the cell (i, j, k) and the fractions (f_r, f_g, f_b).  Tetrahedral (the default): the three fractions sorted descending
+ *     by a stable sort - ties keep r before g before b - are a >= b >= c on the axes A, B, C;
+ *       P0 = V(i, j, k); P1 = P0's neighbour one step along A; P2 = P1's one step along B; P3 = V(i + 1, j + 1, k + 1)
+ *       out = ((P0 + a (P1 - P0)) + b (P2 - P1)) + c (P3 - P2)       per output channel
+ *     FF_GRADE_TRILINEAR: ff_texture's form, each lerp A + f (B - A): four along r (at (j, k), (j + 1, k), (j, k + 1),
+ *     (j + 1, k + 1)), two along g (at k and k + 1) of those, one along b.
+ * Consequences.  Both forms return a constant lattice's value bit for bit (a lattice of -0 returns +0), and the lattice value
+ * exactly where every fraction is 0; constant curves return their value likewise.  A value outside the curve's or the lattice's
+ * range reads as the nearest end.  Negative values and -0 go the ordinary way.
+ * Special pixels.  A pixel with any channel that is not finite is copied to radiance_out bit for bit, whatever the flags; its bytes
+ * follow the rule below.  What the stages produce is stored as it comes: a matrix that overflows gives Inf (and a saturation of
+ * Inf - Inf, NaN).
+ * rgb8 = trunc(clamp(out * 255)), the rule of every rgb8 output here (NaN -> 0).  rgb8 (W*H*3 bytes) and radiance_out (W*H*3
+ * floats) may each be NULL.  radiance_out may be radiance_in itself (a pixel is read before it is written, as in ff_display); any
+ * other overlap of an output with the input or the other output is refused.  Every size is 1 .. 65535.  Synchronous, on the
+ * state's stream; host buffers are staged.  The call leaves FfStats, the stored primary hits and their key, every filter's
+ * history, the display exposure and the progressive and adaptive sums as they were.  FF_ERR_INVALID_ARG, naming the field, before
+ * any device work for: a NULL state, params or radiance_in; a size outside 1 .. 65535; unknown flags or a nonzero reserved; a
+ * matrix, offset or saturation that is not finite, or a negative saturation (checked whether or not FF_GRADE_PRIMARY is set);
+ * FF_GRADE_CURVES or FF_GRADE_LUT3D with a lut_id that names no LUT, or one whose LUT lacks that half; a refused overlap.
+ * The kernels keep a lattice of N <= 17 in LDS (FF_GRADE_NO_LDS in the environment at ff_create: never) and larger ones in
+ * global memory; the bits are the same.
+ * Not offered: other channel counts, a per-channel curve axis, shaper curves stored inside a 3D .cube, lattices that are not cubes,
+ * a row pitch, a grade fused into ff_display. */
+FF_API int ff_color_grade(FfState* state, const FfGradeParams* p, int width, int height,
+                          const float* radiance_in, int input_on_device,
+                          void* rgb8, int rgb8_on_device, float* radiance_out, int radiance_out_on_device);
+
+/* Host-only twin (no GPU, no state, host pointers), compiled from the same inline per-pixel functions the kernels use: the
+ * descriptor itself in place of lut_id (NULL: none; p->lut_id is not looked at), the same checks - ff_grade_lut_create's on the
+ * descriptor -, the same bits. */
+FF_API int ff_color_grade_host(const FfGradeParams* p, const FfGradeLut* lut, int width, int height, const float* radiance_in,
+                               unsigned char* rgb8, float* radiance_out);
+
+/* .cube files, the text format of Adobe and Resolve: lines of
+ *   TITLE "text"  |  DOMAIN_MIN r g b  |  DOMAIN_MAX r g b  |  LUT_1D_SIZE K  |  LUT_3D_SIZE N  |  r g b
+ * with '#' comments and blank lines anywhere and LF or CRLF line ends; exactly one of the two sizes, before the first data line;
+ * the domain defaults to 0 0 0 .. 1 1 1; K or N^3 data lines, for 3D red fastest.  ff_load_cube fills *out: a 1D file becomes the
+ * three curves on FF_GRADE_AXIS_LINEAR over curve_lo .. curve_hi (its DOMAIN_MIN and DOMAIN_MAX must be the same for r, g and b), a
+ * 3D file the lattice; out->lut is then what ff_grade_lut_create and ff_color_grade_host take.  The arrays are malloc'ed by the
+ * library: release with ff_free_cube (which leaves *file empty; a NULL or empty one is fine).  FF_ERR_IO for a file that cannot be
+ * opened or that ends before its last data line; FF_ERR_INVALID_ARG, naming the line, for a NULL argument, an unknown keyword, a
+ * malformed line, a missing, repeated or late size, a size outside 2 .. 4096 (1D) or 2 .. 65 (3D), a value that is not finite,
+ * a domain that is not min < max, or more data lines than the size says. */
+FF_API int ff_load_cube(const char* path, FfCubeFile* out);
+FF_API void ff_free_cube(FfCubeFile* file);
+/* Writes `file` - exactly one half of file->lut, curves on FF_GRADE_AXIS_LINEAR or the lattice, under ff_grade_lut_create's
+ * checks - with every number as %.9g, so that ff_load_cube returns the same bits.  A title may not hold '"' or a line end.
+ * FF_ERR_IO when the file cannot be written. */
+FF_API int ff_save_cube(const char* path, const FfCubeFile* file);
+
 /* ---- measurement -------------------------------------------------------------------------------- */
 
 /* Turn per-launch node/triangle visit counters on (1) or off (0, default).  Ray counting is always on. */

@@ -438,6 +438,40 @@ typedef struct FfResizeParams {
     uint32_t reserved;   /* 0 */
 } FfResizeParams;        /* 12 bytes */
 
+/* ff_color_grade: a primary grade, per-channel curves and a 3D lattice per pixel.  ff_grade_params_init gives the defaults; the
+ * operator is in ff_api.h. */
+#define FF_GRADE_PRIMARY   1u         /* stage 1: matrix, offset, saturation */
+#define FF_GRADE_CURVES    2u         /* stage 2: the LUT object's three curves */
+#define FF_GRADE_LUT3D     4u         /* stage 3: the LUT object's lattice, read tetrahedrally ... */
+#define FF_GRADE_TRILINEAR 8u         /* ... or, with this bit, trilinearly */
+#define FF_GRADE_AXIS_LINEAR 0        /* knots evenly spaced over curve_lo .. curve_hi */
+#define FF_GRADE_AXIS_LOG    1        /* knots evenly spaced over the float bit patterns of curve_lo .. curve_hi */
+typedef struct FfGradeParams {
+    uint32_t flags;      /* FF_GRADE_* stage bits and FF_GRADE_TRILINEAR */
+    float    matrix[9];  /* row-major */
+    float    offset[3];
+    float    saturation; /* >= 0; 1 leaves the colour alone, 0 is the luminance */
+    int32_t  lut_id;     /* ff_grade_lut_create's; -1: none */
+    uint32_t reserved;   /* 0 */
+} FfGradeParams;         /* 64 bytes */
+/* What a LUT object is made from (ff_grade_lut_create) and what the host twin reads: host pointers.  Either half may be absent. */
+typedef struct FfGradeLut {
+    int32_t curve_size;          /* K, 2 .. 4096; 0: no curves */
+    int32_t curve_axis;          /* FF_GRADE_AXIS_* */
+    int32_t curve_shift;         /* FF_GRADE_AXIS_LOG: 8 .. 23; else 0 */
+    float   curve_lo, curve_hi;
+    int32_t size;                /* N, 2 .. 65; 0: no lattice */
+    float   domain_min[3], domain_max[3];
+    const float* curves;         /* 3 K floats, channel-major: r's knots, g's, b's */
+    const float* table;          /* 3 N^3 floats: texel i + N (j + N k) holds the r g b of lattice point (r i, g j, b k) */
+} FfGradeLut;                    /* 64 bytes */
+/* A .cube file in memory (ff_load_cube / ff_save_cube): its title and the half of a LUT it holds.  ff_load_cube allocates curves
+ * or table; ff_free_cube frees them. */
+typedef struct FfCubeFile {
+    char title[128];             /* TITLE without its quotes, NUL-terminated; "" when the file has none */
+    FfGradeLut lut;              /* a 1D file: the curves on FF_GRADE_AXIS_LINEAR; a 3D file: the lattice */
+} FfCubeFile;                    /* 192 bytes */
+
 /* ff_texture_create: how a texture is addressed and filtered (the formulas are in ff_api.h).  0 = repeat, bilinear. */
 #define FF_TEX_REPEAT    0   /* coordinates wrap: c - floor(c) */
 #define FF_TEX_CLAMP     1   /* coordinates clamp to [0, 1] */
@@ -479,6 +513,9 @@ static_assert(sizeof(FfAdaptiveParams) == 24, "FfAdaptiveParams is 24 bytes");
 static_assert(sizeof(FfAdaptiveInfo) == 32, "FfAdaptiveInfo is 32 bytes");
 static_assert(sizeof(FfYuvParams) == 24, "FfYuvParams is 24 bytes");
 static_assert(sizeof(FfResizeParams) == 12, "FfResizeParams is 12 bytes");
+static_assert(sizeof(FfGradeParams) == 64, "FfGradeParams is 64 bytes");
+static_assert(sizeof(FfGradeLut) == 64, "FfGradeLut is 64 bytes");
+static_assert(sizeof(FfCubeFile) == 192, "FfCubeFile is 192 bytes");
 #else
 _Static_assert(sizeof(FfBXDF) == 60, "BXDF layout");
 _Static_assert(sizeof(FfTriangle) == 96, "Triangle layout");
@@ -498,6 +535,9 @@ _Static_assert(sizeof(FfAdaptiveParams) == 24, "FfAdaptiveParams layout");
 _Static_assert(sizeof(FfAdaptiveInfo) == 32, "FfAdaptiveInfo layout");
 _Static_assert(sizeof(FfYuvParams) == 24, "FfYuvParams layout");
 _Static_assert(sizeof(FfResizeParams) == 12, "FfResizeParams layout");
+_Static_assert(sizeof(FfGradeParams) == 64, "FfGradeParams layout");
+_Static_assert(sizeof(FfGradeLut) == 64, "FfGradeLut layout");
+_Static_assert(sizeof(FfCubeFile) == 192, "FfCubeFile layout");
 #endif
 
 #endif /* FIREFLY_FF_TYPES_H */
