@@ -160,6 +160,7 @@ int ff_destroy(FfState* s)
     yuv_release(s);
     resize_release(s);
     grade_release(s);
+    lens_release(s);
     free_build_scratch(s->scratch);
     if (s->d_blocksums) (void)hipFree(s->d_blocksums);
     if (s->d_rgb8) (void)hipFree(s->d_rgb8);

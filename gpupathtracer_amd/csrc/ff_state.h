@@ -115,7 +115,7 @@ struct FfState {
     int accum_width = 0, accum_height = 0, accum_frames = 0;
     // The image work buffer, the one device buffer every image-space entry point (ff_gbuffer, the denoisers, ff_taa*, ff_upscale,
     // ff_display, ff_motion_blur, ff_depth_of_field, ff_despeckle, ff_sharpen, ff_local_tonemap, ff_interpolate, ff_encode_yuv,
-    // ff_resize, ff_color_grade) works in: the running entry point's own scratch at the head (counts, grids, a packed plane, the bloom pyramid; each
+    // ff_resize, ff_color_grade, ff_lens) works in: the running entry point's own scratch at the head (counts, grids, a packed plane, the bloom pyramid; each
     // *_api.cpp says what), the staging of host buffers behind it (ff::Staging).  Grown on demand, and nothing in it outlives the
     // call that put it there.  Not reset by uploads.
     void* d_img_work = nullptr;
@@ -236,6 +236,19 @@ struct FfState {
         FfGradeLut desc = {};
     };
     std::vector<GradeLut> grade_luts;
+    // lens (ff_lens, ff_lens_api.cpp): the device table of FF_LENS_KNOTS + 1 knots {e, gain} uploaded last, with its key - the
+    // parameters that feed it (k1, k2, k3, center_x, center_y, zoom, vignette, vignette_falloff as bits; the direction) and the
+    // image size: rebuilt and uploaded only when the key changes (`builds` counts how often).  Not reset by uploads.
+    struct LensTable {
+        void* d_table = nullptr;
+        size_t bytes = 0;
+        bool valid = false;
+        struct Key {
+            uint32_t f[8];
+            int direction, width, height;
+        } key = {};
+        uint64_t builds = 0;
+    } lens_table;
     unsigned* d_queue = nullptr;               // work-queue counter: lives right behind the counters (one memset clears both)
     unsigned long long* d_counters = nullptr;  // 28 counters + 4 queue words
     unsigned long long* h_counters = nullptr;  // pinned mirror for the per-frame read-back
@@ -416,6 +429,8 @@ void yuv_release(FfState* s);
 void resize_release(FfState* s);
 // Colour grade (ff_grade_api.cpp): frees the LUT objects (ff_destroy).
 void grade_release(FfState* s);
+// Lens (ff_lens_api.cpp): frees the device table (ff_destroy).
+void lens_release(FfState* s);
 // The pixel buffer registered with ff_register_gl_pbo, mapped on the state's stream (kernel.cu:338-339) and unmapped again
 // (kernel.cu:344): what ff_render_to_pbo and ff_display_to_pbo write (ff_render_api.cpp).  need_bytes: the least size the mapping
 // must have.

@@ -51,6 +51,7 @@ EXPORTS = [
     "ff_resize_params_init", "ff_resize_taps", "ff_resize_weights", "ff_resize", "ff_resize_host",
     "ff_grade_params_init", "ff_grade_lut_create", "ff_grade_lut_destroy", "ff_color_grade", "ff_color_grade_host",
     "ff_load_cube", "ff_free_cube", "ff_save_cube",
+    "ff_lens_params_init", "ff_lens", "ff_lens_host", "ff_lens_tables", "ff_lens_map_host", "ff_lens_fit_zoom", "ff_debug_lens_table_builds",
 ]
 DIST_ID_BYTES = 128
 
@@ -293,6 +294,14 @@ def load():
     lib.ff_free_cube.argtypes = [P(T.FfCubeFile)]
     lib.ff_free_cube.restype = None
     lib.ff_save_cube.argtypes = [C.c_char_p, P(T.FfCubeFile)]
+    lib.ff_lens_params_init.argtypes = [P(T.FfLensParams)]
+    lib.ff_lens_params_init.restype = None
+    lib.ff_lens.argtypes = [vp, i32, i32, P(T.FfLensParams), vp, i32, vp, i32, vp, i32]
+    lib.ff_lens_host.argtypes = [i32, i32, P(T.FfLensParams), vp, vp, vp]
+    lib.ff_lens_tables.argtypes = [P(T.FfLensParams), i32, i32, vp, vp, P(C.c_double)]
+    lib.ff_lens_map_host.argtypes = [P(T.FfLensParams), i32, i32, i32, vp, i32, vp]
+    lib.ff_lens_fit_zoom.argtypes = [P(T.FfLensParams), i32, i32, i32, P(f32)]
+    lib.ff_debug_lens_table_builds.argtypes = [vp, P(C.c_uint64)]
     lib.ff_taa_upscale_params_init.argtypes = [P(T.FfTaaUpscaleParams)]
     lib.ff_taa_upscale_params_init.restype = None
     lib.ff_taa_upscale.argtypes = [vp, P(T.FfCamera), P(T.FfTaaUpscaleParams), i32, i32, vp, vp, i32, i32, vp, vp, i32, vp, i32, vp, i32]
@@ -1000,6 +1009,50 @@ def save_cube(path, lut, title=""):
     f.title = title.encode("utf-8")
     f.lut = lut.desc
     check(load().ff_save_cube(os.fsencode(path), C.byref(f)))
+
+
+def lens_params(**overrides):
+    """ff_lens_params_init's defaults (the identity) with the given fields replaced (any FfLensParams field)."""
+    return _params(T.FfLensParams, "ff_lens_params_init", overrides)
+
+
+def lens_host(radiance, p=None, want_rgb8=True, want_out=True):
+    """ff_lens_host (no GPU): host radiance [H,W,3] -> (rgb8 [H,W,3] uint8, radiance [H,W,3] float32)."""
+    rad, (h, w) = _float3_image(radiance, "lens_host")
+    p = p if p is not None else lens_params()
+    rgb8, out, rgb8_ptr, out_ptr = _image_outputs(h, w, want_rgb8, want_out)
+    check(load().ff_lens_host(w, h, C.byref(p), rad.ctypes.data, rgb8_ptr, out_ptr))
+    return rgb8, out
+
+
+def lens_tables(width, height, p=None):
+    """ff_lens_tables -> (e float32 [LENS_KNOTS + 1], gain float32 [LENS_KNOTS + 1], r2_max) as the kernel gets them."""
+    p = p if p is not None else lens_params()
+    e = np.zeros(T.LENS_KNOTS + 1, dtype=np.float32)
+    gain = np.zeros(T.LENS_KNOTS + 1, dtype=np.float32)
+    r2_max = C.c_double(0.0)
+    check(load().ff_lens_tables(C.byref(p), width, height, e.ctypes.data, gain.ctypes.data, C.byref(r2_max)))
+    return e, gain, float(r2_max.value)
+
+
+def lens_map(width, height, xy_out, p=None, channel=1):
+    """ff_lens_map_host: output positions [n,2] (x y in pixels, a pixel's centre at + 0.5) -> the source positions float32 [n,2] of
+    `channel` (0 red, 1 green, 2 blue)."""
+    p = p if p is not None else lens_params()
+    xy = np.ascontiguousarray(xy_out, dtype=np.float32)
+    if xy.ndim != 2 or xy.shape[1] != 2:
+        raise ValueError("lens_map: xy_out must be [n,2]")
+    src = np.zeros_like(xy)
+    check(load().ff_lens_map_host(C.byref(p), width, height, channel, xy.ctypes.data, xy.shape[0], src.ctypes.data))
+    return src
+
+
+def lens_fit_zoom(width, height, p=None, mode=T.LENS_FIT_FILL):
+    """ff_lens_fit_zoom -> the zoom that fills the frame (LENS_FIT_FILL) or keeps the whole source in view (LENS_FIT_ALL)."""
+    p = p if p is not None else lens_params()
+    zoom = C.c_float(0.0)
+    check(load().ff_lens_fit_zoom(C.byref(p), width, height, mode, C.byref(zoom)))
+    return float(zoom.value)
 
 
 def interpolate_params(**overrides):
@@ -1750,6 +1803,33 @@ class Tracer:
         """ff_color_grade on DEVICE buffers (raw pointers); radiance_out_ptr may be radiance_ptr."""
         p = p if p is not None else grade_params()
         check(self._lib.ff_color_grade(self._state, C.byref(p), width, height, _vp(radiance_ptr), 1, _vp(rgb8_ptr), 1, _vp(radiance_out_ptr), 1))
+
+    def lens(self, radiance, p=None, want_rgb8=True, want_out=True):
+        """ff_lens of radiance [H,W,3] -> (rgb8 [H,W,3] uint8, radiance [H,W,3] float32).  A host array gives host arrays; a
+        contiguous float32 device tensor (torch) gives device tensors."""
+        p = p if p is not None else lens_params()
+        if hasattr(radiance, "data_ptr"):
+            import torch
+            h, w = _device_image(radiance, torch.float32, "lens: radiance", "float32")
+            rgb8, out, rgb8_ptr, out_ptr = _image_outputs(h, w, want_rgb8, want_out, radiance.device)
+            torch.cuda.synchronize(radiance.device)
+            self.lens_device(w, h, radiance.data_ptr(), p, rgb8_ptr, out_ptr)
+            return rgb8, out
+        rad, (h, w) = _float3_image(radiance, "lens")
+        rgb8, out, rgb8_ptr, out_ptr = _image_outputs(h, w, want_rgb8, want_out)
+        check(self._lib.ff_lens(self._state, w, h, C.byref(p), rad.ctypes.data, 0, rgb8_ptr, 0, out_ptr, 0))
+        return rgb8, out
+
+    def lens_device(self, width, height, radiance_ptr, p=None, rgb8_ptr=None, radiance_out_ptr=None):
+        """ff_lens on DEVICE buffers (raw pointers); the outputs must not overlap the input."""
+        p = p if p is not None else lens_params()
+        check(self._lib.ff_lens(self._state, width, height, C.byref(p), _vp(radiance_ptr), 1, _vp(rgb8_ptr), 1, _vp(radiance_out_ptr), 1))
+
+    def lens_table_builds(self):
+        """ff_debug_lens_table_builds: how often this tracer has built and uploaded ff_lens's table."""
+        n = C.c_uint64(0)
+        check(self._lib.ff_debug_lens_table_builds(self._state, C.byref(n)))
+        return int(n.value)
 
     def interpolate(self, mid, a, b, p=None, geom_maps=None, want_rgb8=True, want_out=True):
         """ff_interpolate of host arrays: mid = (camera, gbuffer), a and b = (camera, radiance [H,W,3], gbuffer), a gbuffer being a

@@ -297,6 +297,22 @@ GRADE_LDS_MAX_SIZE, GRADE_LDS_BYTES = 17, 65536
 GRADE_THREADS, GRADE_PIXELS_PER_LANE, GRADE_MAX_BLOCKS = 256, 4, 512
 assert (C.sizeof(FfGradeParams), C.sizeof(FfGradeLut), C.sizeof(FfCubeFile)) == (GRADE_PARAMS_BYTES, GRADE_LUT_BYTES, CUBE_FILE_BYTES)
 
+
+class FfLensParams(C.Structure):
+    _fields_ = [("k1", C.c_float), ("k2", C.c_float), ("k3", C.c_float), ("center_x", C.c_float), ("center_y", C.c_float), ("zoom", C.c_float),
+                ("ca_red", C.c_float), ("ca_blue", C.c_float), ("vignette", C.c_float), ("vignette_falloff", C.c_float),
+                ("direction", C.c_int32), ("filter", C.c_int32), ("border", C.c_int32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+LENS_PARAMS_BYTES = 60
+LENS_KNOTS = 1024
+LENS_UNDISTORT, LENS_DISTORT = 0, 1
+LENS_BILINEAR, LENS_CATMULL_ROM = 0, 1
+LENS_BORDER_BLACK, LENS_BORDER_CLAMP = 0, 1
+LENS_FIT_FILL, LENS_FIT_ALL = 0, 1
+LENS_ANTI_RING = 1
+assert C.sizeof(FfLensParams) == LENS_PARAMS_BYTES
+
 BUILD_HOST_SAH, BUILD_GPU_LBVH, BUILD_GPU_PLOC = 0, 1, 2
 UPDATE_REFIT, UPDATE_REBUILD = 0, 1
 

@@ -1643,6 +1643,105 @@ FF_API void ff_free_cube(FfCubeFile* file);
  * FF_ERR_IO when the file cannot be written. */
 FF_API int ff_save_cube(const char* path, const FfCubeFile* file);
 
+/* ---- lens (radial distortion, lateral chromatic aberration, vignetting) --------------------------- */
+
+/* Defaults, the identity: k1 = k2 = k3 = 0, center 0 0, zoom 1, ca_red = ca_blue = 0, vignette 0, vignette_falloff 0,
+ * FF_LENS_UNDISTORT, FF_LENS_CATMULL_ROM, FF_LENS_BORDER_BLACK, FF_LENS_ANTI_RING, reserved 0. */
+FF_API void ff_lens_params_init(FfLensParams* p);
+
+/* The lens: bends a W x H float3 radiance image the way a real lens does (FF_LENS_DISTORT: the render cut against footage, fed
+ * to a head-mounted or projector optic) or straightens a plate the way the render is (FF_LENS_UNDISTORT), with the two other lens
+ * effects a compositor expects, lateral chromatic aberration and vignetting.  A pure image operation like ff_sharpen: no scene, no
+ * G-buffer, no history.  It sits after ff_taa / ff_sharpen / ff_motion_blur / ff_depth_of_field and before ff_color_grade /
+ * ff_local_tonemap / ff_display; G-buffer, motion and id planes are not warped, so the stages that need them come first.  It is a
+ * gather: every output pixel computes where in the source each of its channels comes from and resamples there.
+ * THE TABLES, on the host, in double (ff_lens_tables returns them), every formula evaluated left to right as written.
+ *   cx = 0.5f * float(W) + center_x, cy likewise (float; the optical centre c in pixels, pixel (x, y) having its centre at
+ *   (x + 0.5, y + 0.5)); D2 = 0.25 (W W + H H), the square of half the diagonal: lengths are normalised by it, so r^2 = 1 at the
+ *   corners of a centred image and no square root is taken per pixel.  r2_max = the largest ((dx dx + dy dy) / D2) of the four
+ *   corner pixels' centres, (dx, dy) their offsets from c; at least 2^-20.
+ *   The radial model is Brown-Conrady: d(t) = 1 + k1 t + k2 t t + k3 t t t, f(s) = s d(s s) the lens's radius of the ideal radius s.
+ *   Knot j = 0 .. FF_LENS_KNOTS: r2 = r2_max j / FF_LENS_KNOTS; r = sqrt(r2); rho = r / zoom (zoom magnifies the output about c);
+ *     FF_LENS_UNDISTORT  the output is the ideal image, the source the lens's: src = f(rho)
+ *     FF_LENS_DISTORT    the output is what the lens with these coefficients records of the rectilinear source: src = the s with
+ *                        f(s) = rho (Newton inside a bisection bracket, to the last bit that moves)
+ *     e_j = float(src / r - 1), and for j = 0 float(1 / zoom - 1): the source radius over the output radius, less 1
+ *     R = rho (DISTORT) or src (UNDISTORT): the radius in the LENS's image, where the vignette lives;
+ *     v = 1 / (c c) with c = 1 + (vignette_falloff R) (vignette_falloff R) - cos^4 of the field angle, the natural law;
+ *     gain = (1 - vignette) + vignette v;  g_j = float(gain) under DISTORT, which adds the vignette, float(1 / gain) under
+ *     UNDISTORT, which removes it.  vignette = 0 gives a table of exact 1.0f; no distortion and zoom 1 give e_j = 0 exactly.
+ *   f must rise strictly on the range the image needs - [0, sqrt(r2_max) / zoom] under UNDISTORT, up to where it reaches that under
+ *   DISTORT -, or the image would fold over: f'(s) = 1 + 3 k1 t + 5 k2 t t + 7 k3 t t t (t = s s) is tested through its exact
+ *   extrema, and such parameters are refused with FF_ERR_INVALID_ARG and a message naming the radius of the fold.
+ * PIXELS.  All arithmetic is float32 + - * and floor with no fused multiply-add, every formula evaluated as parenthesised;
+ * min(a, b) is b < a ? b : a and max(a, b) is a < b ? b : a; lerp(a, b, t) = a + t * (b - a).  Per output pixel (x, y):
+ *   1 radial   px = float(x) + 0.5, py likewise; dx = px - cx, dy = py - cy; r2 = ((dx dx) + (dy dy)) * float(1 / D2);
+ *              u = min(r2 * float(FF_LENS_KNOTS / r2_max), FF_LENS_KNOTS); i = min(int(floor(u)), FF_LENS_KNOTS - 1); t = u - float(i);
+ *              e = lerp(e_i, e_i+1, t), g = lerp(g_i, g_i+1, t): one floor, one fraction, one linear interpolation each
+ *   2 source   per channel, q = ca_red for red, 0 for green, ca_blue for blue (the channel's magnification against green):
+ *              ec = (e + q) + (e * q), which is (1 + e)(1 + q) - 1; sx = px + (dx * ec), sy = py + (dy * ec): the displacement form,
+ *              so that e = 0 and q = 0 give (px, py) exactly.  When both q are 0 the three channels share one position and one set
+ *              of taps
+ *   3 border   FF_LENS_BORDER_BLACK: a channel whose (sx, sy) is not inside [0, W] x [0, H] is 0, and step 4 is skipped for it.
+ *              Otherwise, and under FF_LENS_BORDER_CLAMP always, sx = sx > 0 ? min-of(sx, W) : 0 and sy likewise - edge replication
+ *   4 resample ux = sx - 0.5; ix = floor(ux); fx = ux - ix; uy, iy, fy likewise.  Tap (i, j) reads pixel (clamp(ix + i, 0, W - 1),
+ *              clamp(iy + j, 0, H - 1)); a non-finite tap reads as +0, as in ff_resize.
+ *              FF_LENS_BILINEAR: i, j in 0 .. 1; v = lerp(lerp(v00, v10, fx), lerp(v01, v11, fx), fy).
+ *              FF_LENS_CATMULL_ROM: i, j in -1 .. 2, 4 x 4 taps, the weights ff_taa's history resampling uses, for fraction t:
+ *              w_-1 = ((-t3 + 2 t2) - t) 0.5, w_0 = ((3 t3 - 5 t2) + 2) 0.5, w_1 = ((-3 t3 + 4 t2) + t) 0.5, w_2 = (t3 - t2) 0.5
+ *              (t2 = t t, t3 = t2 t).  Rows first, taps in the order of i: row_j = (((wx_-1 v_-1j) + (wx_0 v_0j)) + (wx_1 v_1j)) +
+ *              (wx_2 v_2j); then v = (((wy_-1 row_-1) + (wy_0 row_0)) + (wy_1 row_1)) + (wy_2 row_2).  With FF_LENS_ANTI_RING lo and
+ *              hi are the min and max of the inner taps v_00, v_10, v_01, v_11 taken in this order, and v = min(max(v, lo), hi):
+ *              radiance stays >= 0 beside an HDR edge.  Without the flag the negative lobes may produce NEGATIVE radiance.
+ *              Under either filter a position on a pixel's centre (fx = 0 and fy = 0) returns that tap v_00 itself
+ *   5 gain     out = v * g, per channel; rgb8 = trunc(clamp(out * 255)), the rule of every rgb8 output here.
+ * Consequences.  The defaults return a finite image bit for bit, -0 included (a non-finite value comes back as +0).  Under CLAMP
+ * with ANTI_RING or BILINEAR a constant finite image comes back bit for bit under any geometry (a constant -0 may return as +0).
+ * The green channel does not depend on ca_red and ca_blue.  No geometry and a vignette give the input times g.  Minification is
+ * NOT filtered - one set of taps per channel whatever the local scale: for coefficients that compress the corners strongly,
+ * render larger and ff_resize afterwards.
+ * rgb8 (W*H*3 bytes) and radiance_out (W*H*3 floats) may each be NULL.  Neither may overlap the input - this is a gather - and the
+ * two may not overlap each other.  Width and height are 1 .. 65535.  Synchronous, on the state's stream; host buffers are staged.
+ * The call leaves FfStats, the stored primary hits and their key, every filter's history, the display exposure and the progressive
+ * and adaptive sums as they were, and ff_upload_scene resets nothing of it; its own state is the staging buffer and the device
+ * table with its key (k1, k2, k3, center, zoom, vignette, vignette_falloff, direction, W, H) - rebuilt and uploaded only when the
+ * key changes -, allocated on first use and freed by ff_destroy.  FF_ERR_INVALID_ARG, naming the field, before any device work,
+ * in this order, for: a NULL state or params; a bad size; a k outside -10 .. 10, |center_x| > W/2, |center_y| > H/2, a zoom
+ * outside 1/16 .. 16, a ca outside -0.25 .. 0.25, a vignette outside 0 .. 1, a vignette_falloff outside 0 .. 8, or any of them
+ * not finite; an unknown direction, filter or border; a nonzero reserved; unknown flags; coefficients that fold the image over;
+ * a NULL radiance_in; an output that overlaps the input or the other output.
+ * Not offered: tangential (decentering) terms, fisheye and other projections (a host-only addition to the tables), filtered
+ * minification, film grain, a `lens` statement in the scene file, warping of G-buffer planes, a multi-GPU twin. */
+FF_API int ff_lens(FfState* state, int width, int height, const FfLensParams* p,
+                   const float* radiance_in, int input_on_device,
+                   void* rgb8, int rgb8_on_device, float* radiance_out, int radiance_out_on_device);
+
+/* Host-only twin (no GPU, no state, host pointers), compiled from the same inline per-pixel functions the kernel uses: the same
+ * image arguments, the same checks, the same bits. */
+FF_API int ff_lens_host(int width, int height, const FfLensParams* p, const float* radiance_in,
+                        unsigned char* rgb8, float* radiance_out);
+
+/* The two tables as the kernel gets them: out_e and out_gain, FF_LENS_KNOTS + 1 floats each, and r2_max; each output may be NULL.
+ * The checks are ff_lens's for the size and the parameters. */
+FF_API int ff_lens_tables(const FfLensParams* p, int width, int height, float* out_e, float* out_gain, double* out_r2_max);
+
+/* The source positions of n output positions (xy_out, xy_src: n pairs x y, in pixels, a pixel's centre at + 0.5) for `channel`
+ * 0 = red, 1 = green, 2 = blue, through steps 1 and 2 as ff_lens runs them, before the border rule: what a viewer needs to pick
+ * through a distorted frame.  A position beyond r2_max reads the tables' last knot.  The checks are ff_lens's for the size and
+ * the parameters; every xy_out must be finite. */
+FF_API int ff_lens_map_host(const FfLensParams* p, int width, int height, int channel, const float* xy_out, int n, float* xy_src);
+
+/* The zoom that fits the frame, for the other parameters as given (p->zoom is not read), computed in double from the model along
+ * the image border.  FF_LENS_FIT_FILL: the smallest zoom at which no output pixel's green position leaves the source, so that no
+ * border shows, times 1 + 1e-4.  FF_LENS_FIT_ALL: the largest zoom at which the whole source - every point of its edge - stays
+ * in view, times 1 - 1e-4.  The margin covers the float arithmetic and the tables of steps 1 and 2.  FF_ERR_INVALID_ARG for
+ * ff_lens's parameter checks, an unknown mode, a NULL out_zoom, a fold-over that hides the source's edge (ALL), or a fitting zoom
+ * outside 1/16 .. 16. */
+FF_API int ff_lens_fit_zoom(const FfLensParams* p, int width, int height, int mode, float* out_zoom);
+
+/* How often this state has built and uploaded ff_lens's table (tests: it is rebuilt only when its key changes). */
+FF_API int ff_debug_lens_table_builds(FfState* state, uint64_t* out_builds);
+
 /* ---- measurement -------------------------------------------------------------------------------- */
 
 /* Turn per-launch node/triangle visit counters on (1) or off (0, default).  Ray counting is always on. */

@@ -472,6 +472,28 @@ typedef struct FfCubeFile {
     FfGradeLut lut;              /* a 1D file: the curves on FF_GRADE_AXIS_LINEAR; a 3D file: the lattice */
 } FfCubeFile;                    /* 192 bytes */
 
+/* ff_lens: radial lens distortion, lateral chromatic aberration and vignetting as one gather.  ff_lens_params_init gives the
+ * defaults (the identity); the operator is in ff_api.h. */
+#define FF_LENS_KNOTS 1024            /* cells of the two radial tables: FF_LENS_KNOTS + 1 knots over r^2 = 0 .. r2_max */
+enum { FF_LENS_UNDISTORT = 0, FF_LENS_DISTORT = 1 };          /* direction */
+enum { FF_LENS_BILINEAR = 0, FF_LENS_CATMULL_ROM = 1 };       /* filter */
+enum { FF_LENS_BORDER_BLACK = 0, FF_LENS_BORDER_CLAMP = 1 };  /* border */
+enum { FF_LENS_FIT_FILL = 0, FF_LENS_FIT_ALL = 1 };           /* ff_lens_fit_zoom's mode */
+#define FF_LENS_ANTI_RING 1u          /* a Catmull-Rom result is clamped to the range of its inner 2 x 2 taps */
+typedef struct FfLensParams {
+    float    k1, k2, k3;        /* Brown-Conrady: d(r^2) = 1 + k1 r^2 + k2 r^4 + k3 r^6; each finite, -10 .. 10 */
+    float    center_x, center_y; /* the optical centre's offset from the image centre in pixels; |center_x| <= W/2, |center_y| <= H/2 */
+    float    zoom;              /* a uniform magnification of the output about the optical centre; 1/16 .. 16 */
+    float    ca_red, ca_blue;   /* relative magnification of red and of blue against green; -0.25 .. 0.25 */
+    float    vignette;          /* the strength of the natural vignette; 0 .. 1 */
+    float    vignette_falloff;  /* F of v = 1 / (1 + (F r)^2)^2; 0 .. 8 */
+    int32_t  direction;         /* FF_LENS_UNDISTORT or FF_LENS_DISTORT */
+    int32_t  filter;            /* FF_LENS_BILINEAR or FF_LENS_CATMULL_ROM */
+    int32_t  border;            /* FF_LENS_BORDER_BLACK or FF_LENS_BORDER_CLAMP */
+    uint32_t flags;             /* FF_LENS_ANTI_RING */
+    uint32_t reserved;          /* 0 */
+} FfLensParams;                 /* 60 bytes; every float must be finite */
+
 /* ff_texture_create: how a texture is addressed and filtered (the formulas are in ff_api.h).  0 = repeat, bilinear. */
 #define FF_TEX_REPEAT    0   /* coordinates wrap: c - floor(c) */
 #define FF_TEX_CLAMP     1   /* coordinates clamp to [0, 1] */
@@ -516,6 +538,7 @@ static_assert(sizeof(FfResizeParams) == 12, "FfResizeParams is 12 bytes");
 static_assert(sizeof(FfGradeParams) == 64, "FfGradeParams is 64 bytes");
 static_assert(sizeof(FfGradeLut) == 64, "FfGradeLut is 64 bytes");
 static_assert(sizeof(FfCubeFile) == 192, "FfCubeFile is 192 bytes");
+static_assert(sizeof(FfLensParams) == 60, "FfLensParams is 60 bytes");
 #else
 _Static_assert(sizeof(FfBXDF) == 60, "BXDF layout");
 _Static_assert(sizeof(FfTriangle) == 96, "Triangle layout");
@@ -538,6 +561,7 @@ _Static_assert(sizeof(FfResizeParams) == 12, "FfResizeParams layout");
 _Static_assert(sizeof(FfGradeParams) == 64, "FfGradeParams layout");
 _Static_assert(sizeof(FfGradeLut) == 64, "FfGradeLut layout");
 _Static_assert(sizeof(FfCubeFile) == 192, "FfCubeFile layout");
+_Static_assert(sizeof(FfLensParams) == 60, "FfLensParams layout");
 #endif
 
 #endif /* FIREFLY_FF_TYPES_H */
