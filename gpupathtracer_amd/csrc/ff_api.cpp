@@ -6,6 +6,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <new>
+#include <vector>
 
 #include <hip/hip_runtime.h>
 
@@ -237,6 +238,43 @@ int ff_debug_check_ieee(FfState* s, unsigned long long* out_mismatches2)
 }
 
 const char* ff_debug_kernel_name(FfState* s) { return s && s->last_kernel_name ? s->last_kernel_name : ""; }
+
+int ff_debug_layout(FfState* s, int* out8)
+{
+    clear_error();
+    if (!s || !out8) return fail(FF_ERR_INVALID_ARG, "ff_debug_layout: null argument");
+    if (!s->has_scene) return fail(FF_ERR_NO_SCENE, "ff_debug_layout: no scene uploaded");
+    const int v[8] = { s->scene_block_threads, s->stack_entries, s->stack_lds_levels, s->lds_cap, s->setup_threshold, s->leaf_threshold, s->max_depth4, s->top_depth };
+    std::memcpy(out8, v, sizeof v);
+    return FF_OK;
+}
+
+// No stack entry equals this word (ff_k_traverse.h inner_step / pop_entry are the only writers): a leaf is ~ref, negative, and so is
+// a geometry-tree leaf ~(kGeomLeaf | record); an inner link is a node index below 1 << 22; a packed entry has kPackedEntry (bit 30)
+// set.  The sentinel is non-negative, at least 1 << 22 and has bit 30 clear.
+constexpr unsigned kSpillSentinel = 0x2A5A5A5Au;
+static_assert((int)kSpillSentinel >= (1 << 22) && (kSpillSentinel & 0x40000000u) == 0u, "the sentinel must lie outside the stack entries' encodings");
+
+int ff_debug_stack_spill(FfState* s, int reset, unsigned long long* words)
+{
+    clear_error();
+    if (!s || !words) return fail(FF_ERR_INVALID_ARG, "ff_debug_stack_spill: null argument");
+    *words = 0;
+    const size_t n = s->d_stack_spill ? s->stack_spill_bytes / sizeof(unsigned) : 0;
+    if (n == 0) return FF_OK;
+    FF_HIP(hipSetDevice(s->device));
+    if (reset) {
+        std::vector<unsigned> fill(n, kSpillSentinel);
+        FF_HIP(hipMemcpyAsync(s->d_stack_spill, fill.data(), n * sizeof(unsigned), hipMemcpyHostToDevice, s->stream));
+        FF_HIP(hipStreamSynchronize(s->stream)); // (`fill` goes out of scope)
+        return FF_OK;
+    }
+    std::vector<unsigned> got(n);
+    FF_HIP(hipMemcpyAsync(got.data(), s->d_stack_spill, n * sizeof(unsigned), hipMemcpyDeviceToHost, s->stream));
+    FF_HIP(hipStreamSynchronize(s->stream));
+    *words = (unsigned long long)std::count_if(got.begin(), got.end(), [](unsigned w) { return w != kSpillSentinel; });
+    return FF_OK;
+}
 
 int ff_stats(FfState* s, FfStats* out)
 {

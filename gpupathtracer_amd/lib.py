@@ -21,7 +21,7 @@ EXPORTS = [
     "ff_scene_info", "ff_debug_wall_table", "ff_debug_wall_entries", "ff_render", "ff_render_strips", "ff_strips_local_rows", "ff_deinterleave_strips",
     "ff_intersect_rays", "ff_register_gl_pbo", "ff_unregister_gl_pbo", "ff_render_to_pbo",
     "ff_render_progressive", "ff_render_to_pbo_progressive", "ff_save_ppm",
-    "ff_set_collect_stats", "ff_stats", "ff_debug_kernel_name", "ff_debug_counters", "ff_debug_timeline", "ff_debug_check_ieee", "ff_debug_reload_switches", "ff_load_obj", "ff_free_triangles",
+    "ff_set_collect_stats", "ff_stats", "ff_debug_kernel_name", "ff_debug_layout", "ff_debug_stack_spill", "ff_debug_counters", "ff_debug_timeline", "ff_debug_check_ieee", "ff_debug_reload_switches", "ff_load_obj", "ff_free_triangles",
     "ff_scene_file_load", "ff_scene_file_geometries", "ff_scene_file_camera", "ff_scene_file_free",
     "ff_dist_unique_id", "ff_dist_init", "ff_dist_available", "ff_dist_shutdown", "ff_dist_strip_rows", "ff_dist_strip_rows_for", "ff_dist_part_bytes", "ff_render_distributed", "ff_debug_dist_fail_rank",
     "ff_multi_create", "ff_multi_destroy", "ff_multi_count", "ff_multi_state", "ff_multi_uses_rccl", "ff_multi_upload_scene",
@@ -138,6 +138,8 @@ def load():
     lib.ff_debug_timeline.argtypes = [vp, P(C.c_uint), P(C.c_int)]
     lib.ff_debug_kernel_name.argtypes = [vp]
     lib.ff_debug_kernel_name.restype = C.c_char_p
+    lib.ff_debug_layout.argtypes = [vp, P(i32)]
+    lib.ff_debug_stack_spill.argtypes = [vp, i32, P(C.c_ulonglong)]
     lib.ff_debug_check_ieee.argtypes = [vp, P(C.c_ulonglong)]
     lib.ff_debug_reload_switches.argtypes = [vp]
     lib.ff_load_obj.argtypes = [C.c_char_p, P(P(T.FfTriangle)), P(i32)]
@@ -1222,6 +1224,10 @@ GBUFFER_CHANNELS = (("depth", np.float32, ()), ("position", np.float32, (3,)), (
                     ("ids", np.int32, (3,)))
 
 
+# the eight values of ff_debug_layout, in order
+LAYOUT_FIELDS = ("scene_block_threads", "stack_entries", "stack_lds_levels", "lds_cap", "setup_threshold", "leaf_threshold", "max_depth4", "top_depth")
+
+
 class Tracer:
     """Owner of one FfState (one HIP device). Mirrors the call sequence of the reference's main():
     upload once (kernel.cu:268-298), then render per frame (kernel.cu:335-344)."""
@@ -1354,6 +1360,23 @@ class Tracer:
     def kernel_name(self):
         """Trace-kernel instantiation of the last frame, as rocprofv3 names it."""
         return self._lib.ff_debug_kernel_name(self._state).decode()
+
+    def debug_layout(self):
+        """ff_debug_layout: what the next BVH launch on the uploaded scene will use -> dict of ints (LAYOUT_FIELDS)."""
+        buf = (C.c_int * 8)()
+        check(self._lib.ff_debug_layout(self._state, buf))
+        return dict(zip(LAYOUT_FIELDS, (int(v) for v in buf)))
+
+    def reset_stack_spill(self):
+        """ff_debug_stack_spill(reset): fill the traversal stacks' global spill area, if there is one, with the sentinel word."""
+        n = C.c_ulonglong(0)
+        check(self._lib.ff_debug_stack_spill(self._state, 1, C.byref(n)))
+
+    def stack_spill_words(self):
+        """ff_debug_stack_spill: words of the spill area that differ from the sentinel (0 where there is no area)."""
+        n = C.c_ulonglong(0)
+        check(self._lib.ff_debug_stack_spill(self._state, 0, C.byref(n)))
+        return int(n.value)
 
     def check_ieee(self):
         """(reciprocal mismatches, square-root mismatches) of the kernels' lean IEEE sequences over all 2^32 floats."""

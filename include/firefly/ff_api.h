@@ -1751,6 +1751,16 @@ FF_API int ff_stats(FfState* state, FfStats* out);
 /* Name of the trace-kernel instantiation the last frame launched, spelled as rocprofv3 prints it ("" before the first frame). */
 FF_API const char* ff_debug_kernel_name(FfState* state);
 
+/* The layout the next BVH launch on the uploaded scene will use (tests), out8 = workgroup size of the trace kernel (0: the trees are too
+ * deep for any), traversal-stack entries per lane, how many of them live in LDS, LDS node slots in use, setup threshold, leaf threshold,
+ * depth of the deepest 4-wide mesh tree, depth of the tree over the geometries (0: none).  FF_ERR_NO_SCENE before an upload. */
+FF_API int ff_debug_layout(FfState* state, int* out8);
+
+/* The global spill area of the traversal stacks (tests).  reset != 0: fill it, if there is one, with a word that no stack entry can
+ * equal.  reset == 0: *words = how many of its words differ from that word now (0 where there is no area).  A launch may reallocate the
+ * area when it needs a larger one: reset it after a first launch of the same size, then launch again and count. */
+FF_API int ff_debug_stack_spill(FfState* state, int reset, unsigned long long* words);
+
 /* Raw device counters of the last instrumented render (ff_set_collect_stats(1)), 28 values: [0] rays [1] inner-node
  * visits [2] triangle tests [3] plane tests (all summed over lanes) [8] inner-step rounds [9] leaf rounds [10] triangle
  * rounds [11] plane rounds [12] segment rounds (wave-level executions of each phase): lanes / (64 * rounds) is the SIMD
