@@ -24,6 +24,61 @@ def test_library_exports_every_declared_symbol(ff):
     assert lib.ff_version() >= 100
 
 
+_SCALARS = {"int": C.c_int, "unsigned": C.c_uint, "unsigned int": C.c_uint, "float": C.c_float, "double": C.c_double,
+            "long long": C.c_longlong, "uint32_t": C.c_uint32, "uint64_t": C.c_uint64, "int32_t": C.c_int32}
+
+
+def _is_pointer(ctype):
+    return ctype in (C.c_void_p, C.c_char_p) or (isinstance(ctype, type) and issubclass(ctype, C._Pointer))
+
+
+def _declarations():
+    """(name, return type, [parameter, ...]) of every FF_API declaration of ff_api.h, comments stripped."""
+    header = open(os.path.join(ROOT, "include", "firefly", "ff_api.h")).read()
+    header = re.sub(r"/\*.*?\*/", " ", header, flags=re.S)
+    header = re.sub(r"//[^\n]*", " ", header)
+    out = []
+    for ret, name, params in re.findall(r"FF_API\s+([\w\s\*]+?)\s*\b(ff_\w+)\s*\(([^()]*)\)\s*;", header):
+        params = [" ".join(p.split()) for p in params.split(",")]
+        out.append((name, " ".join(ret.split()), [] if params in ([""], ["void"]) else params))
+    return out
+
+
+def _scalar_ctype(text):
+    """The ctype of a by-value C type as the header spells it: `const` dropped, a struct by its mirror in types.py."""
+    base = " ".join(w for w in text.split() if w != "const")
+    return _SCALARS[base] if base in _SCALARS else getattr(T, base)
+
+
+def test_prototype_table_matches_the_header(ff):
+    """Every FF_API declaration against ff.PROTOTYPES, the table load() declares the ctypes prototypes from: as many parameters, a
+    pointer-like ctype exactly where the parameter is a pointer or an array, the ctype of its base type where it is passed by
+    value, and the return type.  No declaration is exempt."""
+    decls = _declarations()
+    assert {name for name, _, _ in decls} == set(ff.PROTOTYPES) and len(decls) == len(ff.PROTOTYPES)
+    assert ff.EXPORTS == list(ff.PROTOTYPES)
+    handle = ff.load()
+    for name, ret, params in decls:
+        argtypes, restype = ff.PROTOTYPES[name]
+        assert len(params) == len(argtypes), (name, params, argtypes)
+        for param, ctype in zip(params, argtypes):
+            if "*" in param or "[" in param:
+                assert _is_pointer(ctype), (name, param, ctype)
+            else:
+                assert ctype is _scalar_ctype(param.rsplit(" ", 1)[0]), (name, param, ctype)   # (the last word is the parameter's name)
+        if ret == "void":
+            assert restype is None, name
+        elif ret == "const char*":
+            assert restype is C.c_char_p, name
+        elif "*" in ret:
+            assert _is_pointer(restype) and restype is not C.c_char_p, (name, ret, restype)
+        else:
+            assert restype is _scalar_ctype(ret), (name, ret, restype)
+        # ... and load() has applied the entry to the function it declares
+        fn = getattr(handle, name)
+        assert list(fn.argtypes) == list(argtypes) and fn.restype is restype, name
+
+
 def test_struct_layouts_match_reference_sizes():
     # g++ x86-64 sizes of the reference's structs (SURVEY.md §8a row a7)
     assert (C.sizeof(T.FfTriangle), C.sizeof(T.FfGeometry), C.sizeof(T.FfCamera), C.sizeof(T.FfRay), C.sizeof(T.FfIntersect),
